@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- repaired cells/sec of the repair-model hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 10m16|100m32]
+    python bench.py --gpus N --steps K --warmup W [--config 10m16|100m32] [--dump-outputs DIR] [--full]
 
 Workloads (config.workload):
   10m16  (default) BASELINE.json configs[2]: synthetic 10M rows x 16 categorical columns, 1 % injected NULLs, seed 42, every
@@ -13,10 +13,13 @@ ALL rows (model.max_training_row_num = N).
 
 Timing contract: W untimed warm-up boosting iterations, then EXACTLY K boosting iterations ("steps") of EVERY target model
 (+ the chained repair of every dirty row + the result exchange) between barrier + synchronize brackets, max over ranks ->
-`ms_per_step`.  The reference's job is n_estimators = 300 iterations (train.py:53-55), so the headline `value` is always the
-cells/sec of the COMPLETE 300-iteration job: when K != 300 that job is run (and timed the same way) right after the K-step
-region; `value_basis` says which run the number comes from.  --no-full-job skips it (value then describes the K-step job and
-says so).  With --gpus N (N > 1) and no torchrun environment the script launches its N ranks itself.
+`ms_per_step`.  A plain run does nothing else: set-up, warm-up, the K steps, --dump-outputs, the result line, whose `value` is
+the cells/sec of the job of the K-step region (`value_basis` says so).  The reference's job is n_estimators = 300 iterations
+(train.py:53-55): with --steps 300 the K-step region is that job.  --full adds what takes runs of its own: the COMPLETE 300-iteration
+job when K != 300, run (and timed the same way) right after the K-step region, which then gives the headline `value` (--no-full-job
+skips it), the sequential roofline pass, the CPU baselines and the repair accuracy.  --dump-outputs DIR writes what the K-step job
+returned (repaired labels and probabilities of the dirty rows, the serialised models) as .npy files; the inputs depend on the
+arguments only.  With --gpus N (N > 1) and no torchrun environment the script launches its N ranks itself.
 
 Multi-GPU ("scaling": "strong", the SAME job on more GPUs): expensive targets are trained row-sharded over all ranks (every
 rank holds a row shard, librepairgbm all-reduces integer histograms over RCCL -- the model is bit-identical for any N), cheap
@@ -198,6 +201,29 @@ def _load_traffic(config, world, rows, cols, train_rows, forced_collectives):
     return None
 
 
+DUMP_CELLS_BYTES, DUMP_MODEL_BYTES = 24 << 20, 32 << 20      # --dump-outputs: 56 MB at most, within the 64 MB it may write
+
+
+def _sample(n, cap):
+    """All of range(n), or a fixed seeded sorted sample of `cap` of its indices: the same for every run with the same arguments."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.Generator(np.random.PCG64(1234)).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, res, targets):
+    """What the timed job handed its caller: labels.npy / probs.npy (float32 / float64 [targets, dirty rows]: the repaired code and its
+    probability of every target cell of every dirty row) and models.npy (float32: the bytes of the serialised models in target order).
+    Larger outputs are cut to the same seeded sample of dirty rows / model bytes in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    labels, probs = np.asarray(res["labels"]), np.asarray(res["probs"])
+    cols = _sample(labels.shape[1], DUMP_CELLS_BYTES // (12 * max(1, labels.shape[0])))
+    np.save(os.path.join(out_dir, "labels.npy"), labels[:, cols].astype(np.float32))
+    np.save(os.path.join(out_dir, "probs.npy"), probs[:, cols].astype(np.float64))
+    blob = np.frombuffer(b"".join(res["models"][t] for t in targets), np.uint8)
+    np.save(os.path.join(out_dir, "models.npy"), blob[_sample(blob.size, DUMP_MODEL_BYTES // 4)].astype(np.float32))
+
+
 def true_reference_baseline(cols, seed, targets, steps_full):
     """The REAL reference arithmetic, when it can be imported: lightgbm (pinned 3.3.1 in bin/requirements.txt:6; python/repair/train.py:92,
     121-131) with the reference's fixed parameters on the bounded sample cpu_baseline() uses.  Neither this container nor the GPU box has
@@ -233,13 +259,13 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="10m16")
     ap.add_argument("--rows", type=int, default=0, help="override the config's row count (testing)")
     ap.add_argument("--cols", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-job", action="store_true", help="do not run the 300-iteration job when --steps differs from 300")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--no-full-job", action="store_true", help="with --full: do not run the 300-iteration job when --steps differs from 300")
     ap.add_argument("--mode", choices=["auto", "targets"], default="auto", help="multi-GPU split: auto = hybrid row/target sharding")
     ap.add_argument("--force-row-sharding", action="store_true", help="testing: run the collective (RCCL) path with a world of one")
     ap.add_argument("--row-shard-all", action="store_true", help="testing, with --force-row-sharding: EVERY target takes the collective path (what a rank of the "
                                                                   "shard-only multi-GPU job does; with --rows 12500000 --config 100m32 this is one rank's share of the 8-GPU job)")
-    ap.add_argument("--roofline-steps", type=int, default=20, help="boosting iterations of the sequential pass that measures the kernel roofline")
+    ap.add_argument("--roofline-steps", type=int, default=20, help="with --full: boosting iterations of the sequential pass that measures the kernel roofline")
     ap.add_argument("--concurrency", type=int, default=None, help="target models trained at once per rank (default: RGBM_TARGET_CONCURRENCY or 6)")
     ap.add_argument("--train-rows", type=int, default=0,
                     help="train every model on a seeded sample of this many rows (the reference's DEFAULT behaviour is "
@@ -249,7 +275,14 @@ def main():
                          "(repair.pipeline.distinct_rows + rgbm_table_set_row_multiplicity): byte-identical models -- models_md5 must equal the row-for-row "
                          "line's -- at the cost of the distinct rows; one rank, whole tables")
     ap.add_argument("--dump-labels", default="", help="debug: np.save the repaired labels / probabilities of the job here")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed K-step job returned to DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded sample when larger)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the complete 300-iteration job (when --steps differs from 300), "
+                         "the sequential roofline pass, the CPU baselines and the repair accuracy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(_spawn_ranks(a))
@@ -443,36 +476,39 @@ def main():
         timed_job(a.warmup)
     # ---- timed region: exactly K steps
     res_k, elapsed_k = timed_job(a.steps)
-    # ---- the reference-configured job (n_estimators = 300), timed the same way, unless the K-step region already was that job
-    run_full = a.steps != REF_N_ESTIMATORS and not a.no_full_job
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, res_k, targets)
+    # ---- --full: the reference-configured job (n_estimators = 300), timed the same way, unless the K-step region already was that job
+    run_full = a.full and a.steps != REF_N_ESTIMATORS and not a.no_full_job
     res, elapsed = timed_job(REF_N_ESTIMATORS) if run_full else (res_k, elapsed_k)
     job_steps = REF_N_ESTIMATORS if run_full else a.steps
-
-    # ---- roofline inputs: hist_build algorithmic bytes / its summed launch time.  Every launch is bracketed by HIP events on the
-    # stream it is launched on (rgbm_train_stats); with several training streams in flight a bracket also spans the other streams'
-    # kernels, so the kernel figures come from a dedicated pass of the SAME job with ONE target at a time (not part of `value`).
-    roof_steps = max(1, min(a.steps, a.roofline_steps))
-    res_roof, elapsed_roof = timed_job(roof_steps, want_stats=True, concurrency=1)
-
-    def agg(key, r=res_roof):
-        return rdist.sum_over_ranks(sum(s.get(key, 0) for s in r["stats"]))
-    hist_ms_all, hist_bytes_all, launches_all = agg("hist_ms"), agg("hist_bytes"), agg("hist_launches")
-    root_ms = sum(s["root_ms"] for s in res_roof["stats"]); root_bytes = sum(s["root_rows"] * (cols - 1 + 8) for s in res_roof["stats"])
-    n_root = rdist.sum_over_ranks(roof_steps * len(res_roof["stats"]))       # one root launch per boosting iteration and trained model (nchunk = 1 workloads)
-    # level launches of a target x 9 B x (training-table rows of this rank) x class trees (an upper bound: finished class trees are skipped)
-    level_stream_bytes = rdist.sum_over_ranks(sum((s_["hist_launches"] - roof_steps) * 9.0 * float(getattr(row_tab if shard_only else train_tab, "n", 0)) *
-                                                  (1 if int(cards[s_["target"]]) <= 2 else int(cards[s_["target"]])) for s_ in res_roof["stats"]))
     train_s = rdist.max_over_ranks(res["times"]["train"]); infer_s = rdist.max_over_ranks(res["times"]["infer"])
-    # what the FINISHED trees of the roofline pass needed below their roots (rows of the smaller child of every split whose children can be
-    # split again): the level grower accumulates a superset (it cannot know at level 3 which nodes best-first growth will take), and
-    # `roofline.achieved` counts what it accumulated -- `frac_needed` prices the same launches at the bytes LightGBM's own growth order needs
-    from repair import _native as _N
-    needed_level_rows = 0
-    if rank == 0 and world == 1:      # (one rank: its statistics cover every launch the figure is priced over)
-        needed_level_rows = sum(_N.needed_built_rows(res_roof["models"][s_["target"]], BASE_PARAMS["max_depth"]) for s_ in res_roof["stats"])
+
+    if a.full:
+        # ---- roofline inputs: hist_build algorithmic bytes / its summed launch time.  Every launch is bracketed by HIP events on the
+        # stream it is launched on (rgbm_train_stats); with several training streams in flight a bracket also spans the other streams'
+        # kernels, so the kernel figures come from a dedicated pass of the SAME job with ONE target at a time (not part of `value`).
+        roof_steps = max(1, min(a.steps, a.roofline_steps))
+        res_roof, elapsed_roof = timed_job(roof_steps, want_stats=True, concurrency=1)
+
+        def agg(key, r=res_roof):
+            return rdist.sum_over_ranks(sum(s.get(key, 0) for s in r["stats"]))
+        hist_ms_all, hist_bytes_all, launches_all = agg("hist_ms"), agg("hist_bytes"), agg("hist_launches")
+        root_ms = sum(s["root_ms"] for s in res_roof["stats"]); root_bytes = sum(s["root_rows"] * (cols - 1 + 8) for s in res_roof["stats"])
+        n_root = rdist.sum_over_ranks(roof_steps * len(res_roof["stats"]))       # one root launch per boosting iteration and trained model (nchunk = 1 workloads)
+        # level launches of a target x 9 B x (training-table rows of this rank) x class trees (an upper bound: finished class trees are skipped)
+        level_stream_bytes = rdist.sum_over_ranks(sum((s_["hist_launches"] - roof_steps) * 9.0 * float(getattr(row_tab if shard_only else train_tab, "n", 0)) *
+                                                      (1 if int(cards[s_["target"]]) <= 2 else int(cards[s_["target"]])) for s_ in res_roof["stats"]))
+        # what the FINISHED trees of the roofline pass needed below their roots (rows of the smaller child of every split whose children can be
+        # split again): the level grower accumulates a superset (it cannot know at level 3 which nodes best-first growth will take), and
+        # `roofline.achieved` counts what it accumulated -- `frac_needed` prices the same launches at the bytes LightGBM's own growth order needs
+        from repair import _native as _N
+        needed_level_rows = 0
+        if rank == 0 and world == 1:      # (one rank: its statistics cover every launch the figure is priced over)
+            needed_level_rows = sum(_N.needed_built_rows(res_roof["models"][s_["target"]], BASE_PARAMS["max_depth"]) for s_ in res_roof["stats"])
 
     fixed_shards = 0.0
-    if shard_only:   # every rank checks the cells of its own dirty rows against the clean values it generated
+    if shard_only and a.full:   # every rank checks the cells of its own dirty rows against the clean values it generated
         mine_l = res["labels"][:, res["dirty_row0"]:res["dirty_row0"] + dirty_rows.shape[1]]
         for i, t in enumerate(targets):
             pos, truth = null_truth[t]
@@ -486,53 +522,13 @@ def main():
             for t in targets:
                 with open(a.dump_labels + "_model_%d.bin" % t, "wb") as f:
                     f.write(res["models"][t])
-        fixed = int(fixed_shards)
-        for i, t in enumerate(targets if not shard_only else []):
-            pos, truth = null_truth[t]
-            # the dirty table holds the dirty rows in ascending row order: map the nulled cells of t to their dirty-row index
-            idx = np.searchsorted(dirty_pos, pos)
-            fixed += int((labels[i][idx] == truth).sum())
-        achieved = hist_bytes_all / max(hist_ms_all, 1e-9) * 1e-6
-        traffic = _load_traffic(a.config, world, rows, cols, a.train_rows, a.force_row_sharding or a.dedup)
-        # LDS atomics the launches of each class issued, target by target (the joint-bin groups of a root pass depend on the target's feature set)
-        atom_ops = {"root": sum(float(s_.get("root_rows", 0)) * float(s_.get("root_atomics_per_row", 0)) for s_ in res_roof["stats"]),
-                    "level": sum(float(s_.get("hist_rows", 0) - s_.get("root_rows", 0)) * float(s_.get("level_atomics_per_row", 0)) for s_ in res_roof["stats"])}
-        # the two kernel classes of the histogram build, each with its own algorithmic bytes, launch time and (from the committed PMC
-        # profile of the same target set) HBM-side bytes per launch
-        classes = {}
-        n_root_l = max(1, int(round(n_root)))
-        for name, ms, nbytes, nl in (("root", root_ms, root_bytes, n_root_l), ("level", hist_ms_all - root_ms, hist_bytes_all - root_bytes, max(1, int(launches_all) - n_root_l))):
-            c = {"kernel": "rg::k_level_root" if name == "root" else "rg::k_level_mt", "launches": int(nl), "avg_launch_us": ms * 1e3 / nl, "alg_bytes_per_launch": nbytes / nl,
-                 "achieved": nbytes / max(ms, 1e-9) * 1e-6, "frac": nbytes / max(ms, 1e-9) * 1e-6 / HBM_PEAK_GBS}
-            if name == "level":   # what a level pass streams by construction: 1 B node id + 8 B (g, h) of every (row, class tree) of its target
-                c["stream_bytes_per_launch"] = level_stream_bytes / nl
-                c["bound"] = "the CU's LDS pipeline: 30 ds_add_u64 per built row + ring traffic (DESIGN 5: with two steps of loads in flight per wave neither the stream nor instruction issue binds); its HBM stream alone would take stream_bytes / ~5 TB/s"
-                if needed_level_rows:
-                    c["needed_alg_bytes_per_launch"] = needed_level_rows * (cols - 1 + 8) / nl
-                    c["frac_needed"] = needed_level_rows * (cols - 1 + 8) / max(ms, 1e-9) * 1e-6 / HBM_PEAK_GBS
-            else:
-                c["bound"] = "lds-atomic: 14 ds_add_u64 per row (7 joint-bin groups x (g, h)) at ~12.8 cycles per wave instruction; algorithmic bytes follow SURVEY 8(d) (F + 8 per row), the pass's HBM traffic is about half of them"
-            if atom_ops[name] > 0 and world == 1:     # the LDS-atomic floor of this class: (accumulated rows x atomics per row / 64 lanes) wave instructions at the conflict-free rate
-                c["atomics_per_row"] = atom_ops[name] / max(nbytes / (cols - 1 + 8), 1e-9)
-                c["atomic_floor_us"] = atom_ops[name] / nl / 64.0 * LDS_ATOMIC_CYCLES / (N_CUS * CLOCK_HZ) * 1e6
-                c["atomic_floor_share_of_launch"] = c["atomic_floor_us"] / max(c["avg_launch_us"], 1e-9)
-            if traffic and name in traffic["classes"]:
-                tc = traffic["classes"][name]
-                gbps = tc["bytes_per_launch"] / max(ms / nl, 1e-9) * 1e-6
-                if gbps <= HBM_PEAK_GBS:      # (a figure above the HBM peak means the profile does not describe THIS run: not evidence, not printed)
-                    c["traffic"] = {"fetch_bytes_per_launch": tc["fetch_bytes_per_launch"], "write_bytes_per_launch": tc["write_bytes_per_launch"],
-                                    "ratio_to_algorithmic": tc["bytes_per_launch"] / max(nbytes / nl, 1e-9), "hbm_GBps": gbps}
-                else:
-                    c["traffic"] = {"dropped": "profiles/traffic.json would put this class at %.0f GB/s, above the HBM peak: the committed counters are not of this run" % gbps}
-                    traffic = None
-            classes[name] = c
         out = {
             "metric": "repaired cells/sec", "value": n_cells / elapsed, "unit": "cells/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed_k * 1e3 / a.steps,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32 gradients (LightGBM's score_t), exact int64 fixed-point histogram sums, f64 scores",
             "data": "synthetic",
             "value_basis": "complete job: n_estimators=%d per target model, %.2f s" % (job_steps, elapsed) +
-                           ("" if job_steps == REF_N_ESTIMATORS else " (NOT the reference's 300-iteration job: --no-full-job)"),
+                           ("" if job_steps == REF_N_ESTIMATORS else " (NOT the reference's 300-iteration job: %s)" % ("--no-full-job" if a.full else "--full runs it")),
             "config": {"workload": "synthetic %dM rows x %d categorical cols, 1%% NULLs, seed %d (BASELINE %s); %d target attributes, "
                                    "n_estimators=%d (reference default), %s" % (rows // 1_000_000, cols, cfg["seed"], cfg["baseline"], len(targets), REF_N_ESTIMATORS,
                                                                                  "train on all rows" if not (0 < a.train_rows < rows) else "train on a %d-row sample (reference default)" % a.train_rows),
@@ -546,38 +542,80 @@ def main():
                        "plan": plan_of(row_tab is not None or a.force_row_sharding)},
             "steps_region_sec": elapsed_k, "job_steps": job_steps, "elapsed_sec": elapsed,
             "model_train_sec": train_s, "repair_sec": infer_s,
-            "repair_accuracy_vs_clean": fixed / max(n_cells, 1),
             # digest of every trained model of the job, in target order: two runs of the same build must print the same value
             "models_md5": hashlib.md5(b"".join(res["models"][t] for t in targets)).hexdigest(),
             "upload": {"bytes": int(upload_bytes), "sec": t_up, "GBps": upload_bytes / max(t_up, 1e-9) * 1e-9, "generate_sec": t_gen},
-            "roofline": {"bound": "hbm",
-                         "kernel": "rg::k_level_root + rg::k_level_mt (histogram build of the level grower; a level pass also routes the rows of its level: DataPartition::Split is not a separate kernel)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         # the same launches priced at what the finished trees needed (root passes in full + the smaller child of every final split)
-                         "frac_needed": ((root_bytes + needed_level_rows * (cols - 1 + 8)) / max(hist_ms_all, 1e-9) * 1e-6 / HBM_PEAK_GBS) if needed_level_rows else None,
-                         "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_source": traffic["source"] if traffic else None,
-                         "classes": classes,
-                         "measured_on": "sequential pass (one target model at a time) of %d boosting iterations of the same job, %.2f s; HIP events per launch" % (roof_steps, elapsed_roof),
-                         "launches": int(launches_all), "avg_launch_us": hist_ms_all * 1e3 / max(launches_all, 1),
-                         "alg_bytes_per_launch": hist_bytes_all / max(launches_all, 1),
-                         "root_scan_GBps_rank0": root_bytes / max(root_ms, 1e-9) * 1e-6,
-                         # the ceiling of the two-64-bit-atomics-per-feature numerics: the same algorithmic bytes over the LDS-atomic floors of both classes
-                         "atomic_floor": ({"ms_per_roofline_pass": sum(classes[n]["atomic_floor_us"] * classes[n]["launches"] for n in classes) * 1e-3,
-                                           "frac_at_floor": hist_bytes_all / max(sum(classes[n]["atomic_floor_us"] * classes[n]["launches"] for n in classes) * 1e-3, 1e-9) * 1e-6 / HBM_PEAK_GBS,
-                                           "cycles_per_wave_atomic": LDS_ATOMIC_CYCLES, "cus": N_CUS, "clock_hz": CLOCK_HZ,
-                                           "note": "frac cannot exceed frac_at_floor with two 64-bit LDS atomics per feature and built row (DESIGN 5, the ceiling)"}
-                                          if all("atomic_floor_us" in classes[n] for n in classes) else None)},
         }
+        if a.full:
+            fixed = int(fixed_shards)
+            for i, t in enumerate(targets if not shard_only else []):
+                pos, truth = null_truth[t]
+                # the dirty table holds the dirty rows in ascending row order: map the nulled cells of t to their dirty-row index
+                idx = np.searchsorted(dirty_pos, pos)
+                fixed += int((labels[i][idx] == truth).sum())
+            achieved = hist_bytes_all / max(hist_ms_all, 1e-9) * 1e-6
+            traffic = _load_traffic(a.config, world, rows, cols, a.train_rows, a.force_row_sharding or a.dedup)
+            # LDS atomics the launches of each class issued, target by target (the joint-bin groups of a root pass depend on the target's feature set)
+            atom_ops = {"root": sum(float(s_.get("root_rows", 0)) * float(s_.get("root_atomics_per_row", 0)) for s_ in res_roof["stats"]),
+                        "level": sum(float(s_.get("hist_rows", 0) - s_.get("root_rows", 0)) * float(s_.get("level_atomics_per_row", 0)) for s_ in res_roof["stats"])}
+            # the two kernel classes of the histogram build, each with its own algorithmic bytes, launch time and (from the committed PMC
+            # profile of the same target set) HBM-side bytes per launch
+            classes = {}
+            n_root_l = max(1, int(round(n_root)))
+            for name, ms, nbytes, nl in (("root", root_ms, root_bytes, n_root_l), ("level", hist_ms_all - root_ms, hist_bytes_all - root_bytes, max(1, int(launches_all) - n_root_l))):
+                c = {"kernel": "rg::k_level_root" if name == "root" else "rg::k_level_mt", "launches": int(nl), "avg_launch_us": ms * 1e3 / nl, "alg_bytes_per_launch": nbytes / nl,
+                     "achieved": nbytes / max(ms, 1e-9) * 1e-6, "frac": nbytes / max(ms, 1e-9) * 1e-6 / HBM_PEAK_GBS}
+                if name == "level":   # what a level pass streams by construction: 1 B node id + 8 B (g, h) of every (row, class tree) of its target
+                    c["stream_bytes_per_launch"] = level_stream_bytes / nl
+                    c["bound"] = "the CU's LDS pipeline: 30 ds_add_u64 per built row + ring traffic (DESIGN 5: with two steps of loads in flight per wave neither the stream nor instruction issue binds); its HBM stream alone would take stream_bytes / ~5 TB/s"
+                    if needed_level_rows:
+                        c["needed_alg_bytes_per_launch"] = needed_level_rows * (cols - 1 + 8) / nl
+                        c["frac_needed"] = needed_level_rows * (cols - 1 + 8) / max(ms, 1e-9) * 1e-6 / HBM_PEAK_GBS
+                else:
+                    c["bound"] = "lds-atomic: 14 ds_add_u64 per row (7 joint-bin groups x (g, h)) at ~12.8 cycles per wave instruction; algorithmic bytes follow SURVEY 8(d) (F + 8 per row), the pass's HBM traffic is about half of them"
+                if atom_ops[name] > 0 and world == 1:     # the LDS-atomic floor of this class: (accumulated rows x atomics per row / 64 lanes) wave instructions at the conflict-free rate
+                    c["atomics_per_row"] = atom_ops[name] / max(nbytes / (cols - 1 + 8), 1e-9)
+                    c["atomic_floor_us"] = atom_ops[name] / nl / 64.0 * LDS_ATOMIC_CYCLES / (N_CUS * CLOCK_HZ) * 1e6
+                    c["atomic_floor_share_of_launch"] = c["atomic_floor_us"] / max(c["avg_launch_us"], 1e-9)
+                if traffic and name in traffic["classes"]:
+                    tc = traffic["classes"][name]
+                    gbps = tc["bytes_per_launch"] / max(ms / nl, 1e-9) * 1e-6
+                    if gbps <= HBM_PEAK_GBS:      # (a figure above the HBM peak means the profile does not describe THIS run: not evidence, not printed)
+                        c["traffic"] = {"fetch_bytes_per_launch": tc["fetch_bytes_per_launch"], "write_bytes_per_launch": tc["write_bytes_per_launch"],
+                                        "ratio_to_algorithmic": tc["bytes_per_launch"] / max(nbytes / nl, 1e-9), "hbm_GBps": gbps}
+                    else:
+                        c["traffic"] = {"dropped": "profiles/traffic.json would put this class at %.0f GB/s, above the HBM peak: the committed counters are not of this run" % gbps}
+                        traffic = None
+                classes[name] = c
+            out["repair_accuracy_vs_clean"] = fixed / max(n_cells, 1)
+            out["roofline"] = {"bound": "hbm",
+                               "kernel": "rg::k_level_root + rg::k_level_mt (histogram build of the level grower; a level pass also routes the rows of its level: DataPartition::Split is not a separate kernel)",
+                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               # the same launches priced at what the finished trees needed (root passes in full + the smaller child of every final split)
+                               "frac_needed": ((root_bytes + needed_level_rows * (cols - 1 + 8)) / max(hist_ms_all, 1e-9) * 1e-6 / HBM_PEAK_GBS) if needed_level_rows else None,
+                               "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_source": traffic["source"] if traffic else None,
+                               "classes": classes,
+                               "measured_on": "sequential pass (one target model at a time) of %d boosting iterations of the same job, %.2f s; HIP events per launch" % (roof_steps, elapsed_roof),
+                               "launches": int(launches_all), "avg_launch_us": hist_ms_all * 1e3 / max(launches_all, 1),
+                               "alg_bytes_per_launch": hist_bytes_all / max(launches_all, 1),
+                               "root_scan_GBps_rank0": root_bytes / max(root_ms, 1e-9) * 1e-6,
+                               # the ceiling of the two-64-bit-atomics-per-feature numerics: the same algorithmic bytes over the LDS-atomic floors of both classes
+                               "atomic_floor": ({"ms_per_roofline_pass": sum(classes[n]["atomic_floor_us"] * classes[n]["launches"] for n in classes) * 1e-3,
+                                                 "frac_at_floor": hist_bytes_all / max(sum(classes[n]["atomic_floor_us"] * classes[n]["launches"] for n in classes) * 1e-3, 1e-9) * 1e-6 / HBM_PEAK_GBS,
+                                                 "cycles_per_wave_atomic": LDS_ATOMIC_CYCLES, "cus": N_CUS, "clock_hz": CLOCK_HZ,
+                                                 "note": "frac cannot exceed frac_at_floor with two 64-bit LDS atomics per feature and built row (DESIGN 5, the ceiling)"}
+                                                if all("atomic_floor_us" in classes[n] for n in classes) else None)}
         if row_sharding_note:
             out["config"]["row_sharding"] = row_sharding_note
         if inp.get("dedup"):
             # a separately named workload: same table, same models (compare models_md5 with the row-for-row line), trained on its distinct rows
             out["config"]["workload"] += "; VARIANT distinct-rows: every model trained on the %d distinct rows of the table with integer multiplicities (rgbm_table_set_row_multiplicity)" % inp["dedup"]["distinct_rows"]
             out["config"]["variant"] = dict(inp["dedup"], name="distinct-rows", note="host dedup (numpy unique of mixed-radix row keys) is outside the timed region, like encoding and upload")
-            # the device counts accumulated rows in ORIGINAL rows (a row of multiplicity m counts m times): algorithmic bytes over launches that touch the
-            # distinct rows only would overstate the rate -- the variant is not priced against the roofline
-            out["roofline"] = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
-                               "note": "not priced for the distinct-rows variant: the kernels count accumulated rows in original rows; see the row-for-row line"}
+            if a.full:
+                # the device counts accumulated rows in ORIGINAL rows (a row of multiplicity m counts m times): algorithmic bytes over launches that touch the
+                # distinct rows only would overstate the rate -- the variant is not priced against the roofline
+                out["roofline"] = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
+                                   "note": "not priced for the distinct-rows variant: the kernels count accumulated rows in original rows; see the row-for-row line"}
         if world > 1:   # what the first multi-rank runs need to show: did RCCL really span the world, how long did it take, did the job fall back
             rc = dict(rdist.ROW_COMM)
             out["config"]["rccl"] = {"asked": rc["asked"], "ranks_seen_by_ncclCommCount": rc["ranks"], "comm_init_sec": round(rc["init_sec"], 3), "fell_back": rc["fell_back"],
@@ -585,7 +623,7 @@ def main():
                                      "fusion": res.get("fusion") or None,
                                      # C1 / C2: which path carried the model blobs and the repaired cells, and what it moved
                                      "gather": dict(rdist.GATHER)}
-        if not a.no_cpu_baseline and world == 1:      # the CPU leg is timed at N = 1 only (the other ranks would sit in the barrier below)
+        if a.full and not a.no_cpu_baseline and world == 1:      # the CPU leg is timed at N = 1 only (the other ranks would sit in the barrier below)
             out["cpu_baseline"] = cpu_baseline(cols, cfg["seed"], targets, REF_N_ESTIMATORS, full_rows=rows if not (0 < a.train_rows < rows) else 0, cells_full=n_cells)
             out["cpu_baseline"]["true_reference"] = true_reference_baseline(cols, cfg["seed"], targets, REF_N_ESTIMATORS)
             fst = out["cpu_baseline"].get("full_size_target")
