@@ -247,6 +247,27 @@ int rgbm_table_repair_pmf(rgbm_table* t, const rgbm_model* m, int32_t target_col
                           int32_t top_k, double threshold, const int32_t* cur_code, int64_t cap, int64_t* n_cells_out,
                           int64_t* rows_out /* [cap] */, int32_t* class_out /* [cap][top_k] */,
                           double* prob_out /* [cap][top_k] */, double* cur_prob_out /* [cap] or NULL */);
+/* The same with the update costs of the probability modes (python/repair/model.py `_compute_repair_pmf` / `_compute_score`;
+ * reference model.py:1145-1165 `_compute_weighted_probs`, 1167-1212, 1223-1277).  Per NULL cell, in the order of the Python loop:
+ *   p_c = p_c * (1.0 / (1.0 + weight * cost[cost_row[cell]][c]))  for cost_row[cell] >= 0 and a cost that is not NaN (NaN = None);
+ *   renormalise != 0: p_c = p_c / norm when norm = p_0 + p_1 + ... (sequential, in class order) > 0;
+ *   cur_prob_out = p[cur_code] (0.0 when cur_code is -1 / not a class), then the stable top-k of rgbm_table_repair_pmf;
+ *   top1_cost_out = cost[base][top-1 class], base = cost_row[cell] when >= 0 else the self row n_cost_rows; NaN without a top-1.
+ * cost: [n_cost_rows + 1][K] row-major (K = the model's classes; the last row holds the cost of each class against itself), at most
+ * 2^28 entries; NULL = no costs (cost_row must then be NULL too).  cost_row: per cell, -1 = leave the cell's probabilities alone.
+ * With cost = NULL and renormalise = 0 the outputs are those of rgbm_table_repair_pmf, bit for bit. */
+int rgbm_table_repair_pmf_weighted(rgbm_table* t, const rgbm_model* m, int32_t target_col, const int32_t* feat_cols, int32_t f,
+                                   int32_t top_k, double threshold, const int32_t* cur_code /* [cells] or NULL */,
+                                   const int32_t* cost_row /* [cells] or NULL */, const double* cost /* [n_cost_rows + 1][K] or NULL */,
+                                   int64_t n_cost_rows, double weight, int32_t renormalise, int64_t cap, int64_t* n_cells_out,
+                                   int64_t* rows_out /* [cap] */, int32_t* class_out /* [cap][top_k] */, double* prob_out /* [cap][top_k] */,
+                                   double* cur_prob_out /* [cap] or NULL */, double* top1_cost_out /* [cap] or NULL */);
+/* Levenshtein distances (insert / delete / substitute, unit costs) of every pair of two string pools: the `Levenshtein` update
+ * cost (python/repair/costs.py; reference costs.py:50-58, used by model.py:1145-1165 and 1223-1240).  Strings are int32 Unicode
+ * code points, string i of a pool is cp[off[i] .. off[i + 1]) (off[0] = 0, non-decreasing, n + 1 entries).
+ * dist_out: [n_a][n_b] row-major, host memory.  Strings of any length; both pools are copied to device `device_id`. */
+int rgbm_edit_distance(int32_t device_id, const int32_t* a_cp, const int64_t* a_off, int64_t n_a, const int32_t* b_cp,
+                       const int64_t* b_off, int64_t n_b, int32_t* dist_out);
 int rgbm_table_shape(const rgbm_table* t, int64_t* n_out, int32_t* c_out, int32_t* n_codes_out /* [c] or NULL */);
 
 /* ---- row-sharded multi-GPU training ------------------------------------------------------------

@@ -83,7 +83,8 @@ def lib():
                      "rgbm_local_group_create", "rgbm_comm_init_local",
                      "rgbm_table_detect_nulls", "rgbm_table_detect_constraint", "rgbm_table_rows_of_cells", "rgbm_table_cells_fetch",
                      "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict",
-                     "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells"):
+                     "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
+                     "rgbm_edit_distance"):
             getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -105,6 +106,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict", "rgbm_table_shape",
     "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_write_cells", "rgbm_host_alloc", "rgbm_host_free",
     "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
+    "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance",
 ]
 
 COMM_ID_BYTES = 128
@@ -474,6 +476,28 @@ def pinned_empty(shape, dtype=np.int32):
     return np.asarray(_PinnedBlock(max(n, 1)))[:n].view(dtype).reshape(shape)
 
 
+def pack_code_points(strings):
+    """Python strings -> (int32 Unicode code points, int64 offsets [len + 1]): the string pools of rgbm_edit_distance.  Code points,
+    not UTF-8 bytes: Python's str indexes code points, so the distances are those of repair.costs.edit_distance."""
+    strings = [str(s) for s in strings]
+    off = np.zeros(len(strings) + 1, np.int64)
+    if strings:
+        np.cumsum([len(s) for s in strings], out=off[1:])
+    cp = np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype="<u4").astype(np.int32)
+    return cp, off
+
+
+def edit_distance(a, b, device_id=0):
+    """Levenshtein distance of every pair of two lists of strings on the device: int32 [len(a)][len(b)] (include/rgbm.h)."""
+    a_cp, a_off = pack_code_points(a)
+    b_cp, b_off = pack_code_points(b)
+    out = np.zeros((len(a_off) - 1, len(b_off) - 1), np.int32)
+    _check(lib().rgbm_edit_distance(C.c_int32(device_id), _p(a_cp, C.c_int32), _p(a_off, C.c_int64), C.c_int64(len(a_off) - 1),
+                                    _p(b_cp, C.c_int32), _p(b_off, C.c_int64), C.c_int64(len(b_off) - 1), _p(out, C.c_int32)),
+           "rgbm_edit_distance")
+    return out
+
+
 class Table:
     """An int32 code table resident in HBM (``rgbm_table``)."""
 
@@ -598,6 +622,35 @@ class Table:
                                            _p(cls, C.c_int32), _p(pr, C.c_double), _p(cp, C.c_double)), "rgbm_table_repair_pmf")
         assert int(n.value) == n_null
         return (rows, cls, pr, cp) if cp is not None else (rows, cls, pr)
+
+    def repair_pmf_weighted(self, model, target_col, feat_cols, top_k=32, threshold=0.0, cur_codes=None, cost_rows=None, cost=None,
+                            weight=0.0, renormalise=False):
+        """`repair_pmf` with the update costs of the probability modes (model.py `_compute_repair_pmf`; include/rgbm.h
+        rgbm_table_repair_pmf_weighted).  ``cost`` [R + 1][K] float64 (NaN = no cost; the last row: each class against itself),
+        ``cost_rows`` [m] int32 per NULL cell (-1 = leave the cell alone).  Returns (rows, classes, probs, cur_prob, top1_cost)."""
+        fc = _i32(feat_cols)
+        _, n_null = self.count_codes(target_col)
+        cur, crow = _i32(cur_codes), _i32(cost_rows)
+        for name, a in (("cur_codes", cur), ("cost_rows", crow)):
+            if a is not None and len(a) != n_null:
+                raise ValueError("%s must hold one entry per NULL cell of the target (%d)" % (name, n_null))
+        cst = None if cost is None else np.ascontiguousarray(np.atleast_2d(cost), np.float64)
+        if crow is not None and cst is None:
+            raise ValueError("cost_rows without a cost matrix")
+        n_cost_rows = 0 if cst is None else cst.shape[0] - 1
+        rows = np.zeros(n_null, np.int64)
+        cls = np.zeros((n_null, top_k), np.int32)
+        pr = np.zeros((n_null, top_k), np.float64)
+        cp = np.zeros(n_null, np.float64)
+        tc = np.full(n_null, np.nan, np.float64)
+        n = C.c_int64(0)
+        _check(lib().rgbm_table_repair_pmf_weighted(self.h, model.h, C.c_int32(target_col), _p(fc, C.c_int32), C.c_int32(len(fc)), C.c_int32(top_k),
+                                                    C.c_double(threshold), _p(cur, C.c_int32), _p(crow, C.c_int32), _p(cst, C.c_double),
+                                                    C.c_int64(n_cost_rows), C.c_double(weight), C.c_int32(1 if renormalise else 0), C.c_int64(n_null),
+                                                    C.byref(n), _p(rows, C.c_int64), _p(cls, C.c_int32), _p(pr, C.c_double), _p(cp, C.c_double),
+                                                    _p(tc, C.c_double)), "rgbm_table_repair_pmf_weighted")
+        assert int(n.value) == n_null
+        return rows, cls, pr, cp, tc
 
     def count_codes(self, col):
         """(rows per code [n_codes[col]], NULL rows) of one column."""

@@ -79,6 +79,10 @@ class HipEngine:
     def repair_chain(self, table, models, targets, feats, row_begin, n_rows):
         return table.repair_chain(models, targets, feats, row_begin=row_begin, n_rows=n_rows)
 
+    def edit_distance(self, a, b):
+        """Levenshtein distances [len(a)][len(b)] (int32) of two lists of strings (rgbm_edit_distance): the `Levenshtein` update cost."""
+        return _native.edit_distance(a, b, device_id=self.device_id)
+
     def repair_chain_gather(self, table, models, targets, feats, row_begin, n_rows):
         """C2 on device buffers: the chain over this rank's rows, labels / probabilities all-gathered over the rank's communicator before
         they leave the device (include/rgbm.h rgbm_table_repair_chain_gather) -> (labels, probs of ALL ranks' rows in rank order, first row of this rank)."""

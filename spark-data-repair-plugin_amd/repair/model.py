@@ -95,13 +95,15 @@ class RepairModel():
     _opt_cost_weight = _option("repair.pmf.cost_weight", 0.1, float, lambda v: v > 0.0, "`{}` should be positive")
     _opt_prob_threshold = _option("repair.pmf.prob_threshold", 0.0, float, None, None)
     _opt_prob_top_k = _option("repair.pmf.prob_top_k", 32, int, lambda v: v >= 3, "`{}` should be greater than 2")
+    # new in this engine: the probability modes (pmf / prob / score / maximal likelihood) on the HBM-resident pipeline
+    _opt_pmf_resident = _option("repair.pmf.resident", False, bool, None, None)
     # new in this engine: which HIP device trains/predicts (read by repair.train.fixed_params)
     _opt_gpu_device_id = _train_opt_gpu_device_id
 
     option_keys = set([o.key for o in (
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
-        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_gpu_device_id)] +
+        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -572,15 +574,16 @@ class RepairModel():
             return None
 
     def _resident_plan(self, input_df: DataFrame, target_columns: List[str], continous_columns: List[str], domain_stats: Dict[str, int],
-                       compute_repair_candidate_prob: bool, maximal_likelihood_repair: bool) -> Optional[Dict[str, Any]]:
+                       compute_repair_candidate_prob: bool, maximal_likelihood_repair: bool, prob_modes: bool = False) -> Optional[Dict[str, Any]]:
         """Decides whether this run can take the HBM-resident pipeline (repair.pipeline) and with which parameters.
+        `prob_modes`: the caller shapes the probability modes itself (`_run_resident_prob`), so they and a cost function qualify.
 
         It can when everything between error detection and the result frame is the per-attribute model loop itself:
         no rule-based repairs, no functional-dependency rule models, no rebalancing, no cost function, plain repair output
         (cells or repaired data), no feature selection, and every discrete target has at least two classes.  The
         hyper-parameter search (`model.hp.max_evals` > 1) runs on the resident tables too (pipeline.search_on_table).
         Otherwise the value-space path (pandas + one estimator per attribute) below handles the run."""
-        if compute_repair_candidate_prob or maximal_likelihood_repair or self.repair_by_rules or self.cf is not None:
+        if self.repair_by_rules or (not prob_modes and (compute_repair_candidate_prob or maximal_likelihood_repair or self.cf is not None)):
             return None
         if self.training_data_rebalancing_enabled:
             return None
@@ -749,6 +752,147 @@ class RepairModel():
         keep = cand["repaired"].isna() | ~((cand["current_value"] == cand["repaired"]) | (cand["current_value"].isna() & cand["repaired"].isna()))
         return cand[keep.to_numpy()].reset_index(drop=True)
 
+    def _cost_spec(self, engine: Any, attr: str, classes: Any, cur: List[Any], ml: bool) -> Dict[str, Any]:
+        """The update costs of one target's cells as `repair.pipeline.repair_table(pmf_costs=...)` takes them, from the values
+        `_compute_repair_pmf` / `_compute_score` see: the error cells' current values and `_to_str` of the classes.  One cost row per
+        distinct current value plus the self row (each class against itself: the score's base when a cell has no current value);
+        None costs are NaN.  Raises NotResidentEligible where the Python expressions would not be reproduced (a division by zero, a
+        NaN cost, a matrix over 2^28 entries)."""
+        from repair.costs import Levenshtein
+        from repair.pipeline import NotResidentEligible
+        cls = [_to_str(c) for c in classes]
+        code = {c: i for i, c in enumerate(cls)}
+        cur_code = np.array([code.get(v, -1) if v is not None else -1 for v in cur], np.int32)
+        cf = self.cf
+        if cf is None:
+            return dict(cost=None, cur_code=cur_code, weight=0.0, renormalise=False)
+        weight = float(self._get_option_value(*self._opt_cost_weight))
+        if cf.targets and attr not in cf.targets:        # no re-weighting, but the renormalisation runs for every attribute
+            return dict(cost=None, cur_code=cur_code, weight=weight, renormalise=True)
+        vals = list(dict.fromkeys(v for v in cur if v is not None))
+        K = len(cls)
+        if (len(vals) + 1) * K > (1 << 28):
+            raise NotResidentEligible("attribute `%s`: the cost matrix would hold %d x %d entries" % (attr, len(vals) + 1, K))
+        cost = np.full((len(vals) + 1, K), np.nan, np.float64)
+        if type(cf) is Levenshtein:
+            # compute() is None for a falsy side: those rows / columns stay NaN
+            rv = [i for i, v in enumerate(vals) if v]
+            kc = [j for j, c in enumerate(cls) if c]
+            if rv and kc:
+                d = engine.edit_distance([str(vals[i]) for i in rv], [cls[j] for j in kc]).astype(np.float64)
+                cost[np.ix_(rv, kc)] = d
+            cost[len(vals), kc] = 0.0
+        else:
+            nan_seen = False
+            for i, v in enumerate(list(vals) + [None]):
+                for j, c in enumerate(cls):
+                    x = cf.compute(v if v is not None else c, c)
+                    if x is not None:
+                        cost[i, j] = float(x)
+                        nan_seen = nan_seen or np.isnan(cost[i, j])
+            if nan_seen:
+                raise NotResidentEligible("attribute `%s`: the cost function returned NaN" % attr)
+        # a falsy current value is never weighed (`if cur`) but is the score's base: its costs must all be None, as compute() gives them
+        if any(not v and not np.isnan(cost[i]).all() for i, v in enumerate(vals)):
+            raise NotResidentEligible("attribute `%s`: the cost function has costs for an empty current value" % attr)
+        body = cost[:len(vals)]
+        with np.errstate(invalid="ignore"):
+            if bool(((1.0 + weight * body) == 0.0).any()) or (ml and bool(((1.0 + cost) == 0.0).any())):
+                raise NotResidentEligible("attribute `%s`: a cost makes a weight 1 / 0" % attr)
+        row_of = {v: i for i, v in enumerate(vals)}
+        cost_row = np.array([row_of[v] if v is not None else -1 for v in cur], np.int32)
+        return dict(cost=cost, cost_row=cost_row, cur_code=cur_code, weight=weight, renormalise=True)
+
+    def _run_resident_prob(self, plan: Dict[str, Any], input_df: DataFrame, error_cells_df: DataFrame, target_columns: List[str],
+                           continous_columns: List[str], compute_repair_candidate_prob: bool, compute_repair_prob: bool,
+                           compute_repair_score: bool, repair_data: bool, maximal_likelihood_repair: bool) -> DataFrame:
+        """Steps 2 and 3 of `_run` for the probability modes (option `repair.pmf.resident`): the models, the candidate
+        distributions, the update-cost re-weighting and the score inputs come from the resident pipeline (rgbm_table_repair_pmf_weighted,
+        rgbm_edit_distance); the host shapes the frames of the value-space branch below (`_compute_repair_pmf`, `_compute_score`,
+        `_maximal_likelihood_repair`), the score's log and percentile vectorised."""
+        import time
+        from repair.pipeline import repair_frame
+        rid = self._row_id
+        max_rows = int(self._get_option_value(*self._opt_max_training_row_num))
+        thres = float(self._get_option_value(*self._opt_prob_threshold))
+        top_k = int(self._get_option_value(*self._opt_prob_top_k))
+        engine = plan["engine"]
+        ml = maximal_likelihood_repair
+
+        def sample(_attr: str, rows: np.ndarray) -> Optional[np.ndarray]:
+            if len(rows) <= max_rows:
+                return None
+            _logger.info("To reduce training data, extracts %s%% samples from %d rows" % (100.0 * max_rows / len(rows), len(rows)))
+            return rows[np.random.RandomState(42).choice(len(rows), max_rows, replace=False)]
+
+        # the error cells' current values by attribute and row position (what `_compute_repair_pmf` reads from `error_cells_df`)
+        rpos = pd.Series(np.arange(len(input_df)), index=input_df[rid].to_numpy()).reindex(error_cells_df[rid].to_numpy()).to_numpy(np.int64)
+        curv = error_cells_df["current_value"].to_numpy(dtype=object)
+        by_attr = {}
+        for a, idx in error_cells_df.groupby("attribute").indices.items():
+            o = np.argsort(rpos[idx], kind="stable")
+            by_attr[a] = (rpos[idx][o], curv[idx][o])
+
+        def costs(attr: str, classes: Any, rows: np.ndarray) -> Dict[str, Any]:
+            pos, cur = by_attr[attr]
+            return self._cost_spec(engine, attr, classes, list(cur[np.searchsorted(pos, rows)]), ml)
+
+        _logger.info("[Repair Model Training Phase] Building %d models on the HBM-resident table to compute the repair distributions of %s" % (
+            len(target_columns), to_list_str(target_columns)))
+        t0 = time.perf_counter()
+        frame, info = repair_frame(engine, input_df, rid, targets=target_columns, base_params=plan["params"],
+                                   error_cells=error_cells_df[[rid, "attribute"]], detect_nulls=False,
+                                   continuous_columns=[c for c in continous_columns if c in target_columns], train_rows=sample,
+                                   want_details=True, search_opts=dict(self.opts) if plan.get("search") else None,
+                                   want_pmf=True, top_k=top_k, threshold=thres, pmf_costs=costs)
+        info["times"]["pipeline_wall"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        self._last_resident_info = info
+        key = pd.MultiIndex.from_arrays([frame[rid].to_numpy(), frame["attribute"].to_numpy()])
+        at = key.get_indexer(pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()]))
+        assert (at >= 0).all()
+        pmf_l = frame["pmf"].to_numpy(dtype=object)[at]
+        cp = frame["current_prob"].to_numpy(np.float64)[at]
+        tc = frame["top1_cost"].to_numpy(np.float64)[at]
+        pval = frame["pmf_value"].to_numpy(dtype=object)[at]
+        cont = set(continous_columns)
+        rows = []
+        for i, r in enumerate(error_cells_df.itertuples(index=False)):
+            rowid, attr, cur = r[0], r[1], r[2]
+            if attr in cont:
+                v = pval[i]
+                rows.append((rowid, attr, {"value": cur, "prob": 0.0}, [{"class": None if v is None else _to_str(v), "prob": 1.0}]))
+            else:
+                rows.append((rowid, attr, {"value": cur, "prob": float(cp[i])}, [{"class": _to_str(d["class"]), "prob": d["prob"]} for d in pmf_l[i]]))
+        pmf_df = pd.DataFrame(rows, columns=[rid, "attribute", "current_value", "pmf"])
+        try:
+            if compute_repair_candidate_prob and not maximal_likelihood_repair:
+                pmf_df = pmf_df.assign(current_value=[c["value"] for c in pmf_df["current_value"]])
+                if compute_repair_prob:
+                    return pd.DataFrame({rid: pmf_df[rid], "attribute": pmf_df["attribute"], "current_value": pmf_df["current_value"],
+                                         "repaired": [p[0]["class"] if p else None for p in pmf_df["pmf"]],
+                                         "prob": [p[0]["prob"] if p else None for p in pmf_df["pmf"]]})
+                return pmf_df
+            # _compute_score, vectorised: log(p_top1 / max(p_cur, 1e-6)) / (1 + cost(base, top-1)), None cost = 256
+            top_p = np.array([p[0]["prob"] if p else 0.0 for p in pmf_l], np.float64)
+            p_cur = np.where(cp > 0.0, cp, 1e-6)
+            cost = np.where(np.isnan(tc), 256.0, tc)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                score = np.where(top_p > 0, np.log(top_p / p_cur) * (1.0 / (1.0 + cost)), -np.inf)
+            score_df = pd.DataFrame([(r[0], r[1], r[2]["value"], r[3][0]["class"] if r[3] else None, float(sc))
+                                     for r, sc in zip(rows, score)], columns=[rid, "attribute", "current_value", "repaired", "score"])
+            if compute_repair_score:
+                return score_df
+            top = self._maximal_likelihood_repair(score_df, error_cells_df)
+            if not repair_data:
+                return top
+            base = self._prepare_repair_base_cells(input_df, error_cells_df, target_columns)
+            is_dirty = base[rid].isin(set(error_cells_df[rid].tolist())).to_numpy()
+            dirty = self._repair_attrs(top, base[is_dirty].reset_index(drop=True))
+            return pd.concat([base[~is_dirty], dirty], ignore_index=True)
+        finally:
+            info["times"]["host_shape"] = time.perf_counter() - t0
+
     # ------------------------------------------------------------------ pipeline
     @elapsed_time  # type: ignore
     def _run(self, input_df: DataFrame, continous_columns: List[str], detect_errors_only: bool,
@@ -779,10 +923,20 @@ class RepairModel():
             raise ValueError("At least one valid discretizable feature is needed to repair error cells, but no such feature found")
         error_cells_df = error_cells_df[error_cells_df["attribute"].isin(target_columns)].reset_index(drop=True)
 
-        # 2. + 3. on the HBM-resident table when the run is the plain per-attribute model loop (the hot path of this engine)
+        # 2. + 3. on the HBM-resident table when the run is the plain per-attribute model loop (the hot path of this engine), or one of
+        # the probability modes with `repair.pmf.resident` set
+        prob_modes = (compute_repair_candidate_prob or maximal_likelihood_repair) and bool(self._get_option_value(*self._opt_pmf_resident))
         plan = self._resident_plan(input_df, target_columns, continous_columns, domain_stats, compute_repair_candidate_prob,
-                                   maximal_likelihood_repair)
-        if plan is not None:
+                                   maximal_likelihood_repair, prob_modes=prob_modes)
+        if plan is not None and prob_modes:
+            from repair.pipeline import NotResidentEligible
+            try:
+                return self._run_resident_prob(plan, input_df, error_cells_df, target_columns, continous_columns, compute_repair_candidate_prob,
+                                               compute_repair_prob, compute_repair_score, repair_data, maximal_likelihood_repair)
+            except NotResidentEligible as e:
+                self._last_resident_info = None
+                _logger.info("resident path not taken: %s" % e)
+        elif plan is not None:
             from repair.pipeline import NotResidentEligible
             try:
                 return self._run_resident(plan, input_df, error_cells_df, target_columns, continous_columns, repair_data)

@@ -220,7 +220,7 @@ def unseen_categories(table, dirty_tab, targets, ordered_cols=(), train_tables=N
 
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
@@ -236,8 +236,14 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     train_rows : {target: row positions} or a callable (target, positions of its non-NULL rows) -> positions -- train that
                  target's model on these rows only (model.max_training_row_num sampling, model.py:755-766); default: every row
                  whose target cell is not NULL.
-    Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob], dirty_rows, models,
-    times, stats): one entry per error cell, ordered by (column, row).
+    pmf_costs  : (want_pmf) the probability modes of RepairModel.run(): a callable (target, ascending row positions of its error cells)
+                 -> dict(cost [R + 1][K] float64 or None, cost_row [cells] int32 (-1 = no cost), cur_code [cells] int32 (the current
+                 value's class, -1 = none), weight, renormalise) or None, handed to `Table.repair_pmf_weighted`; adds `top1_cost` and
+                 `pmf_value`.  With it the pmf table is chained as the value-space `_repair` chains it (model.py): in target order, a
+                 continuous target's prediction fills its NULL cells before the later targets are scored (`pmf_value` holds it),
+                 discrete targets stay NULL.
+    Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
+    dirty_rows, models, times, stats): one entry per error cell, ordered by (column, row).
     """
     continuous = dict(continuous or {})
     t0 = time.perf_counter()
@@ -314,20 +320,45 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         pc = np.full((len(rows), top_k), -1, np.int32)
         pp = np.zeros((len(rows), top_k), np.float64)
         cp = np.zeros(len(rows), np.float64)
+        tc = np.full(len(rows), np.nan, np.float64)
+        pv = np.full(len(rows), np.nan, np.float64)
         for t in targets:
             sel = np.flatnonzero(cols == t)
-            if len(sel) == 0 or t in continuous:       # continuous attributes have no pmf (model.py:1215-1222: the value with prob 1.0)
-                continue
             feats = [c for c in range(table.c) if c != t]
+            if t in continuous:       # continuous attributes have no pmf (model.py:1215-1222: the value with prob 1.0)
+                if pmf_costs is not None and t in res["models"]:
+                    from repair.engine import chained_repair
+                    _, _, v = chained_repair(engine, pmf_tab, [engine.load_model(res["models"][t])], [t], [feats], 0, pmf_tab.n, y_values, integral)
+                    pv[sel] = v[0][np.searchsorted(dirty_rows, rows[sel])]
+                continue
+            if len(sel) == 0:
+                continue
             model = engine.load_model(res["models"][t])
             # NULL cells of t in the dirty frame: a superset of this target's error cells when NULL detection is off
             drows, _ = pmf_tab.detect_nulls([t])
             j = np.searchsorted(dirty_rows[drows], rows[sel])
             cur_for = np.full(len(drows), -1, np.int32)
             cur_for[j] = current[sel]                          # the value the cell held (model.py:1196-1199: its probability)
-            _, dcls, dpr, dcp = pmf_tab.repair_pmf(model, t, feats, top_k=top_k, threshold=threshold, cur_codes=cur_for)
+            spec = pmf_costs(t, rows[sel]) if pmf_costs is not None else None
+            if pmf_costs is None:
+                _, dcls, dpr, dcp = pmf_tab.repair_pmf(model, t, feats, top_k=top_k, threshold=threshold, cur_codes=cur_for)
+            else:
+                spec = dict(spec or {})
+                if spec.get("cur_code") is not None:
+                    cur_for[j] = spec["cur_code"]
+                crow = None
+                if spec.get("cost") is not None:
+                    crow = np.full(len(drows), -1, np.int32)
+                    if spec.get("cost_row") is not None:
+                        crow[j] = spec["cost_row"]
+                _, dcls, dpr, dcp, dtc = pmf_tab.repair_pmf_weighted(model, t, feats, top_k=top_k, threshold=threshold, cur_codes=cur_for,
+                                                                     cost_rows=crow, cost=spec.get("cost"), weight=float(spec.get("weight", 0.0)),
+                                                                     renormalise=bool(spec.get("renormalise", False)))
+                tc[sel] = dtc[j]
             pc[sel], pp[sel], cp[sel] = dcls[j], dpr[j], dcp[j]
         out.update(pmf_class=pc, pmf_prob=pp, current_prob=cp)
+        if pmf_costs is not None:
+            out.update(top1_cost=tc, pmf_value=pv)
     t_shape = time.perf_counter() - t0
     times = dict(res["times"])
     times.update(detect=t_detect, prepare=t_prep, shape=t_shape)
@@ -367,15 +398,20 @@ def encode_frame(df, columns):
 
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
     Columns are discrete (one class per distinct value) unless named in `continuous_columns` (numeric columns; those targets
     get regressors and `repaired` is the predicted number, rounded for integer columns); `constraints` are `X1,..,Xm -> Y`
     dependencies given as ([x names], y name); `error_cells` is a frame with `row_id` and `attribute` columns
-    (RepairModel.setErrorCells).  Regex / outlier detectors, rule-based repairs and cost functions stay with
-    `repair.model.RepairModel` (the value-space API)."""
+    (RepairModel.setErrorCells).  Regex / outlier detectors and rule-based repairs stay with `repair.model.RepairModel` (the
+    value-space API).
+
+    pmf_costs (with want_pmf): the update costs of RepairModel.run()'s probability modes, a callable (attribute, its classes (the
+    target's dictionary, ascending), ascending row positions of its error cells) -> the dict `repair_table` describes, or None.  The
+    frame then also holds `top1_cost` (cost of the top-1 class against the current value) and `pmf_value` (continuous targets: the
+    prediction of the un-repaired pmf chain)."""
     import pandas as pd
     cols = [c for c in df.columns if c != row_id]
     targets = list(targets) if targets is not None else list(cols)
@@ -444,6 +480,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                 cont_[pos[c]] = (np.asarray(dicts[pos[c]], np.float64), pd.api.types.is_integer_dtype(df[c]))
         return cont_, repair_table(engine, table, [pos[t] for t in targets], dict(base_params or {}), constraints=cons, detect_nulls=detect_nulls_,
                                    error_cells=cells_, want_pmf=want_pmf, top_k=top_k, threshold=threshold, continuous=cont_, search_opts=search_opts,
+                                   pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
                                    only_noisy_targets=only_noisy_targets,
                                    check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
                                    train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
@@ -504,6 +541,15 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             pmf.append([{"class": d[k], "prob": float(p)} for k, p in zip(pc[i], pp[i]) if k >= 0])
         frame["pmf"] = pmf
         frame["current_prob"] = res["current_prob"]
+        if pmf_costs is not None:
+            frame["top1_cost"] = res["top1_cost"]
+            pval = np.empty(len(rows), object)
+            pval[:] = None
+            for j, (_, is_int) in cont.items():
+                sel = np.flatnonzero(ccols == j)
+                v = res["pmf_value"][sel]
+                pval[sel] = [None if np.isnan(x) else (int(x) if is_int else float(x)) for x in v]
+            frame["pmf_value"] = pval
     if want_details:
         return frame, dict(times=res.get("times", {}), stats=res.get("stats", []), models=res.get("models", {}), columns=cols)
     return frame
