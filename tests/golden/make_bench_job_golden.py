@@ -12,10 +12,19 @@ compares every iteration; tools/job_determinism.py repeats that across processes
     python tests/golden/make_bench_job_golden.py [--iters 60] [--threads 8] [--targets 10,0]
 
 Takes about an hour of host time for the K = 64 target on 8 cores (64 class trees x 10M rows per iteration).  Needs no reference files.
+
+The other files of tests/golden/bench_*_digests.json come from the same script (tests/bench_golden_expect.py lists what each must hold;
+an existing file's other targets are kept when table, --iters and the numerics version match):
+    bench_shard_digests.json      --rows 12500000 --cols 32 --seed 43 --targets 0,7 --iters 30 --out bench_shard_digests.json
+    bench_whole_digests.json      --rows 100000000 --cols 32 --seed 43 --parallel --targets 0,1 --iters 5 --out bench_whole_digests.json
+    bench_big_index_digests.json  --rows 35000000 --cols 32 --seed 43 --targets 10 --iters 2 --out bench_big_index_digests.json
+                                  (K x n_train = 2.22e9 > 2^31; the oracle holds 24 bytes per (row, class): 60 GB of peak memory)
+Every entry records the host time, the thread count and the peak resident memory of the run that made it.
 """
 import argparse
 import json
 import os
+import resource
 import sys
 import time
 
@@ -76,7 +85,8 @@ def main():
         blob = O.train(X, cards[feats], dirty[t][rows], K, class_weight=cw, **kw).save()
         del X
         doc["targets"]["c%d" % t] = {"K": K, "train_rows": int(rows.sum()), "digests": iteration_digests(blob),
-                                      "oracle_seconds": round(time.time() - t0, 1), "threads": a.threads}
+                                      "oracle_seconds": round(time.time() - t0, 1), "threads": a.threads,
+                                      "peak_rss_gb": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2.0 ** 20, 1)}   # (of the process so far: table + oracle state)
         with open(OUT_, "w") as f:
             json.dump(doc, f, indent=1)
         print("c%d (K=%d): %d iterations in %.0f s" % (t, K, n_it, time.time() - t0), flush=True)

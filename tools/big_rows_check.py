@@ -1,6 +1,10 @@
 """One-off check of the 64-bit row arithmetic: train on >= 2^26 rows (more than 2^22 rows per workgroup, several carry-word
 ranges, node-id buffers beyond 4 GB for K = 12) and compare the model bytes with the CPU oracle.
-    python tools/big_rows_check.py [--rows 100000000]"""
+    python tools/big_rows_check.py [--rows 100000000]
+What it was written for is now in the suite (tests/test_gpu_bench_shapes.py, -m gpu, against committed oracle digests): 100M-row trees in
+test_config3_whole_table_100m_x_32_matches_the_oracle_digests (K <= 3) and per-(row, class) indices beyond 2^31 ELEMENTS in
+test_two_chunk_k64_35m_x_32_indexes_beyond_2_to_31_elements (K x n_train = 2.22e9; this script reaches 1.2e9, on one feature chunk).
+Kept as a probe for other row counts; the suite does not run K = 12 on 100M rows."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
