@@ -475,7 +475,11 @@ class RepairModel():
                     costs = [self.cf.compute(cur, c) for c in cls] if cur else None
                     if costs is not None:
                         pr = [p * (1.0 / (1.0 + weight * c)) if c is not None else p for p, c in zip(pr, costs)]
-                norm = sum(pr)
+                # the reference's `aggregate(probs, 0.0, (acc, x) -> acc + x)` (model.py:1158): a plain left-to-right double sum.
+                # Not `sum()`: from Python 3.12 on it is a compensated sum and rounds differently.
+                norm = 0.0
+                for p in pr:
+                    norm = norm + p
                 pr = [p / norm for p in pr] if norm > 0 else pr
             cur_prob = pr[cls.index(cur)] if cur in cls else 0.0
             order = sorted(range(len(cls)), key=lambda j: -pr[j])   # stable: ties keep class order

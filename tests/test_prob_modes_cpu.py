@@ -18,30 +18,55 @@ from tests.helpers import OracleEngine, frame, load_golden
 from tests.synth import make_table
 
 
-def _weighted_pmf(proba, top_k, threshold, cur_codes, cost_rows, cost, weight, renormalise):
-    """Per cell, the loop of RepairModel._compute_repair_pmf / _compute_score on class indices (the contract of
-    rgbm_table_repair_pmf_weighted, include/rgbm.h)."""
-    m, K = proba.shape
-    cls = np.full((m, top_k), -1, np.int32)
-    pr = np.zeros((m, top_k), np.float64)
-    cp = np.zeros(m, np.float64)
-    tc = np.full(m, np.nan, np.float64)
-    for i in range(m):
+def _seq_sum(xs):
+    """The reference's `aggregate(probs, 0.0, (acc, x) -> acc + x)`: a plain left-to-right double sum.  Not `sum()`, which is a
+    compensated sum from Python 3.12 on."""
+    acc = 0.0
+    for x in xs:
+        acc = acc + x
+    return acc
+
+
+def _weighted_probs(proba, cost_rows, cost, weight, renormalise):
+    """Per cell, the re-weighting and renormalisation of RepairModel._compute_repair_pmf on class indices: [m][K] float64."""
+    out = np.empty(np.shape(proba), np.float64)
+    for i in range(len(out)):
         p = [float(x) for x in proba[i]]
         row = int(cost_rows[i]) if cost is not None and cost_rows is not None else -1
         if row >= 0:
             p = [x * (1.0 / (1.0 + weight * c)) if not math.isnan(c) else x for x, c in zip(p, cost[row])]
         if renormalise:
-            norm = sum(p)
+            norm = _seq_sum(p)
             p = [x / norm for x in p] if norm > 0 else p
+        out[i] = p
+    return out
+
+
+def _select(p, top_k, threshold, cur_codes, cost_rows, cost):
+    """The stable top-k, the current value's probability and the top-1's cost of final probabilities `p` [m][K]."""
+    m, K = p.shape
+    cls = np.full((m, top_k), -1, np.int32)
+    pr = np.zeros((m, top_k), np.float64)
+    cp = np.zeros(m, np.float64)
+    tc = np.full(m, np.nan, np.float64)
+    for i in range(m):
+        q = p[i].tolist()
+        row = int(cost_rows[i]) if cost is not None and cost_rows is not None else -1
         cc = int(cur_codes[i]) if cur_codes is not None else -1
-        cp[i] = p[cc] if 0 <= cc < K else 0.0
-        order = [j for j in sorted(range(K), key=lambda j: -p[j]) if p[j] > threshold][:top_k]
+        cp[i] = q[cc] if 0 <= cc < K else 0.0
+        order = [j for j in sorted(range(K), key=lambda j: -q[j]) if q[j] > threshold][:top_k]
         for k, j in enumerate(order):
-            cls[i, k], pr[i, k] = j, p[j]
+            cls[i, k], pr[i, k] = j, q[j]
         if cost is not None and order:
             tc[i] = cost[row if row >= 0 else len(cost) - 1][order[0]]
     return cls, pr, cp, tc
+
+
+def _weighted_pmf(proba, top_k, threshold, cur_codes, cost_rows, cost, weight, renormalise):
+    """Per cell, the loop of RepairModel._compute_repair_pmf / _compute_score on class indices (the contract of
+    rgbm_table_repair_pmf_weighted, include/rgbm.h)."""
+    return _select(_weighted_probs(np.asarray(proba, np.float64), cost_rows, cost, weight, renormalise), top_k, threshold, cur_codes,
+                   cost_rows, cost)
 
 
 class CostOracleEngine(OracleEngine):
