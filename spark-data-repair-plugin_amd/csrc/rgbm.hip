@@ -239,6 +239,12 @@ struct Fusion {
 
 void all_reduce_on(Comm& c, void* buf, size_t count, int type, hipStream_t s);
 
+// RGBM_COMM_TIMEOUT_S: seconds without progress after which a collective is given up (default 600; read once)
+double comm_timeout_s() {
+    static const double limit = [] { const char* e = getenv("RGBM_COMM_TIMEOUT_S"); double v = e ? atof(e) : 600.0; return v > 0.0 ? v : 600.0; }();
+    return limit;
+}
+
 // the collective of one step for every member that is parked in it (called with f->mu held, by the last member to arrive -- or by a member
 // that leaves while all the remaining ones are parked).  Members may be at different points of their sequences (one is counting codes for
 // its next target while another is in the middle of an iteration): the parts are grouped by element type, one all-reduce per type present,
@@ -293,7 +299,7 @@ void fused_all_reduce(Fusion* f, int me, void* buf, size_t count, int type, hipS
     else {
         // bounded: a member of this rank that never arrives and never leaves -- its thread died before its next collective -- must not
         // park the others (and, through them, the peer ranks) for ever: after RGBM_COMM_TIMEOUT_S the group is broken and everybody raises
-        static const double limit = [] { const char* e = getenv("RGBM_COMM_TIMEOUT_S"); double v = e ? atof(e) : 600.0; return v > 0.0 ? v : 600.0; }();
+        const double limit = comm_timeout_s();
         if (!f->cv.wait_for(lk, std::chrono::duration<double>(limit), [&] { return f->gen != gen || f->broken; })) {
             f->broken = true; f->why = "a member of this rank did not reach its next collective within " + std::to_string((int)limit) + " s";
             if (f->comm.kind == 1 && f->comm.nccl) { (void)ncclCommAbort(f->comm.nccl); f->comm.nccl = nullptr; f->comm.kind = 0; }
@@ -336,7 +342,7 @@ void stream_sync_watchdog(hipStream_t s) {
     Comm& c = g_comm;
     const bool fused_rccl = c.kind == 3 && c.fusion && c.fusion->comm.kind == 1;
     if (c.kind != 1 && !fused_rccl) { HIPCHK(hipStreamSynchronize(s)); return; }
-    static const double limit = [] { const char* e = getenv("RGBM_COMM_TIMEOUT_S"); double v = e ? atof(e) : 600.0; return v > 0.0 ? v : 600.0; }();
+    const double limit = comm_timeout_s();
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
         const hipError_t q = hipStreamQuery(s);
@@ -560,21 +566,38 @@ void find_bin(const unsigned int* cnt, int32_t n_codes, int64_t n_train, const r
 }
 
 
-// LightGBM utils/random.h (as remembered; DESIGN.md D4)
 // Test / experiment switches, read from the environment at the start of every training call (tests flip them between calls); none
-// is needed in normal use.  RGBM_GROWER=leafwise|level, RGBM_TIMING=1 (host wall-clock of the phases to stderr), RGBM_LV_LDS=bytes
-// (shrinks the LDS pool of the level passes: more built-slot windows per level), RGBM_LV_BLOCKS / RGBM_MT_BLOCKS (row blocks per class
-// tree of the root / level passes), RGBM_MT_TREES (cap on the class trees per level-pass workgroup), RGBM_MT_REP (LDS replication the
-// level passes are sized for, default 8), RGBM_JOINT_ROOT=0, RGBM_MT_ACC2=0 (tables of 17..32 features: one level pass per 16-feature chunk
-// instead of one pass that accumulates both), RGBM_MT_SPEC=0|1 (wave-specialised level pass), RGBM_MT_SPARSE=0 (no sparse sweep: class trees
-// with few live rows are walked tile by tile like the others).  Round 5: RGBM_MT_ROT=-1|0|1 (feature rotation of a level pass's histogram updates:
-// per launch where fewer than RGBM_MT_ROT_COPIES2 / 2 copies of its histograms fit the LDS -- the default --, never, every launch that has the
-// instantiation; RGBM_MT_ROT_T=0 keeps the replicated layout's class trees per workgroup), RGBM_MT_LOCK=<rounds> (lock-step of the class-tree groups
-// of a row block, wave-specialised pass), RGBM_JOINT_WIDE=1 (16-bit joint codes in the root pass), RGBM_FX_MEASURE=separate (the coarse gradient sums of
-// numerics v2.2 from a pass of their own instead of out of the gradient kernels), round 6: RGBM_DEFER_SCORE=1 (AddScore inside the next iteration's gradient kernel; slower, off), RGBM_TEST_HOOKS=1 + RGBM_FX_ROWS=R (TEST hook: the fixed-point grid of a
-// table of R rows; the oracle reads the same pair; a warning goes to stderr when it is active).
-constexpr int LV_THREADS_DEFAULT = 1024;
-struct RunSwitches { int grower = 0; int lv_lds = 0; long long lv_blocks = 0; long long mt_blocks = 0; int mt_T = 0; int mt_rep = MT_ROT ? 4 : 8 /* replicas the level passes are sized for: under feature rotation four resolve every conflict */; bool joint_root = true; bool timing = false; bool mt_acc2 = true; int mt_threads = LV_THREADS_DEFAULT; int mt_spec = -1 /* -1: wave-specialised pass for two-chunk tables only (measured) */; bool mt_sparse = true /* class trees with < 1/MT_SPARSE_DIV (= 1/16) live rows are swept through their node ids */; int mt_rot = -1 /* RGBM_MT_ROT: feature rotation of the level pass atomics: -1 = where the LDS holds fewer than mt_rot_copies2 / 2 = EIGHT copies of the launch's worst-case histograms (default), 0 = never, 1 = every pass that has the instantiation */; bool joint_wide = false /* RGBM_JOINT_WIDE=1: 16-bit joint codes in the root pass (groups of <= 1024 joint bins, 10 atomics per row instead of 14 on the synthetic table): measured neutral (the two copies that fit conflict more), off */; int mt_rot_tmin = 2 /* RGBM_MT_ROT_TMIN: a launch whose replicated layout holds fewer class trees per workgroup than this (2: a single one) rotates when one copy holds at least twice as many (0 = off).  Measured (profiles/EXPERIMENTS.md, r7m / r7n): 0 / 2 / 4: bench step 80.4-80.8 / 80.0-80.1 / 80.8-81.2 ms, roofline frac 0.196 / 0.200 / 0.200 */; int mt_rot_tdiv = 1 /* RGBM_MT_ROT_TDIV=d: a rotated launch takes 1/d of the class trees one copy would allow and replicates with the rest (measured: see profiles/EXPERIMENTS.md) */; bool mt_rot_T = true /* RGBM_MT_ROT_T=0: rotated launches keep the class trees per workgroup of the replicated layout */; int mt_rot_copies2 = 16 /* RGBM_MT_ROT_COPIES2: twice the number of plain copies of a launch's histograms below which it rotates (16 = eight copies: every launch that cannot have the eight copies the replicated layout is sized for; round 5 had 6 -- the flat pipeline of round 6 moved the balance, profiles/r6r_*) */; int mt_lock = -1 /* RGBM_MT_LOCK=<tile rounds>: lock-step window of the class-tree groups of a row block in the wave-specialised pass; -1 / 0 = off (default) */; bool defer_score = false /* RGBM_DEFER_SCORE=1: the level grower adds a tree's output to the scores inside the NEXT iteration's gradient kernel (PendingScore; k_level_last finishes routing + counts on the node ids alone) instead of in a pass of its own (k_level_final) -- same scores, same models; the tests run both.  Measured SLOWER (round 6, profiles/r7b_*: k_grad_mc 2.08 -> 3.91 ms per launch for 0.81 ms saved in the last pass; bench step 80.8 / 81.1 -> 83.1 / 83.3 ms): the gradient kernel is FP64-bound at 3.6 TB/s, the pass of its own streams at 4.7 TB/s -- the third fusion of these two that lost; off */; bool fx_separate = false /* RGBM_FX_MEASURE=separate: the coarse sums behind every class tree's fixed-point grid come from a pass of their own over the (g, h) array (k_fx_measure) instead of out of the gradient kernels -- same sums, same models; the tests run both */; };
+// is needed in normal use.  Next to the fields below: RGBM_TRACE / RGBM_TRACE_K / RGBM_TRACE_ITERS (LevelTrace) and RGBM_TEST_HOOKS=1 +
+// RGBM_FX_ROWS=R (fit_setup).
+// Retired with their code paths; DESIGN.md ("Retired experiments") names the switches, and the parent of the commit that removed them is the
+// last one where they can be rebuilt (the measurements stay in profiles/EXPERIMENTS.md):
+//   lock-step of the class-tree groups of a row block                  -63 % HBM fetch, +23 % time
+//   score update inside the next iteration's gradient kernel           bench step 80.8 -> 83.1 ms, the third fusion of the two that lost
+//   16-bit joint codes in the root pass                                neutral
+//   768-thread plain one-chunk level pass                              84.4 ms against 80.8
+//   wave-specialised pass as a switch                                  one chunk: 3 % slower; two chunks: the measured default, now the only form
+//   partial-T rotation (two switches)                                  81.8 -> 86.1 -> 89.6 ms
+//   compile-time: rotate every level pass / 64-entry rings             loses 35-60 % at levels 1-4 / neutral
+struct RunSwitches {
+    int grower = 0;                // RGBM_GROWER=level|leafwise (1 | 2): 0 picks the level grower wherever it applies; both give the same models
+    bool timing = false;           // RGBM_TIMING: host wall-clock of the phases and the launch plan, to stderr
+    int lv_lds = 0;                // RGBM_LV_LDS=bytes: a smaller LDS pool for the level passes (tests: several built-slot windows per level)
+    long long lv_blocks = 0;       // RGBM_LV_BLOCKS: row blocks per class tree of the root pass (0: planned)
+    long long mt_blocks = 0;       // RGBM_MT_BLOCKS: row blocks per class tree of the level passes (0: planned)
+    int mt_T = 0;                  // RGBM_MT_TREES: cap on the class trees per level-pass workgroup (0: none)
+    int mt_rep = 8;                // RGBM_MT_REP: LDS copies of every bin the level passes are sized for
+    bool joint_root = true;        // RGBM_JOINT_ROOT=0: root pass over the plain records instead of the joint-bin record
+    bool mt_acc2 = true;           // RGBM_MT_ACC2=0: tables of 17..32 features take one level pass per 16-feature chunk instead of one that
+                                   // accumulates both (the per-chunk form is what > 32 features and histograms too large for the LDS get)
+    bool mt_sparse = true;         // RGBM_MT_SPARSE=0: class trees with < 1/MT_SPARSE_DIV live rows are walked tile by tile like the others
+    int mt_rot = -1;               // RGBM_MT_ROT: feature rotation of a level pass's atomics: -1 per launch (the rule below), 0 never, 1 wherever the form exists
+    int mt_rot_copies2 = 16;       // RGBM_MT_ROT_COPIES2: a launch rotates when the LDS holds fewer than this / 2 (eight) copies of its worst-case
+                                   // histograms, the eight the replicated layout is sized for (profiles/r6r_*)
+    int mt_rot_tmin = 2;           // RGBM_MT_ROT_TMIN: ... or when replication leaves the workgroup fewer class trees than this although one copy
+                                   // holds twice as many (0 = off).  0 / 2 / 4: bench step 80.4-80.8 / 80.0-80.1 / 80.8-81.2 ms (profiles/EXPERIMENTS.md, r7m / r7n)
+    bool fx_separate = false;      // RGBM_FX_MEASURE=separate: the coarse gradient sums of numerics v2.2 from a pass of their own (k_fx_measure, the
+                                   // live path for K > 112) instead of out of the gradient kernels; same sums, same models
+};
 RunSwitches read_switches() {
     RunSwitches w;
     if (const char* e = getenv("RGBM_GROWER")) w.grower = strcmp(e, "leafwise") == 0 ? 2 : (strcmp(e, "level") == 0 ? 1 : 0);
@@ -585,22 +608,16 @@ RunSwitches read_switches() {
     if (const char* e = getenv("RGBM_MT_REP")) w.mt_rep = atoi(e);
     if (const char* e = getenv("RGBM_JOINT_ROOT")) w.joint_root = atoi(e) != 0;
     if (const char* e = getenv("RGBM_MT_ACC2")) w.mt_acc2 = atoi(e) != 0;
-    if (const char* e = getenv("RGBM_MT_THREADS")) w.mt_threads = atoi(e) == 768 ? 768 : 1024;
-    if (const char* e = getenv("RGBM_MT_SPEC")) w.mt_spec = atoi(e) != 0 ? 1 : 0;
     if (const char* e = getenv("RGBM_MT_SPARSE")) w.mt_sparse = atoi(e) != 0;
     if (const char* e = getenv("RGBM_FX_MEASURE")) w.fx_separate = strcmp(e, "separate") == 0;
-    if (const char* e = getenv("RGBM_DEFER_SCORE")) w.defer_score = atoi(e) != 0;
-    if (const char* e = getenv("RGBM_MT_LOCK")) w.mt_lock = atoi(e);
     if (const char* e = getenv("RGBM_MT_ROT")) w.mt_rot = atoi(e);
     if (const char* e = getenv("RGBM_MT_ROT_COPIES2")) w.mt_rot_copies2 = atoi(e);
-    if (const char* e = getenv("RGBM_MT_ROT_TDIV")) w.mt_rot_tdiv = std::max(1, atoi(e));
     if (const char* e = getenv("RGBM_MT_ROT_TMIN")) w.mt_rot_tmin = atoi(e);
-    if (const char* e = getenv("RGBM_MT_ROT_T")) w.mt_rot_T = atoi(e) != 0;
-    if (const char* e = getenv("RGBM_JOINT_WIDE")) w.joint_wide = atoi(e) != 0;
     w.timing = getenv("RGBM_TIMING") != nullptr;
     return w;
 }
 
+// LightGBM utils/random.h (as remembered; DESIGN.md D4)
 struct LgbRand {
     uint32_t x;
     explicit LgbRand(uint32_t seed) : x(seed) {}
@@ -843,6 +860,320 @@ std::vector<uint8_t> make_used_masks(const rgbm_params& p, size_t NT, int F, con
 }
 
 // ---------------------------------------------------------------------------------------------
+// Level grower, host side: the launch plan of the root pass and the level passes (pure arithmetic), the joint-bin packing of the
+// root pass, and the table of the level-pass forms.
+// ---------------------------------------------------------------------------------------------
+// one k_level_mt launch of a level: (chunk, window of built slots); the first one of a level routes
+struct MtLaunch { int ch, slot0, nslots, route, T, G, gx, acc2, rot; };
+struct LevelPassPlan {
+    int root_gx = 8;                                // row blocks per class tree of the root pass
+    std::vector<std::vector<MtLaunch>> mt;          // [level] the launches of the level, levels 1 .. max_depth - 1
+    std::vector<int> mt_gx;                         // [level] row blocks per class tree of the level's launches (one value per level: the partials share it)
+    size_t part_items = 0;                          // nodes of the largest set of workgroup partials (root or level)
+};
+
+LevelPassPlan plan_level_passes(const RunSwitches& sw, const std::vector<rg::FeatMeta>& fmeta, const std::vector<rg::ChunkMeta>& cmeta,
+                                long long N, int K, int max_depth, bool wm /* rows carry multiplicities */, int lds_bytes) {
+    using namespace rg;
+    const int nchunk = (int)cmeta.size();
+    LevelPassPlan P;
+    P.mt.resize(LV_MAX_DEPTH + 1); P.mt_gx.assign(LV_MAX_DEPTH + 1, 8);
+    const long long ntiles = (N + LV_TILE - 1) / LV_TILE;
+    // ---- root pass: one 1024-thread workgroup per CU and (class tree, row block, chunk).  Contiguous row blocks, a multiple of 8 per
+    // class tree with all class trees of a row block on one XCD (k_level_root), about four rounds of 256 workgroups when the class
+    // trees alone nearly fill the chip (measured at K = 64, 10M rows: 8 / 16 / 40 blocks per class tree = 23.0 / 21.0 / 23.2 ms per
+    // iteration), else the fewest blocks that fill one round; <= 2^22 rows per workgroup.  RGBM_LV_BLOCKS overrides.
+    {
+        const long long cu_slots = 256, per = (long long)K * nchunk;
+        const long long gmin = std::max<long long>(1, (N + (1ll << 22) - 1) >> 22);
+        auto eff_of = [&](long long g) { const long long tot = g * per, rounds = (tot + cu_slots - 1) / cu_slots; return (double)tot / (double)(rounds * cu_slots); };
+        const long long gfloor = std::max<long long>(8, (gmin + 7) / 8 * 8), gcap = std::max<long long>(gfloor, std::min<long long>(512, (ntiles + 7) / 8 * 8));
+        long long g2 = gfloor; double best2 = -1.0;
+        for (long long g = gfloor; g <= gcap; g += 8) {
+            if (per >= 16 && (g * per < 3 * cu_slots || g * per > 5 * cu_slots)) continue;
+            const double e = eff_of(g);
+            if (e > best2 + 1e-9) { best2 = e; g2 = g; }
+            if (e >= 0.99) break;
+        }
+        if (best2 < 0.0) for (long long g = gfloor; g <= gcap; g += 8) { const double e = eff_of(g); if (e > best2 + 1e-9) { best2 = e; g2 = g; } if (e >= 0.99) break; }
+        if (sw.lv_blocks >= 1) g2 = (sw.lv_blocks + 7) / 8 * 8;
+        P.root_gx = (int)g2;
+    }
+    for (int ch = 0; ch < nchunk; ++ch)
+        if ((long long)lv_slots(fmeta.data() + cmeta[ch].first_feat, cmeta[ch].nfeat, 0) * 16 + LV_ROOT_FIXED > lds_bytes)
+            throw std::invalid_argument("histogram of one node exceeds LDS");
+    // ---- level passes (k_level_mt).  Per chunk: how many built nodes the LDS holds next to the rings (cap), hence how many class
+    // trees share a workgroup (T = cap / worst-case built nodes of the level, 2^(L-1)) or, when one class tree's nodes do not fit,
+    // how many launches ("windows" of built slots) the level takes.  Every class tree group gets the same row blocks, a multiple of 8
+    // (one XCD each), enough to fill the chip once (<= 2^22 rows per workgroup).
+    P.part_items = (size_t)K * P.root_gx;                   // root partials: one node per (class tree, row block)
+    for (int level = 1; level < max_depth; ++level) {
+        const int worst = 1 << (level - 1);
+        int G_first = 1;
+        // tables of 17..32 features: ONE wave-specialised pass per level accumulates both 16-feature chunks (k_level_mt<2, ., ., MT_THREADS_ACC2, true, true>:
+        // both records of a row in registers and in the ring) instead of one pass per chunk that streams every (node id, g, h) again
+        bool acc2 = nchunk == 2 && sw.mt_acc2;
+        if (acc2) {   // ... when one node's histograms of both chunks fit the LDS of the 768-thread workgroup (else: one pass per chunk, as for > 32 features)
+            const long long nb2 = ((long long)lv_slots(fmeta.data() + cmeta[0].first_feat, cmeta[0].nfeat, 0) + lv_slots(fmeta.data() + cmeta[1].first_feat, cmeta[1].nfeat, 0)) * 16;
+            if (nb2 > mt_hist_bytes(lds_bytes, MT_THREADS_ACC2, true, true, cmeta[1].nfeat > 15 || wm)) acc2 = false;
+        }
+        if (wm && nchunk == 2 && !acc2) throw std::invalid_argument("a two-chunk table with row multiplicities needs the one-pass level form (the multiplicity rides in the second record)");
+        for (int ch = 0; ch < (acc2 ? 1 : nchunk); ++ch) {
+            const FeatMeta* fm = fmeta.data() + cmeta[ch].first_feat;
+            long long node_bytes = (long long)lv_slots(fm, cmeta[ch].nfeat, 0) * 16;
+            if (acc2) node_bytes += (long long)lv_slots(fmeta.data() + cmeta[1].first_feat, cmeta[1].nfeat, 0) * 16;
+            const int mt_thr = acc2 ? MT_THREADS_ACC2 : LV_THREADS;
+            const bool li_arr = cmeta[acc2 ? 1 : ch].nfeat > 15 || wm;          // the ring needs a slot array (k_level_mt: !li_in_rec)
+            const long long hist_room = mt_hist_bytes(lds_bytes, mt_thr, acc2, acc2 /* the both-chunk pass is the wave-specialised one */, li_arr);
+            long long cap = hist_room / std::max<long long>(node_bytes, 1);
+            cap = std::min<long long>(cap, MT_MAX_NODES);
+            if (cap < 1) throw std::invalid_argument("histogram of one node exceeds LDS");
+            const int win = (int)std::min<long long>(worst, cap);                    // built slots per launch
+            // LDS left over after the T class trees' nodes becomes replication (2^s copies of every bin).  A batch of 64 built rows comes from
+            // one or two class trees (a wave walks them one after another) and, at the shallow levels, from one or two nodes: without
+            // replication its lanes pile up on a handful of addresses (measured at K = 64: 23-31 cycles per atomic instruction at
+            // replication 1 against 12.8 in the root pass).  So T is sized for `mt_rep` copies first; the records the extra workgroups
+            // re-read come out of the XCD's L2 (all class tree groups of a row block run on one XCD at the same time).
+            const long long rep_target = std::max(1, sw.mt_rep);
+            const long long t_nodes = std::max<long long>(win, cap / rep_target);
+            int T = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(t_nodes / win, MT_MAX_T), std::min<long long>(K, MT_RT_BUDGET / (2 * worst))));
+            if (sw.mt_T >= 1) T = std::max(1, std::min(T, sw.mt_T));
+            // Feature rotation of the histogram updates (rgbm_level.h, "FEATURE ROTATION") for the launches whose LDS holds fewer than eight copies (RGBM_MT_ROT_COPIES2 / 2) of their
+            // worst-case histograms -- the deepest dense levels, where rows of one cluster pile up on one address per feature: measured -11 % at
+            // level 5 of the K = 64 target and +35-60 % where there IS room for replicas (profiles/r5c_*), hence per launch.
+            const bool plain1 = nchunk == 1 || acc2;      // the two forms that exist with rotation (RGBM_MT_FORMS)
+            // (a rotated step works on sixteen feature slots per chunk whatever the chunk holds: with few features most lanes of a step idle -- rotate only chunks
+            // that fill at least three quarters of them)
+            const bool rot_full = cmeta[ch].nfeat >= 12 && (!acc2 || cmeta[1].nfeat >= 12);
+            // ... and (round 6) where the replicated layout would leave the workgroup fewer than RGBM_MT_ROT_TMIN (2: a single one) class trees although one copy holds at least twice
+            // as many: every doubling of the class trees per workgroup is ~5 % of a deep level (the records are read once per T steps), which eight copies do not buy back
+            const long long rot_node_bytes = node_bytes + mt_rot_dummy(true) * 16;
+            const long long cap_rot = std::min<long long>(hist_room / rot_node_bytes, MT_MAX_NODES);
+            const long long T_rot = std::min<long long>(std::min<long long>(cap_rot / win, MT_MAX_T), std::min<long long>(K, MT_RT_BUDGET / (2 * worst)));
+            const bool few_trees = T < sw.mt_rot_tmin && T_rot >= 2 * (long long)T;
+            const bool rot = plain1 && (sw.mt_rot == 1 || (sw.mt_rot < 0 && rot_full && (cap * 2 < (long long)sw.mt_rot_copies2 * T * win || few_trees))) &&
+                             (long long)T * win * rot_node_bytes <= hist_room;
+            // a rotated launch needs ONE copy: as many class trees per workgroup as the LDS holds
+            if (rot && sw.mt_T < 1) T = (int)std::max<long long>(T, T_rot);
+            const int G = (K + T - 1) / T;
+            if (ch == 0) G_first = G;
+            for (int s0 = 0; s0 < worst; s0 += win)
+                P.mt[level].push_back(MtLaunch{ch, s0, win, (ch == 0 && s0 == 0) ? 1 : 0, T, G, 0, acc2 ? 1 : 0, rot ? 1 : 0});
+        }
+        const long long gmin = std::max<long long>(1, (N + (1ll << 22) - 1) >> 22);
+        // row blocks per class tree: a multiple of 8 (one XCD each); G * gx workgroups should fill whole rounds of 256 CUs (G = 24: 8 row
+        // blocks leave a quarter of the chip idle, 32 make three full rounds) without cutting the table into slivers
+        const long long nwt = (N + MT_WT_ROWS - 1) / MT_WT_ROWS;
+        const long long gx_lo = std::max<long long>(8, (gmin + 7) / 8 * 8), gx_hi = std::max<long long>(gx_lo, std::min<long long>(512, (nwt / (4 * (LV_THREADS / 64)) + 7) / 8 * 8));
+        long long gx = gx_lo; double best = -1.0;
+        for (long long g = gx_lo; g <= gx_hi; g += 8) {
+            const long long tot = g * G_first, rounds = (tot + 255) / 256;
+            const double eff = (double)tot / (double)(rounds * 256) - 0.01 * (double)rounds;   // fuller rounds first, then fewer of them
+            if (eff > best + 1e-9) { best = eff; gx = g; }
+            if (tot >= 256 && (double)tot / (double)(rounds * 256) >= 0.97) break;
+        }
+        if (sw.mt_blocks >= 1) gx = (sw.mt_blocks + 7) / 8 * 8;
+        P.mt_gx[level] = (int)gx;
+        for (auto& L : P.mt[level]) L.gx = (int)gx;
+        P.part_items = std::max(P.part_items, (size_t)K * (size_t)gx * (size_t)worst);
+    }
+    return P;
+}
+
+// Joint bins for the root pass, host half: best-fit-decreasing packing of the features into groups whose bin counts multiply to <= 256;
+// worth it when it saves at least two atomics per row, the groups fit one 16-byte record (15 bytes when byte 15 carries the row's
+// multiplicity) and their histograms fit the LDS.  on == false: the root pass keeps the plain records.
+struct JointRootPlan {
+    bool on = false;
+    std::vector<std::vector<int>> groups;           // features of every group
+    std::vector<rg::FeatMeta> vfm; rg::ChunkMeta vcm;   // the groups as the features of ONE virtual chunk
+    std::vector<rg::JointFeat> jf;                  // [F] where a feature sits in its group's joint code
+    std::vector<int16_t> binfeat;                   // [totbins] bin -> feature
+};
+JointRootPlan plan_joint_root(const std::vector<rg::FeatMeta>& fmeta, int totbins, bool wm, int lds_bytes) {
+    using namespace rg;
+    const int F = (int)fmeta.size();
+    JointRootPlan J;
+    std::vector<int> order(F); for (int f = 0; f < F; ++f) order[f] = f;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return fmeta[a].nbins > fmeta[b].nbins; });
+    std::vector<int> prod;
+    for (int f : order) {
+        int best = -1;
+        for (size_t g = 0; g < J.groups.size(); ++g)
+            if ((long long)prod[g] * fmeta[f].nbins <= 256 && (best < 0 || prod[g] > prod[best])) best = (int)g;
+        if (best < 0) { J.groups.emplace_back(); prod.push_back(1); best = (int)J.groups.size() - 1; }
+        J.groups[best].push_back(f); prod[best] *= fmeta[f].nbins;
+    }
+    const int VF = (int)J.groups.size();
+    if (VF > (wm ? 15 : 16) || VF > F - 2) return J;
+    J.vfm.resize(VF); J.jf.resize(F); J.binfeat.assign(totbins, 0);
+    ChunkMeta& vcm = J.vcm; vcm.first_feat = 0; vcm.nfeat = VF; vcm.fast_slots = 0; vcm.wide_bins = 0;
+    for (int v = 0; v < VF; ++v) {
+        FeatMeta& m = J.vfm[v]; memset(&m, 0, sizeof(m));
+        m.V = prod[v]; m.has_nan = 0; m.nbins = prod[v]; m.hoff = vcm.wide_bins; m.wide_off = vcm.wide_bins;
+        int sh = 0; while (sh < 5 && (m.nbins << (sh + 1)) <= 256) ++sh;
+        m.rep_shift = sh; m.fast_base = vcm.fast_slots; vcm.fast_slots += m.nbins << sh; vcm.wide_bins += m.nbins;
+        int stride = 1;
+        for (int f : J.groups[v]) {
+            JointFeat& j = J.jf[f]; memset(&j, 0, sizeof(j));
+            j.voff = m.hoff; j.stride = stride; j.nbins = fmeta[f].nbins; j.nbv = prod[v]; j.hoff = fmeta[f].hoff; j.vbyte = v;
+            stride *= fmeta[f].nbins;
+            for (int b = 0; b < fmeta[f].nbins; ++b) J.binfeat[fmeta[f].hoff + b] = (int16_t)f;
+        }
+    }
+    J.on = (long long)lv_slots(J.vfm.data(), VF, 0) * 16 + LV_ROOT_FIXED <= lds_bytes;
+    return J;
+}
+
+// The forms of the level pass that exist, (NCHR, THREADS, ACC2, SPEC, ROTP), each for BAG x ROUTE: the ONE list behind the LDS attribute
+// and the launch, so a form cannot be launched without its attribute.  k_level_mt's static_assert admits the same six.
+#define RGBM_MT_FORMS(X) \
+    X(0, rg::LV_THREADS, false, false, false) /* any number of chunks: the split byte is gathered */ \
+    X(1, rg::LV_THREADS, false, false, false) /* one chunk */ \
+    X(1, rg::LV_THREADS, false, false, true)  /* one chunk, rotated */ \
+    X(2, rg::LV_THREADS, false, false, false) /* two chunks, one pass per chunk */ \
+    X(2, rg::MT_THREADS_ACC2, true, true, false) /* two chunks in one wave-specialised pass */ \
+    X(2, rg::MT_THREADS_ACC2, true, true, true)  /* ... rotated */
+struct MtForm { int nchr, threads; bool acc2, spec, rot; };
+constexpr MtForm MT_FORMS[] = {
+#define RGBM_MT_FORM_ENTRY(NCHR, THR, ACC, SPEC, ROT) {NCHR, THR, ACC, SPEC, ROT},
+    RGBM_MT_FORMS(RGBM_MT_FORM_ENTRY)
+#undef RGBM_MT_FORM_ENTRY
+};
+using MtKernel = decltype(&rg::k_level_mt<1, false, true, rg::LV_THREADS, false, false, false>);      // (every instantiation has this signature)
+MtKernel mt_kernel(const MtForm& f, bool bag, bool route) {
+#define RGBM_MT_FORM_KERNEL(NCHR, THR, ACC, SPEC, ROT) \
+    if (f.nchr == NCHR && f.threads == THR && f.acc2 == ACC && f.spec == SPEC && f.rot == ROT) \
+        return bag ? (route ? rg::k_level_mt<NCHR, true, true, THR, ACC, SPEC, ROT> : rg::k_level_mt<NCHR, true, false, THR, ACC, SPEC, ROT>) \
+                   : (route ? rg::k_level_mt<NCHR, false, true, THR, ACC, SPEC, ROT> : rg::k_level_mt<NCHR, false, false, THR, ACC, SPEC, ROT>);
+    RGBM_MT_FORMS(RGBM_MT_FORM_KERNEL)
+#undef RGBM_MT_FORM_KERNEL
+    throw std::logic_error("level pass: no such launch form");
+}
+// (the parameter list is k_level_mt's own)
+void launch_level_mt(const MtForm& f, bool bag, bool route, dim3 grid, hipStream_t s, const uint4* rec, const float2* gh, uint8_t* node, const uint8_t* inbag,
+                     const rg::LvPlan* plan, rg::HistBin* part, int32_t* count, const rg::FeatMeta* fmeta, const rg::ChunkMeta* cmeta, int32_t* err_flag,
+                     const rg::FxScale* fxs, const rg::LevelConst& c) {
+    // (always the CU's whole LDS: the hessian sums sit a compile-time distance behind the gradient sums; LevelConst::lds_bytes, the test hook, only sizes the histograms)
+    hipLaunchKernelGGL(mt_kernel(f, bag, route), grid, dim3(f.threads), rg::LV_LDS_BYTES, s, rec, gh, node, inbag, plan, part, count, fmeta, cmeta, err_flag, fxs, c);
+}
+// the level grower's kernels may use the CU's whole LDS.  Once per process and device: the attribute belongs to the function, not to the
+// call, and other threads are launching these kernels while a new training call sets up
+void set_level_lds_attributes(int device) {
+    static std::mutex attr_mu; static std::vector<char> attr_done(64, 0);
+    std::lock_guard<std::mutex> lk(attr_mu);
+    if (attr_done[device & 63]) return;
+    HIPCHK(hipFuncSetAttribute((const void*)rg::k_level_root, hipFuncAttributeMaxDynamicSharedMemorySize, rg::LV_LDS_BYTES));
+    for (const MtForm& f : MT_FORMS) for (int bag = 0; bag < 2; ++bag) for (int route = 0; route < 2; ++route)
+        HIPCHK(hipFuncSetAttribute((const void*)mt_kernel(f, bag != 0, route != 0), hipFuncAttributeMaxDynamicSharedMemorySize, rg::LV_LDS_BYTES));
+    attr_done[device & 63] = 1;
+}
+
+// HIP events around every histogram launch of a training call, on the stream it is launched on; only when stats are requested
+struct HistTimers {
+    bool on; hipStream_t s;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; std::vector<char> root;
+    template <typename Fn> void timed(bool is_root, Fn&& fn) {
+        hipEvent_t a = nullptr, b = nullptr;
+        if (on) { HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b)); HIPCHK(hipEventRecord(a, s)); }
+        fn();
+        if (on) { HIPCHK(hipEventRecord(b, s)); ev.emplace_back(a, b); root.push_back(is_root ? 1 : 0); }
+    }
+};
+
+// RGBM_TRACE=<dir> (debugging; with RGBM_TRACE_K=<class trees> and RGBM_TRACE_ITERS=lo:hi): snapshots of the level grower's state after every
+// level of the iterations lo..hi and a checksum of (score, g/h, node ids) after every iteration, written to <dir>/target<col>.{bin,idx}
+struct LevelTrace {
+    struct Rec { std::string name; int it, level; size_t off, bytes; };
+    const char* dir; bool on; hipStream_t s;
+    int lo = 44, hi = 44, cur_it = 0;
+    std::vector<Rec> idx; size_t used = 0;
+    DevBuf<unsigned char> buf;              // sized by the caller when `on`
+    LevelTrace(bool level_mode, int K, hipStream_t stream) : dir(getenv("RGBM_TRACE")), s(stream) {
+        on = dir && level_mode && (!getenv("RGBM_TRACE_K") || atoi(getenv("RGBM_TRACE_K")) == K);
+        if (on && getenv("RGBM_TRACE_ITERS")) sscanf(getenv("RGBM_TRACE_ITERS"), "%d:%d", &lo, &hi);
+    }
+    void copy(const char* name, int level, const void* src, size_t bytes) {
+        if (!on || cur_it < lo || cur_it > hi) return;
+        if (used + bytes > buf.n) return;
+        HIPCHK(hipMemcpyAsync(buf.p + used, src, bytes, hipMemcpyDeviceToDevice, s));
+        idx.push_back({name, cur_it, level, used, bytes}); used += (bytes + 15) & ~(size_t)15;
+    }
+    void sum(const char* name, const void* src, size_t bytes) {
+        if (!on || used + 16 > buf.n) return;
+        HIPCHK(hipMemsetAsync(buf.p + used, 0, 8, s));
+        hipLaunchKernelGGL(k_trace_sum, dim3(2048), dim3(256), 0, s, (const unsigned long long*)src, bytes / 8, (unsigned long long*)(buf.p + used));
+        idx.push_back({name, cur_it, -1, used, 8}); used += 16;
+    }
+    void write(int target_col) {            // (after the stream has drained)
+        if (!on || !used) return;
+        std::vector<unsigned char> h(used);
+        HIPCHK(hipMemcpy(h.data(), buf.p, used, hipMemcpyDeviceToHost));
+        char path[512];
+        snprintf(path, sizeof(path), "%s/target%d.bin", dir, target_col);
+        if (FILE* f = fopen(path, "wb")) { fwrite(h.data(), 1, h.size(), f); fclose(f); }
+        snprintf(path, sizeof(path), "%s/target%d.idx", dir, target_col);
+        if (FILE* f = fopen(path, "w")) { for (const auto& r : idx) fprintf(f, "%s %d %d %zu %zu\n", r.name.c_str(), r.it, r.level, r.off, r.bytes); fclose(f); }
+    }
+};
+
+// rgbm_train_stats of a finished training call (destroys the timers' events)
+void fill_train_stats(rgbm_train_stats* stats, float total_ms, HistTimers& timers, const HostTrees& h, const rgbm_params& p, bool level_mode, bool use_bagging,
+                      int nranks /* row-sharded: the ranks that share the table */, int64_t N, int64_t n_train, int F, int root_feats /* feature groups of the root pass */,
+                      int K, unsigned long long statrows) {
+    const int NE = p.n_estimators, NL = p.num_leaves;
+    memset(stats, 0, sizeof(*stats));
+    stats->total_ms = total_ms;
+    stats->hist_launches = (int64_t)timers.ev.size();
+    for (size_t i = 0; i < timers.ev.size(); ++i) {
+        float m2 = 0.f; HIPCHK(hipEventElapsedTime(&m2, timers.ev[i].first, timers.ev[i].second));
+        stats->hist_ms += m2; if (timers.root[i]) stats->root_ms += m2;
+        (void)hipEventDestroy(timers.ev[i].first); (void)hipEventDestroy(timers.ev[i].second);
+    }
+    stats->trees = (int64_t)NE * K;
+    const bool root_done = n_train >= (int64_t)p.min_data_in_leaf * 2;
+    if (level_mode) {
+        // rows whose (g,h) were accumulated: counted on the device (k_level_split); root passes = trees with a searched root
+        // (bag sizes vary: not tracked separately).  Row-sharded: the device counter sums GLOBAL child counts on every rank; report this rank's share
+        const int64_t root_rows = (root_done && !use_bagging) ? (int64_t)NE * K * n_train : 0;
+        const int64_t rows_acc = (int64_t)(statrows / (unsigned long long)nranks);
+        stats->hist_rows = rows_acc; stats->root_rows = root_rows / nranks;
+        stats->root_atomics_per_row = 2 * (int64_t)root_feats; stats->level_atomics_per_row = 2 * (int64_t)F;
+        // algorithmic bytes: F bin bytes + 8 B (g,h) per accumulated row
+        stats->hist_bytes = rows_acc * ((int64_t)F + 8);
+        return;
+    }
+    // rows scanned: root = N per class tree; otherwise the smaller child of every split, which the
+    // trees record (leaf_count of both children is known at the end only for final leaves), so
+    // replay the growth order on the host from the stored counts.
+    int64_t rows = 0, root_rows = 0;
+    for (size_t t = 0; t < (size_t)NE * K; ++t) {
+        const int L = h.L[t];
+        const int32_t* left = h.left + t * (NL - 1); const int32_t* right = h.right + t * (NL - 1);
+        if (root_done) { rows += N; root_rows += N; }
+        // final leaf counts -> internal counts: node j created leaf j+1 from some leaf; recover via children links
+        std::vector<int64_t> fin(h.cnt + t * NL, h.cnt + t * NL + NL);
+        std::vector<int64_t> nodecnt(std::max(L - 1, 1), 0);
+        auto sub = [&](int ch) -> int64_t { return ch < 0 ? fin[~ch] : nodecnt[ch]; };
+        for (int j = L - 2; j >= 0; --j) nodecnt[j] = sub(left[j]) + sub(right[j]);
+        std::vector<int> node_depth(std::max(L - 1, 1), 0);
+        for (int j = 0; j < L - 1; ++j) {
+            const int lc = left[j], rc = right[j];
+            if (lc >= 0) node_depth[lc] = node_depth[j] + 1;
+            if (rc >= 0) node_depth[rc] = node_depth[j] + 1;
+            const int64_t a = sub(lc), b = sub(rc);
+            bool go = j + 2 < NL;
+            if (p.max_depth > 0 && node_depth[j] + 1 >= p.max_depth) go = false;
+            if (a < (int64_t)p.min_data_in_leaf * 2 && b < (int64_t)p.min_data_in_leaf * 2) go = false;
+            if (go) rows += std::min(a, b);
+        }
+    }
+    stats->hist_rows = rows; stats->root_rows = root_rows;
+    // algorithmic bytes use the USEFUL feature bytes (F), not the padded record
+    stats->hist_bytes = rows * ((int64_t)F + 8) + (rows - root_rows) * 4;
+}
+
+// ---------------------------------------------------------------------------------------------
 // The trainer (GBDT::Train) on a resident table.
 // ---------------------------------------------------------------------------------------------
 rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t* feat_cols, int32_t F,
@@ -906,22 +1237,21 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     d_fmeta.upload(fmeta.data(), F, s); d_cmeta.upload(cmeta.data(), nchunk, s); d_lut_off.upload(lut_off.data(), F + 1, s);
     d_lut.upload(lut.data(), lut.size(), s); d_miss.upload(miss.data(), F, s);
     DevBuf<uint4> d_rec((size_t)nchunk * N);
+    // grower choice: the level-synchronous streaming grower (rgbm_level.h) whenever it applies; RGBM_GROWER=leafwise forces the
+    // index-list grower (both are HIP; they produce identical models)
+    const bool use_bagging = p.bagging_freq > 0 && p.bagging_fraction < 1.0;
+    const bool level_mode = p.max_depth >= 1 && p.max_depth <= LV_MAX_DEPTH && F <= 255 && sw.grower != 2;
     // rows with multiplicities (rgbm_table_set_row_multiplicity): the multiplicity rides in byte 15 of the row's LAST bin record, so that chunk
     // must leave the byte free; the level grower only (one chunk, or two chunks in one pass), no bagging (LightGBM draws per ORIGINAL row), no per-row weights
     const bool wm = tab.has_mult;
     const uint8_t* d_mult = wm ? tab.mult.p : (const uint8_t*)nullptr;
     if (wm) {
-        const bool lvl = p.max_depth >= 1 && p.max_depth <= LV_MAX_DEPTH && F <= 255 && read_switches().grower != 2;
-        if (!lvl || nchunk > 2 || (F % 16) == 0 || sample_weight_host || (p.bagging_freq > 0 && p.bagging_fraction < 1.0))
+        if (!level_mode || nchunk > 2 || (F % 16) == 0 || sample_weight_host || use_bagging)
             throw std::invalid_argument("a table with row multiplicities trains with the level grower (1 <= max_depth <= 7), at most 32 features of which the last 16-feature "
                                         "chunk holds at most 15, without bagging and without per-row weights");
     }
     hipLaunchKernelGGL(k_pack_bins, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, tab.codes.p, (long long)N, 0ll, (long long)N,
                        d_cols.p, d_ncod.p, d_lut_off.p, d_lut.p, d_miss.p, F, nchunk, d_rec.p, d_mult);
-    // grower choice: the level-synchronous streaming grower (rgbm_level.h) whenever it applies; RGBM_GROWER=leafwise forces the
-    // index-list grower (both are HIP; they produce identical models)
-    const bool use_bagging = p.bagging_freq > 0 && p.bagging_fraction < 1.0;
-    const bool level_mode = p.max_depth >= 1 && p.max_depth <= LV_MAX_DEPTH && F <= 255 && sw.grower != 2;
     if (dp && (!level_mode || sample_weight_host))
         throw std::invalid_argument("row-sharded training supports the level grower (1 <= max_depth <= 7) without per-row weights");
     DevBuf<int32_t> d_base; DevBuf<unsigned int> d_counter(1); d_counter.zero(s);
@@ -948,20 +1278,15 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     LevelConst lc; memset(&lc, 0, sizeof(lc));
     DevBuf<uint8_t> d_node; DevBuf<LvPlan> d_plan; DevBuf<SNode> d_snodes; DevBuf<Cand> d_lcand;
     DevBuf<HistBin> d_part, d_lpool; DevBuf<int32_t> d_count, d_count_g, d_err, d_leafnode; DevBuf<HistBin> d_part_red; DevBuf<double> d_ndelta; DevBuf<unsigned long long> d_statrows;
-    DevBuf<uint32_t> d_prog; uint32_t mt_epoch = 0;   // lock-step progress words of the wave-specialised level pass: [row blocks][tree groups]
     int n_hnodes = 1;
     bool use_reduce = false;   // root pass: sum the per-workgroup partials in a separate kernel (many workgroups per class tree, joint bins, or row-sharded)
     // joint bins for the root pass (rgbm_level.h, k_pack_joint): a second record whose bytes hold GROUPS of low-cardinality features
-    bool joint_root = false, joint_wide = false; int vtotbins = 0;
+    bool joint_root = false; int vtotbins = 0;
     LevelConst lcj; memset(&lcj, 0, sizeof(lcj));
     DevBuf<FeatMeta> d_vfmeta; DevBuf<ChunkMeta> d_vcmeta; DevBuf<uint4> d_rec_j; DevBuf<HistBin> d_part_j, d_red_j;
     DevBuf<JointFeat> d_jf; DevBuf<int16_t> d_binfeat;
-    // one k_level_mt launch of a level: (chunk, window of built slots); the first one of a level routes
-    struct MtLaunch { int ch, slot0, nslots, route, T, G, gx, acc2, rot; };
-    std::vector<std::vector<MtLaunch>> mt_plan(LV_MAX_DEPTH + 1);
-    std::vector<int> mt_gx(LV_MAX_DEPTH + 1, 8);           // row blocks per class tree of a level's launches (one value per level: the partials share it)
+    LevelPassPlan passes;
     if (level_mode) {
-        const long long ntiles = (N + LV_TILE - 1) / LV_TILE;
         lc.lds_bytes = LV_LDS_BYTES;
         if (sw.lv_lds >= 65536 && sw.lv_lds <= LV_LDS_BYTES) lc.lds_bytes = sw.lv_lds;      // testing: a smaller LDS pool forces several built-slot windows per level
         lc.nchunk = nchunk; lc.K = K; lc.F = F; lc.totbins = tc.totbins;
@@ -969,209 +1294,44 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
         lc.sib_local = (dp && g_comm.rank == 0) ? 1 : 0;
         lc.has_mult = wm ? 1u : 0u;
         n_hnodes = (1 << p.max_depth) - 1;
-        // ---- root pass: one 1024-thread workgroup per CU and (class tree, row block, chunk).  Contiguous row blocks, a multiple of 8 per
-        // class tree with all class trees of a row block on one XCD (k_level_root), about four rounds of 256 workgroups when the class
-        // trees alone nearly fill the chip (measured at K = 64, 10M rows: 8 / 16 / 40 blocks per class tree = 23.0 / 21.0 / 23.2 ms per
-        // iteration), else the fewest blocks that fill one round; <= 2^22 rows per workgroup.  RGBM_LV_BLOCKS overrides.
-        {
-            const long long cu_slots = 256, per = (long long)K * nchunk;
-            const long long gmin = std::max<long long>(1, (N + (1ll << 22) - 1) >> 22);
-            auto eff_of = [&](long long g) { const long long tot = g * per, rounds = (tot + cu_slots - 1) / cu_slots; return (double)tot / (double)(rounds * cu_slots); };
-            const long long gfloor = std::max<long long>(8, (gmin + 7) / 8 * 8), gcap = std::max<long long>(gfloor, std::min<long long>(512, (ntiles + 7) / 8 * 8));
-            long long g2 = gfloor; double best2 = -1.0;
-            for (long long g = gfloor; g <= gcap; g += 8) {
-                if (per >= 16 && (g * per < 3 * cu_slots || g * per > 5 * cu_slots)) continue;
-                const double e = eff_of(g);
-                if (e > best2 + 1e-9) { best2 = e; g2 = g; }
-                if (e >= 0.99) break;
-            }
-            if (best2 < 0.0) for (long long g = gfloor; g <= gcap; g += 8) { const double e = eff_of(g); if (e > best2 + 1e-9) { best2 = e; g2 = g; } if (e >= 0.99) break; }
-            if (sw.lv_blocks >= 1) g2 = (sw.lv_blocks + 7) / 8 * 8;
-            lc.gx = (int)g2; lc.xcd_blocks = 1; lc.max_built = 1;
-        }
-        for (int ch = 0; ch < nchunk; ++ch)
-            if ((long long)lv_slots(fmeta.data() + cmeta[ch].first_feat, cmeta[ch].nfeat, 0) * 16 + LV_ROOT_FIXED > lc.lds_bytes)
-                throw std::invalid_argument("histogram of one node exceeds LDS");
-        // ---- level passes (k_level_mt).  Per chunk: how many built nodes the LDS holds next to the rings (cap), hence how many class
-        // trees share a workgroup (T = cap / worst-case built nodes of the level, 2^(L-1)) or, when one class tree's nodes do not fit,
-        // how many launches ("windows" of built slots) the level takes.  Every class tree group gets the same row blocks, a multiple of 8
-        // (one XCD each), enough to fill the chip once (<= 2^22 rows per workgroup).
-        size_t part_items = (size_t)K * lc.gx;                   // root partials: one node per (class tree, row block)
-        for (int level = 1; level < p.max_depth; ++level) {
-            const int worst = 1 << (level - 1);
-            int G_first = 1;
-            // tables of 17..32 features: ONE pass per level accumulates both 16-feature chunks (k_level_mt<2, ., ., MT_THREADS_ACC2, true>: both
-            // records of a row in registers and in the ring) instead of one pass per chunk that streams every (node id, g, h) again
-            bool acc2 = nchunk == 2 && sw.mt_acc2;
-            if (acc2) {   // ... when one node's histograms of both chunks fit the LDS of the 768-thread workgroup (else: one pass per chunk, as for > 32 features)
-                const long long nb2 = ((long long)lv_slots(fmeta.data() + cmeta[0].first_feat, cmeta[0].nfeat, 0) + lv_slots(fmeta.data() + cmeta[1].first_feat, cmeta[1].nfeat, 0) + MT_ROT_DUMMY) * 16;
-                if (nb2 > mt_hist_bytes(lc.lds_bytes, MT_THREADS_ACC2, true, sw.mt_spec != 0, cmeta[1].nfeat > 15 || wm)) acc2 = false;
-            }
-            if (wm && nchunk == 2 && !acc2) throw std::invalid_argument("a two-chunk table with row multiplicities needs the one-pass level form (the multiplicity rides in the second record)");
-            for (int ch = 0; ch < (acc2 ? 1 : nchunk); ++ch) {
-                const FeatMeta* fm = fmeta.data() + cmeta[ch].first_feat;
-                long long node_bytes = (long long)lv_slots(fm, cmeta[ch].nfeat, 0) * 16 + MT_ROT_DUMMY * 16;
-                if (acc2) node_bytes += (long long)lv_slots(fmeta.data() + cmeta[1].first_feat, cmeta[1].nfeat, 0) * 16;
-                const int mt_thr = acc2 ? MT_THREADS_ACC2 : ((nchunk == 1 && sw.mt_threads == 768 && sw.mt_spec != 1) ? 768 : LV_THREADS);
-                const bool spec = acc2 ? sw.mt_spec != 0 : (nchunk == 1 && sw.mt_spec == 1);
-                const bool li_arr = cmeta[acc2 ? 1 : ch].nfeat > 15 || wm;          // the ring needs a slot array (k_level_mt: !li_in_rec)
-                const long long hist_room = mt_hist_bytes(lc.lds_bytes, mt_thr, acc2, spec, li_arr);
-                long long cap = hist_room / std::max<long long>(node_bytes, 1);
-                cap = std::min<long long>(cap, MT_MAX_NODES);
-                if (cap < 1) throw std::invalid_argument("histogram of one node exceeds LDS");
-                const int win = (int)std::min<long long>(worst, cap);                    // built slots per launch
-                // LDS left over after the T class trees' nodes becomes replication (2^s copies of every bin).  A batch of 64 built rows comes from
-                // one or two class trees (a wave walks them one after another) and, at the shallow levels, from one or two nodes: without
-                // replication its lanes pile up on a handful of addresses (measured at K = 64: 23-31 cycles per atomic instruction at
-                // replication 1 against 12.8 in the root pass).  So T is sized for `mt_rep` copies first; the records the extra workgroups
-                // re-read come out of the XCD's L2 (all class tree groups of a row block run on one XCD at the same time).
-                const long long rep_target = std::max(1, sw.mt_rep);
-                const long long t_nodes = std::max<long long>(win, cap / rep_target);
-                int T = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(t_nodes / win, MT_MAX_T), std::min<long long>(K, MT_RT_BUDGET / (2 * worst))));
-                if (sw.mt_T >= 1) T = std::max(1, std::min(T, sw.mt_T));
-                // Feature rotation of the histogram updates (rgbm_level.h, MT_ROT) for the launches whose LDS holds fewer than eight copies (RGBM_MT_ROT_COPIES2 / 2) of their
-                // worst-case histograms -- the deepest dense levels, where rows of one cluster pile up on one address per feature: measured -11 % at
-                // level 5 of the K = 64 target and +35-60 % where there IS room for replicas (profiles/r5c_*), hence per launch.  Plain one-chunk pass only.
-                const bool plain1 = (!acc2 && nchunk == 1 && !spec && mt_thr == LV_THREADS) || (acc2 && spec);      // the two instantiations that exist with rotation
-                // (a rotated step works on sixteen feature slots per chunk whatever the chunk holds: with few features most lanes of a step idle -- rotate only chunks
-                // that fill at least three quarters of them)
-                const bool rot_full = cmeta[ch].nfeat >= 12 && (!acc2 || cmeta[1].nfeat >= 12);
-                // ... and (round 6) where the replicated layout would leave the workgroup fewer than RGBM_MT_ROT_TMIN (2: a single one) class trees although one copy holds at least twice
-                // as many: every doubling of the class trees per workgroup is ~5 % of a deep level (the records are read once per T steps), which eight copies do not buy back
-                const long long cap_rot1 = std::min<long long>(hist_room / (node_bytes + mt_rot_dummy(true) * 16), MT_MAX_NODES);
-                const long long T_rot1 = std::min<long long>(std::min<long long>(cap_rot1 / win, MT_MAX_T), std::min<long long>(K, MT_RT_BUDGET / (2 * worst)));
-                const bool few_trees = T < sw.mt_rot_tmin && T_rot1 >= 2 * (long long)T;
-                const bool rot = plain1 && (sw.mt_rot == 1 || (sw.mt_rot < 0 && rot_full && (cap * 2 < (long long)sw.mt_rot_copies2 * T * win || few_trees))) &&
-                                 (long long)T * win * (node_bytes + mt_rot_dummy(true) * 16) <= hist_room;
-                // a rotated launch needs ONE copy: as many class trees per workgroup as the LDS holds (RGBM_MT_ROT_T=0: keep the T sized for replication)
-                if (rot && sw.mt_rot_T && sw.mt_T < 1) {
-                    const long long cap_rot = std::min<long long>(hist_room / (node_bytes + mt_rot_dummy(true) * 16), MT_MAX_NODES);
-                    T = (int)std::max<long long>(T, std::min<long long>(std::min<long long>(cap_rot / win / std::max(1, sw.mt_rot_tdiv), MT_MAX_T), std::min<long long>(K, MT_RT_BUDGET / (2 * worst))));
-                }
-                const int G = (K + T - 1) / T;
-                if (ch == 0) G_first = G;
-                for (int s0 = 0; s0 < worst; s0 += win)
-                    mt_plan[level].push_back(MtLaunch{ch, s0, win, (ch == 0 && s0 == 0) ? 1 : 0, T, G, 0, acc2 ? 1 : 0, rot ? 1 : 0});
-            }
-            const long long gmin = std::max<long long>(1, (N + (1ll << 22) - 1) >> 22);
-            // row blocks per class tree: a multiple of 8 (one XCD each); G * gx workgroups should fill whole rounds of 256 CUs (G = 24: 8 row
-            // blocks leave a quarter of the chip idle, 32 make three full rounds) without cutting the table into slivers
-            const long long nwt = (N + MT_WT_ROWS - 1) / MT_WT_ROWS;
-            const long long gx_lo = std::max<long long>(8, (gmin + 7) / 8 * 8), gx_hi = std::max<long long>(gx_lo, std::min<long long>(512, (nwt / (4 * (LV_THREADS / 64)) + 7) / 8 * 8));
-            long long gx = gx_lo; double best = -1.0;
-            for (long long g = gx_lo; g <= gx_hi; g += 8) {
-                const long long tot = g * G_first, rounds = (tot + 255) / 256;
-                const double eff = (double)tot / (double)(rounds * 256) - 0.01 * (double)rounds;   // fuller rounds first, then fewer of them
-                if (eff > best + 1e-9) { best = eff; gx = g; }
-                if (tot >= 256 && (double)tot / (double)(rounds * 256) >= 0.97) break;
-            }
-            if (sw.mt_blocks >= 1) gx = (sw.mt_blocks + 7) / 8 * 8;
-            mt_gx[level] = (int)gx;
-            for (auto& L : mt_plan[level]) L.gx = (int)gx;
-            part_items = std::max(part_items, (size_t)K * (size_t)gx * (size_t)worst);
-        }
-        if (sw.timing) for (int level = 1; level < p.max_depth; ++level) for (const auto& L : mt_plan[level])
-            fprintf(stderr, "[rgbm] level %d launch: chunk %d slots %d..%d route %d T %d G %d gx %d acc2 %d rot %d\n", level, L.ch, L.slot0, L.slot0 + L.nslots - 1, L.route, L.T, L.G, L.gx, L.acc2, L.rot);
-        {
-            size_t prog_words = 0;
-            for (int level = 1; level < p.max_depth; ++level) for (const auto& L : mt_plan[level]) prog_words = std::max(prog_words, (size_t)L.G * (size_t)L.gx);
-            d_prog.alloc(std::max<size_t>(prog_words, 1)); d_prog.zero(s);
-        }
+        passes = plan_level_passes(sw, fmeta, cmeta, N, K, p.max_depth, wm, lc.lds_bytes);
+        lc.gx = passes.root_gx; lc.xcd_blocks = 1; lc.max_built = 1;
         d_node.alloc((size_t)K * lc.NS);
         // the padding rows [N, NS) of every class tree stay LV_INACTIVE for the whole fit (the gradient kernels reset rows < N only): the level pass
         // routes rows by their id alone, and an id past the end of a class tree's table takes the dummy entry
         HIPCHK(hipMemsetAsync(d_node.p, 0xFF, (size_t)K * lc.NS, s));
         d_plan.alloc(K); d_snodes.alloc((size_t)K * 256); d_lcand.alloc((size_t)K * 256 * F);
-        d_part.alloc(part_items * tc.totbins); d_lpool.alloc((size_t)K * n_hnodes * tc.totbins);
+        d_part.alloc(passes.part_items * tc.totbins); d_lpool.alloc((size_t)K * n_hnodes * tc.totbins);
         d_count.alloc((size_t)K * 256); use_reduce = dp || lc.gx > 4;
         if (dp) d_count_g.alloc((size_t)K * 256);
         const int max_built_all = 1 << std::max(0, p.max_depth - 2);
         d_part_red.alloc((size_t)K * max_built_all * tc.totbins + (size_t)K * 128 /* K*256 int64 counts */);
         d_leafnode.alloc((size_t)K * LV_MAX_LEAVES); d_err.alloc(1); d_err.zero(s); d_ndelta.alloc((size_t)K * 256); d_statrows.alloc(1); d_statrows.zero(s);
-        // Joint bins for the root pass (the tables where the root pass runs at the LDS-atomic rate).  Best-fit-decreasing packing of the
-        // features into groups whose bin counts multiply to <= 256; worth it when it saves at least two atomics per row and the groups
-        // fit one 16-byte record.  RGBM_JOINT_ROOT=0 disables it (same models either way: the sums are exact integers).
-        joint_root = sw.joint_root && ((long long)K * N >= (1ll << 21) || (wm && nchunk == 2));
-        if (joint_root) {
-            std::vector<int> order(F); for (int f = 0; f < F; ++f) order[f] = f;
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return fmeta[a].nbins > fmeta[b].nbins; });
-            std::vector<std::vector<int>> groups; std::vector<int> prod;
-            auto pack = [&](int cap, std::vector<std::vector<int>>& gs, std::vector<int>& pr) {      // best-fit-decreasing into groups whose bin counts multiply to <= cap
-                gs.clear(); pr.clear();
-                for (int f : order) {
-                    int best = -1;
-                    for (size_t g = 0; g < gs.size(); ++g)
-                        if ((long long)pr[g] * fmeta[f].nbins <= cap && (best < 0 || pr[g] > pr[best])) best = (int)g;
-                    if (best < 0) { gs.emplace_back(); pr.push_back(1); best = (int)gs.size() - 1; }
-                    gs[best].push_back(f); pr[best] *= fmeta[f].nbins;
-                }
-            };
-            pack(256, groups, prod);
-            // WIDE joint codes (round 5): 16-bit fields, groups of up to 1024 joint bins, at most eight per 16-byte record -- fewer groups = fewer atomics per row
-            // (the synthetic table: 5 groups instead of 7, 10 atomics instead of 14) as long as two copies of the joint histograms fit the LDS
-            {
-                std::vector<std::vector<int>> gw; std::vector<int> pw;
-                pack(JOINT_WIDE_CAP, gw, pw);
-                long long slots2 = 0; for (int v : pw) slots2 += (long long)v * 2;
-                if (sw.joint_wide && !wm && gw.size() <= 8 && gw.size() + 2 <= groups.size() && slots2 * 16 + LV_ROOT_FIXED <= lc.lds_bytes) { groups.swap(gw); prod.swap(pw); joint_wide = true; }
-            }
-            const int VF = (int)groups.size();
-            if (VF > (joint_wide ? 8 : (wm ? 15 : 16)) || VF > F - 2) joint_root = false;
-            else {
-                std::vector<FeatMeta> vfm(VF); std::vector<JointFeat> jf(F); std::vector<int16_t> binfeat(tc.totbins, 0);
-                ChunkMeta vcm; vcm.first_feat = 0; vcm.nfeat = VF; vcm.fast_slots = 0; vcm.wide_bins = 0;
-                for (int v = 0; v < VF; ++v) {
-                    FeatMeta& m = vfm[v]; memset(&m, 0, sizeof(m));
-                    m.V = prod[v]; m.has_nan = 0; m.nbins = prod[v]; m.hoff = vcm.wide_bins; m.wide_off = vcm.wide_bins;
-                    int sh = 0; while (sh < 5 && (m.nbins << (sh + 1)) <= 256) ++sh;
-                    m.rep_shift = sh; m.fast_base = vcm.fast_slots; vcm.fast_slots += m.nbins << sh; vcm.wide_bins += m.nbins;
-                    int stride = 1;
-                    for (int f : groups[v]) {
-                        JointFeat& j = jf[f]; memset(&j, 0, sizeof(j));
-                        j.voff = m.hoff; j.stride = stride; j.nbins = fmeta[f].nbins; j.nbv = prod[v]; j.hoff = fmeta[f].hoff; j.vbyte = v;
-                        stride *= fmeta[f].nbins;
-                        for (int b = 0; b < fmeta[f].nbins; ++b) binfeat[fmeta[f].hoff + b] = (int16_t)f;
-                    }
-                }
-                vtotbins = vcm.wide_bins;
-                if ((long long)lv_slots(vfm.data(), VF, 0) * 16 + LV_ROOT_FIXED > lc.lds_bytes) joint_root = false;
-                else {
-                    d_vfmeta.alloc(VF); d_vfmeta.upload(vfm.data(), VF, s); d_vcmeta.alloc(1); d_vcmeta.upload(&vcm, 1, s);
-                    d_jf.alloc(F); d_jf.upload(jf.data(), F, s); d_binfeat.alloc(binfeat.size()); d_binfeat.upload(binfeat.data(), binfeat.size(), s);
-                    d_rec_j.alloc((size_t)N);
-                    hipLaunchKernelGGL(k_pack_joint, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_rec.p, (long long)N, F, d_jf.p, d_rec_j.p, joint_wide ? 1 : 0, wm ? nchunk - 1 : -1);
-                    d_part_j.alloc((size_t)K * lc.gx * vtotbins); d_red_j.alloc((size_t)K * vtotbins + (size_t)K * 128 /* k_level_reduce parks the counts behind the bins */);
-                    lcj = lc; lcj.nchunk = 1; lcj.F = VF; lcj.totbins = vtotbins; lcj.max_built = 1;
-                    use_reduce = true;
-                    HIPCHK(hipStreamSynchronize(s));   // the vectors above are locals
-                }
+        // Joint bins for the root pass (the tables where the root pass runs at the LDS-atomic rate); RGBM_JOINT_ROOT=0 disables it (same
+        // models either way: the sums are exact integers)
+        if (sw.joint_root && ((long long)K * N >= (1ll << 21) || (wm && nchunk == 2))) {
+            const JointRootPlan jp = plan_joint_root(fmeta, tc.totbins, wm, lc.lds_bytes);
+            if (jp.on) {
+                const int VF = (int)jp.vfm.size();
+                joint_root = true; vtotbins = jp.vcm.wide_bins;
+                d_vfmeta.alloc(VF); d_vfmeta.upload(jp.vfm.data(), VF, s); d_vcmeta.alloc(1); d_vcmeta.upload(&jp.vcm, 1, s);
+                d_jf.alloc(F); d_jf.upload(jp.jf.data(), F, s); d_binfeat.alloc(jp.binfeat.size()); d_binfeat.upload(jp.binfeat.data(), jp.binfeat.size(), s);
+                d_rec_j.alloc((size_t)N);
+                hipLaunchKernelGGL(k_pack_joint, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_rec.p, (long long)N, F, d_jf.p, d_rec_j.p, wm ? nchunk - 1 : -1);
+                d_part_j.alloc((size_t)K * lc.gx * vtotbins); d_red_j.alloc((size_t)K * vtotbins + (size_t)K * 128 /* k_level_reduce parks the counts behind the bins */);
+                lcj = lc; lcj.nchunk = 1; lcj.F = VF; lcj.totbins = vtotbins; lcj.max_built = 1;
+                use_reduce = true;
+                HIPCHK(hipStreamSynchronize(s));   // jp's vectors are locals
             }
         }
         if (wm && nchunk == 2 && !joint_root)
             throw std::invalid_argument("a two-chunk table with row multiplicities needs the joint-bin root pass (its record carries the multiplicity); this feature set does not pack into 15 groups");
-        // once per process and device: the attribute belongs to the function, not to the call, and other threads are launching these
-        // kernels while a new training call sets up
-        {
-            static std::mutex attr_mu; static std::vector<char> attr_done(64, 0);
-            std::lock_guard<std::mutex> lk(attr_mu);
-            if (!attr_done[tab.device & 63]) {
-                HIPCHK(hipFuncSetAttribute((const void*)k_level_root<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LV_LDS_BYTES));
-                HIPCHK(hipFuncSetAttribute((const void*)k_level_root<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LV_LDS_BYTES));
-#define RGBM_MT_ATTR1(NCHR, BAG, ROUTE, THR, ACC, ...) HIPCHK(hipFuncSetAttribute((const void*)k_level_mt<NCHR, BAG, ROUTE, THR, ACC, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, LV_LDS_BYTES))
-#define RGBM_MT_ATTR(NCHR, THR, ACC, SPEC) RGBM_MT_ATTR1(NCHR, false, true, THR, ACC, SPEC); RGBM_MT_ATTR1(NCHR, false, false, THR, ACC, SPEC); \
-                                           RGBM_MT_ATTR1(NCHR, true, true, THR, ACC, SPEC); RGBM_MT_ATTR1(NCHR, true, false, THR, ACC, SPEC)
-                RGBM_MT_ATTR(0, LV_THREADS, false, false); RGBM_MT_ATTR(1, LV_THREADS, false, false); RGBM_MT_ATTR(2, LV_THREADS, false, false);
-                RGBM_MT_ATTR(2, MT_THREADS_ACC2, true, false); RGBM_MT_ATTR(1, 768, false, false);
-                RGBM_MT_ATTR(1, LV_THREADS, false, true); RGBM_MT_ATTR(2, MT_THREADS_ACC2, true, true);
-                RGBM_MT_ATTR1(1, false, true, LV_THREADS, false, false, true); RGBM_MT_ATTR1(1, false, false, LV_THREADS, false, false, true);
-                RGBM_MT_ATTR1(1, true, true, LV_THREADS, false, false, true); RGBM_MT_ATTR1(1, true, false, LV_THREADS, false, false, true);
-                RGBM_MT_ATTR1(2, false, true, MT_THREADS_ACC2, true, true, true); RGBM_MT_ATTR1(2, false, false, MT_THREADS_ACC2, true, true, true);
-                RGBM_MT_ATTR1(2, true, true, MT_THREADS_ACC2, true, true, true); RGBM_MT_ATTR1(2, true, false, MT_THREADS_ACC2, true, true, true);
-#undef RGBM_MT_ATTR
-#undef RGBM_MT_ATTR1
-                attr_done[tab.device & 63] = 1;
-            }
+        if (sw.timing) {
+            fprintf(stderr, "[rgbm] root: gx %d joint %d groups %d\n", lc.gx, joint_root ? 1 : 0, joint_root ? lcj.F : 0);
+            for (int level = 1; level < p.max_depth; ++level) for (const auto& L : passes.mt[level])
+                fprintf(stderr, "[rgbm] level %d launch: chunk %d slots %d..%d route %d T %d G %d gx %d acc2 %d rot %d\n", level, L.ch, L.slot0, L.slot0 + L.nslots - 1, L.route, L.T, L.G, L.gx, L.acc2, L.rot);
         }
+        set_level_lds_attributes(tab.device);
     }
     const size_t NT = (size_t)NE * K;
     DevBuf<int32_t> t_L(NT), t_feat(NT * (NL - 1)), t_theta(NT * (NL - 1)), t_dleft(NT * (NL - 1)), t_left(NT * (NL - 1)), t_right(NT * (NL - 1)), t_cnt(NT * NL);
@@ -1232,99 +1392,43 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     const int grad_gx = (int)std::min<long long>((N + 255) / 256, 4096);
     const size_t upd_lds = (size_t)(3 * NL + (NL & 1)) * 4 + (size_t)NL * 8;
 
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> hist_ev;   // only when stats are requested
-    std::vector<char> hist_ev_root;
-    auto launch_hist = [&](bool root) {
-        hipEvent_t a = nullptr, b = nullptr;
-        if (stats) { HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b)); HIPCHK(hipEventRecord(a, s)); }
-        hipLaunchKernelGGL(k_hist, dim3(hist_gx, K, nchunk), dim3(256), lds_hist, s, d_rec.p, d_gh.p, d_idx0.p, d_idx1.p, d_base.p,
-                           d_state.p, d_pool.p, d_fmeta.p, d_cmeta.p, d_fxs.p, tc);
-        if (stats) { HIPCHK(hipEventRecord(b, s)); hist_ev.emplace_back(a, b); hist_ev_root.push_back(root ? 1 : 0); }
-    };
-
+    HistTimers timers{stats != nullptr, s};
     const int score_gx = (int)std::max<long long>(1, std::min<long long>((N + 1023) / 1024, (2048 + K - 1) / K));
-    const int last_gx = (int)std::max<long long>(1, std::min<long long>((N + 4095) / 4096, (2048 + K - 1) / K));      // k_level_last: 16 rows per thread and step
-    const bool defer_score = sw.defer_score;
-    auto timed = [&](bool root, auto&& fn) {   // HIP events around one histogram launch, on the stream it is launched on
-        hipEvent_t a = nullptr, b = nullptr;
-        if (stats) { HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b)); HIPCHK(hipEventRecord(a, s)); }
-        fn();
-        if (stats) { HIPCHK(hipEventRecord(b, s)); hist_ev.emplace_back(a, b); hist_ev_root.push_back(root ? 1 : 0); }
-    };
     auto launch_root = [&]() {
-        timed(true, [&]() {
-            if (joint_root && joint_wide)
-                hipLaunchKernelGGL(k_level_root<true>, dim3((unsigned)lc.gx * (unsigned)K, 1, 1), dim3(LV_THREADS), lc.lds_bytes, s, d_rec_j.p, d_gh.p, d_node.p, d_plan.p, d_part_j.p,
-                                   d_vfmeta.p, d_vcmeta.p, d_fxs.p, lcj);
-            else if (joint_root)   // the root pass over the joint record: one pair of atomics per feature GROUP and row
-                hipLaunchKernelGGL(k_level_root<false>, dim3((unsigned)lc.gx * (unsigned)K, 1, 1), dim3(LV_THREADS), lc.lds_bytes, s, d_rec_j.p, d_gh.p, d_node.p, d_plan.p, d_part_j.p,
+        timers.timed(true, [&]() {
+            if (joint_root)   // the root pass over the joint record: one pair of atomics per feature GROUP and row
+                hipLaunchKernelGGL(k_level_root, dim3((unsigned)lc.gx * (unsigned)K, 1, 1), dim3(LV_THREADS), lc.lds_bytes, s, d_rec_j.p, d_gh.p, d_node.p, d_plan.p, d_part_j.p,
                                    d_vfmeta.p, d_vcmeta.p, d_fxs.p, lcj);
             else
-                hipLaunchKernelGGL(k_level_root<false>, dim3((unsigned)lc.gx * (unsigned)K, 1, nchunk), dim3(LV_THREADS), lc.lds_bytes, s, d_rec.p, d_gh.p, d_node.p, d_plan.p, d_part.p,
+                hipLaunchKernelGGL(k_level_root, dim3((unsigned)lc.gx * (unsigned)K, 1, nchunk), dim3(LV_THREADS), lc.lds_bytes, s, d_rec.p, d_gh.p, d_node.p, d_plan.p, d_part.p,
                                    d_fmeta.p, d_cmeta.p, d_fxs.p, lc);
         });
     };
     // the k_level_mt launches of one level; returns the LevelConst that describes the partials they wrote
     auto launch_level = [&](int level) -> LevelConst {
         LevelConst ll = lc;
-        ll.xcd_blocks = 0; ll.gx = mt_gx[level]; ll.max_built = 1 << (level - 1);
-        for (const MtLaunch& L : mt_plan[level]) {
+        ll.xcd_blocks = 0; ll.gx = passes.mt_gx[level]; ll.max_built = 1 << (level - 1);
+        for (const MtLaunch& L : passes.mt[level]) {
             LevelConst l1 = ll;
             l1.mt_T = L.T; l1.mt_G = L.G; l1.mt_ch = L.ch; l1.mt_slot0 = L.slot0; l1.mt_nslots = L.nslots; l1.mt_route = L.route; l1.mt_sparse = sw.mt_sparse ? 1 : 0;
-            // lock-step of the class-tree groups of a row block (wave-specialised pass): window in tile rounds, one round = 8 wave tiles of records
-            // off by default: measured -63 % HBM fetch and +23 % time on 100M x 32 (profiles/r5e_*): the pass is not bound by that traffic
-            l1.mt_window = sw.mt_lock < 0 ? 0 : sw.mt_lock;
-            l1.mt_epoch = (mt_epoch++ % 4095u) + 1u;      // (never 0: the words start zeroed)
-            const dim3 grid((unsigned)L.G * (unsigned)L.gx);
-            const int nchr = nchunk == 1 ? 1 : (nchunk == 2 ? 2 : 0);
-            timed(false, [&]() {
-#define RGBM_LAUNCH_MT2(NCHR, BAG, INBAG, THR, ACC, ...) do { if (L.route) hipLaunchKernelGGL((k_level_mt<NCHR, BAG, true, THR, ACC, __VA_ARGS__>), grid, dim3(THR), LV_LDS_BYTES /* (always the CU's whole LDS: the hessian sums sit a compile-time distance behind the gradient sums; lc.lds_bytes, the test hook, only sizes the histograms) */, s, d_rec.p, d_gh.p, d_node.p, (const uint8_t*)(INBAG), d_plan.p, \
-                                                                          d_part.p, d_count.p, d_fmeta.p, d_cmeta.p, d_err.p, d_prog.p, d_fxs.p, l1); \
-                                           else hipLaunchKernelGGL((k_level_mt<NCHR, BAG, false, THR, ACC, __VA_ARGS__>), grid, dim3(THR), LV_LDS_BYTES, s, d_rec.p, d_gh.p, d_node.p, (const uint8_t*)(INBAG), d_plan.p, \
-                                                                   d_part.p, d_count.p, d_fmeta.p, d_cmeta.p, d_err.p, d_prog.p, d_fxs.p, l1); } while (0)
-#define RGBM_LAUNCH_MT(NCHR, THR, ACC, ...) do { if (use_bagging) RGBM_LAUNCH_MT2(NCHR, true, d_inbag.p, THR, ACC, __VA_ARGS__); else RGBM_LAUNCH_MT2(NCHR, false, nullptr, THR, ACC, __VA_ARGS__); } while (0)
-                if (L.acc2) { if (sw.mt_spec != 0 && L.rot) RGBM_LAUNCH_MT(2, MT_THREADS_ACC2, true, true, true); else if (sw.mt_spec != 0) RGBM_LAUNCH_MT(2, MT_THREADS_ACC2, true, true); else RGBM_LAUNCH_MT(2, MT_THREADS_ACC2, true, false); }
-                else if (nchr == 1 && sw.mt_spec == 1) RGBM_LAUNCH_MT(1, LV_THREADS, false, true);
-                else if (nchr == 1 && sw.mt_threads == 768) RGBM_LAUNCH_MT(1, 768, false, false);
-                else if (nchr == 1 && L.rot) RGBM_LAUNCH_MT(1, LV_THREADS, false, false, true);
-                else if (nchr == 1) RGBM_LAUNCH_MT(1, LV_THREADS, false, false);
-                else if (nchr == 2) RGBM_LAUNCH_MT(2, LV_THREADS, false, false);
-                else RGBM_LAUNCH_MT(0, LV_THREADS, false, false);
-#undef RGBM_LAUNCH_MT2
-#undef RGBM_LAUNCH_MT
+            const bool acc2 = L.acc2 != 0;
+            const MtForm form{acc2 ? 2 : (nchunk <= 2 ? nchunk : 0), acc2 ? MT_THREADS_ACC2 : LV_THREADS, acc2, acc2, L.rot != 0};
+            timers.timed(false, [&]() {
+                launch_level_mt(form, use_bagging, L.route != 0, dim3((unsigned)L.G * (unsigned)L.gx), s, d_rec.p, d_gh.p, d_node.p, use_bagging ? d_inbag.p : nullptr,
+                                d_plan.p, d_part.p, d_count.p, d_fmeta.p, d_cmeta.p, d_err.p, d_fxs.p, l1);
             });
         }
         return ll;
     };
 
     DevBuf<int32_t> d_it(1); d_it.zero(s);   // device-side iteration counter (k_next_iteration)
-    // RGBM_TRACE=<dir> (debugging; with RGBM_TRACE_K=<class trees> and RGBM_TRACE_ITERS=lo:hi): snapshots of the grower's state after every
-    // level of the iterations lo..hi and a checksum of (score, g/h, node ids) after every iteration, written to <dir>/target<col>.{bin,idx}
-    const char* trace_dir = getenv("RGBM_TRACE");
-    const bool trace_on = trace_dir && level_mode && (!getenv("RGBM_TRACE_K") || atoi(getenv("RGBM_TRACE_K")) == K);
-    int trace_lo = 44, trace_hi = 44, cur_it = 0;
-    if (trace_on && getenv("RGBM_TRACE_ITERS")) sscanf(getenv("RGBM_TRACE_ITERS"), "%d:%d", &trace_lo, &trace_hi);
-    struct TraceRec { std::string name; int it, level; size_t off, bytes; };
-    std::vector<TraceRec> trace_idx; size_t trace_used = 0;
-    DevBuf<unsigned char> d_trace;
-    if (trace_on) d_trace.alloc(((size_t)K * n_hnodes * tc.totbins * 16 + (size_t)K * 256 * (sizeof(SNode) + 4) + (size_t)K * sizeof(LvPlan) + 4096) * (size_t)(p.max_depth + 1) * (size_t)(trace_hi - trace_lo + 1) + (size_t)NE * 64 + 4096);
-    auto trace_copy = [&](const char* name, int level, const void* src, size_t bytes) {
-        if (!trace_on || cur_it < trace_lo || cur_it > trace_hi) return;
-        if (trace_used + bytes > d_trace.n) return;
-        HIPCHK(hipMemcpyAsync(d_trace.p + trace_used, src, bytes, hipMemcpyDeviceToDevice, s));
-        trace_idx.push_back({name, cur_it, level, trace_used, bytes}); trace_used += (bytes + 15) & ~(size_t)15;
-    };
-    auto trace_sum = [&](const char* name, const void* src, size_t bytes) {
-        if (!trace_on || trace_used + 16 > d_trace.n) return;
-        HIPCHK(hipMemsetAsync(d_trace.p + trace_used, 0, 8, s));
-        hipLaunchKernelGGL(k_trace_sum, dim3(2048), dim3(256), 0, s, (const unsigned long long*)src, bytes / 8, (unsigned long long*)(d_trace.p + trace_used));
-        trace_idx.push_back({name, cur_it, -1, trace_used, 8}); trace_used += 16;
-    };
+    LevelTrace trace(level_mode, K, s);
+    if (trace.on) trace.buf.alloc(((size_t)K * n_hnodes * tc.totbins * 16 + (size_t)K * 256 * (sizeof(SNode) + 4) + (size_t)K * sizeof(LvPlan) + 4096) * (size_t)(p.max_depth + 1) * (size_t)(trace.hi - trace.lo + 1) + (size_t)NE * 64 + 4096);
     auto trace_level = [&](int level) {
-        trace_copy("count", level, d_count.p, (size_t)K * 256 * 4);
-        trace_copy("plan", level, d_plan.p, (size_t)K * sizeof(LvPlan));
-        trace_copy("snodes", level, d_snodes.p, (size_t)K * 256 * sizeof(SNode));
-        trace_copy("lpool", level, d_lpool.p, (size_t)K * n_hnodes * tc.totbins * 16);
+        trace.copy("count", level, d_count.p, (size_t)K * 256 * 4);
+        trace.copy("plan", level, d_plan.p, (size_t)K * sizeof(LvPlan));
+        trace.copy("snodes", level, d_snodes.p, (size_t)K * 256 * sizeof(SNode));
+        trace.copy("lpool", level, d_lpool.p, (size_t)K * n_hnodes * tc.totbins * 16);
     };
     // one boosting iteration of the level grower after the gradients: an iteration-invariant launch sequence
     auto enqueue_level_growth = [&]() {
@@ -1364,17 +1468,13 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
             // last level: plan -> replay (leaf values never depend on the deepest counts) -> route + count + score in one pass
             hipLaunchKernelGGL(k_level_plan, dim3(K), dim3(256), 0, s, d_plan.p, d_snodes.p, d_lcand.p, d_fmeta.p, p.max_depth, tc, lc);
             hipLaunchKernelGGL(k_level_replay, dim3(K), dim3(64), 0, s, d_plan.p, d_snodes.p, cntg, to, d_init.p, d_ndelta.p, d_leafnode.p, d_any.p, d_err.p, d_it.p, tc);
-            // AddScore: the pass that routes, counts and adds in one (k_level_final).  RGBM_DEFER_SCORE=1 (measured slower, off): folded into the NEXT iteration's
-            // gradient kernel, with k_level_last for the last routing step + the deepest counts; the last iteration has no next one and keeps k_level_final
-            if (defer_score && cur_it + 1 < NE)
-                hipLaunchKernelGGL(k_level_last, dim3(last_gx, K), dim3(256), 0, s, d_rec.p, d_node.p, use_bagging ? d_inbag.p : (const uint8_t*)nullptr, d_plan.p, to, d_count.p, d_it.p, lc);
-            else
+            // AddScore: the pass that routes, counts and adds in one
             hipLaunchKernelGGL(k_level_final, dim3(score_gx, K), dim3(256), 0, s, d_rec.p, d_node.p, use_bagging ? d_inbag.p : (const uint8_t*)nullptr,
                                d_plan.p, to, d_ndelta.p, d_score.p, d_count.p, d_it.p, lc);
             if (dp) { hipLaunchKernelGGL(k_copy_i32, dim3(K), dim3(256), 0, s, d_count.p, d_count_g.p, (long long)K * 256); all_reduce(d_count_g.p, (size_t)K * 256, AR_I32, s); }
             hipLaunchKernelGGL(k_level_leafcount, dim3(K), dim3(LV_MAX_LEAVES), 0, s, d_plan.p, cntg, d_leafnode.p, to, d_it.p, tc);
             trace_level(p.max_depth);
-            trace_sum("score", d_score.p, (size_t)K * N * 8); trace_sum("node", d_node.p, (size_t)K * lc.NS);
+            trace.sum("score", d_score.p, (size_t)K * N * 8); trace.sum("node", d_node.p, (size_t)K * lc.NS);
     };
 
     // numerics v2.2: every class tree of an iteration gets its own fixed-point grid from the coarse sums Q_g, Q_h of its (g, h) (rgbm_numerics.h).  The
@@ -1390,16 +1490,13 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
         const uint8_t* inbag = use_bagging ? d_inbag.p : nullptr;
         uint8_t* node0 = level_mode ? d_node.p : nullptr;
         unsigned long long* qp = fx_fused ? d_qpart.p : nullptr;
-        // level grower: the AddScore of the previous iteration's trees rides in this kernel (PendingScore, rgbm_kernels.h)
-        PendingScore pd{nullptr, nullptr, nullptr, 0};
-        if (level_mode && defer_score && cur_it > 0) pd = PendingScore{d_node.p, d_ndelta.p, to.L + (size_t)(cur_it - 1) * K, lc.NS};
-        if (obj == 0) hipLaunchKernelGGL(k_grad<0>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, pd, tc);
+        if (obj == 0) hipLaunchKernelGGL(k_grad<0>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
         else if (mc_rows)
-            hipLaunchKernelGGL(k_grad_mc_rows<256>, dim3((unsigned)((N + 255) / 256)), dim3(256), (size_t)K * 256 * 8, s, d_score.p, d_ycol, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, pd, tc);
+            hipLaunchKernelGGL(k_grad_mc_rows<256>, dim3((unsigned)((N + 255) / 256)), dim3(256), (size_t)K * 256 * 8, s, d_score.p, d_ycol, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
         else if (mc_tile)
-            hipLaunchKernelGGL(k_grad_mc, dim3((unsigned)((N + 63) / 64)), dim3(256), (size_t)(K * 64 + 320) * 8, s, d_score.p, d_ycol, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, pd, tc);
-        else if (obj == 1) hipLaunchKernelGGL(k_grad<1>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, (unsigned long long*)nullptr, d_mult, pd, tc);
-        else hipLaunchKernelGGL(k_grad<2>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, pd, tc);
+            hipLaunchKernelGGL(k_grad_mc, dim3((unsigned)((N + 63) / 64)), dim3(256), (size_t)(K * 64 + 320) * 8, s, d_score.p, d_ycol, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
+        else if (obj == 1) hipLaunchKernelGGL(k_grad<1>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, (unsigned long long*)nullptr, d_mult, tc);
+        else hipLaunchKernelGGL(k_grad<2>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
         if (fx_fused) {
             const long long total = fx_parts * K * 2;
             const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(256, (total + 8191) / 8192));
@@ -1430,9 +1527,9 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     };
     for (int it = 0; it < NE; ++it) {
         if (use_bagging && it % p.bagging_freq == 0) enqueue_bagging();
-        cur_it = it;
+        trace.cur_it = it;
         enqueue_grad();
-        trace_sum("gh", d_gh.p, (size_t)K * tc.NG * 8);
+        trace.sum("gh", d_gh.p, (size_t)K * tc.NG * 8);
         const uint8_t* usedp = d_used.p + (size_t)it * K * F;
         if (level_mode) {
             enqueue_level_growth();
@@ -1441,7 +1538,10 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
         }
         hipLaunchKernelGGL(k_init_iter, dim3(K), dim3(64), 0, s, d_state.p, d_leaves.p, d_pool.p, to, n_in_ptr, it, tc);
         for (int step = 0; step < NL - 1; ++step) {
-            launch_hist(step == 0);
+            timers.timed(step == 0, [&]() {
+                hipLaunchKernelGGL(k_hist, dim3(hist_gx, K, nchunk), dim3(256), lds_hist, s, d_rec.p, d_gh.p, d_idx0.p, d_idx1.p, d_base.p,
+                                   d_state.p, d_pool.p, d_fmeta.p, d_cmeta.p, d_fxs.p, tc);
+            });
             hipLaunchKernelGGL(k_split_find, dim3((F + 3) / 4, K), dim3(256), 0, s, d_pool.p, d_state.p, d_leaves.p, d_fmeta.p, usedp, d_cand.p, d_fxs.p, tc);
             hipLaunchKernelGGL(k_tree_step, dim3(K), dim3(64), 0, s, d_state.p, d_leaves.p, d_cand.p, d_pool.p, d_fmeta.p, to, it, tc);
             hipLaunchKernelGGL(k_partition, dim3(part_gx, K), dim3(256), 0, s, reinterpret_cast<const uint8_t*>(d_rec.p), d_idx0.p, d_idx1.p, d_base.p, d_state.p, tc);
@@ -1468,83 +1568,16 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     HIPCHK(hipEventRecord(ev_end, s));
     if (dp) stream_sync_watchdog(s); else HIPCHK(hipStreamSynchronize(s));
     if (timing) fprintf(stderr, "[rgbm] target %d K=%d: count+bins %.1f ms, alloc+pack %.1f ms, enqueue %.1f ms, drain+download %.1f ms\n", target_col, K, t_bins - t_start, t_setup - t_bins, t_enq - t_setup, now() - t_enq);
-    if (trace_on && trace_used) {
-        std::vector<unsigned char> h(trace_used);
-        HIPCHK(hipMemcpy(h.data(), d_trace.p, trace_used, hipMemcpyDeviceToHost));
-        char path[512];
-        snprintf(path, sizeof(path), "%s/target%d.bin", trace_dir, target_col);
-        if (FILE* f = fopen(path, "wb")) { fwrite(h.data(), 1, h.size(), f); fclose(f); }
-        snprintf(path, sizeof(path), "%s/target%d.idx", trace_dir, target_col);
-        if (FILE* f = fopen(path, "w")) { for (const auto& r : trace_idx) fprintf(f, "%s %d %d %zu %zu\n", r.name.c_str(), r.it, r.level, r.off, r.bytes); fclose(f); }
-    }
+    trace.write(target_col);
     if (h_err & 2) throw std::runtime_error("level grower: a level pass was launched with more built nodes / route entries than its workgroup tables hold (sizing violated)");
     if (h_err) throw std::runtime_error("level grower: a node outside the speculative expansion was selected (expansion bound violated)");
 
     HostTrees ht{hL.data(), hfeat.data(), htheta.data(), hdleft.data(), hleft.data(), hright.data(), hcnt.data(), hgain.data(), hval.data(), hany.data()};
     model_from_trees(model, ht, NE, K, NL);
     if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end)); stats->total_ms = ms;
-        stats->hist_launches = (int64_t)hist_ev.size();
-        for (size_t i = 0; i < hist_ev.size(); ++i) {
-            float m2 = 0.f; HIPCHK(hipEventElapsedTime(&m2, hist_ev[i].first, hist_ev[i].second));
-            stats->hist_ms += m2; if (hist_ev_root[i]) stats->root_ms += m2;
-            (void)hipEventDestroy(hist_ev[i].first); (void)hipEventDestroy(hist_ev[i].second);
-        }
-        if (level_mode) {
-            // rows whose (g,h) were accumulated: counted on the device (k_level_split); root passes = trees with a searched root
-            int64_t root_rows = 0;
-            const bool root_done = n_train >= (int64_t)p.min_data_in_leaf * 2;
-            for (int it = 0; it < NE; ++it) for (int k = 0; k < K; ++k) { if (root_done && !use_bagging) root_rows += n_train; stats->trees += 1; }
-            if (use_bagging) root_rows = 0;   // bag sizes vary; not tracked separately
-            // row-sharded: the device counter sums GLOBAL child counts on every rank; report this rank's share
-            const int64_t rows_acc = dp ? (int64_t)(h_statrows / (unsigned long long)g_comm.nranks) : (int64_t)h_statrows;
-            if (dp) root_rows /= g_comm.nranks;
-            stats->hist_rows = rows_acc; stats->root_rows = root_rows;
-            stats->root_atomics_per_row = 2 * (int64_t)(joint_root ? lcj.F : F); stats->level_atomics_per_row = 2 * (int64_t)F;
-            // algorithmic bytes: F bin bytes + 8 B (g,h) per accumulated row
-            stats->hist_bytes = rows_acc * ((int64_t)F + 8);
-            (void)hipEventDestroy(ev_begin); (void)hipEventDestroy(ev_end);
-            return guard.release();
-        }
-        // rows scanned: root = N per class tree; otherwise the smaller child of every split, which the
-        // trees record (leaf_count of both children is known at the end only for final leaves), so
-        // replay the growth order on the host from the stored counts.
-        int64_t rows = 0, root_rows = 0, bytes = 0;
-        for (int it = 0; it < NE; ++it) for (int k = 0; k < K; ++k) {
-            const size_t t = (size_t)it * K + k;
-            const int L = hL[t];
-            const bool root_done = n_train >= (int64_t)p.min_data_in_leaf * 2;
-            if (root_done) { rows += N; root_rows += N; bytes += N * ((int64_t)nchunk * 16 + 8); }
-            // subtree sizes by unfolding the splits in creation order
-            std::vector<int64_t> cntl(NL, 0); std::vector<int> depth(NL, 0);
-            cntl[0] = n_train;
-            std::vector<int64_t> fin(hcnt.begin() + t * NL, hcnt.begin() + t * NL + NL);
-            // final leaf counts -> internal counts: node j created leaf j+1 from some leaf; recover via children links
-            std::vector<int64_t> nodecnt(std::max(L - 1, 1), 0);
-            for (int j = L - 2; j >= 0; --j) {
-                auto sub = [&](int ch) -> int64_t { return ch < 0 ? fin[~ch] : nodecnt[ch]; };
-                nodecnt[j] = sub(hleft[t * (NL - 1) + j]) + sub(hright[t * (NL - 1) + j]);
-            }
-            std::vector<int> node_depth(std::max(L - 1, 1), 0);
-            for (int j = 0; j < L - 1; ++j) {
-                int lc = hleft[t * (NL - 1) + j], rc = hright[t * (NL - 1) + j];
-                if (lc >= 0) node_depth[lc] = node_depth[j] + 1;
-                if (rc >= 0) node_depth[rc] = node_depth[j] + 1;
-                auto sub = [&](int ch) -> int64_t { return ch < 0 ? fin[~ch] : nodecnt[ch]; };
-                const int64_t a = sub(lc), b = sub(rc);
-                const bool last = (j + 2 >= NL);
-                bool go = !last;
-                if (p.max_depth > 0 && node_depth[j] + 1 >= p.max_depth) go = false;
-                if (a < (int64_t)p.min_data_in_leaf * 2 && b < (int64_t)p.min_data_in_leaf * 2) go = false;
-                if (go) { int64_t sm = std::min(a, b); rows += sm; bytes += sm * ((int64_t)nchunk * 16 + 8 + 4); }
-            }
-            stats->trees += 1;
-        }
-        stats->hist_rows = rows; stats->root_rows = root_rows;
-        // algorithmic bytes use the USEFUL feature bytes (F), not the padded record
-        stats->hist_bytes = rows * ((int64_t)F + 8) + (rows - root_rows) * 4;
-        (void)bytes;
+        float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
+        const int nranks = dp ? g_comm.nranks : 1;
+        fill_train_stats(stats, ms, timers, ht, p, level_mode, use_bagging, nranks, N, n_train, F, joint_root ? lcj.F : F, K, h_statrows);
     }
     (void)hipEventDestroy(ev_begin); (void)hipEventDestroy(ev_end);
     return guard.release();

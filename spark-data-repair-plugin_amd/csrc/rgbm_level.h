@@ -54,11 +54,8 @@ constexpr int MT_MAX_NODES = 128;            // built nodes per workgroup (all i
 constexpr int MT_RT_BUDGET = 256;            // table entries the host sizes T for: 2^L per class tree (the nodes so far / the children of the level)
 constexpr int MT_MAX_RT = MT_RT_BUDGET + MT_MAX_T;      // ... + one dummy entry per class tree (ids past the end of a table are clamped to it)
 constexpr int MT_WT_ROWS = 256;              // rows of one wave tile: 4 consecutive rows per lane
-#ifndef MT_RING_N
-#define MT_RING_N 128
-#endif
-constexpr int MT_RING_PLAIN = MT_RING_N;           // entries of a wave's built-row ring: <= 63 waiting + <= 64 appended per row step (64: the waiting ones leave first)
-constexpr int MT_RING_SPEC = MT_RING_N < 128 ? 128 : MT_RING_N;    // wave-specialised pass: the consumer takes full batches only, so a ring holds two of them
+constexpr int MT_RING_PLAIN = 128;           // entries of a wave's built-row ring: <= 63 waiting + <= 64 appended per row step (64: the waiting ones leave first)
+constexpr int MT_RING_SPEC = 128;            // wave-specialised pass: the consumer takes full batches only, so a ring holds two of them
 __host__ __device__ constexpr int mt_ring(bool spec) { return spec ? MT_RING_SPEC : MT_RING_PLAIN; }
 constexpr int MT_CNT_REP = 4;              // copies of a built node's row counter (one LDS atomic per ring entry)
 
@@ -66,7 +63,6 @@ constexpr int MT_THREADS_ACC2 = 768;
 #ifndef MT_CONSUMERS_N
 #define MT_CONSUMERS_N 4
 #endif
-constexpr int MT_LOCK_EVERY = 4;              // lock-step: tile rounds between two looks at the row block's progress words
 constexpr int MT_CONSUMERS = MT_CONSUMERS_N;              // wave-specialised pass: consumer waves of a workgroup (one per SIMD)         // workgroup of a two-chunk pass: 12 waves with 168 VGPRs each (two records per row stay in registers), a third less ring
 
 struct SNode {   // speculative node of one class tree
@@ -96,9 +92,8 @@ struct LevelConst {
     int32_t xcd_blocks;          // root pass: 1-D grid of K * gx blocks, contiguous row blocks, all class trees of a row block on one XCD
     // k_level_mt launch: class trees per workgroup, tree groups, chunk whose features are accumulated, built-slot window, routing?
     int32_t mt_T, mt_G, mt_ch, mt_slot0, mt_nslots, mt_route;
-    int32_t mt_sparse, mt_window;   // mt_sparse 1: class trees with few live rows are swept through their node ids (k_level_mt, plain single-chunk pass);
-                                    // mt_window > 0: the class-tree groups of a row block walk it in step (wave-specialised pass, see "lock-step")
-    uint32_t mt_epoch, has_mult;    // lock-step: tag of this launch in the progress words; has_mult: rows carry multiplicities in byte 15 of their (last / joint) record
+    int32_t mt_sparse;           // 1: class trees with few live rows are swept through their node ids (k_level_mt, plain single-chunk pass)
+    uint32_t has_mult;           // rows carry multiplicities in byte 15 of their (last / joint) record
     long long N, NS, NG;         // rows; row stride of the node-id arrays and of the (g, h) arrays (both N rounded up to a whole wave tile of 256 rows)
 };
 
@@ -143,21 +138,16 @@ __host__ __device__ inline int lv_slots(const FeatMeta* fm, int nfeat, int q) {
 // bank conflict at all), while the rotated lanes land on pseudo-random banks -- and it wins where the LDS holds one or two copies: level 5 of K = 64
 // 3.93 -> 3.43 ms, of K = 32 2.41 -> 1.41, of K = 16 1.44 -> 0.82, and most levels of the two-chunk pass (a node's two histograms are 10 KB).  So rotation is a
 // TEMPLATE PARAMETER (ROTP) and the host picks it per launch: fewer than EIGHT copies (round 5: three; the flat pipeline of round 6 moved the balance towards many class trees per workgroup) of the launch's worst-case histograms fit -> rotate, and give the
-// workgroup as many class trees as one copy allows (rgbm.hip, RGBM_MT_ROT / RGBM_MT_ROT_COPIES2 / RGBM_MT_ROT_T).  Bench step 83.9 -> 80.5 ms (same box),
-// one rank's 12.5M x 32 shard 72.1 -> 64.1 ms.  -DMT_ROT=1 still rotates everything (the experiment).
-#ifndef MT_ROT
-#define MT_ROT 0
-#endif
-constexpr bool MT_ROT_ALL = MT_ROT != 0;             // -DMT_ROT=1: every level pass rotates (the experiment); default: only the launches the host picks (template parameter ROTP)
+// workgroup as many class trees as one copy allows (rgbm.hip, RGBM_MT_ROT / RGBM_MT_ROT_COPIES2 / RGBM_MT_ROT_TMIN).  Bench step 83.9 -> 80.5 ms (same box),
+// one rank's 12.5M x 32 shard 72.1 -> 64.1 ms.
 __host__ __device__ constexpr int mt_rot_dummy(bool rot) { return rot ? 4 : 0; }         // dummy slots per node (one per replica index): where masked-off lanes add
-__host__ __device__ inline int mt_shift(int nbins, int q, bool rot = MT_ROT_ALL) { return rot ? (q < 0 ? 0 : (q > 2 ? 2 : q)) : lv_shift(nbins, q); }
-__host__ __device__ inline int mt_slots(const FeatMeta* fm, int nfeat, int q, bool rot = MT_ROT_ALL) {
+__host__ __device__ inline int mt_shift(int nbins, int q, bool rot) { return rot ? (q < 0 ? 0 : (q > 2 ? 2 : q)) : lv_shift(nbins, q); }
+__host__ __device__ inline int mt_slots(const FeatMeta* fm, int nfeat, int q, bool rot) {
     int t = 0;
     for (int j = 0; j < nfeat; ++j) t += fm[j].nbins << mt_shift(fm[j].nbins, q, rot);
     return t;
 }
 __host__ __device__ constexpr int mt_max_q(bool rot) { return rot ? 2 : LV_MAX_Q; }
-constexpr int MT_ROT_DUMMY = mt_rot_dummy(MT_ROT_ALL);
 
 // bytes the root pass needs besides the histogram: nothing but alignment slack
 constexpr int LV_ROOT_FIXED = 256;
@@ -228,7 +218,6 @@ __global__ __launch_bounds__(64) void k_level_init(LvPlan* __restrict__ plan, SN
 //         of a row block on ONE XCD, which then shares its L2 copy of the block's records) : (gx, K), strided tiles;  grid.z = chunk.
 // Algorithmic bytes per row: F bin bytes + 8 B (g, h).
 // ------------------------------------------------------------------------------------------------
-template <bool WIDE /* the record holds eight 16-bit joint codes (groups of up to JOINT_WIDE_CAP joint bins) instead of sixteen bytes */>
 __global__ __launch_bounds__(LV_THREADS, 1) void k_level_root(const uint4* __restrict__ rec, const float2* __restrict__ gh, const uint8_t* __restrict__ node,
                                                               const LvPlan* __restrict__ plan, HistBin* __restrict__ part,
                                                               const FeatMeta* __restrict__ fmeta, const ChunkMeta* __restrict__ cmeta,
@@ -298,11 +287,11 @@ __global__ __launch_bounds__(LV_THREADS, 1) void k_level_root(const uint4* __res
             if (c.has_mult) { const unsigned long long m = r.w >> 24; gq *= m; hq *= m; }     // (a row that stands for m identical rows: exact integers, so m times the value IS their sum)
             unsigned char* hb = reinterpret_cast<unsigned char*>(hist_g);
             const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#define LV_ATOM(j) { const uint32_t code_ = WIDE ? ((w[((j) & 7) >> 1] >> (16 * ((j) & 1))) & 0xFFFFu) : ((w[(j) >> 2] >> (8 * ((j) & 3))) & 0xFFu); \
+#define LV_ATOM(j) { const uint32_t code_ = (w[(j) >> 2] >> (8 * ((j) & 3))) & 0xFFu; \
                      unsigned long long* p_ = reinterpret_cast<unsigned long long*>(hb + cj[j] + (int)(code_ << sh3[j])); \
                      atomicAdd(p_, gq); atomicAdd(p_ + hdelta, hq); }
 #pragma unroll
-            for (int j = 0; j < (WIDE ? 8 : 16); ++j) if (j < nfeat) LV_ATOM(j);
+            for (int j = 0; j < 16; ++j) if (j < nfeat) LV_ATOM(j);
 #undef LV_ATOM
         }
     };
@@ -367,19 +356,23 @@ template <int NCHR /* records a row needs for ROUTING: 1, 2 (both in registers),
           bool ROUTE /* the first launch of a level: moves the rows to their children; later launches find the built rows by the final ids */,
           int THREADS /* 1024, or MT_THREADS_ACC2 */, bool ACC2 /* NCHR == 2 only: the histograms of BOTH chunks are accumulated by this launch */,
           bool SPEC /* wave-specialised: the last MT_CONSUMERS waves only run the batches (LDS atomics) out of the other waves' rings */,
-          bool ROTP = false /* feature rotation of the histogram updates (see MT_ROT): the host picks it for the launches whose LDS holds fewer than eight copies of their worst-case histograms (RGBM_MT_ROT_COPIES2 = 16) */>
+          bool ROTP = false /* feature rotation of the histogram updates ("FEATURE ROTATION" above): the host picks it for the launches whose LDS holds fewer than eight copies of their worst-case histograms (RGBM_MT_ROT_COPIES2 = 16) */>
 __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict__ rec, const float2* __restrict__ gh, uint8_t* __restrict__ node /* [K][NS], in place */,
                                                          const uint8_t* __restrict__ inbag, const LvPlan* __restrict__ plan, HistBin* __restrict__ part,
                                                          int32_t* __restrict__ count, const FeatMeta* __restrict__ fmeta, const ChunkMeta* __restrict__ cmeta,
-                                                         int32_t* __restrict__ err_flag, uint32_t* __restrict__ prog /* [row blocks][tree groups] lock-step progress words (SPEC), or null */,
+                                                         int32_t* __restrict__ err_flag,
                                                          const FxScale* __restrict__ fxs /* [K] this iteration's grid per class tree */, LevelConst c) {
     static_assert(!ACC2 || NCHR == 2, "a two-chunk pass keeps both records in registers");
+    // the six forms the host launches (RGBM_MT_FORMS in rgbm.hip): the plain pass for any / one / two records per row, the wave-specialised
+    // pass over both chunks, and the rotated form of the one-chunk and of the both-chunk pass
+    static_assert(ACC2 == SPEC && THREADS == (ACC2 ? MT_THREADS_ACC2 : LV_THREADS) && (!ROTP || NCHR == 1 || ACC2) && (NCHR == 0 || NCHR == 1 || NCHR == 2),
+                  "k_level_mt: not one of the six launch forms");
     constexpr int WAVES = THREADS / 64;
     constexpr int NCONS = SPEC ? MT_CONSUMERS : 0, NPROD = WAVES - NCONS;     // waves that walk the rows / waves that only run batches
     constexpr int NACC = ACC2 ? 2 : 1;                     // chunks accumulated by this launch
     constexpr int NRINGS = SPEC ? NPROD : WAVES;
     constexpr int MT_RING = mt_ring(SPEC);
-    constexpr bool ROT = ROTP || MT_ROT_ALL;
+    constexpr bool ROT = ROTP;
     // SPARSE: class trees whose expanded parents hold a few per cent of the rows (the deep levels of many-class targets: 1.3 % at level 6
     // of the K = 64 target, profiles/r04z_*) are not walked tile by tile; see "sparse sweep" below
     constexpr bool SPARSE = (NCHR == 1) && !ACC2 && !SPEC;
@@ -576,7 +569,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
     }
     constexpr int hdelta = MT_HD / 8;
     __syncthreads();
-    // feature rotation (MT_ROT): lane l works on feature slot (j + l) mod 16 in step j.  cj[a][j] becomes the byte offset of THAT feature's
+    // feature rotation: lane l works on feature slot (j + l) mod 16 in step j.  cj[a][j] becomes the byte offset of THAT feature's
     // first slot (+ the lane's replica l / 16), or of the lane's dummy slot when the chunk has no such feature; rmask[a] zeroes the bytes of
     // the rotated record that are not features, so that a masked lane adds to bin 0 of its dummy slot.
     uint32_t rmask[NACC][4];
@@ -825,7 +818,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
                         if (p_tail + n_new - p_head_seen > (uint32_t)MT_RING) __builtin_amdgcn_s_sleep(2);
                     }
                 }
-                // a ring smaller than 128 entries (MT_RING_N=64: 26 KB more LDS for histograms) may not hold this row step's entries next to the
+                // a ring smaller than 128 entries may not hold this row step's entries next to the
                 // waiting ones: those leave first, as a partial batch (never taken with 128 entries: <= 63 wait, <= 64 arrive)
                 if (!SPEC && MT_RING < 128 && r_cnt + (int)__popcll(m) > MT_RING) run_batch(r_cnt);
                 if (built) {
@@ -856,37 +849,6 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
             for (int j = 0; j < 4; ++j) liv[j] = e[j].y & 0xFFu;
         }
         append4(ra, r1, bagmask, g0, g1, liv);
-    };
-
-    // ---- lock-step of the class-tree groups of a row block (round 5; wave-specialised pass; off by default).  Every group's workgroup reads the block's bin
-    // records; they run on one XCD at the same time (launch order), but nothing keeps them at the same place: on the 100M x 32 shape the groups
-    // drifted further apart than the XCD's 4 MB L2 holds and a level pass moved 25.5 GB for 8.3 GB of (node id, g, h) stream and
-    // 3.2 GB of records (profiles/traffic.json, round 4).  Wave 0 of a workgroup publishes the tile round it is in (a word per
-    // (row block, group), tagged with the launch's epoch), and every producer wave looks at the block's words every MT_LOCK_EVERY
-    // rounds: it sleeps while the slowest group that HAS STARTED in this launch and has not finished is more than mt_window rounds
-    // behind.  The slowest started group never waits, so the wait ends; a group that is not resident yet is not waited for.
-    // Measured: -63 % fetch, +23 % time (profiles/r5e_*): the pass is not bound by that traffic.
-    const bool lock = SPEC && c.mt_window > 0 && prog != nullptr && c.mt_G > 1;
-    uint32_t* prog_rb = prog + (size_t)rb * (size_t)c.mt_G;
-    const uint32_t ep_tag = c.mt_epoch << 20;
-    auto lock_step = [&](const uint32_t round) __attribute__((always_inline)) {
-        if ((round & (MT_LOCK_EVERY - 1)) != 0u) return;
-        if (wave == 0 && lane == 0) __hip_atomic_store(prog_rb + grp, ep_tag | (round < 0xFFFFEu ? round + 1u : 0xFFFFEu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int spin = 0; spin < 4096; ++spin) {        // (bounded: a lost update can cost time, never the pass)
-            uint32_t slow = 0xFFFFFFFFu;
-            for (int g0 = 0; g0 < c.mt_G; g0 += 64) {
-                uint32_t v = 0xFFFFFFFFu;
-                if (g0 + lane < c.mt_G) {
-                    const uint32_t w = __hip_atomic_load(prog_rb + g0 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((w >> 20) == c.mt_epoch && (w & 0xFFFFFu) != 0xFFFFFu) v = w & 0xFFFFFu;     // started in this launch, not finished
-                }
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) { const uint32_t v2 = (uint32_t)__shfl_xor((int)v, o); v = v2 < v ? v2 : v; }
-                slow = v < slow ? v : slow;
-            }
-            if (slow == 0xFFFFFFFFu || round + 1u <= slow + (uint32_t)c.mt_window) break;
-            __builtin_amdgcn_s_sleep(32);
-        }
     };
 
         // ---- routing launch: ONE software pipeline over all steps of the wave (tile-major, class trees inside).  What bounds the pass is the number of
@@ -922,7 +884,6 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
                 lookup(S0.n4, tree_entry(kk_c), e_cur);
                 long long q = 0;
                 auto step = [&](TS& cur, TS& nxt, TS& in) __attribute__((always_inline)) {
-                    if (SPEC && lock && kk_c == 0) lock_step((uint32_t)((wt_c - my_first) / NPROD));
                     load_tree(wt_l, kk_l, in.n4, in.g0, in.g1);                              // step q + 2 (past the end: the last step once more, never used)
                     if (cross) {      // (AFTER this step's loads have been requested: the wait in front of these copies then lets those three stay in flight -- in front
                                       // of them it was a vmcnt(0) at every tile boundary, i.e. at every step or second step of the deep levels, where T is 1 or 2)
@@ -1038,9 +999,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
             }
         }
     }
-    if (SPEC) { if (wave < NPROD) { asm volatile("" ::: "memory"); if (lane == 0) { RS_STORE(wave, p_tail); asm volatile("" ::: "memory"); RS_STORE(32 + wave, 1u); } }
-                if (c.mt_window > 0 && prog != nullptr && wave == 0 && lane == 0)      // lock-step: this group is done with the block (nobody waits for it any more)
-                    __hip_atomic_store(prog + (size_t)rb * (size_t)c.mt_G + grp, (c.mt_epoch << 20) | 0xFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    if (SPEC) { if (wave < NPROD) { asm volatile("" ::: "memory"); if (lane == 0) { RS_STORE(wave, p_tail); asm volatile("" ::: "memory"); RS_STORE(32 + wave, 1u); } } }
 #undef RS_LOAD
 #undef RS_STORE
     else while (r_cnt > 0) run_batch(r_cnt < 64 ? r_cnt : 64);
@@ -1116,8 +1075,7 @@ __global__ __launch_bounds__(256) void k_level_reduce(const HistBin* __restrict_
 struct JointFeat { int32_t voff /* offset of the group's joint histogram */, stride, nbins /* of this feature */, nbv /* joint bins of the group */, hoff, vbyte /* byte of the joint record */, pad0, pad1; };
 
 // joint record of every row from its plain bin record(s); thread per row
-constexpr int JOINT_WIDE_CAP = 1024;     // joint bins of a group with 16-bit codes (k_level_root<true>)
-__global__ __launch_bounds__(256) void k_pack_joint(const uint4* __restrict__ rec, long long N, int F, const JointFeat* __restrict__ jf, uint4* __restrict__ rec_joint, int wide,
+__global__ __launch_bounds__(256) void k_pack_joint(const uint4* __restrict__ rec, long long N, int F, const JointFeat* __restrict__ jf, uint4* __restrict__ rec_joint,
                                                     int mult_chunk = -1 /* >= 0: byte 15 of that chunk's record holds the row's multiplicity and moves to byte 15 of the joint record */) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
@@ -1126,8 +1084,7 @@ __global__ __launch_bounds__(256) void k_pack_joint(const uint4* __restrict__ re
     for (int f = 0; f < F; ++f) {
         const uint32_t bin = rec8[((long long)(f >> 4) * N + i) * 16 + (f & 15)];
         const int vb = jf[f].vbyte;
-        if (wide) w[vb >> 1] += (bin * (uint32_t)jf[f].stride) << (16 * (vb & 1));   // (a group's code stays below 65536)
-        else w[vb >> 2] += (bin * (uint32_t)jf[f].stride) << (8 * (vb & 3));    // a group's code stays below 256: no carry into the next byte
+        w[vb >> 2] += (bin * (uint32_t)jf[f].stride) << (8 * (vb & 3));    // a group's code stays below 256: no carry into the next byte
     }
     if (mult_chunk >= 0) w[3] = (w[3] & 0x00FFFFFFu) | ((uint32_t)rec8[((long long)mult_chunk * N + i) * 16 + 15] << 24);
     rec_joint[i] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -1530,62 +1487,6 @@ __global__ __launch_bounds__(256) void k_level_final(const uint4* __restrict__ r
             }
             sk[row] += nd[n];
         }
-    }
-    __syncthreads();
-    for (int ci = tid; ci < 2 * n_exp; ci += 256) {
-        int tot = 0;
-        for (int r2 = 0; r2 < LV_CNT_REP; ++r2) tot += cnt[ci * LV_CNT_REP + r2];
-        if (tot) atomicAdd(&count[(long long)k * 256 + child_first + ci], tot);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_level_last: what is left of k_level_final when the score update rides in the next iteration's gradient kernel (PendingScore, rgbm_kernels.h): the
-// last DataPartition::Split -- the rows of the nodes expanded at depth max_depth - 1 move to their children, in place -- and the exact counts of those
-// children.  Reads the node ids (1 B per (row, class tree)) of the class trees that expanded anything at that depth, and the split byte of the rows concerned.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_level_last(const uint4* __restrict__ rec, uint8_t* __restrict__ node_all, const uint8_t* __restrict__ inbag,
-                                                    const LvPlan* __restrict__ plan, const TreeOut out, int32_t* __restrict__ count, const int32_t* __restrict__ itp, LevelConst c) {
-    const int it = *itp;
-    __shared__ uint32_t route0[256], route1[256];
-    __shared__ int32_t cnt[2 * LV_MAX_EXP * LV_CNT_REP];
-    const int k = blockIdx.y;
-    if (out.L[(long long)it * c.K + k] <= 1) return;   // no split
-    const LvPlan* pp = &plan[k];
-    if (pp->done) return;                              // plan(max_depth) expanded nothing: every row already sits in its leaf
-    const int n_exp = pp->n_exp, child_first = pp->child_first;
-    const int tid = threadIdx.x, lane = tid & 63;
-    route0[tid] = pp->route0[tid]; route1[tid] = pp->route1[tid];
-    for (int i = tid; i < 2 * n_exp * LV_CNT_REP; i += 256) cnt[i] = 0;
-    __syncthreads();
-    const long long N = c.N;
-    uint8_t* node = node_all + (long long)k * c.NS;
-    const uint8_t* rec8 = reinterpret_cast<const uint8_t*>(rec);
-    // 16 rows per thread and step (the node-id arrays are padded with LV_INACTIVE to whole wave tiles)
-    for (long long i = ((long long)blockIdx.x * 256 + tid) * 16; i < N; i += (long long)gridDim.x * 4096) {
-        uint4 v = *reinterpret_cast<const uint4*>(node + i);
-        uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        bool changed = false;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = (int)((w[d] >> (8 * j)) & 0xFFu);
-                const uint32_t w0 = route0[n];             // (LV_INACTIVE: never expanded)
-                if (w0 & (1u << 24)) {
-                    const long long row = i + d * 4 + j;
-                    const int f = (int)(w0 & 0xFFu), theta1 = (int)((w0 >> 8) & 0xFFu), nanbin = (int)((w0 >> 16) & 0xFFu);
-                    const int bin = (int)rec8[((long long)(f >> 4) * N + row) * 16 + (f & 15)];
-                    const bool left = (bin == nanbin) ? ((w0 >> 25) & 1u) != 0u : (bin < theta1);
-                    const uint32_t w1 = route1[n];
-                    const int nn = left ? (int)(w1 & 0xFFu) : (int)((w1 >> 8) & 0xFFu);
-                    if (!inbag || inbag[row]) atomicAdd(&cnt[(nn - child_first) * LV_CNT_REP + (lane & (LV_CNT_REP - 1))], c.has_mult ? (int)rec8[((long long)(c.nchunk - 1) * N + row) * 16 + 15] : 1);
-                    w[d] = (w[d] & ~(0xFFu << (8 * j))) | ((uint32_t)nn << (8 * j));
-                    changed = true;
-                }
-            }
-        }
-        if (changed) *reinterpret_cast<uint4*>(node + i) = make_uint4(w[0], w[1], w[2], w[3]);
     }
     __syncthreads();
     for (int ci = tid; ci < 2 * n_exp; ci += 256) {

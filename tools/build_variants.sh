@@ -1,5 +1,7 @@
 #!/bin/bash
 # A/B builds of librepairgbm.so for timing experiments (RGBM_LIB_PATH=<file> selects one): tools/build_variants.sh name "-DFLAG ..." [name flags ...]
+# Knobs that exist: -DMT_DBL_ATOM=1, -DMT_CONSUMERS_N=n, -DMT_SPARSE_DIV_N=n, -DSM_THREADS_N=n, -DSM_PROF=1.  The rotate-everything and ring-size knobs of the
+# level pass were removed with the other rejected experiments ("Retired experiments": the last commit that builds them is named there).
 cd "$(dirname "$0")/../spark-data-repair-plugin_amd/csrc" || exit 1
 mkdir -p ../lib/variants
 while [ $# -ge 2 ]; do

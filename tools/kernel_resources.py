@@ -16,7 +16,7 @@ for line in out.splitlines():
     if m and cur is not None:
         cur[m.group(1).strip()] = int(m.group(2))
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
-print("%-70s %5s %5s %7s %7s %7s %4s" % ("kernel", "VGPR", "SGPR", "vspill", "sspill", "scratch", "occ"))
+print("%-70s %5s %5s %7s %7s %7s %6s %4s" % ("kernel", "VGPR", "SGPR", "vspill", "sspill", "scratch", "LDS", "occ"))
 for r in rows:
     if flt in r["name"]:
-        print("%-70s %5d %5d %7d %7d %7d %4d" % (r["name"][:70], r.get("VGPRs", -1), r.get("TotalSGPRs", -1), r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1), r.get("ScratchSize", -1), r.get("Occupancy", -1)))
+        print("%-70s %5d %5d %7d %7d %7d %6d %4d" % (r["name"][:70], r.get("VGPRs", -1), r.get("TotalSGPRs", -1), r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1), r.get("ScratchSize", -1), r.get("LDS Size", -1), r.get("Occupancy", -1)))
