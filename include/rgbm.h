@@ -268,6 +268,27 @@ int rgbm_table_repair_pmf_weighted(rgbm_table* t, const rgbm_model* m, int32_t t
  * dist_out: [n_a][n_b] row-major, host memory.  Strings of any length; both pools are copied to device `device_id`. */
 int rgbm_edit_distance(int32_t device_id, const int32_t* a_cp, const int64_t* a_off, int64_t n_a, const int32_t* b_cp,
                        const int64_t* b_off, int64_t n_b, int32_t* dist_out);
+/* ---- cell-domain analysis and weak labels (python/repair/errors.py:488-578; the value-space statement is repair/domain.py) ----
+ * Dense joint counts of column pairs in one pass over the rows (RepairApi.computeFreqStats, src/main/scala/.../python/RepairApi.scala:231-273,
+ * GROUPING SETS over (x, y); and the exact stand-in for approx_count_distinct(struct(x, y)) of computeAttrStats, :429-448).
+ * pair_cols [n_pairs][2]; n_bins[col] = bins of a column of the discretised view (RepairApi.discretizeTable, :126-149); luts[col] (or luts
+ * itself) NULL = the codes are the bins, else int32 [n_codes[col]] code -> bin.  A code / bin outside its range counts as NULL.
+ * counts_out: the pairs' tables one after the other, pair (x, y) as int64 [(n_bins[x] + 1)][(n_bins[y] + 1)] row-major with NULL in the last
+ * slot of each side.  More than 2^24 dense cells in a pair or 2^25 in a call: RGBM_ERR_PARAM (count sparsely on the host).
+ * The tables, bins and LUTs stay with the table (device memory) for rgbm_table_cell_domains until the next call. */
+int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, int32_t n_pairs, const int32_t* const* luts /* [c] or NULL */,
+                           const int32_t* n_bins /* [c] */, int64_t* counts_out);
+/* Domains of the error cells of ONE discrete target with the naive-Bayes posterior of RepairApi.computeDomainInErrorCells (:479-675)
+ * and the weak-label rule of errors.py:517-521, on the tables the last rgbm_table_pair_counts left on the device.  rows: the cells' row
+ * positions; pair_idx [k <= 8]: the pairs (of that call) holding the target and its correlated attributes, in order; an element (value c of
+ * the target) exists for attribute j iff cnt > min_cnt[j] and carries max(cnt - 1, 0.1); an attribute without elements for the cell (its
+ * value is NULL / no group) wipes the attributes before it (the SQL's IF(ISNOTNULL(domain), CONCAT(domain, d), d));
+ * score_c = sum over the attributes, in order, of element / row_count (0 where single_ok[c] == 0), prob_c = score_c / (score_0 + score_1 + ...).
+ * top_out: the value of the largest prob > beta (ties: smallest code), -1 = none; weak_out: the cell holds exactly that value now.
+ * probs_out [n_cells][n_bins[target]] is optional. */
+int rgbm_table_cell_domains(rgbm_table* t, int32_t target_col, const int64_t* rows, int64_t n_cells, const int32_t* pair_idx, int32_t k,
+                            const int64_t* min_cnt /* [k] */, const uint8_t* single_ok /* [n_bins[target]] */, double beta, int64_t row_count,
+                            uint8_t* weak_out, int32_t* top_out, double* top_prob_out, double* probs_out /* or NULL */);
 int rgbm_table_shape(const rgbm_table* t, int64_t* n_out, int32_t* c_out, int32_t* n_codes_out /* [c] or NULL */);
 
 /* ---- row-sharded multi-GPU training ------------------------------------------------------------

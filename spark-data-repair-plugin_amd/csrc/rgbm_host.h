@@ -113,5 +113,10 @@ struct rgbm_table {
     mutable std::mutex prep_mu;
     mutable hipStream_t stream = nullptr;
     mutable rgh::DevBuf<unsigned char> scratch[12];
+    // result of the last rgbm_table_pair_counts call, kept on the device for rgbm_table_cell_domains: the dense joint tables
+    // (pair p at pc_off[p], (pc_dx[p] + 1) x (pc_dy[p] + 1) cells, NULL in the last slot of each side), the bins per column and the LUTs
+    mutable rgh::DevBuf<unsigned long long> pc_counts; mutable rgh::DevBuf<int32_t> pc_luts; mutable rgh::DevBuf<long long> pc_lut_off;
+    mutable rgh::DevBuf<int32_t> pc_bins;
+    mutable std::vector<int32_t> pc_x, pc_y, pc_dx, pc_dy, pc_nbins; mutable std::vector<long long> pc_off; mutable std::vector<uint8_t> pc_has_lut;
     ~rgbm_table() { if (stream) (void)hipStreamDestroy(stream); }
 };

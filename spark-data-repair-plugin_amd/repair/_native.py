@@ -84,7 +84,7 @@ def lib():
                      "rgbm_table_detect_nulls", "rgbm_table_detect_constraint", "rgbm_table_rows_of_cells", "rgbm_table_cells_fetch",
                      "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict",
                      "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
-                     "rgbm_edit_distance"):
+                     "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains"):
             getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -106,7 +106,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict", "rgbm_table_shape",
     "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_write_cells", "rgbm_host_alloc", "rgbm_host_free",
     "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
-    "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance",
+    "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
 ]
 
 COMM_ID_BYTES = 128
@@ -278,7 +278,9 @@ class LocalGroup:
 
 def _check(rc, what):
     if rc != 0:
-        raise RepairGbmError("%s failed (%d): %s" % (what, rc, lib().rgbm_last_error().decode("utf-8", "replace")))
+        err = RepairGbmError("%s failed (%d): %s" % (what, rc, lib().rgbm_last_error().decode("utf-8", "replace")))
+        err.code = rc                      # the RGBM_ERR_* value of include/rgbm.h
+        raise err
 
 
 def device_count():
@@ -658,6 +660,45 @@ class Table:
         nn = C.c_int64(0)
         _check(lib().rgbm_table_count_codes(self.h, C.c_int32(col), _p(out, C.c_int64), C.byref(nn)), "rgbm_table_count_codes")
         return out, int(nn.value)
+
+    def pair_counts(self, pairs, luts=None, n_bins=None):
+        """Dense joint counts of column pairs, one pass over the rows (include/rgbm.h rgbm_table_pair_counts): a list of int64
+        [(n_bins[x] + 1)][(n_bins[y] + 1)] arrays, NULL in the last slot of each side.  ``luts``: {column: int32 [n_codes] code -> bin};
+        ``n_bins``: {column: bins} (default: the column's codes are its bins).  The result stays on the device for ``cell_domains``."""
+        pc = _i32(np.asarray(pairs, np.int32).reshape(-1, 2))
+        nb = np.asarray(self.n_codes, np.int32).copy()
+        for c, d in dict(n_bins or {}).items():
+            nb[int(c)] = int(d)
+        keep = {int(c): _i32(l) for c, l in dict(luts or {}).items() if l is not None}
+        for c, l in keep.items():
+            if len(l) != int(self.n_codes[c]):
+                raise ValueError("the LUT of column %d must hold one bin per code (%d)" % (c, int(self.n_codes[c])))
+        ptrs = (C.POINTER(C.c_int32) * self.c)(*[_p(keep[c] if len(keep[c]) else np.zeros(1, np.int32), C.c_int32) if c in keep else None
+                                                 for c in range(self.c)])
+        shapes = [(int(nb[x]) + 1, int(nb[y]) + 1) for x, y in pc]
+        out = np.zeros(int(sum(a * b for a, b in shapes)), np.int64)
+        _check(lib().rgbm_table_pair_counts(self.h, _p(pc, C.c_int32), C.c_int32(len(pc)), ptrs if keep else None, _p(nb, C.c_int32),
+                                            _p(out, C.c_int64)), "rgbm_table_pair_counts")
+        res, at = [], 0
+        for a, b in shapes:
+            res.append(out[at:at + a * b].reshape(a, b)); at += a * b
+        return res
+
+    def cell_domains(self, target_col, rows, pair_idx, min_cnt, single_ok, beta, row_count, want_probs=False):
+        """Domains / weak labels of the error cells (``rows``) of one discrete target on the tables of the last ``pair_counts`` call
+        (include/rgbm.h rgbm_table_cell_domains).  Returns (weak [m] uint8, top [m] int32, top_prob [m] float64, probs [m][d] or None)."""
+        r = np.ascontiguousarray(rows, np.int64)
+        pi, mc = _i32(np.asarray(pair_idx, np.int32).reshape(-1)), np.ascontiguousarray(min_cnt, np.int64).reshape(-1)
+        ok = np.ascontiguousarray(single_ok, np.uint8).reshape(-1)
+        if len(pi) != len(mc):
+            raise ValueError("one min_cnt per pair")
+        m = len(r)
+        weak, top, tp = np.zeros(m, np.uint8), np.full(m, -1, np.int32), np.zeros(m, np.float64)
+        probs = np.zeros((m, len(ok)), np.float64) if want_probs else None
+        _check(lib().rgbm_table_cell_domains(self.h, C.c_int32(target_col), _p(r, C.c_int64), C.c_int64(m), _p(pi, C.c_int32), C.c_int32(len(pi)),
+                                             _p(mc, C.c_int64), _p(ok, C.c_uint8), C.c_double(beta), C.c_int64(row_count), _p(weak, C.c_uint8),
+                                             _p(top, C.c_int32), _p(tp, C.c_double), _p(probs, C.c_double)), "rgbm_table_cell_domains")
+        return weak, top, tp, probs
 
     def close(self):
         h, self.h = getattr(self, "h", None), None

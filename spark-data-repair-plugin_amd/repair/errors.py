@@ -387,9 +387,11 @@ class LOFOutlierErrorDetector(ScikitLearnBackedErrorDetector):
 class ErrorModel:
     """detect -> error cells with current values + the repairable target columns (errors.py:545-582).
 
-    The reference additionally prunes "weak-labelled" cells with a naive-Bayes domain analysis in the
-    JVM (RepairApi.computeDomainInErrorCells); that relational step is outside the accelerated path
-    and is not re-stated: every detected cell is handed to the repair models (out of scope).
+    The reference additionally computes pairwise attribute statistics and prunes "weak-labelled" cells with a naive-Bayes
+    domain analysis in the JVM (RepairApi.computeAttrStats / computeDomainInErrorCells).  That step is re-stated in
+    `repair.domain` and runs when `error.domain_analysis.enabled` is set (default off: every detected cell is handed to the
+    repair models and the pairwise statistics stay empty; DESIGN.md "Cell-domain analysis").  On the resident path the same
+    step runs on the device (repair.pipeline.analyse_cell_domains).
     """
     from collections import namedtuple
     _option = namedtuple("_option", "key default_value type_class validator err_msg")
@@ -399,9 +401,11 @@ class ErrorModel:
     _opt_max_attrs_to_compute_domains = _option("error.max_attrs_to_compute_domains", 2, int, lambda v: v >= 2, "`{}` should be greater than 1")
     _opt_domain_threshold_alpha = _option("error.domain_threshold_alpha", 0.0, float, lambda v: 0.0 <= v < 1.0, "`{}` should be in [0.0, 1.0)")
     _opt_domain_threshold_beta = _option("error.domain_threshold_beta", 0.70, float, lambda v: 0.0 <= v < 1.0, "`{}` should be in [0.0, 1.0)")
+    # new in this engine: run the reference's cell-domain analysis (pairwise statistics + weak-label pruning, repair.domain)
+    _opt_domain_analysis_enabled = _option("error.domain_analysis.enabled", False, bool, None, None)
     option_keys = set(o.key for o in (_opt_attr_freq_ratio_threshold, _opt_pairwise_freq_ratio_threshold,
                                       _opt_max_attrs_to_compute_pairwise_stats, _opt_max_attrs_to_compute_domains,
-                                      _opt_domain_threshold_alpha, _opt_domain_threshold_beta))
+                                      _opt_domain_threshold_alpha, _opt_domain_threshold_beta, _opt_domain_analysis_enabled))
 
     def __init__(self, row_id: str, targets: List[str], discrete_thres: int, error_detectors: List[ErrorDetector],
                  error_cells: Optional[pd.DataFrame], opts: Dict[str, str]) -> None:
@@ -428,11 +432,33 @@ class ErrorModel:
         from repair.utils import get_option_value
         return {o.key: get_option_value(self.opts, *o) for o in (
             self._opt_attr_freq_ratio_threshold, self._opt_pairwise_freq_ratio_threshold, self._opt_max_attrs_to_compute_pairwise_stats,
-            self._opt_max_attrs_to_compute_domains, self._opt_domain_threshold_alpha, self._opt_domain_threshold_beta)}
+            self._opt_max_attrs_to_compute_domains, self._opt_domain_threshold_alpha, self._opt_domain_threshold_beta,
+            self._opt_domain_analysis_enabled)}
+
+    def _analyse_domains(self, input_df: pd.DataFrame, continous_columns: List[str], cells: pd.DataFrame, target_columns: List[str],
+                         domain_stats: Dict[str, int], options: Dict[str, Any]) -> Tuple[Dict[str, Any], np.ndarray]:
+        """errors.py:565-576 of the reference in value space: (pairwise statistics, weak-label mask of `cells`) from `repair.domain` on the
+        label codes of the frame."""
+        from repair import domain
+        from repair.pipeline import encode_frame
+        rid = self.row_id
+        cols = [c for c in input_df.columns if c != rid]
+        pos = {c: i for i, c in enumerate(cols)}
+        idx, remaps, dicts = encode_frame(input_df, cols)
+        codes = np.stack([np.where(idx[j] >= 0, remaps[j][np.maximum(idx[j], 0)] if len(remaps[j]) else -1, -1) for j in range(len(cols))]).astype(np.int32)
+        stats = [int(domain_stats[c]) for c in cols]
+        cont = {pos[c]: np.asarray(dicts[pos[c]], np.float64) for c in continous_columns if c in pos and dicts[pos[c]].dtype != object}
+        view = domain.discretised_view([max(len(d), 1) for d in dicts], stats, cont, self.discrete_thres)
+        rpos = pd.Series(np.arange(len(input_df)), index=input_df[rid].to_numpy()).reindex(cells[rid].to_numpy()).to_numpy(np.int64)
+        cpos = np.array([pos[a] for a in cells["attribute"]], np.int32)
+        res = domain.analyse(domain.HostBackend(codes, view), len(input_df), view, [pos[t] for t in target_columns], stats, rpos, cpos, options,
+                             want_weak=self.error_cells is None)
+        pairwise = {cols[t]: [(cols[y], float(h)) for y, h in lst] for t, lst in res["pairwise"].items()}
+        return pairwise, res["weak"]
 
     def detect(self, input_df: pd.DataFrame, continous_columns: List[str]) -> Tuple[pd.DataFrame, List[str], Dict[str, Any], Dict[str, int]]:
         rid = self.row_id
-        self._checked_options()
+        options = self._checked_options()
         if self.error_cells is not None:
             cells = self.error_cells[[rid, "attribute"]]
             if cells[rid].dtype != input_df[rid].dtype:   # e.g. 'tid STRING' cells against an int row id
@@ -475,7 +501,13 @@ class ErrorModel:
         # discretizable attributes (RepairApi.discretizeTable): continuous ones, or 1 < |domain| <= threshold
         discretized = [c for c in input_df.columns if c != rid and (c in continous_columns or 1 < domain_stats[c] <= self.discrete_thres)]
         target_columns = [c for c in noisy_columns if c in discretized]
-        return cells, target_columns, {}, domain_stats
+        if not options[self._opt_domain_analysis_enabled.key] or len(target_columns) == 0 or len(discretized) <= 1:
+            return cells, target_columns, {}, domain_stats
+        pairwise, weak = self._analyse_domains(input_df, continous_columns, cells, target_columns, domain_stats, options)
+        if self.error_cells is None:     # given error cells are taken as they are (errors.py:570)
+            _logger.info("[Error Detection Phase] %d noisy cells fixed and %d error cells remaining..." % (int(weak.sum()), int((~weak).sum())))
+            cells = cells[~weak].reset_index(drop=True)
+        return cells, target_columns, pairwise, domain_stats
 
 
 def _to_sql_string(v: Any) -> str:

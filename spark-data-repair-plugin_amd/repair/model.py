@@ -665,6 +665,11 @@ class RepairModel():
         if plan is None:
             return None
         plan.update(candidates=cands, constraints=cons, detect_nulls=has_null)
+        eopts = ErrorModel(row_id=self._row_id, targets=self.targets, discrete_thres=self.discrete_thres, error_detectors=self.error_detectors,
+                           error_cells=None, opts=self.opts)._checked_options()
+        if eopts[ErrorModel._opt_domain_analysis_enabled.key]:
+            # the reference's cell-domain analysis on the same resident table (repair.pipeline.analyse_cell_domains)
+            plan.update(domain_analysis=dict(options=eopts, discrete_thres=self.discrete_thres, continuous_columns=list(continous_columns)))
         return plan
 
     def _run_resident_detect(self, plan: Dict[str, Any], input_df: DataFrame, continous_columns: List[str], repair_data: bool) -> DataFrame:
@@ -687,7 +692,7 @@ class RepairModel():
         frame, info = repair_frame(plan["engine"], input_df, rid, targets=cands, base_params=plan["params"], constraints=plan["constraints"],
                                    detect_nulls=plan["detect_nulls"], continuous_columns=[c for c in continous_columns if c in cands],
                                    train_rows=sample, want_details=True, search_opts=dict(self.opts) if plan.get("search") else None,
-                                   only_noisy_targets=True)
+                                   only_noisy_targets=True, domain_analysis=plan.get("domain_analysis"))
         self._last_resident_info = info
         self._last_detection_on_device = True
         if len(frame) == 0:

@@ -218,9 +218,45 @@ def unseen_categories(table, dirty_tab, targets, ordered_cols=(), train_tables=N
     return out
 
 
+class TableBackend:
+    """`repair.domain` backend on a resident table: `Table.pair_counts` / `Table.cell_domains` (csrc/rgbm_prep.hip).  Dense tables
+    beyond the library's cap (RGBM_ERR_PARAM) or more correlated attributes than the kernel takes leave the resident path."""
+    MAX_CORR = 8
+
+    def __init__(self, table, view):
+        self.table, self.view = table, view
+
+    def pair_counts(self, pairs):
+        from repair.domain import Joint
+        try:
+            dense = self.table.pair_counts(pairs, luts=self.view.luts, n_bins=self.view.n_bins)
+        except Exception as e:  # noqa: BLE001
+            if getattr(e, "code", None) == -2:
+                raise NotResidentEligible("cell-domain analysis: %s" % e)
+            raise
+        return [Joint.from_dense(d) for d in dense]
+
+    def cell_domains(self, target, rows, corr, ptable, min_cnt, single_ok, beta, row_count, want_probs=False):
+        if len(corr) > self.MAX_CORR:
+            raise NotResidentEligible("cell-domain analysis: %d correlated attributes (the device entry takes %d)" % (len(corr), self.MAX_CORR))
+        pidx = [ptable.index[frozenset((int(c), int(target)))] for c in corr]
+        return self.table.cell_domains(target, rows, pidx, min_cnt, single_ok, beta, row_count, want_probs=want_probs)
+
+
+def analyse_cell_domains(table, targets, rows, cols, spec):
+    """The second half of ErrorModel.detect (errors.py:553-578) on the resident table, BEFORE any cell is NULLed: pair counts on the
+    device, entropies and attribute selection on the host from the integer counts, cell domains on the device.
+    spec: dict(options={error.*: value}, discrete_thres, domain_stats [C], continuous={column: ascending distinct values},
+    keep_weak=False).  Returns repair.domain.analyse's dict."""
+    from repair import domain
+    view = domain.discretised_view(table.n_codes, spec["domain_stats"], spec.get("continuous") or {}, int(spec["discrete_thres"]))
+    return domain.analyse(TableBackend(table, view), int(table.n), view, targets, spec["domain_stats"], rows, cols, spec.get("options") or {},
+                          want_weak=not spec.get("keep_weak", False))
+
+
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
@@ -242,8 +278,11 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
                  `pmf_value`.  With it the pmf table is chained as the value-space `_repair` chains it (model.py): in target order, a
                  continuous target's prediction fills its NULL cells before the later targets are scored (`pmf_value` holds it),
                  discrete targets stay NULL.
+    domain_analysis: the checked `error.*` options and the view's inputs (`analyse_cell_domains`): the reference's cell-domain analysis
+                 runs on the detected cells of the noisy targets before anything is NULLed, and the weak-labelled cells (the current
+                 value is the most probable one) leave the error cells (errors.py:507-530).  None = every detected cell is repaired.
     Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
-    dirty_rows, models, times, stats): one entry per error cell, ordered by (column, row).
+    dirty_rows, models, times, stats[, domain]): one entry per error cell, ordered by (column, row).
     """
     continuous = dict(continuous or {})
     t0 = time.perf_counter()
@@ -253,12 +292,22 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     if only_noisy_targets:
         noisy = set(int(c) for c in np.unique(cols))
         targets = [t for t in targets if t in noisy]
+    domain_info = None
+    if domain_analysis is not None and len(rows):
+        noisy = set(int(c) for c in np.unique(cols))
+        da = analyse_cell_domains(table, [t for t in targets if t in noisy], rows, cols, domain_analysis)
+        domain_info = dict(pairwise=da["pairwise"], noisy_cells=int(len(rows)), weak_cells=int(da["weak"].sum()))
+        _logger.info("[Error Detection Phase] %d noisy cells fixed and %d error cells remaining..." % (domain_info["weak_cells"],
+                                                                                                   len(rows) - domain_info["weak_cells"]))
+        rows, cols = rows[~da["weak"]], cols[~da["weak"]]
     t_detect = time.perf_counter() - t0
     t0 = time.perf_counter()
     current = table.read_cells(rows, cols)
     table.null_cells(rows, cols, targets)                       # convertErrorCellsToNull (RepairApi.scala:171-211)
     dirty_rows = table.rows_of_cells(rows)                      # model.py:549-553
     out = dict(rows=rows, cols=cols, current=current, dirty_rows=dirty_rows, models={}, stats=[])
+    if domain_info is not None:
+        out["domain"] = domain_info
     if len(rows) == 0:
         out.update(repaired=np.zeros(0, np.int32), repaired_value=np.zeros(0, np.float64), prob=np.zeros(0, np.float64),
                    times=dict(detect=t_detect, prepare=time.perf_counter() - t0))
@@ -272,7 +321,9 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
             if int((cnt > 0).sum()) < 1:
                 raise NotResidentEligible("continuous target column %d has no non-NULL row to learn from" % t)
         elif only_noisy_targets and int((cnt > 0).sum()) < len(cnt):
-            raise DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, int((cnt <= 0).sum()), len(cnt)), rows, cols)
+            e = DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, int((cnt <= 0).sum()), len(cnt)), rows, cols)
+            e.domain_info = domain_info          # the cells it carries are the pruned ones: the second pass does not analyse again
+            raise e
         elif int((cnt > 0).sum()) < 2:
             raise NotResidentEligible("target column %d has fewer than two classes among its non-NULL rows; the reference short-cuts such "
                              "attributes with a constant model (model.py:1008-1017) -- drop it from `targets`" % t)
@@ -398,7 +449,7 @@ def encode_frame(df, columns):
 
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
@@ -411,7 +462,11 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     pmf_costs (with want_pmf): the update costs of RepairModel.run()'s probability modes, a callable (attribute, its classes (the
     target's dictionary, ascending), ascending row positions of its error cells) -> the dict `repair_table` describes, or None.  The
     frame then also holds `top1_cost` (cost of the top-1 class against the current value) and `pmf_value` (continuous targets: the
-    prediction of the un-repaired pmf chain)."""
+    prediction of the un-repaired pmf chain).
+
+    domain_analysis: dict(options={error.*: checked value}, discrete_thres[, continuous_columns]) -- the cell-domain analysis and the
+    weak-label pruning of the detected cells (`repair_table`); the details then hold `pairwise_attr_stats` {attribute: [(attribute, H)]},
+    `noisy_cells` and `weak_cells`."""
     import pandas as pd
     cols = [c for c in df.columns if c != row_id]
     targets = list(targets) if targets is not None else list(cols)
@@ -466,8 +521,16 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             if live < (1 if t in continuous_columns else 2):
                 raise NotResidentEligible("target `%s` is left with %d distinct value(s) once the error cells are removed" % (t, live))
 
-    def build_and_run(cells_, detect_nulls_, constraints_):
+    def build_and_run(cells_, detect_nulls_, constraints_, analyse=True):
         table = engine.upload_dictionaries(indices, remaps)
+        da_spec = None
+        if domain_analysis is not None and analyse:
+            ccols_ = domain_analysis.get("continuous_columns")
+            if ccols_ is None:
+                ccols_ = [c for j, c in enumerate(cols) if dicts[j].dtype != object]
+            da_spec = dict(options=domain_analysis.get("options") or {}, discrete_thres=domain_analysis["discrete_thres"],
+                           domain_stats=[len(d) for d in dicts], keep_weak=error_cells is not None,
+                           continuous={pos[c]: np.asarray(dicts[pos[c]], np.float64) for c in ccols_ if c in pos and dicts[pos[c]].dtype != object})
         for j, c in enumerate(cols):               # numeric columns: bin bounds at the midpoints of the values, like LightGBM on raw numbers
             if dicts[j].dtype != object and len(dicts[j]) > 0:
                 table.set_column_values(j, dicts[j])
@@ -481,7 +544,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         return cont_, repair_table(engine, table, [pos[t] for t in targets], dict(base_params or {}), constraints=cons, detect_nulls=detect_nulls_,
                                    error_cells=cells_, want_pmf=want_pmf, top_k=top_k, threshold=threshold, continuous=cont_, search_opts=search_opts,
                                    pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
-                                   only_noisy_targets=only_noisy_targets,
+                                   only_noisy_targets=only_noisy_targets, domain_analysis=da_spec,
                                    check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
                                    train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
 
@@ -500,7 +563,9 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             # one knows what they held
             fresh = ~np.isin(given_current[0], first[0])
             given_current = (np.concatenate([first[0], given_current[0][fresh]]), np.concatenate([first[1], given_current[1][fresh]]))
-        cont, res = build_and_run(cells, False, ())
+        cont, res = build_and_run(cells, False, (), analyse=False)
+        if getattr(e, "domain_info", None) is not None:
+            res["domain"] = e.domain_info
     rows, ccols = res["rows"], res["cols"]
 
     def decode(codes, col_idx):
@@ -551,7 +616,12 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                 pval[sel] = [None if np.isnan(x) else (int(x) if is_int else float(x)) for x in v]
             frame["pmf_value"] = pval
     if want_details:
-        return frame, dict(times=res.get("times", {}), stats=res.get("stats", []), models=res.get("models", {}), columns=cols)
+        details = dict(times=res.get("times", {}), stats=res.get("stats", []), models=res.get("models", {}), columns=cols)
+        if res.get("domain") is not None:
+            d = res["domain"]
+            details.update(pairwise_attr_stats={cols[t]: [(cols[y], h) for y, h in lst] for t, lst in d["pairwise"].items()},
+                           noisy_cells=d["noisy_cells"], weak_cells=d["weak_cells"])
+        return frame, details
     return frame
 
 
