@@ -289,6 +289,23 @@ int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, int32_t n_pa
 int rgbm_table_cell_domains(rgbm_table* t, int32_t target_col, const int64_t* rows, int64_t n_cells, const int32_t* pair_idx, int32_t k,
                             const int64_t* min_cnt /* [k] */, const uint8_t* single_ok /* [n_bins[target]] */, double beta, int64_t row_count,
                             uint8_t* weak_out, int32_t* top_out, double* top_prob_out, double* probs_out /* or NULL */);
+/* ---- rule-based repairs (python/repair/model.py `_build_rule_model`, `_repair`, `_repair_by_nearest_values`) ----
+ * The rule model of a functional dependency x -> y (reference model.py:928-953, `FunctionalDepModel` :64-100): over the rows where both
+ * cells are non-NULL, map_out[x] is the single y code that x occurs with; -1 when x occurs with two or more y codes, or with none. */
+int rgbm_table_fd_map(const rgbm_table* t, int32_t x_col, int32_t y_col, int32_t* map_out /* [n_codes[x_col]] */);
+/* One rule step of the chained repair on rows [row_begin, row_begin + n_rows) (reference model.py:1107-1133 with `FunctionalDepModel.predict`
+ * :83-84 or `PoorModel.predict` :55-56):  pred = x_col < 0 ? lut[0] : (x >= 0 && x < n_lut ? lut[x] : -1).  out_label gets pred for every
+ * row; a NULL y cell receives pred and stays NULL when pred is -1, so the later models of the chain see it as missing (predict gave None).
+ * lut entries are -1 or codes of y_col. */
+int rgbm_table_rule_fill(rgbm_table* t, int32_t y_col, int32_t x_col /* -1: constant */, const int32_t* lut, int32_t n_lut, int64_t row_begin,
+                         int64_t n_rows, int32_t* out_label /* [n_rows] or NULL */);
+/* Nearest-value merges (reference model.py:1279-1291 `_repair_by_nearest_values`): for every string of pool a the position in pool b of the
+ * closest string when its cost is <= threshold and strictly below every other cost of the row, else -1.  cost == NULL: the costs are the
+ * Levenshtein distances of the pools (layout as in rgbm_edit_distance; the [n_a][n_b] matrix never leaves the device).  Otherwise cost is
+ * [n_a][n_b] row-major, NaN = the pair has no cost and does not take part, and the pools are not read.  At most 2^30 entries; n_b == 0 gives
+ * -1 everywhere. */
+int rgbm_nearest_values(int32_t device_id, const int32_t* a_cp, const int64_t* a_off, int64_t n_a, const int32_t* b_cp, const int64_t* b_off,
+                        int64_t n_b, const double* cost /* [n_a][n_b] or NULL */, double threshold, int32_t* nearest_out /* [n_a] */);
 int rgbm_table_shape(const rgbm_table* t, int64_t* n_out, int32_t* c_out, int32_t* n_codes_out /* [c] or NULL */);
 
 /* ---- row-sharded multi-GPU training ------------------------------------------------------------

@@ -84,7 +84,8 @@ def lib():
                      "rgbm_table_detect_nulls", "rgbm_table_detect_constraint", "rgbm_table_rows_of_cells", "rgbm_table_cells_fetch",
                      "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict",
                      "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
-                     "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains"):
+                     "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
+                     "rgbm_nearest_values"):
             getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -107,6 +108,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_write_cells", "rgbm_host_alloc", "rgbm_host_free",
     "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
+    "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values",
 ]
 
 COMM_ID_BYTES = 128
@@ -500,6 +502,27 @@ def edit_distance(a, b, device_id=0):
     return out
 
 
+def nearest_values(a=None, b=None, cost=None, threshold=0.0, device_id=0):
+    """Per string of ``a`` the position in ``b`` of the closest string when its cost is <= ``threshold`` and strictly below every other
+    cost of the row, else -1 (include/rgbm.h rgbm_nearest_values): int32 [len(a)].  ``cost`` None: Levenshtein distances of the two
+    lists of strings, computed and reduced on the device; else a float64 [n_a][n_b] matrix (NaN = no cost) and the strings are not read."""
+    if cost is not None:
+        m = _f64(cost)
+        if m.ndim != 2:
+            raise ValueError("cost must be a [n_a][n_b] matrix")
+        out = np.full(m.shape[0], -1, np.int32)
+        _check(lib().rgbm_nearest_values(C.c_int32(device_id), None, None, C.c_int64(m.shape[0]), None, None, C.c_int64(m.shape[1]),
+                                         _p(m, C.c_double), C.c_double(threshold), _p(out, C.c_int32)), "rgbm_nearest_values")
+        return out
+    a_cp, a_off = pack_code_points(a)
+    b_cp, b_off = pack_code_points(b)
+    out = np.full(len(a_off) - 1, -1, np.int32)
+    _check(lib().rgbm_nearest_values(C.c_int32(device_id), _p(a_cp, C.c_int32), _p(a_off, C.c_int64), C.c_int64(len(a_off) - 1),
+                                     _p(b_cp, C.c_int32), _p(b_off, C.c_int64), C.c_int64(len(b_off) - 1), None, C.c_double(threshold),
+                                     _p(out, C.c_int32)), "rgbm_nearest_values")
+    return out
+
+
 class Table:
     """An int32 code table resident in HBM (``rgbm_table``)."""
 
@@ -660,6 +683,23 @@ class Table:
         nn = C.c_int64(0)
         _check(lib().rgbm_table_count_codes(self.h, C.c_int32(col), _p(out, C.c_int64), C.byref(nn)), "rgbm_table_count_codes")
         return out, int(nn.value)
+
+    def fd_map(self, x, y):
+        """The rule model of the functional dependency x -> y (include/rgbm.h rgbm_table_fd_map): int32 [n_codes[x]], the single y code
+        each x code occurs with over the rows where both are non-NULL, -1 for none or several."""
+        out = np.full(int(self.n_codes[x]), -1, np.int32)
+        _check(lib().rgbm_table_fd_map(self.h, C.c_int32(x), C.c_int32(y), _p(out, C.c_int32)), "rgbm_table_fd_map")
+        return out
+
+    def rule_fill(self, y, x, lut, row_begin=0, n_rows=None, want_labels=True):
+        """One rule step of the chained repair (include/rgbm.h rgbm_table_rule_fill): pred = lut[x code] (x = -1: the constant lut[0]);
+        NULL cells of column y in the row range receive pred >= 0.  Returns pred per row (int32 [n_rows]) or None."""
+        n_rows = self.n - row_begin if n_rows is None else n_rows
+        l = _i32(np.asarray(lut, np.int32).reshape(-1))
+        out = np.full(n_rows, -1, np.int32) if want_labels else None
+        _check(lib().rgbm_table_rule_fill(self.h, C.c_int32(y), C.c_int32(x), _p(l, C.c_int32), C.c_int32(len(l)), C.c_int64(row_begin),
+                                          C.c_int64(n_rows), _p(out, C.c_int32)), "rgbm_table_rule_fill")
+        return out
 
     def pair_counts(self, pairs, luts=None, n_bins=None):
         """Dense joint counts of column pairs, one pass over the rows (include/rgbm.h rgbm_table_pair_counts): a list of int64

@@ -83,6 +83,14 @@ class HipEngine:
         """Levenshtein distances [len(a)][len(b)] (int32) of two lists of strings (rgbm_edit_distance): the `Levenshtein` update cost."""
         return _native.edit_distance(a, b, device_id=self.device_id)
 
+    def nearest_values(self, a, b, threshold, cost=None):
+        """Nearest-value merges (rgbm_nearest_values): per string of `a` the position in `b` of its closest string when that cost is
+        <= threshold and strictly below the second closest, else -1.  cost None: the Levenshtein distances, computed and reduced on
+        the device; else the float64 [len(a)][len(b)] cost matrix (NaN = no cost) the same reduction kernel takes."""
+        if cost is not None:
+            return _native.nearest_values(cost=cost, threshold=threshold, device_id=self.device_id)
+        return _native.nearest_values(a, b, threshold=threshold, device_id=self.device_id)
+
     def repair_chain_gather(self, table, models, targets, feats, row_begin, n_rows):
         """C2 on device buffers: the chain over this rank's rows, labels / probabilities all-gathered over the rank's communicator before
         they leave the device (include/rgbm.h rgbm_table_repair_chain_gather) -> (labels, probs of ALL ranks' rows in rank order, first row of this rank)."""
@@ -108,8 +116,13 @@ def nearest_code(values, v):
     return np.where(pick_lo, lo, pos).astype(np.int32)
 
 
-def chained_repair(engine, table, models, targets, feats_l, row_begin, n_rows, y_values, integral):
+def chained_repair(engine, table, models, targets, feats_l, row_begin, n_rows, y_values, integral, rule_steps=None):
     """`_repair` of the reference (model.py:1107-1133) on rows [row_begin, row_begin + n_rows) of a resident table.
+
+    rule_steps = {target: dict(x=column or -1, lut=int32 array)}: such a target has no trained model (its entry of `models` is not
+    read); its step is `Table.rule_fill` -- the label is lut[x code] (x = -1: the constant lut[0]; `FunctionalDepModel.predict` /
+    `PoorModel.predict`, model.py:55-56, 83-84), NULL cells take it, and a label of -1 leaves the cell NULL.  probs is 1.0 where the
+    label is >= 0.
 
     Discrete targets are scored and filled by the device chain (`repair_chain`), run by run.  A CONTINUOUS target is one more
     model of the same chain: its regressor scores every row, integral attributes are rounded (np.round, half to even,
@@ -120,11 +133,17 @@ def chained_repair(engine, table, models, targets, feats_l, row_begin, n_rows, y
     labels = np.full((T, n_rows), -1, np.int32)
     probs = np.zeros((T, n_rows), np.float64)
     values = np.full((T, n_rows), np.nan, np.float64)
+    rule_steps = rule_steps or {}
     i = 0
     while i < T:
         j = i
-        if targets[i] not in y_values:
-            while j < T and targets[j] not in y_values:
+        if targets[i] in rule_steps:
+            j = i + 1
+            step = rule_steps[targets[i]]
+            labels[i] = table.rule_fill(targets[i], int(step["x"]), step["lut"], row_begin, n_rows)
+            probs[i] = (labels[i] >= 0).astype(np.float64)
+        elif targets[i] not in y_values:
+            while j < T and targets[j] not in y_values and targets[j] not in rule_steps:
                 j += 1
             lab, prob = engine.repair_chain(table, models[i:j], targets[i:j], feats_l[i:j], row_begin, n_rows)
             labels[i:j] = lab
@@ -168,7 +187,7 @@ def _train_concurrency(engine, table, costs, requested, search_fits=0):
 
 def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, base_params, want_stats=False, row_table=None,
             force_row_sharding=False, train_concurrency=None, y_values=None, integral=(), train_tables=None, param_search=None,
-            dirty_is_shard=False, row_shard_all=False):
+            dirty_is_shard=False, row_shard_all=False, rule_steps=None):
     """Train + repair, sharded over the ranks of the current torch.distributed group (if any).
 
     train_table / dirty_table : engine tables (all rows with error cells NULLed / the dirty rows)
@@ -181,9 +200,12 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
                                 all-gather concatenates the ranks' rows in rank order (`dirty_row0` = position of this rank's first row)
     y_values[t]               : CONTINUOUS targets only -- the ascending distinct values behind the codes of column t: the target gets
                                 an L2 regressor (train.py:97-100) on those values; `integral` names the ones rounded after prediction
+    rule_steps[t]             : dict(x=column or -1, lut): target t is answered by a rule (`chained_repair`), not by a model: it is not
+                                trained, has no blob and no label counts; the chain then runs through `chained_repair`
     Returns dict(labels [T][D], probs [T][D], values [T][D] or None, models {target: bytes}, times, stats).
     """
     y_values = dict(y_values or {})
+    rule_steps = dict(rule_steps or {})
     integral = set(integral)
     train_tables = dict(train_tables or {})     # {target: table}: that target trains on its own (sampled) table, model.py:755-766
     # param_search(target, table) -> {LightGBM core parameter: value} found by the hyper-parameter search for that target (train.py:133-209),
@@ -192,6 +214,8 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
     n_cols = len(n_codes)
     costs = []
     for t in targets:
+        if t in rule_steps:
+            continue
         k = int(n_codes[t])
         costs.append((t, (1 if (k <= 2 or t in y_values) else k) * float(np.sum(label_counts[t]))))
     big, small = dist.split_targets(costs, ws, row_table is not None, force=force_row_sharding, all_targets=row_shard_all)
@@ -311,14 +335,14 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
     t0 = time.perf_counter()
     all_blobs = dist.exchange_blobs(blobs)
     all_blobs.update(shared)
-    todo = [t for t in targets if t not in trained]
+    todo = [t for t in targets if t not in trained and t not in rule_steps]
     if len(todo) > 1:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=min(8, len(todo))) as ex:
             trained.update(zip(todo, ex.map(lambda t: engine.load_model(all_blobs[t]), todo)))
     else:
         trained.update((t, engine.load_model(all_blobs[t])) for t in todo)
-    models = [trained[t] for t in targets]
+    models = [trained.get(t) for t in targets]
     t_xchg = time.perf_counter() - t0
     # data-parallel chained inference on this rank's row shard
     t0 = time.perf_counter()
@@ -330,7 +354,7 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
     # C2 = the union of the ranks' repaired cells (the UDF outputs, model.py:1142).  When the rank's librepairgbm communicator spans the
     # job (RCCL; the thread group of the tests) the chain's outputs stay on the device, are all-gathered there (ncclAllGather over xGMI on
     # the ONE communicator the rank holds) and leave it once; otherwise they are gathered from the host through the process group.
-    if not y_values and ws > 1 and hasattr(engine, "repair_chain_gather") and dist._lib_comm_spans_world():
+    if not y_values and not rule_steps and ws > 1 and hasattr(engine, "repair_chain_gather") and dist._lib_comm_spans_world():
         labels, probs, row0 = engine.repair_chain_gather(dirty_table if dirty_table is not None else row_table, models, targets, feats_l, b, c)
         values = None
         dist._note_gather("librepairgbm communicator (device buffers, all-gather)")
@@ -342,8 +366,10 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
         if D == 0:
             lab, prob = np.zeros((len(targets), 0), np.int32), np.zeros((len(targets), 0), np.float64)
             val = np.zeros((len(targets), 0), np.float64) if y_values else None
-        elif y_values:
-            lab, prob, val = chained_repair(engine, dirty_table, models, targets, feats_l, b, c, y_values, integral)
+        elif y_values or rule_steps:
+            lab, prob, val = chained_repair(engine, dirty_table, models, targets, feats_l, b, c, y_values, integral, rule_steps=rule_steps)
+            if not y_values:
+                val = None
         else:
             lab, prob = engine.repair_chain(dirty_table, models, targets, feats_l, b, c)
             val = None

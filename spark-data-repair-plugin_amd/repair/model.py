@@ -97,13 +97,17 @@ class RepairModel():
     _opt_prob_top_k = _option("repair.pmf.prob_top_k", 32, int, lambda v: v >= 3, "`{}` should be greater than 2")
     # new in this engine: the probability modes (pmf / prob / score / maximal likelihood) on the HBM-resident pipeline
     _opt_pmf_resident = _option("repair.pmf.resident", False, bool, None, None)
+    # new in this engine: the rule-based repairs (`setRepairByRules`: FD rule models, constant models, nearest-value merges) on the
+    # HBM-resident pipeline
+    _opt_rule_resident = _option("model.rule.resident", False, bool, None, None)
     # new in this engine: which HIP device trains/predicts (read by repair.train.fixed_params)
     _opt_gpu_device_id = _train_opt_gpu_device_id
 
     option_keys = set([o.key for o in (
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
-        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_gpu_device_id)] +
+        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident,
+        _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -586,8 +590,18 @@ class RepairModel():
         no rule-based repairs, no functional-dependency rule models, no rebalancing, no cost function, plain repair output
         (cells or repaired data), no feature selection, and every discrete target has at least two classes.  The
         hyper-parameter search (`model.hp.max_evals` > 1) runs on the resident tables too (pipeline.search_on_table).
-        Otherwise the value-space path (pandas + one estimator per attribute) below handles the run."""
-        if self.repair_by_rules or (not prob_modes and (compute_repair_candidate_prob or maximal_likelihood_repair or self.cf is not None)):
+        Otherwise the value-space path (pandas + one estimator per attribute) below handles the run.
+
+        With `model.rule.resident` set, `setRepairByRules(True)` qualifies as well (`_resident_rules`): the plan then carries `rules`."""
+        rules = None
+        if self.repair_by_rules:
+            if not bool(self._get_option_value(*self._opt_rule_resident)):
+                return None
+            rules = self._resident_rules(input_df, target_columns, continous_columns, domain_stats,
+                                         compute_repair_candidate_prob or maximal_likelihood_repair)
+            if rules is None:
+                return None
+        elif not prob_modes and (compute_repair_candidate_prob or maximal_likelihood_repair or self.cf is not None):
             return None
         if self.training_data_rebalancing_enabled:
             return None
@@ -599,7 +613,7 @@ class RepairModel():
         features = len(input_df.columns) - 2
         if int(self._get_option_value(*self._opt_max_training_column_num)) < features:
             return None
-        if self._repair_by_functional_deps_enabled and self._get_functional_deps(target_columns):
+        if rules is None and self._repair_by_functional_deps_enabled and self._get_functional_deps(target_columns):
             return None
         for y in target_columns:
             if y not in continous_columns and int(domain_stats.get(y, 0)) < 2:
@@ -614,7 +628,62 @@ class RepairModel():
                       max_bin=int(g(_opt_max_bin)), lambda_l1=float(g(_opt_reg_alpha)), min_gain_to_split=float(g(_opt_min_split_gain)),
                       num_leaves=31, min_data_in_leaf=20, min_sum_hessian_in_leaf=1e-3, lambda_l2=0.0, bagging_fraction=1.0, bagging_freq=0,
                       feature_fraction=1.0, seed=42)
-        return dict(engine=engine, params=params, search=int(g(_opt_max_evals)) > 1)
+        return dict(engine=engine, params=params, search=int(g(_opt_max_evals)) > 1, rules=rules)
+
+    def _resident_rules(self, input_df: DataFrame, target_columns: List[str], continous_columns: List[str], domain_stats: Dict[str, int],
+                        prob_modes: bool) -> Optional[Dict[str, Any]]:
+        """The rule-based repairs of this run as `repair.pipeline.repair_frame(rules=...)` takes them, or None (with the reason in the
+        log) where the resident pipeline does not restate them: the probability modes, regex-structure repair, an FD model for a
+        continuous attribute or from a continuous target (its chain value is the raw prediction, not a dictionary entry), a cycle
+        among the FD sources.  The FD attributes are selected as `_build_repair_models` selects them."""
+        from repair.costs import Levenshtein
+        from repair.errors import _to_sql_string
+
+        def no(reason: str) -> None:
+            _logger.info("rule-based repairs stay on the value-space path: %s" % reason)
+
+        if prob_modes:
+            return no("the probability modes are combined with rules")
+        if self._repair_by_regex_enabled:
+            return no("regex-structure repair is enabled")
+        fd: Dict[str, str] = {}
+        deps = self._get_functional_deps(target_columns) if self._repair_by_functional_deps_enabled else None
+        max_dom = int(self._get_option_value(*self._opt_max_domain_size))
+        for y in target_columns:
+            fx = [x for x in (deps or {}).get(y, []) if x in domain_stats and int(domain_stats[x]) < max_dom]
+            if not fx:
+                continue
+            if y in continous_columns:
+                return no("an FD model for the continuous attribute `%s`" % y)
+            if fx[0] in continous_columns and fx[0] in target_columns:
+                return no("the FD source `%s` of `%s` is a continuous target" % (fx[0], y))
+            fd[y] = fx[0]
+        for y in fd:
+            seen, x = {y}, fd[y]
+            while x in fd:
+                if x in seen:
+                    return no("a cycle among the FD sources of `%s`" % y)
+                seen.add(x)
+                x = fd[x]
+        nearest = None
+        if self._repair_by_nearest_values_enabled:
+            cf = self.cf
+            assert cf is not None
+            integral = {c for c in input_df.columns if is_numeric_column(input_df[c]) and is_integral_column(input_df[c])}
+
+            def current_str(attr: str, values: List[Any]) -> List[Any]:
+                # CAST(value AS STRING) of the error cells (ErrorModel.detect): integral attributes print as '2', never '2.0'
+                out = [None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_sql_string(v) for v in values]
+                return [v if v is None or attr not in integral else str(int(float(v))) for v in out]
+
+            def domain_str(attr: str, values: List[Any]) -> List[Any]:
+                # `_to_str` of the column's values as `_repair_by_nearest_values` reads them from the frame
+                return [str(int(v)) if attr in integral else _to_str(float(v) if isinstance(v, (float, np.floating)) else v) for v in values]
+
+            nearest = dict(targets=[c for c in target_columns if c in cf.targets] if cf.targets else list(target_columns),
+                           threshold=float(self._get_option_value(*self._opt_merge_threshold)),
+                           cost=None if type(cf) is Levenshtein else cf.compute, current_str=current_str, domain_str=domain_str)
+        return dict(fd=fd, nearest=nearest)
 
     def _device_detection_plan(self, input_df: DataFrame, continous_columns: List[str], compute_repair_candidate_prob: bool,
                                maximal_likelihood_repair: bool) -> Optional[Dict[str, Any]]:
@@ -692,10 +761,13 @@ class RepairModel():
         frame, info = repair_frame(plan["engine"], input_df, rid, targets=cands, base_params=plan["params"], constraints=plan["constraints"],
                                    detect_nulls=plan["detect_nulls"], continuous_columns=[c for c in continous_columns if c in cands],
                                    train_rows=sample, want_details=True, search_opts=dict(self.opts) if plan.get("search") else None,
-                                   only_noisy_targets=True, domain_analysis=plan.get("domain_analysis"))
+                                   only_noisy_targets=True, domain_analysis=plan.get("domain_analysis"), rules=plan.get("rules"))
         self._last_resident_info = info
         self._last_detection_on_device = True
-        if len(frame) == 0:
+        merged = info.get("merged_cells")              # nearest-value merges: repaired by rule, appended as `_run` appends them
+        if merged is not None and len(merged) == 0:
+            merged = None
+        if len(frame) == 0 and merged is None:
             _logger.info("Any error cell not found, so the input data is already clean")
             return input_df if repair_data else pd.DataFrame({rid: pd.Series([], dtype=input_df[rid].dtype), "attribute": pd.Series([], dtype=object),
                                                               "current_value": pd.Series([], dtype=object), "repaired": pd.Series([], dtype=object)})
@@ -709,12 +781,16 @@ class RepairModel():
                 m = (cand["attribute"] == a).to_numpy() & cand["current_value"].notna().to_numpy()
                 cand.loc[m, "current_value"] = [str(int(float(v))) for v in cand.loc[m, "current_value"]]
         if repair_data:
-            base = self._prepare_repair_base_cells(input_df, cand, sorted(set(cand["attribute"])))
+            cells = cand if merged is None else pd.concat([cand, merged], ignore_index=True)
+            base = self._prepare_repair_base_cells(input_df, cells, sorted(set(cells["attribute"])))
+            if merged is not None:
+                base = self._repair_attrs(merged, base)
             is_dirty = base[rid].isin(set(cand[rid].tolist())).to_numpy()
             dirty = self._repair_attrs(cand[[rid, "attribute", "repaired"]], base[is_dirty].reset_index(drop=True))
             return pd.concat([base[~is_dirty], dirty], ignore_index=True)
         keep = cand["repaired"].isna() | ~((cand["current_value"] == cand["repaired"]) | (cand["current_value"].isna() & cand["repaired"].isna()))
-        return cand[keep.to_numpy()].reset_index(drop=True)
+        cand = cand[keep.to_numpy()].reset_index(drop=True)
+        return cand if merged is None else pd.concat([cand, merged], ignore_index=True)
 
     def _run_resident(self, plan: Dict[str, Any], input_df: DataFrame, error_cells_df: DataFrame, target_columns: List[str],
                       continous_columns: List[str], repair_data: bool) -> DataFrame:
@@ -740,26 +816,49 @@ class RepairModel():
             _logger.info("To reduce training data, extracts %s%% samples from %d rows" % (100.0 * max_rows / len(rows), len(rows)))
             return rows[np.random.RandomState(42).choice(len(rows), max_rows, replace=False)]
 
+        rules = plan.get("rules")
+        if rules is not None and rules.get("nearest") is not None:
+            # the cost functions see the error cells' current values as `error_cells_df` holds them
+            rpos = pd.Series(np.arange(len(input_df)), index=input_df[rid].to_numpy()).reindex(error_cells_df[rid].to_numpy()).to_numpy(np.int64)
+            curv = error_cells_df["current_value"].to_numpy(dtype=object)
+            by_attr = {}
+            for a, idx in error_cells_df.groupby("attribute").indices.items():
+                o = np.argsort(rpos[idx], kind="stable")
+                by_attr[a] = (rpos[idx][o], curv[idx][o])
+            rules = dict(rules, nearest=dict(rules["nearest"], current=lambda a, rows: list(by_attr[a][1][np.searchsorted(by_attr[a][0], rows)])))
         _logger.info("[Repair Model Training Phase] Building %d models on the HBM-resident table to repair the cells in %s" % (
             len(target_columns), to_list_str(target_columns)))
         frame, info = repair_frame(plan["engine"], input_df, rid, targets=target_columns, base_params=plan["params"],
                                    error_cells=error_cells_df[[rid, "attribute"]], detect_nulls=False,
                                    continuous_columns=[c for c in continous_columns if c in target_columns], train_rows=sample,
-                                   want_details=True, search_opts=dict(self.opts) if plan.get("search") else None)
+                                   want_details=True, search_opts=dict(self.opts) if plan.get("search") else None, rules=rules)
         self._last_resident_info = info
+        by_rules = None
+        merged = info.get("merged_cells")
+        if merged is not None and len(merged):
+            # nearest-value merges: they leave the error cells and are appended as `_run` appends `repaired_by_rules_df`
+            mrep = pd.Series(merged["repaired"].to_numpy(dtype=object),
+                             index=pd.MultiIndex.from_arrays([merged[rid].to_numpy(), merged["attribute"].to_numpy()]))
+            mkey = pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()])
+            is_merged = mkey.isin(mrep.index)
+            by_rules = error_cells_df[is_merged].assign(repaired=mrep.reindex(mkey[is_merged]).to_numpy(dtype=object))
+            all_cells_df, error_cells_df = error_cells_df, error_cells_df[~is_merged].reset_index(drop=True)
         rep = pd.Series(frame["repaired"].to_numpy(dtype=object),
                         index=pd.MultiIndex.from_arrays([frame[rid].to_numpy(), frame["attribute"].to_numpy()]))
         key = pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()])
         values = rep.reindex(key).to_numpy(dtype=object)
         if repair_data:
-            base = self._prepare_repair_base_cells(input_df, error_cells_df, target_columns)
+            base = self._prepare_repair_base_cells(input_df, error_cells_df if by_rules is None else all_cells_df, target_columns)
+            if by_rules is not None:
+                base = self._repair_attrs(by_rules, base)
             is_dirty = base[rid].isin(set(error_cells_df[rid].tolist())).to_numpy()
             upd = error_cells_df[[rid, "attribute"]].assign(repaired=[None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_str(v) for v in values])
             dirty = self._repair_attrs(upd, base[is_dirty].reset_index(drop=True))
             return pd.concat([base[~is_dirty], dirty], ignore_index=True)
         cand = error_cells_df.assign(repaired=[None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_str(v) for v in values])
         keep = cand["repaired"].isna() | ~((cand["current_value"] == cand["repaired"]) | (cand["current_value"].isna() & cand["repaired"].isna()))
-        return cand[keep.to_numpy()].reset_index(drop=True)
+        cand = cand[keep.to_numpy()].reset_index(drop=True)
+        return cand if by_rules is None else pd.concat([cand, by_rules], ignore_index=True)
 
     def _cost_spec(self, engine: Any, attr: str, classes: Any, cur: List[Any], ml: bool) -> Dict[str, Any]:
         """The update costs of one target's cells as `repair.pipeline.repair_table(pmf_costs=...)` takes them, from the values

@@ -254,9 +254,71 @@ def analyse_cell_domains(table, targets, rows, cols, spec):
                           want_weak=not spec.get("keep_weak", False))
 
 
+def nearest_value_merges(engine, table, targets, rows, cols, current, spec):
+    """`_repair_by_nearest_values` (python/repair/model.py; reference model.py:1279-1291) on the NULLed table: per error cell the code of
+    the value it is merged to, or -1.  A cell of one of spec["targets"] with a truthy current value is merged to the closest live value
+    of its column (`count_codes` > 0 after the NULL-out) when that cost is <= spec["threshold"] and strictly below the second closest;
+    pairs whose cost is None do not take part.  The distinct current values and the live values go to the engine as two string pools
+    (`engine.nearest_values`: Levenshtein distances and the row reduction on the device; any other cost function fills the matrix on the
+    host, NaN for None, for the same reduction)."""
+    out = np.full(len(rows), -1, np.int32)
+    cost_fn = spec.get("cost")
+    for t in [int(t) for t in spec["targets"] if int(t) in targets]:
+        sel = np.flatnonzero(cols == t)
+        if len(sel) == 0:
+            continue
+        live = np.flatnonzero(table.count_codes(t)[0] > 0)
+        dom = list(spec["domain"](t, live))
+        cur = list(spec["current"](t, rows[sel], current[sel]))
+        b_at = [j for j, v in enumerate(dom) if v]               # compute() is None for a falsy side
+        vals = list(dict.fromkeys(v for v in cur if v))
+        if not vals or not b_at:
+            continue
+        if len(vals) * len(b_at) > (1 << 28):
+            raise NotResidentEligible("target column %d: the nearest-value cost matrix would hold %d x %d entries" % (t, len(vals), len(b_at)))
+        pool_b = [dom[j] for j in b_at]
+        if cost_fn is None:
+            near = engine.nearest_values(vals, pool_b, float(spec["threshold"]))
+        else:
+            cost = np.full((len(vals), len(pool_b)), np.nan, np.float64)
+            for i, v in enumerate(vals):
+                for j, d in enumerate(pool_b):
+                    x = cost_fn(v, d)
+                    if x is not None:
+                        cost[i, j] = float(x)
+                        if np.isnan(cost[i, j]):
+                            raise NotResidentEligible("target column %d: the cost function returned NaN" % t)
+            near = engine.nearest_values(vals, pool_b, float(spec["threshold"]), cost=cost)
+        near = np.asarray(near, np.int64)
+        code_of = np.where(near >= 0, live[np.asarray(b_at, np.int64)[np.maximum(near, 0)]], -1).astype(np.int32)
+        row_of = {v: i for i, v in enumerate(vals)}
+        at = np.array([row_of[v] if v else -1 for v in cur], np.int64)
+        out[sel] = np.where(at >= 0, code_of[np.maximum(at, 0)], -1)
+    return out
+
+
+def rule_step_summary(table, t, step, cell_rows, dirty_rows, dirty_tab, labels):
+    """What a rule step did to the error cells of its target, for `_last_resident_info`: dict(target, kind, x, cells, mapped[, conflict,
+    unseen, null_source]).  FD steps: `mapped` cells took the source's single value; `conflict`: the source value occurs with several
+    target values; `unseen`: it occurs in no row whose target cell is non-NULL; `null_source`: the source cell itself is NULL."""
+    info = dict(target=int(t), kind=step["kind"], x=int(step["x"]), cells=int(len(cell_rows)), mapped=int((labels >= 0).sum()))
+    if step["kind"] != "fd" or len(cell_rows) == 0:
+        return info
+    x = int(step["x"])
+    xv = dirty_tab.read_column(x)[np.searchsorted(dirty_rows, cell_rows)]      # the source as the step saw it (after the chain before it)
+    total = table.count_codes(x)[0]
+    nrows, _ = table.detect_nulls([t])
+    held = table.gather_rows(nrows).count_codes(x)[0] if len(nrows) else np.zeros_like(total)
+    seen = (total - held) > 0                                                  # the value occurs next to a non-NULL target cell
+    miss = (labels < 0) & (xv >= 0)
+    info.update(conflict=int((miss & seen[np.maximum(xv, 0)]).sum()), unseen=int((miss & ~seen[np.maximum(xv, 0)]).sum()),
+                null_source=int((xv < 0).sum()))
+    return info
+
+
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
@@ -281,8 +343,17 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     domain_analysis: the checked `error.*` options and the view's inputs (`analyse_cell_domains`): the reference's cell-domain analysis
                  runs on the detected cells of the noisy targets before anything is NULLed, and the weak-labelled cells (the current
                  value is the most probable one) leave the error cells (errors.py:507-530).  None = every detected cell is repaired.
+    rules      : the rule-based repairs of `RepairModel.setRepairByRules` (model.py `_repair_by_nearest_values`, `_build_repair_models`,
+                 `_resolve_prediction_order`), None = none of them:  dict(fd={target: source column} -- the target is answered by the
+                 functional dependency source -> target (`Table.fd_map` on the whole NULLed table) unless it is left with fewer than two
+                 classes;  such a discrete target gets a constant step (its one live class, or NULL) instead of NotResidentEligible;
+                 nearest=None or dict(targets=[columns], threshold, current=callable(target, rows, codes) -> the cells' current-value
+                 strings (None / '' = no merge), domain=callable(target, live codes) -> their strings, cost=None (Levenshtein, on the
+                 device) or callable(current string, domain string) -> float or None) -- `nearest_value_merges`).  Merged cells leave the
+                 error cells (`merged` holds them), rule targets are not trained, and the chain runs the non-FD targets in target order,
+                 then each FD target once its source is no longer pending.
     Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
-    dirty_rows, models, times, stats[, domain]): one entry per error cell, ordered by (column, row).
+    dirty_rows, models, times, stats[, domain][, rule_steps, merged]): one entry per error cell, ordered by (column, row).
     """
     continuous = dict(continuous or {})
     t0 = time.perf_counter()
@@ -304,8 +375,18 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     t0 = time.perf_counter()
     current = table.read_cells(rows, cols)
     table.null_cells(rows, cols, targets)                       # convertErrorCellsToNull (RepairApi.scala:171-211)
+    detected = (rows, cols)                                     # every detected cell: what a DeadClasses second pass starts from
+    merged = None
+    if rules is not None and rules.get("nearest") is not None and len(rows):
+        near = nearest_value_merges(engine, table, targets, rows, cols, current, rules["nearest"])
+        done = near >= 0
+        merged = dict(rows=rows[done], cols=cols[done], current=current[done], repaired=near[done])
+        table.write_cells(merged["rows"], merged["cols"], merged["repaired"])     # model.py `_repair_attrs(repaired_by_rules_df, ..)`
+        rows, cols, current = rows[~done], cols[~done], current[~done]
     dirty_rows = table.rows_of_cells(rows)                      # model.py:549-553
     out = dict(rows=rows, cols=cols, current=current, dirty_rows=dirty_rows, models={}, stats=[])
+    if rules is not None:
+        out.update(rule_steps=[], merged=merged)
     if domain_info is not None:
         out["domain"] = domain_info
     if len(rows) == 0:
@@ -315,26 +396,47 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     dirty_tab = table.gather_rows(dirty_rows)
     pmf_tab = table.gather_rows(dirty_rows) if want_pmf else None      # stays un-repaired: pmf mode does not chain
     label_counts = {}
+    rule_steps = {}
+    fd = dict(rules.get("fd") or {}) if rules is not None else {}
     for t in targets:
         cnt, _ = table.count_codes(t)
         if t in continuous:
             if int((cnt > 0).sum()) < 1:
                 raise NotResidentEligible("continuous target column %d has no non-NULL row to learn from" % t)
+        elif t in fd and int((cnt > 0).sum()) >= 2:
+            # FunctionalDepModel (model.py `_build_rule_model`): the map of the whole NULLed table; no model, so no label-count checks
+            rule_steps[t] = dict(x=int(fd[t]), lut=np.asarray(table.fd_map(int(fd[t]), t), np.int32), kind="fd")
+            continue
         elif only_noisy_targets and int((cnt > 0).sum()) < len(cnt):
-            e = DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, int((cnt <= 0).sum()), len(cnt)), rows, cols)
+            e = DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, int((cnt <= 0).sum()), len(cnt)), *detected)
             e.domain_info = domain_info          # the cells it carries are the pruned ones: the second pass does not analyse again
             raise e
+        elif int((cnt > 0).sum()) < 2 and rules is not None:
+            # PoorModel (model.py:1008-1017): the one live class, or NULL when the column has no value left
+            live = np.flatnonzero(cnt > 0)
+            rule_steps[t] = dict(x=-1, lut=np.array([live[0] if len(live) else -1], np.int32), kind="constant")
+            continue
         elif int((cnt > 0).sum()) < 2:
             raise NotResidentEligible("target column %d has fewer than two classes among its non-NULL rows; the reference short-cuts such "
                              "attributes with a constant model (model.py:1008-1017) -- drop it from `targets`" % t)
         label_counts[t] = cnt
+    if rule_steps:
+        # `_resolve_prediction_order`: the other targets in target order, then each FD target once its source is no longer pending
+        pending = [t for t in targets if rule_steps.get(t, {}).get("kind") == "fd"]
+        targets = [t for t in targets if t not in pending]
+        while pending:
+            ready = [t for t in pending if rule_steps[t]["x"] not in pending]
+            if not ready:
+                raise NotResidentEligible("the functional dependencies of target columns %s form a cycle" % pending)
+            targets += ready
+            pending = [t for t in pending if t not in ready]
     t_prep = time.perf_counter() - t0
     y_values = {t: np.asarray(continuous[t][0], np.float64) for t in targets if t in continuous}
     integral = {t for t in targets if t in continuous and continuous[t][1]}
     train_tables = {}
     if callable(train_rows):
         picked = {}
-        for t in targets:
+        for t in [t for t in targets if t not in rule_steps]:
             r = train_rows(t, np.flatnonzero(table.read_column(t) >= 0))
             if r is not None:
                 picked[t] = r
@@ -344,7 +446,7 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
             train_tables[t] = table.gather_rows(np.sort(np.asarray(r, np.int64)))
             label_counts[t] = train_tables[t].count_codes(t)[0]
     if check_unseen:
-        gone = unseen_categories(table, dirty_tab, targets, train_tables=train_tables, ordered_cols=set(continuous) | set(check_unseen if not isinstance(check_unseen, bool) else ()))
+        gone = unseen_categories(table, dirty_tab, [t for t in targets if t not in rule_steps], train_tables=train_tables, ordered_cols=set(continuous) | set(check_unseen if not isinstance(check_unseen, bool) else ()))
         if gone:
             raise UnseenCategories("%d (target, feature) pairs hold categories no training row has, e.g. target column %d / feature column %d"
                                    % (len(gone), gone[0][0], gone[0][1]))
@@ -357,7 +459,7 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         from repair.train import search_fits_in_flight
         search.fits_in_flight = search_fits_in_flight(search_opts)
     res = run_job(engine, table, dirty_tab, n_codes, targets, label_counts, base_params, want_stats=want_stats,
-                  y_values=y_values, integral=integral, train_tables=train_tables, param_search=search)
+                  y_values=y_values, integral=integral, train_tables=train_tables, param_search=search, rule_steps=rule_steps)
     # flatten + join with the error cells (RepairMiscApi.scala:41-49, model.py:1398-1401)
     t0 = time.perf_counter()
     tpos = np.full(table.c, -1, np.int64)
@@ -367,6 +469,9 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     prob = res["probs"][tpos[cols], pos] if res["probs"] is not None else None
     repaired_value = res["values"][tpos[cols], pos] if res.get("values") is not None else np.full(len(rows), np.nan)
     out.update(repaired=repaired, repaired_value=repaired_value, prob=prob, models=res["models"], stats=res["stats"])
+    if rules is not None:
+        out["rule_steps"] = [rule_step_summary(table, t, rule_steps[t], rows[cols == t], dirty_rows, dirty_tab, repaired[cols == t])
+                             for t in targets if t in rule_steps]
     if want_pmf:
         pc = np.full((len(rows), top_k), -1, np.int32)
         pp = np.zeros((len(rows), top_k), np.float64)
@@ -449,7 +554,7 @@ def encode_frame(df, columns):
 
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
@@ -466,7 +571,14 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
 
     domain_analysis: dict(options={error.*: checked value}, discrete_thres[, continuous_columns]) -- the cell-domain analysis and the
     weak-label pruning of the detected cells (`repair_table`); the details then hold `pairwise_attr_stats` {attribute: [(attribute, H)]},
-    `noisy_cells` and `weak_cells`."""
+    `noisy_cells` and `weak_cells`.
+
+    rules: the rule-based repairs by attribute NAME (`repair_table` has the column form): dict(fd={target: source},
+    nearest=None or dict(targets=[attributes], threshold, cost=None (Levenshtein) or callable, current_str=callable(attribute, raw
+    values) -> strings, domain_str=callable(attribute, dictionary values) -> strings[, current=callable(attribute, row positions) ->
+    strings: the error cells' current values where the caller holds them already])).  The frame then lacks the merged cells; the details
+    hold them as `merged_cells` (row_id, attribute, current_value, repaired: strings), their number per attribute as `nearest_values`,
+    and `rule_steps` (`rule_step_summary` with attribute names)."""
     import pandas as pd
     cols = [c for c in df.columns if c != row_id]
     targets = list(targets) if targets is not None else list(cols)
@@ -512,7 +624,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         ok = ~np.isnan(rpos) & (cpos >= 0)                      # cells of unknown rows / attributes drop out (join semantics)
         cells = (rpos[ok].astype(np.int64), cpos[ok].astype(np.int32))
         given_current = null_known_cells(cells[0], cells[1])
-    if error_cells is not None and not detect_nulls and not constraints:
+    if error_cells is not None and not detect_nulls and not constraints and rules is None:
         # every error cell is known and NULLed: the class counts the models will see are final.  Say so BEFORE anything is uploaded
         # (a constraint / regex / user-given cell may hold the only occurrence of a class; an all-NULL numeric column has no value)
         for t in targets:
@@ -520,6 +632,45 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             live = len(np.unique(indices[j][indices[j] >= 0]))
             if live < (1 if t in continuous_columns else 2):
                 raise NotResidentEligible("target `%s` is left with %d distinct value(s) once the error cells are removed" % (t, live))
+
+    def decode(codes, col_idx):
+        out = np.empty(len(codes), object)
+        for j in np.unique(col_idx):
+            sel = col_idx == j
+            d = dicts[j]
+            c = codes[sel]
+            v = np.empty(len(c), object)
+            ok = c >= 0
+            v[ok] = d[c[ok]]
+            v[~ok] = None
+            out[sel] = v
+        return out
+
+    def current_values(rows_, ccols_, codes_):
+        """What the cells held: their codes decoded, or -- for cells NULLed on the host before the upload -- what `null_known_cells` kept."""
+        current = decode(codes_, ccols_)
+        if given_current is not None and len(rows_):
+            key = ccols_.astype(np.int64) * len(df) + rows_
+            order = np.argsort(given_current[0], kind="stable")
+            at = np.searchsorted(given_current[0][order], key)
+            at = np.clip(at, 0, max(len(order) - 1, 0))
+            hit = given_current[0][order][at] == key if len(order) else np.zeros(len(key), bool)
+            current[hit] = given_current[1][order][at[hit]]
+        return current
+
+    def table_rules():
+        if rules is None:
+            return None
+        spec = dict(fd={pos[y]: pos[x] for y, x in dict(rules.get("fd") or {}).items()}, nearest=None)
+        nv = rules.get("nearest")
+        if nv is not None:
+            def cur_strings(t, rows_, codes_):
+                if nv.get("current") is not None:
+                    return nv["current"](cols[t], rows_)
+                return nv["current_str"](cols[t], list(current_values(rows_, np.full(len(rows_), t, np.int32), codes_)))
+            spec["nearest"] = dict(targets=[pos[a] for a in nv["targets"] if a in pos], threshold=nv["threshold"], cost=nv.get("cost"),
+                                   current=cur_strings, domain=lambda t, live: nv["domain_str"](cols[t], list(dicts[t][live])))
+        return spec
 
     def build_and_run(cells_, detect_nulls_, constraints_, analyse=True):
         table = engine.upload_dictionaries(indices, remaps)
@@ -544,7 +695,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         return cont_, repair_table(engine, table, [pos[t] for t in targets], dict(base_params or {}), constraints=cons, detect_nulls=detect_nulls_,
                                    error_cells=cells_, want_pmf=want_pmf, top_k=top_k, threshold=threshold, continuous=cont_, search_opts=search_opts,
                                    pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
-                                   only_noisy_targets=only_noisy_targets, domain_analysis=da_spec,
+                                   only_noisy_targets=only_noisy_targets, domain_analysis=da_spec, rules=table_rules(),
                                    check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
                                    train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
 
@@ -567,33 +718,12 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         if getattr(e, "domain_info", None) is not None:
             res["domain"] = e.domain_info
     rows, ccols = res["rows"], res["cols"]
-
-    def decode(codes, col_idx):
-        out = np.empty(len(codes), object)
-        for j in np.unique(col_idx):
-            sel = col_idx == j
-            d = dicts[j]
-            c = codes[sel]
-            v = np.empty(len(c), object)
-            ok = c >= 0
-            v[ok] = d[c[ok]]
-            v[~ok] = None
-            out[sel] = v
-        return out
-
     repaired = decode(res["repaired"], ccols)
     for j, (_, is_int) in cont.items():                       # continuous attributes: the regressor's value, not a dictionary entry
         sel = ccols == j
         v = res["repaired_value"][sel]
         repaired[sel] = [int(x) for x in v] if is_int else [float(x) for x in v]
-    current = decode(res["current"], ccols)
-    if given_current is not None and len(rows):
-        key = ccols.astype(np.int64) * len(df) + rows
-        order = np.argsort(given_current[0], kind="stable")
-        at = np.searchsorted(given_current[0][order], key)
-        at = np.clip(at, 0, max(len(order) - 1, 0))
-        hit = given_current[0][order][at] == key if len(order) else np.zeros(len(key), bool)
-        current[hit] = given_current[1][order][at[hit]]
+    current = current_values(rows, ccols, res["current"])
     frame = pd.DataFrame({row_id: df[row_id].to_numpy()[rows], "attribute": np.asarray(cols, object)[ccols],
                           "current_value": current, "repaired": repaired})
     if res.get("prob") is not None:
@@ -621,6 +751,22 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             d = res["domain"]
             details.update(pairwise_attr_stats={cols[t]: [(cols[y], h) for y, h in lst] for t, lst in d["pairwise"].items()},
                            noisy_cells=d["noisy_cells"], weak_cells=d["weak_cells"])
+        if rules is not None:
+            details["rule_steps"] = [dict(st, target=cols[st["target"]], x=cols[st["x"]] if st["x"] >= 0 else None) for st in res.get("rule_steps", [])]
+            mg = res.get("merged")
+            mcur, mrep, mrows, mcols = [], [], np.zeros(0, np.int64), np.zeros(0, np.int32)
+            if mg is not None and len(mg["rows"]):
+                nv = rules["nearest"]
+                mrows, mcols = mg["rows"], mg["cols"]
+                raw_cur, raw_rep = current_values(mrows, mcols, mg["current"]), decode(mg["repaired"], mcols)
+                mcur, mrep = np.empty(len(mrows), object), np.empty(len(mrows), object)
+                for j in np.unique(mcols):
+                    sel = np.flatnonzero(mcols == j)
+                    mcur[sel] = nv["current"](cols[j], mrows[sel]) if nv.get("current") is not None else nv["current_str"](cols[j], list(raw_cur[sel]))
+                    mrep[sel] = nv["domain_str"](cols[j], list(raw_rep[sel]))
+            details["merged_cells"] = pd.DataFrame({row_id: df[row_id].to_numpy()[mrows], "attribute": np.asarray(cols, object)[mcols],
+                                                    "current_value": np.asarray(mcur, object), "repaired": np.asarray(mrep, object)})
+            details["nearest_values"] = {cols[j]: int((mcols == j).sum()) for j in np.unique(mcols)}
         return frame, details
     return frame
 
