@@ -206,6 +206,17 @@ int rgbm_table_read_column(const rgbm_table* t, int32_t col, int32_t* out /* [n]
  * returns the count; rgbm_table_cells_fetch copies it out.  One such call at a time per table. */
 /* NullErrorDetector (src/main/scala/.../python/ErrorDetectorApi.scala:128-157): the NULL cells of `cols`. */
 int rgbm_table_detect_nulls(rgbm_table* t, const int32_t* cols, int32_t n_cols, int64_t* n_cells_out);
+/* The VALUE detectors (RegExErrorDetector / DomainValues / GaussianOutlierErrorDetector, ErrorDetectorApi.scala:159-187, 249-300)
+ * with the NULL detector fused in: on a label-encoded column each of them is a predicate on the dictionary code (the host evaluates
+ * a regex once per distinct value, Tukey fences keep a contiguous code range of an ascending numeric dictionary).  The cell
+ * (row, cols[j]) with code v is an error iff   v < 0 and null_is_error[j];   or v >= 0, keep_lo[j] <= keep_hi[j] and
+ * (v < keep_lo[j] or v > keep_hi[j]);   or v >= 0, flag_bits[j] != NULL and bit v of it is set (ceil(n_codes[cols[j]] / 64) words,
+ * bit v = bit v % 64 of word v / 64; a code at or beyond n_codes has no bit).  keep_lo[j] > keep_hi[j]: no range test; flag_bits
+ * (or an entry) NULL: no bitset.  The predicates of a column are ORed before the compaction, so every cell appears once.  Result as
+ * for rgbm_table_detect_nulls.  `cols` must be distinct and in range (RGBM_ERR_ARG); n_cols == 0 gives 0 cells. */
+int rgbm_table_detect_cells(rgbm_table* t, const int32_t* cols, int32_t n_cols, const uint8_t* null_is_error /* [n_cols] */,
+                            const int32_t* keep_lo, const int32_t* keep_hi /* [n_cols] */,
+                            const uint64_t* const* flag_bits /* [n_cols] or NULL */, int64_t* n_cells_out);
 /* ConstraintErrorDetector (ErrorDetectorApi.scala:189-244) for two-tuple denial constraints of the form
  * t1&t2&EQ(t1.X1,t2.X1)&..&EQ(t1.Xm,t2.Xm)&IQ(t1.Y,t2.Y)  (i.e. X1..Xm -> Y): a row violates iff another row
  * agrees with it on every X (NULL-safe, `<=>`) and differs on Y (NULL is a value of its own).  n_eq == 0 is allowed

@@ -4,6 +4,8 @@
 //   detect_nulls          NullErrorDetector                      (reference: ErrorDetectorApi.scala:128-157)
 //   detect_constraint     ConstraintErrorDetector for  X1..Xm -> Y  style denial constraints
 //                         t1&t2&EQ(t1.X,t2.X)&..&IQ(t1.Y,t2.Y)     (ErrorDetectorApi.scala:189-244)
+//   detect_cells          RegEx / DomainValues / GaussianOutlier detectors as predicates on the dictionary codes, NULL detector fused in
+//                         (ErrorDetectorApi.scala:159-187, 249-300; repair/detect_codes.py builds the predicates)
 //   null_cells            convertErrorCellsToNull                 (RepairApi.scala:171-211)
 //   rows_of_cells         clean / dirty row split                 (python/repair/model.py:549-553)
 //   gather_rows           the dirty-row table
@@ -32,9 +34,26 @@ constexpr int PBAL = PROWS / 64;        // 64 ballots per block
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 
+// the 16 x 256 flags of block (b, j) -> its 64 ballots (ballot q covers rows [b*4096 + q*64, +64)) and its count
+__device__ __forceinline__ void flags_to_ballots(const bool (&f)[PSUB], long long e, unsigned long long* __restrict__ ballots,
+                                                 unsigned* __restrict__ bcount) {
+    __shared__ unsigned wsum[PB / 64];
+    unsigned cnt = 0;
+    unsigned long long* bo = ballots + e * PBAL;
+#pragma unroll
+    for (int s = 0; s < PSUB; ++s) {
+        const unsigned long long m = __ballot(f[s]);
+        if (lane_id() == 0) { bo[s * (PB / 64) + (threadIdx.x >> 6)] = m; cnt += (unsigned)__popcll(m); }
+    }
+    if (lane_id() == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) { unsigned t = 0; for (int w = 0; w < PB / 64; ++w) t += wsum[w]; bcount[e] = t; }
+}
+
 // ---------------------------------------------------------------------------------------------
 // stream compaction, pass 1: flags -> 64-row ballots + per-block count.   grid (nblk, ncols)
 //   MODE 0: flag = cell of column cols[blockIdx.y] is NULL;  MODE 1: flag = mask[row] != 0 (blockIdx.y == 0)
+//   (MODE 2 of compact<> is k_detect below: same grid, same ballots)
 // Algorithmic bytes: 4 B per (row, column) for MODE 0, 1 B per row for MODE 1.
 // ---------------------------------------------------------------------------------------------
 template <int MODE>
@@ -52,17 +71,61 @@ __global__ __launch_bounds__(PB) void k_flag(const int32_t* __restrict__ codes, 
         if (MODE == 0) f[s] = r < n ? (col[r] < 0) : false;
         else f[s] = r < n ? (mask[r] != 0) : false;
     }
-    __shared__ unsigned wsum[PB / 64];
-    unsigned cnt = 0;
-    unsigned long long* bo = ballots + ((long long)j * nblk + b) * PBAL;
+    flags_to_ballots(f, (long long)j * nblk + b, ballots, bcount);
+}
+
+// ---------------------------------------------------------------------------------------------
+// pass 1 of the VALUE detectors (regex / value domain / Tukey fences, repair/detect_codes.py): on a label-encoded column each of
+// them is a predicate on the dictionary code, so one read of the column answers all of them and the NULL detector.  grid (nblk, ncols)
+//   flag = v < 0 ? null_is_error : (range given && (v < keep_lo || v > keep_hi)) || (bitset given && bit v set)
+// The bitset of the block's column (1 bit per code) is staged into LDS up to DET_LDS_WORDS 64-bit words (8 KiB = 65536 codes: a
+// fifth of what 8 resident workgroups -- the 32 waves a CU holds -- could declare of its 160 KiB, so LDS never costs occupancy, and at
+// most half the bytes of the block's 16 KiB row tile); larger ones are read where they lie (small next to the column, L2 resident).
+// A column without a bitset never touches one.  Bit tests are on 32-bit halves (little endian: bit v of the 64-bit words is bit v & 31
+// of half v >> 5).  Algorithmic bytes: 4 B per (row, column) + the bitset once per block.
+// ---------------------------------------------------------------------------------------------
+struct DetDesc { int32_t col, null_is_error, keep_lo, keep_hi; long long bit_off; int32_t n_words, pad; };   // bit_off: 64-bit words, -1 = none
+constexpr int DET_LDS_WORDS = 1024;
+
+__global__ __launch_bounds__(PB) void k_detect(const int32_t* __restrict__ codes, const DetDesc* __restrict__ desc,
+                                               const unsigned long long* __restrict__ bits, long long n, long long nblk,
+                                               unsigned long long* __restrict__ ballots, unsigned* __restrict__ bcount) {
+    const long long b = blockIdx.x;
+    const int j = blockIdx.y;
+    const long long base = b * PROWS;
+    const DetDesc d = desc[j];
+    const int32_t* col = codes + (long long)d.col * n;
+    int32_t v[PSUB];
+#pragma unroll
+    for (int s = 0; s < PSUB; ++s) {             // 16 independent coalesced loads in flight per lane
+        const long long r = base + (long long)s * PB + threadIdx.x;
+        v[s] = r < n ? col[r] : 0;
+    }
+    __shared__ unsigned lbits[DET_LDS_WORDS * 2];
+    const bool has_bits = d.bit_off >= 0 && d.n_words > 0;
+    const bool in_lds = has_bits && d.n_words <= DET_LDS_WORDS;          // uniform over the block
+    const unsigned* g32 = reinterpret_cast<const unsigned*>(bits + (has_bits ? d.bit_off : 0));
+    const unsigned nw32 = has_bits ? 2u * (unsigned)d.n_words : 0u;
+    if (in_lds) {
+        for (unsigned i = threadIdx.x; i < nw32; i += PB) lbits[i] = g32[i];
+        __syncthreads();
+    }
+    const bool has_range = d.keep_lo <= d.keep_hi;
+    bool f[PSUB];
 #pragma unroll
     for (int s = 0; s < PSUB; ++s) {
-        const unsigned long long m = __ballot(f[s]);
-        if (lane_id() == 0) { bo[s * (PB / 64) + (threadIdx.x >> 6)] = m; cnt += (unsigned)__popcll(m); }
+        const long long r = base + (long long)s * PB + threadIdx.x;
+        const int32_t x = v[s];
+        bool e;
+        if (x < 0) e = d.null_is_error != 0;
+        else {
+            e = has_range && (x < d.keep_lo || x > d.keep_hi);
+            const unsigned w = (unsigned)x >> 5;
+            if (w < nw32) e = e || (((in_lds ? lbits[w] : g32[w]) >> (x & 31)) & 1u);     // a code beyond the bitset has no bit
+        }
+        f[s] = r < n && e;
     }
-    if (lane_id() == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) { unsigned t = 0; for (int w = 0; w < PB / 64; ++w) t += wsum[w]; bcount[(long long)j * nblk + b] = t; }
+    flags_to_ballots(f, (long long)j * nblk + b, ballots, bcount);
 }
 
 // exclusive scan of m block counts (one workgroup; 8 entries per thread and step)
@@ -326,12 +389,16 @@ T* scr_upload(const rgbm_table& t, int slot, const T* host, size_t count, hipStr
 
 // ordered compaction of the flagged (row, column) cells into t.cell_rows / t.cell_cols; returns the cell count
 template <int MODE>
-long long compact(rgbm_table& t, const uint8_t* d_mask, const int32_t* d_cols, int ncols, bool want_cols, hipStream_t s) {
+long long compact(rgbm_table& t, const uint8_t* d_mask, const int32_t* d_cols, int ncols, bool want_cols, hipStream_t s,
+                  const DetDesc* d_desc = nullptr, const unsigned long long* d_bits = nullptr) {
     const long long n = t.n, nblk = (n + PROWS - 1) / PROWS, m = nblk * ncols;
     unsigned long long* ballots = scr<unsigned long long>(t, 0, (size_t)m * PBAL);
     unsigned* bcount = scr<unsigned>(t, 1, (size_t)m);
     long long* off = scr<long long>(t, 2, (size_t)m + 1);
-    hipLaunchKernelGGL(k_flag<MODE>, dim3((unsigned)nblk, (unsigned)ncols), dim3(PB), 0, s, t.codes.p, d_mask, d_cols, n, nblk, ballots, bcount);
+    if constexpr (MODE == 2)
+        hipLaunchKernelGGL(k_detect, dim3((unsigned)nblk, (unsigned)ncols), dim3(PB), 0, s, t.codes.p, d_desc, d_bits, n, nblk, ballots, bcount);
+    else
+        hipLaunchKernelGGL(k_flag<MODE>, dim3((unsigned)nblk, (unsigned)ncols), dim3(PB), 0, s, t.codes.p, d_mask, d_cols, n, nblk, ballots, bcount);
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, bcount, m, off, off + m);
     long long total = 0;
     HIPCHK(hipMemcpyAsync(&total, off + m, sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -415,6 +482,44 @@ RGBM_EXPORT int rgbm_table_detect_nulls(rgbm_table* t, const int32_t* cols, int3
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
         const int32_t* d_cols = scr_upload<int32_t>(*t, 6, cols, (size_t)n_cols, s);
         *n_cells_out = compact<0>(*t, nullptr, d_cols, n_cols, true, s);
+        return RGBM_OK;
+    });
+}
+
+RGBM_EXPORT int rgbm_table_detect_cells(rgbm_table* t, const int32_t* cols, int32_t n_cols, const uint8_t* null_is_error,
+                                        const int32_t* keep_lo, const int32_t* keep_hi, const uint64_t* const* flag_bits, int64_t* n_cells_out) {
+    if (!t || !n_cells_out || n_cols < 0 || (n_cols > 0 && (!cols || !null_is_error || !keep_lo || !keep_hi)))
+        return fail(RGBM_ERR_ARG, "rgbm_table_detect_cells: bad argument");
+    {
+        std::vector<uint8_t> seen((size_t)t->c, 0);
+        for (int i = 0; i < n_cols; ++i) {
+            if (cols[i] < 0 || cols[i] >= t->c) return fail(RGBM_ERR_ARG, "rgbm_table_detect_cells: column index out of range");
+            if (seen[cols[i]]) return fail(RGBM_ERR_ARG, "rgbm_table_detect_cells: a column is listed twice");
+            seen[cols[i]] = 1;
+        }
+    }
+    return guarded([&]() {
+        use_device(t->device);
+        if (n_cols == 0 || t->n == 0) { t->n_cells = 0; *n_cells_out = 0; return RGBM_OK; }
+        // one descriptor per column; the bitsets one after the other, bits at and beyond n_codes cleared
+        std::vector<DetDesc> desc((size_t)n_cols);
+        std::vector<unsigned long long> bits;
+        for (int i = 0; i < n_cols; ++i) {
+            DetDesc& d = desc[i];
+            d.col = cols[i]; d.null_is_error = null_is_error[i] ? 1 : 0; d.keep_lo = keep_lo[i]; d.keep_hi = keep_hi[i];
+            d.bit_off = -1; d.n_words = 0; d.pad = 0;
+            const uint64_t* fb = flag_bits ? flag_bits[i] : nullptr;
+            if (!fb) continue;
+            const long long nc = std::max<long long>(t->n_codes[cols[i]], 0), nw = (nc + 63) / 64;
+            d.bit_off = (long long)bits.size(); d.n_words = (int32_t)nw;
+            bits.insert(bits.end(), fb, fb + nw);
+            if (nc % 64) bits.back() &= (1ull << (nc % 64)) - 1ull;
+        }
+        std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
+        const int32_t* d_cols = scr_upload<int32_t>(*t, 6, cols, (size_t)n_cols, s);
+        const DetDesc* d_desc = scr_upload<DetDesc>(*t, 3, desc.data(), desc.size(), s);
+        const unsigned long long* d_bits = scr_upload<unsigned long long>(*t, 4, bits.data(), bits.size(), s);
+        *n_cells_out = compact<2>(*t, nullptr, d_cols, n_cols, true, s, d_desc, d_bits);
         return RGBM_OK;
     });
 }

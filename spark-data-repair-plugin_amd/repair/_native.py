@@ -85,7 +85,7 @@ def lib():
                      "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict",
                      "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
-                     "rgbm_nearest_values"):
+                     "rgbm_nearest_values", "rgbm_table_detect_cells"):
             getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -108,7 +108,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_write_cells", "rgbm_host_alloc", "rgbm_host_free",
     "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
-    "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values",
+    "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
 ]
 
 COMM_ID_BYTES = 128
@@ -577,6 +577,33 @@ class Table:
         cc = _i32(np.asarray(cols, np.int32).reshape(-1))
         n = C.c_int64(0)
         _check(lib().rgbm_table_detect_nulls(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), C.byref(n)), "rgbm_table_detect_nulls")
+        return self._fetch_cells(int(n.value), True)
+
+    def detect_cells(self, cols, null_is_error, keep_lo, keep_hi, flag_bits=None):
+        """Cells of ``cols`` flagged by per-column CODE predicates (rgbm_table_detect_cells; repair.detect_codes builds them from the
+        regex / value-domain / outlier detectors) as (rows, cols), ordered by position in ``cols`` then row.  Per column j: NULL cells
+        when ``null_is_error[j]``; codes outside [keep_lo[j], keep_hi[j]] unless keep_lo[j] > keep_hi[j]; codes whose bit is set in
+        ``flag_bits[j]`` (uint64 [ceil(n_codes / 64)], or None)."""
+        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
+        k = len(cc)
+        ne = np.ascontiguousarray(np.asarray(null_is_error).reshape(-1) != 0, np.uint8)
+        lo, hi = _i32(np.asarray(keep_lo, np.int32).reshape(-1)), _i32(np.asarray(keep_hi, np.int32).reshape(-1))
+        fb = list(flag_bits) if flag_bits is not None else [None] * k
+        if not (len(ne) == len(lo) == len(hi) == len(fb) == k):
+            raise ValueError("detect_cells: one predicate per column")
+        keep, ptrs = [], (C.POINTER(C.c_uint64) * max(k, 1))()
+        for j in range(k):
+            if fb[j] is None:
+                continue
+            w = np.ascontiguousarray(fb[j], np.uint64).reshape(-1)
+            if 0 <= cc[j] < self.c and len(w) != (int(self.n_codes[cc[j]]) + 63) // 64:
+                raise ValueError("detect_cells: the bitset of column %d holds %d words, its %d codes need %d"
+                                 % (cc[j], len(w), int(self.n_codes[cc[j]]), (int(self.n_codes[cc[j]]) + 63) // 64))
+            keep.append(w)
+            ptrs[j] = w.ctypes.data_as(C.POINTER(C.c_uint64))
+        n = C.c_int64(0)
+        _check(lib().rgbm_table_detect_cells(self.h, _p(cc, C.c_int32), C.c_int32(k), _p(ne, C.c_uint8), _p(lo, C.c_int32), _p(hi, C.c_int32),
+                                             ptrs, C.byref(n)), "rgbm_table_detect_cells")
         return self._fetch_cells(int(n.value), True)
 
     def detect_constraint(self, eq_cols, iq_col, cell_cols=()):

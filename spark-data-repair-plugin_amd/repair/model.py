@@ -21,8 +21,8 @@ import pandas as pd
 from repair import session
 from repair.costs import UpdateCostFunction
 from repair.encode import is_integral_column, is_numeric_column
-from repair.errors import (ConstraintErrorDetector, ErrorDetector, ErrorModel, NullErrorDetector, RegExErrorDetector, parse_constraint, load_constraints,
-                           parse_and_verify_constraints)
+from repair.errors import (ConstraintErrorDetector, DomainValues, ErrorDetector, ErrorModel, GaussianOutlierErrorDetector, NullErrorDetector,
+                           RegExErrorDetector, parse_constraint, load_constraints, parse_and_verify_constraints)
 from repair.train import build_model, compute_class_nrow_stdv, rebalance_training_data, train_option_keys
 from repair.train import _opt_gpu_device_id as _train_opt_gpu_device_id
 from repair.utils import argtype_check, elapsed_time, get_option_value, job_group, setup_logger, to_list_str
@@ -100,6 +100,9 @@ class RepairModel():
     # new in this engine: the rule-based repairs (`setRepairByRules`: FD rule models, constant models, nearest-value merges) on the
     # HBM-resident pipeline
     _opt_rule_resident = _option("model.rule.resident", False, bool, None, None)
+    # new in this engine: the value detectors (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector) as code predicates on
+    # the HBM-resident table (repair.detect_codes, `Table.detect_cells`)
+    _opt_value_detectors_resident = _option("error.value_detectors.resident", False, bool, None, None)
     # new in this engine: which HIP device trains/predicts (read by repair.train.fixed_params)
     _opt_gpu_device_id = _train_opt_gpu_device_id
 
@@ -107,7 +110,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident,
-        _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -691,8 +694,14 @@ class RepairModel():
         cells come from NULL / denial-constraint detectors only (no own target lists; every constraint in the form the device
         detector handles, `pipeline.constraint_to_columns`) and the rest of the run qualifies for the resident pipeline: the
         frame is then encoded once and `pipeline.repair_frame` detects, NULLs, trains and repairs without an `error_cells_df` ever
-        being built in pandas."""
+        being built in pandas.
+
+        With `error.value_detectors.resident` set, RegExErrorDetector, DomainValues and GaussianOutlierErrorDetector (exactly these
+        types) qualify too: on the encoded table they are predicates on the dictionary codes (repair.detect_codes), found together
+        with the NULL cells by one `Table.detect_cells` call.  The plan then carries `value_detectors`."""
         from repair.pipeline import constraint_to_columns
+        value_resident = bool(self._get_option_value(*self._opt_value_detectors_resident))
+        vdets: List[Dict[str, Any]] = []
         if self.error_cells is not None or not self.error_detectors:
             return None
         cols = [c for c in input_df.columns if c != self._row_id]
@@ -714,6 +723,14 @@ class RepairModel():
                     if cc is None:
                         return None
                     cons.append(([cols[i] for i in cc[0]], cols[cc[1]]))
+            elif value_resident and type(d) is RegExErrorDetector:
+                vdets.append(dict(kind="regex", attr=d.attr, regex=d.regex))
+            elif value_resident and type(d) is DomainValues:
+                if d.attr not in continous_columns:          # `DomainValues._detect_impl`: nothing on a continuous attribute
+                    vdets.append(dict(kind="domain", attr=d.attr, values=list(d.values), autofill=bool(d.autofill),
+                                      min_count_thres=d.min_count_thres))
+            elif value_resident and type(d) is GaussianOutlierErrorDetector:
+                vdets.append(dict(kind="outlier", attrs=None))
             else:
                 return None
         from repair.utils import column_nunique
@@ -730,10 +747,26 @@ class RepairModel():
             return None
         if others and any(a in others for xs, y in cons for a in list(xs) + [y]):
             return None
+        if others and any(d["kind"] != "outlier" and d["attr"] in others for d in vdets):
+            return None
+        if any(d["kind"] == "outlier" for d in vdets):
+            # the columns the outlier detector reads: plain numpy numeric ones only (`pd.to_numeric(.., errors="coerce")` of anything else
+            # and the masked comparison of a nullable column stay with the pandas detector), integers within float64's exact range (the
+            # dictionaries are float64)
+            read = [c for c in continous_columns if c in cands]
+            for c in read:
+                if not isinstance(input_df[c].dtype, np.dtype) or not is_numeric_column(input_df[c]):
+                    return None
+                if pd.api.types.is_integer_dtype(input_df[c]) and len(input_df) and input_df[c].notna().any() \
+                        and float(input_df[c].abs().max()) >= 2.0 ** 53:
+                    return None
+            for d in vdets:
+                if d["kind"] == "outlier":
+                    d["attrs"] = list(read)
         plan = self._resident_plan(input_df, cands, continous_columns, domain_stats, compute_repair_candidate_prob, maximal_likelihood_repair)
         if plan is None:
             return None
-        plan.update(candidates=cands, constraints=cons, detect_nulls=has_null)
+        plan.update(candidates=cands, constraints=cons, detect_nulls=has_null, value_detectors=vdets or None)
         eopts = ErrorModel(row_id=self._row_id, targets=self.targets, discrete_thres=self.discrete_thres, error_detectors=self.error_detectors,
                            error_cells=None, opts=self.opts)._checked_options()
         if eopts[ErrorModel._opt_domain_analysis_enabled.key]:
@@ -758,10 +791,24 @@ class RepairModel():
             return rows[np.random.RandomState(42).choice(len(rows), max_rows, replace=False)]
 
         _logger.info("[Error Detection + Repair Model Training Phase] on the HBM-resident table, candidate attributes %s" % to_list_str(cands))
+        vdets = None
+        if plan.get("value_detectors"):
+            from repair.detect_codes import build_descriptors
+
+            def build(*a: Any, **kw: Any) -> Any:
+                # whatever stops the restatement (a malformed pattern, a dictionary that does not cast back to the column's dtype)
+                # is the value-space detector's to report
+                try:
+                    return build_descriptors(*a, **kw)
+                except Exception as e:  # noqa: BLE001
+                    raise NotResidentEligible("value detectors: %s" % e)
+
+            vdets = dict(detectors=plan["value_detectors"], build=build)
         frame, info = repair_frame(plan["engine"], input_df, rid, targets=cands, base_params=plan["params"], constraints=plan["constraints"],
                                    detect_nulls=plan["detect_nulls"], continuous_columns=[c for c in continous_columns if c in cands],
                                    train_rows=sample, want_details=True, search_opts=dict(self.opts) if plan.get("search") else None,
-                                   only_noisy_targets=True, domain_analysis=plan.get("domain_analysis"), rules=plan.get("rules"))
+                                   only_noisy_targets=True, domain_analysis=plan.get("domain_analysis"), rules=plan.get("rules"),
+                                   value_detectors=vdets)
         self._last_resident_info = info
         self._last_detection_on_device = True
         merged = info.get("merged_cells")              # nearest-value merges: repaired by rule, appended as `_run` appends them

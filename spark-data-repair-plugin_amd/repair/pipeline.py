@@ -29,12 +29,15 @@ def _merge_cells(n, parts):
     return key % n, (key // n).astype(np.int32)
 
 
-def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_cells=None):
+def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_cells=None, value_detectors=None):
     """Error cells of the target attributes.
 
     constraints : [(eq_cols, iq_col)] -- denial constraints  EQ(X1)..EQ(Xm) & IQ(Y)  (ErrorDetectorApi.scala:189-244); a
                   violating row contributes the constraint's attributes that are targets (`attrs`, line 211)
     error_cells : (rows, cols) given by the caller (RepairModel.setErrorCells); non-target attributes are dropped
+    value_detectors : per-column descriptors of the regex / value-domain / outlier detectors as code predicates
+                  (`repair.detect_codes.build_descriptors`); one `Table.detect_cells` call answers them, and the NULL detector
+                  rides in the same read of each column instead of `detect_nulls`.  Each descriptor gets its `cells` count.
     """
     tg = [int(t) for t in targets]
     parts = []
@@ -42,7 +45,23 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
         r, c = np.asarray(error_cells[0], np.int64), np.asarray(error_cells[1], np.int32)
         keep = np.isin(c, tg) & (r >= 0) & (r < table.n)
         parts.append((r[keep], c[keep]))
-    if detect_nulls and tg:
+    if value_detectors:
+        descs = {int(d["col"]): d for d in value_detectors if int(d["col"]) in tg}
+        call = []
+        for t in tg:                                   # position in the list = column order, as `_merge_cells` orders the result
+            d = descs.get(t)
+            null = bool(detect_nulls or (d is not None and d["null_is_error"]))
+            lo, hi, bits = (d["keep_lo"], d["keep_hi"], d["flag_bits"]) if d is not None else (0, -1, None)
+            if null or lo <= hi or bits is not None:
+                call.append((t, null, lo, hi, bits))
+        if call:
+            r, c = table.detect_cells([x[0] for x in call], [x[1] for x in call], [x[2] for x in call], [x[3] for x in call],
+                                      [x[4] for x in call])
+            parts.append((r, c))
+            found = np.bincount(c, minlength=table.c) if len(c) else np.zeros(table.c, np.int64)
+            for d in descs.values():
+                d["cells"] = int(found[int(d["col"])])
+    elif detect_nulls and tg:
         parts.append(table.detect_nulls(tg))
     for eq, iq in constraints:
         attrs = []
@@ -318,7 +337,8 @@ def rule_step_summary(table, t, step, cell_rows, dirty_rows, dirty_tab, labels):
 
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
+                 value_detectors=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
@@ -352,14 +372,19 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
                  device) or callable(current string, domain string) -> float or None) -- `nearest_value_merges`).  Merged cells leave the
                  error cells (`merged` holds them), rule targets are not trained, and the chain runs the non-FD targets in target order,
                  then each FD target once its source is no longer pending.
+    value_detectors: per-column code predicates of the regex / value-domain / outlier detectors (`detect_error_cells`), or a callable
+                 (table) -> such a list, called on the table before any cell is NULLed (autofill and quartiles need its rows per code).
     Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
-    dirty_rows, models, times, stats[, domain][, rule_steps, merged]): one entry per error cell, ordered by (column, row).
+    dirty_rows, models, times, stats[, domain][, rule_steps, merged][, value_detectors]): one entry per error cell, ordered by
+    (column, row).
     """
     continuous = dict(continuous or {})
     t0 = time.perf_counter()
     targets = [int(t) for t in targets]
     n_codes = np.asarray(table.n_codes, np.int32)
-    rows, cols = detect_error_cells(table, targets, constraints, detect_nulls, error_cells)
+    if callable(value_detectors):
+        value_detectors = value_detectors(table)
+    rows, cols = detect_error_cells(table, targets, constraints, detect_nulls, error_cells, value_detectors=value_detectors)
     if only_noisy_targets:
         noisy = set(int(c) for c in np.unique(cols))
         targets = [t for t in targets if t in noisy]
@@ -389,6 +414,9 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         out.update(rule_steps=[], merged=merged)
     if domain_info is not None:
         out["domain"] = domain_info
+    if value_detectors:
+        out["value_detectors"] = [dict(col=int(d["col"]), kinds=list(d.get("kinds", ())), codes_flagged=int(d.get("codes_flagged", 0)),
+                                       cells=int(d.get("cells", 0))) for d in value_detectors]
     if len(rows) == 0:
         out.update(repaired=np.zeros(0, np.int32), repaired_value=np.zeros(0, np.float64), prob=np.zeros(0, np.float64),
                    times=dict(detect=t_detect, prepare=time.perf_counter() - t0))
@@ -410,6 +438,7 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         elif only_noisy_targets and int((cnt > 0).sum()) < len(cnt):
             e = DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, int((cnt <= 0).sum()), len(cnt)), *detected)
             e.domain_info = domain_info          # the cells it carries are the pruned ones: the second pass does not analyse again
+            e.value_detectors = out.get("value_detectors")
             raise e
         elif int((cnt > 0).sum()) < 2 and rules is not None:
             # PoorModel (model.py:1008-1017): the one live class, or NULL when the column has no value left
@@ -554,15 +583,23 @@ def encode_frame(df, columns):
 
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None):
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
+                 value_detectors=None):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
     Columns are discrete (one class per distinct value) unless named in `continuous_columns` (numeric columns; those targets
     get regressors and `repaired` is the predicted number, rounded for integer columns); `constraints` are `X1,..,Xm -> Y`
     dependencies given as ([x names], y name); `error_cells` is a frame with `row_id` and `attribute` columns
-    (RepairModel.setErrorCells).  Regex / outlier detectors and rule-based repairs stay with `repair.model.RepairModel` (the
-    value-space API).
+    (RepairModel.setErrorCells).  Regex / value-domain / outlier detectors come as `value_detectors`; LOF-style detectors stay with
+    `repair.model.RepairModel` (the value-space API).
+
+    value_detectors: dict(detectors=[dict(kind='regex', attr, regex) | dict(kind='domain', attr, values, autofill, min_count_thres) |
+    dict(kind='outlier', attrs)][, build=callable(detectors, columns, dicts, dtypes, counts, targets, null_all) -> descriptors]) -- the
+    detectors by attribute name and what turns them into per-column code predicates (default `repair.detect_codes.build_descriptors`).
+    The descriptors are built after the upload, so `counts(j)` (rows per code of column j: autofill, quartiles) comes from the table;
+    one `Table.detect_cells` call then finds their cells and the NULL cells.  The details hold `value_detectors`: per descriptor the
+    attribute, the kinds merged, the codes flagged and the cells found.
 
     pmf_costs (with want_pmf): the update costs of RepairModel.run()'s probability modes, a callable (attribute, its classes (the
     target's dictionary, ascending), ascending row positions of its error cells) -> the dict `repair_table` describes, or None.  The
@@ -672,6 +709,16 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                                    current=cur_strings, domain=lambda t, live: nv["domain_str"](cols[t], list(dicts[t][live])))
         return spec
 
+    def table_detectors(detect_nulls_):
+        if not value_detectors or not value_detectors.get("detectors"):
+            return None
+        build = value_detectors.get("build")
+        if build is None:
+            from repair.detect_codes import build_descriptors as build
+        dets = list(value_detectors["detectors"])
+        return lambda table: build(dets, cols, dicts, {c: df[c].dtype for c in cols}, lambda j: table.count_codes(j)[0], list(targets),
+                                   null_all=bool(detect_nulls_))
+
     def build_and_run(cells_, detect_nulls_, constraints_, analyse=True):
         table = engine.upload_dictionaries(indices, remaps)
         da_spec = None
@@ -696,6 +743,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                                    error_cells=cells_, want_pmf=want_pmf, top_k=top_k, threshold=threshold, continuous=cont_, search_opts=search_opts,
                                    pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
                                    only_noisy_targets=only_noisy_targets, domain_analysis=da_spec, rules=table_rules(),
+                                   value_detectors=table_detectors(detect_nulls_) if analyse else None,
                                    check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
                                    train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
 
@@ -717,6 +765,8 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         cont, res = build_and_run(cells, False, (), analyse=False)
         if getattr(e, "domain_info", None) is not None:
             res["domain"] = e.domain_info
+        if getattr(e, "value_detectors", None):
+            res["value_detectors"] = e.value_detectors
     rows, ccols = res["rows"], res["cols"]
     repaired = decode(res["repaired"], ccols)
     for j, (_, is_int) in cont.items():                       # continuous attributes: the regressor's value, not a dictionary entry
@@ -751,6 +801,9 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             d = res["domain"]
             details.update(pairwise_attr_stats={cols[t]: [(cols[y], h) for y, h in lst] for t, lst in d["pairwise"].items()},
                            noisy_cells=d["noisy_cells"], weak_cells=d["weak_cells"])
+        if res.get("value_detectors"):
+            details["value_detectors"] = [dict(attribute=cols[d["col"]], kinds=d["kinds"], codes_flagged=d["codes_flagged"], cells=d["cells"])
+                                          for d in res["value_detectors"]]
         if rules is not None:
             details["rule_steps"] = [dict(st, target=cols[st["target"]], x=cols[st["x"]] if st["x"] >= 0 else None) for st in res.get("rule_steps", [])]
             mg = res.get("merged")
