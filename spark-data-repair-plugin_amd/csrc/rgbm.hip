@@ -7,6 +7,10 @@
 //     hist -> split_find -> tree_step -> partition -> finish_split     (num_leaves-1 times)
 // reads its work description from there.  The host only enqueues.
 //
+// Host side of a fit, in the order of this file: the pieces both trainers share (check_fit_args, BinRecords with
+// the code counts, BagState, TreeBlock), then train_core = prologue -> FitState (what both growers work on) -> LevelGrower or
+// LeafwiseGrower (each owns its buffers) -> the boosting loop and the harvest, then train_batch_small on the same set-up pieces.
+//
 // There is NO CPU fallback in this library: without a HIP device every compute entry point
 // returns RGBM_ERR_NO_DEVICE (the CPU oracle under oracle/ is test infrastructure and is never
 // linked or loaded from here).
@@ -20,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -1057,27 +1062,16 @@ void launch_level_mt(const MtForm& f, bool bag, bool route, dim3 grid, hipStream
     // (always the CU's whole LDS: the hessian sums sit a compile-time distance behind the gradient sums; LevelConst::lds_bytes, the test hook, only sizes the histograms)
     hipLaunchKernelGGL(mt_kernel(f, bag, route), grid, dim3(f.threads), rg::LV_LDS_BYTES, s, rec, gh, node, inbag, plan, part, count, fmeta, cmeta, err_flag, fxs, c);
 }
-// the level grower's kernels may use the CU's whole LDS.  Once per process and device: the attribute belongs to the function, not to the
-// call, and other threads are launching these kernels while a new training call sets up
-void set_level_lds_attributes(int device) {
-    static std::mutex attr_mu; static std::vector<char> attr_done(64, 0);
-    std::lock_guard<std::mutex> lk(attr_mu);
-    if (attr_done[device & 63]) return;
-    HIPCHK(hipFuncSetAttribute((const void*)rg::k_level_root, hipFuncAttributeMaxDynamicSharedMemorySize, rg::LV_LDS_BYTES));
-    for (const MtForm& f : MT_FORMS) for (int bag = 0; bag < 2; ++bag) for (int route = 0; route < 2; ++route)
-        HIPCHK(hipFuncSetAttribute((const void*)mt_kernel(f, bag != 0, route != 0), hipFuncAttributeMaxDynamicSharedMemorySize, rg::LV_LDS_BYTES));
-    attr_done[device & 63] = 1;
-}
-
 // HIP events around every histogram launch of a training call, on the stream it is launched on; only when stats are requested
 struct HistTimers {
     bool on; hipStream_t s;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; std::vector<char> root;
+    std::deque<rgh::Event> ev; std::vector<char> root;      // launch i: events 2i (before) and 2i + 1 (after)
     template <typename Fn> void timed(bool is_root, Fn&& fn) {
-        hipEvent_t a = nullptr, b = nullptr;
-        if (on) { HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b)); HIPCHK(hipEventRecord(a, s)); }
+        if (!on) { fn(); return; }
+        HIPCHK(hipEventRecord(ev.emplace_back().e, s));
         fn();
-        if (on) { HIPCHK(hipEventRecord(b, s)); ev.emplace_back(a, b); root.push_back(is_root ? 1 : 0); }
+        HIPCHK(hipEventRecord(ev.emplace_back().e, s));
+        root.push_back(is_root ? 1 : 0);
     }
 };
 
@@ -1117,18 +1111,17 @@ struct LevelTrace {
     }
 };
 
-// rgbm_train_stats of a finished training call (destroys the timers' events)
-void fill_train_stats(rgbm_train_stats* stats, float total_ms, HistTimers& timers, const HostTrees& h, const rgbm_params& p, bool level_mode, bool use_bagging,
+// rgbm_train_stats of a finished training call
+void fill_train_stats(rgbm_train_stats* stats, float total_ms, const HistTimers& timers, const HostTrees& h, const rgbm_params& p, bool level_mode, bool use_bagging,
                       int nranks /* row-sharded: the ranks that share the table */, int64_t N, int64_t n_train, int F, int root_feats /* feature groups of the root pass */,
                       int K, unsigned long long statrows) {
     const int NE = p.n_estimators, NL = p.num_leaves;
     memset(stats, 0, sizeof(*stats));
     stats->total_ms = total_ms;
-    stats->hist_launches = (int64_t)timers.ev.size();
-    for (size_t i = 0; i < timers.ev.size(); ++i) {
-        float m2 = 0.f; HIPCHK(hipEventElapsedTime(&m2, timers.ev[i].first, timers.ev[i].second));
+    stats->hist_launches = (int64_t)timers.root.size();
+    for (size_t i = 0; i < timers.root.size(); ++i) {
+        float m2 = 0.f; HIPCHK(hipEventElapsedTime(&m2, timers.ev[2 * i].e, timers.ev[2 * i + 1].e));
         stats->hist_ms += m2; if (timers.root[i]) stats->root_ms += m2;
-        (void)hipEventDestroy(timers.ev[i].first); (void)hipEventDestroy(timers.ev[i].second);
     }
     stats->trees = (int64_t)NE * K;
     const bool root_done = n_train >= (int64_t)p.min_data_in_leaf * 2;
@@ -1174,191 +1167,453 @@ void fill_train_stats(rgbm_train_stats* stats, float total_ms, HistTimers& timer
 }
 
 // ---------------------------------------------------------------------------------------------
-// The trainer (GBDT::Train) on a resident table.
+// Set-up that the single-fit trainer (train_core) and the batched small-table trainer (train_batch_small) share: the argument
+// checks of a fit, its code counts, its bin records, its bagging state and the block of arrays its trees are written to.
 // ---------------------------------------------------------------------------------------------
-rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t* feat_cols, int32_t F,
-                       const double* y_value, const double* class_weight, const double* sample_weight_host,
-                       const HostLabelStats* hls, const rgbm_params& p, rgbm_train_stats* stats) {
-    using namespace rg;
+void check_fit_args(const rgbm_table& tab, int32_t target_col, const int32_t* feat_cols, int32_t F, const double* y_value, const rgbm_params& p) {
     check_params(p);
     if (F <= 0) throw std::invalid_argument("no feature columns");
     if (target_col < 0 || target_col >= tab.c) throw std::invalid_argument("target column out of range");
     for (int f = 0; f < F; ++f) if (feat_cols[f] < 0 || feat_cols[f] >= tab.c) throw std::invalid_argument("feature column out of range");
-    if (F > 65535) throw std::invalid_argument("more than 65535 feature columns");
-    const int64_t N = tab.n;
-    const int obj = p.objective;
-    const int n_y = tab.n_codes[target_col];
-    const int K = obj == 1 ? p.num_class : 1;
+    const int obj = p.objective, n_y = tab.n_codes[target_col];
     if (obj == 1 && n_y > p.num_class) throw std::out_of_range("target has more label codes than num_class");
     if (obj == 0 && n_y > 2) throw std::out_of_range("binary objective with more than 2 label codes");
     if (obj == 2 && !y_value) throw std::out_of_range("regression needs the y_value dictionary");
-    StreamGuard sg_; hipStream_t s = sg_.s;
-    hipEvent_t ev_begin, ev_end; HIPCHK(hipEventCreate(&ev_begin)); HIPCHK(hipEventCreate(&ev_end));
-    HIPCHK(hipEventRecord(ev_begin, s));
+}
 
+// The bin tables of a fit on the device and the records of its rows: [nchunk][N] x 16 bytes, one byte per feature.  First the device side
+// of FitHost's cols / ncod / cnt_off / cnt: the fit's columns (the features, then the target), their dictionary sizes, the code counts.
+struct BinRecords {
+    DevBuf<int32_t> cols, ncod; DevBuf<long long> cnt_off; DevBuf<unsigned int> cnt;
+    DevBuf<rg::FeatMeta> fmeta; DevBuf<rg::ChunkMeta> cmeta; DevBuf<long long> lut_off; DevBuf<uint8_t> lut, miss; DevBuf<uint4> rec;
+    // Code frequencies of the training rows (features + the target itself).  Enqueue only: download_counts brings them to h.cnt, and the
+    // caller synchronises before it reads them (a batch once for all its fits).
+    void count_codes(const rgbm_table& tab, int32_t target_col, const int32_t* feat_cols, int32_t F, FitHost& h, hipStream_t s) {
+        h.cols.assign(feat_cols, feat_cols + F); h.cols.push_back(target_col);
+        h.ncod.resize(F + 1); h.cnt_off.assign(F + 2, 0);
+        for (int f = 0; f <= F; ++f) { h.ncod[f] = tab.n_codes[h.cols[f]]; h.cnt_off[f + 1] = h.cnt_off[f] + std::max(h.ncod[f], 1); }
+        cols.alloc(F + 1); ncod.alloc(F + 1); cnt_off.alloc(F + 2); cnt.alloc(h.cnt_off[F + 1]);
+        cols.upload(h.cols.data(), F + 1, s); ncod.upload(h.ncod.data(), F + 1, s); cnt_off.upload(h.cnt_off.data(), F + 2, s); cnt.zero(s);
+        const int gx = (int)std::min<int64_t>((tab.n + 255) / 256, 1024);
+        hipLaunchKernelGGL(rg::k_count_codes, dim3(gx, F + 1), dim3(256), 0, s, tab.codes.p, (long long)tab.n, tab.codes.p + (long long)target_col * tab.n, cols.p, ncod.p,
+                           cnt_off.p, cnt.p, tab.has_mult ? tab.mult.p : (const uint8_t*)nullptr);
+    }
+    void download_counts(FitHost& h, hipStream_t s) const { h.cnt.resize(cnt.n); cnt.download(h.cnt.data(), cnt.n, s); }
+    void fill(const FitHost& h, long long N, hipStream_t s) {
+        const int F = h.tc.F;
+        fmeta.alloc(F); cmeta.alloc(h.nchunk); lut_off.alloc(F + 1); lut.alloc(h.lut.size()); miss.alloc(F);
+        fmeta.upload(h.fmeta.data(), F, s); cmeta.upload(h.cmeta.data(), h.nchunk, s); lut_off.upload(h.lut_off.data(), F + 1, s);
+        lut.upload(h.lut.data(), h.lut.size(), s); miss.upload(h.miss.data(), F, s);
+        rec.alloc((size_t)h.nchunk * N);
+    }
+    // bin records of the rows of `t` (the fit's table, or a table with the same columns) through a lookup table of the fit
+    void pack(const rgbm_table& t, const uint8_t* lut_, const uint8_t* miss_, uint4* out, const uint8_t* mult, hipStream_t s) const {
+        hipLaunchKernelGGL(rg::k_pack_bins, dim3((unsigned)((t.n + 255) / 256)), dim3(256), 0, s, t.codes.p, (long long)t.n, 0ll, (long long)t.n, cols.p, ncod.p,
+                           lut_off.p, lut_, miss_, (int)fmeta.n, (int)cmeta.n, out, mult);
+    }
+    void pack(const rgbm_table& tab, hipStream_t s) { pack(tab, lut.p, miss.p, rec.p, tab.has_mult ? tab.mult.p : (const uint8_t*)nullptr, s); }
+};
+
+// bagging state (GBDT::Bagging): stable training-row order, one LCG per 1024 positions
+struct BagState {
+    DevBuf<unsigned int> blk, rand, bagcnt; DevBuf<int32_t> sorted_rows, oob; DevBuf<uint8_t> inbag;      // (inbag.p stays null without bagging: the kernels' "every row")
+    std::vector<unsigned int> seeds;       // host source of an asynchronous upload: alive until the stream has drained
+    long long off = 0, local = 0, nrb = 1;
+    void order_rows(const int32_t* d_ycol, long long N, long long n_train, hipStream_t s) {
+        const long long nblk = (N + 1023) / 1024;
+        blk.alloc(nblk); sorted_rows.alloc(n_train); oob.alloc(n_train); inbag.alloc(N); bagcnt.alloc(2);
+        hipLaunchKernelGGL(rg::k_block_count, dim3((unsigned)nblk), dim3(256), 0, s, d_ycol, N, blk.p);
+        hipLaunchKernelGGL(rg::k_block_scan, dim3(1), dim3(1024), 0, s, blk.p, nblk);
+        hipLaunchKernelGGL(rg::k_stable_compact, dim3((unsigned)nblk), dim3(256), 0, s, d_ycol, N, blk.p, sorted_rows.p);
+    }
+    // the draws go per training-row POSITION: this table's rows hold the positions [bag_off, bag_off + bag_local) of n_train (a row shard: a part of them)
+    void seed(const rgbm_params& p, long long bag_off, long long bag_local, hipStream_t s) {
+        off = bag_off; local = bag_local;
+        nrb = std::max<long long>(1, (off + local + 1023) / 1024 - off / 1024);
+        LgbRand sr2((uint32_t)p.seed); sr2.rnd16();
+        const int bagging_seed = sr2.rnd16();
+        seeds.resize(nrb);
+        for (long long b = 0; b < nrb; ++b) seeds[b] = (unsigned int)(bagging_seed + off / 1024 + b);
+        rand.alloc(nrb); rand.upload(seeds.data(), nrb, s);
+    }
+};
+
+// The trees of a fit as the trainer's kernels write them (rg::TreeOut) plus `any` (per iteration: did any class tree split), and their
+// way to the host: ONE block with the ten arrays at 64-byte boundaries, whoever owns it (a vector, a slice of the page-locked arena).
+struct TreeBlock {
+    DevBuf<int32_t> L, feat, theta, dleft, left, right, cnt, any; DevBuf<double> gain, val;
+    void alloc(size_t NT, int NL, int NE, hipStream_t s) {
+        const size_t nn = NT * (size_t)(NL - 1), nl = NT * (size_t)NL;
+        any.alloc(NE); any.zero(s);
+        L.alloc(NT); feat.alloc(nn); theta.alloc(nn); dleft.alloc(nn); left.alloc(nn); right.alloc(nn); cnt.alloc(nl); gain.alloc(nn); val.alloc(nl);
+        cnt.zero(s); val.zero(s);
+    }
+    rg::TreeOut out() const { return rg::TreeOut{L.p, feat.p, theta.p, dleft.p, left.p, right.p, gain.p, val.p, cnt.p}; }
+    // The host layout: byte offsets of L, feat, theta, dleft, left, right, cnt, gain, val, any, each at a 64-byte boundary; [10] = the block's size
+    void host_layout(size_t (&off)[11]) const {
+        const size_t bytes[10] = {L.n * 4, feat.n * 4, theta.n * 4, dleft.n * 4, left.n * 4, right.n * 4, cnt.n * 4, gain.n * 8, val.n * 8, any.n * 4};
+        off[0] = 0;
+        for (int i = 0; i < 10; ++i) off[i + 1] = off[i] + ((bytes[i] + 63) & ~(size_t)63);
+    }
+    size_t host_bytes() const { size_t off[11]; host_layout(off); return off[10]; }
+    // enqueues the copies into a host block of host_bytes() bytes and returns the view of it (valid once the stream has drained)
+    HostTrees download(char* base, hipStream_t s) const {
+        size_t off[11]; host_layout(off);
+        auto get = [&](const auto& buf, int i) { auto* h = reinterpret_cast<decltype(buf.p)>(base + off[i]); buf.download(h, buf.n, s); return h; };
+        return HostTrees{get(L, 0), get(feat, 1), get(theta, 2), get(dleft, 3), get(left, 4), get(right, 5), get(cnt, 6), get(gain, 7), get(val, 8), get(any, 9)};
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// The trainer (GBDT::Train) on a resident table: train_core = prologue (checks, code counts, bins, records) -> the state both growers
+// work on (FitState) -> one grower (LevelGrower wherever it applies, else LeafwiseGrower; both are HIP and give the same models) ->
+// the boosting loop and the harvest.
+// ---------------------------------------------------------------------------------------------
+// What a boosting iteration works on whichever grower builds the trees.  The growers keep a reference to it and only READ it, when they
+// enqueue: train_core fills the members from the weights on AFTER it has built the grower (the order the work goes on the stream).
+struct FitState {
+    const rgbm_table& tab; const rgbm_params& p; hipStream_t s; const int32_t F;
     const RunSwitches sw = read_switches();
-    const bool timing = sw.timing;   // host wall-clock of the phases, to stderr
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
-    // ---- 1. code frequencies of the training rows (features + the target itself)
-    std::vector<int32_t> cols(feat_cols, feat_cols + F); cols.push_back(target_col);
-    std::vector<int32_t> ncod(F + 1); std::vector<long long> cnt_off(F + 2, 0);
-    for (int f = 0; f <= F; ++f) { ncod[f] = tab.n_codes[cols[f]]; cnt_off[f + 1] = cnt_off[f] + std::max(ncod[f], 1); }
-    DevBuf<int32_t> d_cols(F + 1), d_ncod(F + 1); DevBuf<long long> d_cnt_off(F + 2); DevBuf<unsigned int> d_cnt(cnt_off[F + 1]);
-    d_cols.upload(cols.data(), F + 1, s); d_ncod.upload(ncod.data(), F + 1, s); d_cnt_off.upload(cnt_off.data(), F + 2, s); d_cnt.zero(s);
-    const int32_t* d_ycol = tab.codes.p + (long long)target_col * N;
-    {
-        int gx = (int)std::min<int64_t>((N + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_count_codes, dim3(gx, F + 1), dim3(256), 0, s, tab.codes.p, (long long)N, d_ycol, d_cols.p, d_ncod.p, d_cnt_off.p, d_cnt.p,
-                           tab.has_mult ? tab.mult.p : (const uint8_t*)nullptr);
-    }
-    // row-sharded: this table is one rank's row shard (rgbm_params.reserved bit 0 = RGBM_FLAG_ROW_SHARDED)
-    if ((p.reserved & RGBM_FLAG_ROW_SHARDED) && g_comm.kind == 0) throw std::invalid_argument("row-sharded training requested but this thread has no communicator (rgbm_comm_init)");
-    const bool dp = (p.reserved & RGBM_FLAG_ROW_SHARDED) != 0;
-    if (dp) all_reduce(d_cnt.p, (size_t)cnt_off[F + 1], AR_U32, s);
-    std::vector<unsigned int> cnt(cnt_off[F + 1]);
-    d_cnt.download(cnt.data(), cnt.size(), s);
-    if (dp) stream_sync_watchdog(s); else HIPCHK(hipStreamSynchronize(s));
-    FitHost fh; fh.cols = cols; fh.ncod = ncod; fh.cnt_off = cnt_off; fh.cnt = cnt;
-    fit_setup(tab, y_value, class_weight, hls, p, F, fh);
-    if (obj == 2) y_value = fh.yv32.data();          // LightGBM keeps labels as float32: the dictionary rounded once
-    const int64_t n_train = fh.n_train;
-    rgbm_model* model = fh.model.get();
-    std::unique_ptr<rgbm_model>& guard = fh.model;
-    std::vector<FeatMeta>& fmeta = fh.fmeta; std::vector<ChunkMeta>& cmeta = fh.cmeta;
-    std::vector<long long>& lut_off = fh.lut_off; std::vector<uint8_t>& lut = fh.lut; std::vector<uint8_t>& miss = fh.miss; std::vector<uint8_t>& trivial = fh.trivial;
-    const int nchunk = fh.nchunk; const size_t lds_hist = fh.lds_hist;
-    std::vector<double>& init = fh.init; TrainConst tc = fh.tc;
-    const int NL = p.num_leaves, NE = p.n_estimators;
-
-    const double t_bins = now();
-    // ---- 4. device state
-    DevBuf<FeatMeta> d_fmeta(F); DevBuf<ChunkMeta> d_cmeta(nchunk); DevBuf<long long> d_lut_off(F + 1); DevBuf<uint8_t> d_lut(lut.size()), d_miss(F);
-    d_fmeta.upload(fmeta.data(), F, s); d_cmeta.upload(cmeta.data(), nchunk, s); d_lut_off.upload(lut_off.data(), F + 1, s);
-    d_lut.upload(lut.data(), lut.size(), s); d_miss.upload(miss.data(), F, s);
-    DevBuf<uint4> d_rec((size_t)nchunk * N);
-    // grower choice: the level-synchronous streaming grower (rgbm_level.h) whenever it applies; RGBM_GROWER=leafwise forces the
-    // index-list grower (both are HIP; they produce identical models)
+    const int K = p.objective == 1 ? p.num_class : 1, NL = p.num_leaves, NE = p.n_estimators; const int64_t N = tab.n;
     const bool use_bagging = p.bagging_freq > 0 && p.bagging_fraction < 1.0;
-    const bool level_mode = p.max_depth >= 1 && p.max_depth <= LV_MAX_DEPTH && F <= 255 && sw.grower != 2;
-    // rows with multiplicities (rgbm_table_set_row_multiplicity): the multiplicity rides in byte 15 of the row's LAST bin record, so that chunk
-    // must leave the byte free; the level grower only (one chunk, or two chunks in one pass), no bagging (LightGBM draws per ORIGINAL row), no per-row weights
-    const bool wm = tab.has_mult;
-    const uint8_t* d_mult = wm ? tab.mult.p : (const uint8_t*)nullptr;
-    if (wm) {
-        if (!level_mode || nchunk > 2 || (F % 16) == 0 || sample_weight_host || use_bagging)
-            throw std::invalid_argument("a table with row multiplicities trains with the level grower (1 <= max_depth <= 7), at most 32 features of which the last 16-feature "
-                                        "chunk holds at most 15, without bagging and without per-row weights");
+    // grower choice: the level-synchronous streaming grower (rgbm_level.h) whenever it applies; RGBM_GROWER=leafwise forces the index-list grower
+    const bool level_mode = p.max_depth >= 1 && p.max_depth <= rg::LV_MAX_DEPTH && F <= 255 && sw.grower != 2;
+    const bool dp = (p.reserved & RGBM_FLAG_ROW_SHARDED) != 0;     // the table is one rank's row shard (rgbm_params.reserved bit 0)
+    const int32_t* d_ycol; const uint8_t* d_mult = tab.has_mult ? tab.mult.p : (const uint8_t*)nullptr;
+    FitHost h; BinRecords bins;
+    DevBuf<int32_t> base;              // the training rows in ascending order (the leaf-wise grower's root list, the bag lists' source)
+    DevBuf<unsigned int> counter;      // ... and how many they are
+    DevBuf<float2> gh;                 // float32 (g, h) of every (row, class tree); non-training rows stay (0, 0)
+    DevBuf<double> score, init;
+    DevBuf<unsigned long long> fxq;    // numerics v2.2: coarse gradient sums of the iteration's class trees (k_fx_scale zeroes them again)
+    DevBuf<rg::FxScale> fxs;           // ... and the grid they give every class tree
+    DevBuf<unsigned long long> qpart; long long fx_parts = 0; bool fx_fused = false;      // the gradient kernels measure the coarse sums themselves (qpart.p is null otherwise)
+    TreeBlock trees;
+    DevBuf<double> cw, yv, sw_rows; DevBuf<uint8_t> used;
+    BagState bag; DevBuf<unsigned int> bagcnt_g;
+    const unsigned int* n_in_ptr = nullptr;          // rows in the bag of the current iteration, over ALL ranks when row-sharded (the root count of every tree)
+    DevBuf<int32_t> it;                // device-side iteration counter (k_next_iteration)
+    HistTimers timers;
+
+    FitState(const rgbm_table& tab_, int32_t target_col, int32_t F_, const rgbm_params& p_, bool timed, hipStream_t s_)
+        : tab(tab_), p(p_), s(s_), F(F_), d_ycol(tab_.codes.p + (long long)target_col * tab_.n), timers{timed, s_} {}
+
+    // numerics v2.2: every class tree of an iteration gets its own fixed-point grid from the coarse sums Q_g, Q_h of its (g, h) (rgbm_numerics.h).  The
+    // gradient kernels leave the sums per workgroup / wave (qpart [parts][K][2]: plain stores, no atomics), k_fx_reduce adds them up into fxq [K][2];
+    // k_grad<1> (softmax with K > 112) and RGBM_FX_MEASURE=separate take them from a pass of their own over the (g, h) array (k_fx_measure).  Row-sharded:
+    // ONE more integer all-reduce per iteration (2 K words).  k_fx_scale turns the sums into the FxScale table every accumulating / searching kernel reads.
+    int grad_gx() const { return (int)std::min<long long>((N + 255) / 256, 4096); }
+    bool mc_tile() const { return p.objective == 1 && K >= 16 && K <= 112; }
+    bool mc_rows() const { return p.objective == 1 && K < 16; }
+    void alloc_fx_parts() {
+        if (sw.fx_separate || (p.objective == 1 && !mc_tile() && !mc_rows())) return;
+        fx_fused = true; fx_parts = mc_tile() ? (N + 63) / 64 : (mc_rows() ? ((N + 255) / 256) * 4 : (long long)grad_gx());
+        qpart.alloc((size_t)fx_parts * K * 2);
     }
-    hipLaunchKernelGGL(k_pack_bins, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, tab.codes.p, (long long)N, 0ll, (long long)N,
-                       d_cols.p, d_ncod.p, d_lut_off.p, d_lut.p, d_miss.p, F, nchunk, d_rec.p, d_mult);
-    if (dp && (!level_mode || sample_weight_host))
-        throw std::invalid_argument("row-sharded training supports the level grower (1 <= max_depth <= 7) without per-row weights");
-    DevBuf<int32_t> d_base; DevBuf<unsigned int> d_counter(1); d_counter.zero(s);
-    if (!level_mode || use_bagging) {
-        d_base.alloc(n_train);
-        hipLaunchKernelGGL(k_iota_train, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_ycol, (long long)N, d_base.p, d_counter.p);
-    }
-    if (level_mode) tc.NG = (N + 255) & ~255ll;            // level grower: every wave tile of a class tree's (g, h) row is in bounds and 32-byte aligned
-    DevBuf<float2> d_gh((size_t)K * tc.NG); d_gh.zero(s);      // float32 (g, h) of every (row, class tree); non-training rows stay (0, 0)
-    DevBuf<double> d_score((size_t)K * N), d_init(K);
-    d_init.upload(init.data(), K, s);
-    DevBuf<unsigned long long> d_fxq((size_t)K * 2); d_fxq.zero(s);      // numerics v2.2: coarse gradient sums of the iteration's class trees (k_fx_scale zeroes them again)
-    DevBuf<FxScale> d_fxs(K);                                            // ... and the grid they give every class tree
-    hipLaunchKernelGGL(k_init_score, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_score.p, (long long)N, K, d_init.p);
-    DevBuf<int32_t> d_idx0, d_idx1, d_sorted, d_any(NE); d_any.zero(s);
-    DevBuf<HistBin> d_pool; DevBuf<TreeState> d_state; DevBuf<Leaf> d_leaves; DevBuf<Cand> d_cand; DevBuf<double> d_upd;
-    if (!level_mode) {
-        d_idx0.alloc((size_t)K * n_train); d_idx1.alloc((size_t)K * n_train);
-        d_pool.alloc((size_t)K * NL * tc.totbins);
-        d_state.alloc(K); d_leaves.alloc((size_t)K * NL); d_cand.alloc((size_t)K * 2 * F);
-        d_upd.alloc((size_t)K * NL); d_sorted.alloc((size_t)K * NL * 3);
-    }
-    // ---- level grower state
-    LevelConst lc; memset(&lc, 0, sizeof(lc));
-    DevBuf<uint8_t> d_node; DevBuf<LvPlan> d_plan; DevBuf<SNode> d_snodes; DevBuf<Cand> d_lcand;
-    DevBuf<HistBin> d_part, d_lpool; DevBuf<int32_t> d_count, d_count_g, d_err, d_leafnode; DevBuf<HistBin> d_part_red; DevBuf<double> d_ndelta; DevBuf<unsigned long long> d_statrows;
-    int n_hnodes = 1;
+    // the gradients of an iteration and the grid they give its class trees; node0 [K][NS]: the level grower's node ids (every training row goes back to the root)
+    void enqueue_grad(uint8_t* node0, long long NS);
+    void enqueue_bagging();    // the bag of the iterations from this one on
+};
+
+// The two ways of growing the K class trees of a boosting iteration.  Each is built from the fit's common state (which it reads, never writes),
+// allocates its own buffers and enqueues its set-up; enqueue_iteration(it) follows the gradients of iteration `it`: its trees and the score update.
+// The level-synchronous grower (rgbm_level.h): max_depth passes over the rows per iteration, every class tree's open nodes at once.
+struct LevelGrower {
+    FitState& st; hipStream_t s;
+    int root_feats;                         // feature groups the root pass accumulates per row (statistics)
+    unsigned long long statrows = 0;        // rows whose (g, h) were accumulated, counted on the device (statistics)
+    rg::LevelConst lc, lcj; LevelPassPlan passes;
+    const int n_hnodes = (1 << st.p.max_depth) - 1;
     bool use_reduce = false;   // root pass: sum the per-workgroup partials in a separate kernel (many workgroups per class tree, joint bins, or row-sharded)
     // joint bins for the root pass (rgbm_level.h, k_pack_joint): a second record whose bytes hold GROUPS of low-cardinality features
     bool joint_root = false; int vtotbins = 0;
-    LevelConst lcj; memset(&lcj, 0, sizeof(lcj));
-    DevBuf<FeatMeta> d_vfmeta; DevBuf<ChunkMeta> d_vcmeta; DevBuf<uint4> d_rec_j; DevBuf<HistBin> d_part_j, d_red_j;
-    DevBuf<JointFeat> d_jf; DevBuf<int16_t> d_binfeat;
-    LevelPassPlan passes;
-    if (level_mode) {
+    DevBuf<rg::FeatMeta> vfmeta; DevBuf<rg::ChunkMeta> vcmeta; DevBuf<uint4> rec_j; DevBuf<rg::HistBin> part_j, red_j; DevBuf<rg::JointFeat> jf; DevBuf<int16_t> binfeat;
+    DevBuf<uint8_t> node; DevBuf<rg::LvPlan> plan; DevBuf<rg::SNode> snodes; DevBuf<rg::Cand> lcand;
+    DevBuf<rg::HistBin> part, lpool, part_red; DevBuf<int32_t> count, count_g, err, leafnode; DevBuf<double> ndelta; DevBuf<unsigned long long> d_statrows;
+    const int score_gx = (int)std::max<long long>(1, std::min<long long>((st.N + 1023) / 1024, (2048 + st.K - 1) / st.K));
+    LevelTrace trace;
+    int32_t h_err = 0;
+
+    explicit LevelGrower(FitState& st_) : st(st_), s(st_.s), root_feats(st_.F), trace(true, st_.K, st_.s) {
+        using namespace rg;
+        memset(&lc, 0, sizeof(lc)); memset(&lcj, 0, sizeof(lcj));
         lc.lds_bytes = LV_LDS_BYTES;
-        if (sw.lv_lds >= 65536 && sw.lv_lds <= LV_LDS_BYTES) lc.lds_bytes = sw.lv_lds;      // testing: a smaller LDS pool forces several built-slot windows per level
-        lc.nchunk = nchunk; lc.K = K; lc.F = F; lc.totbins = tc.totbins;
-        lc.num_leaves = NL; lc.max_depth = p.max_depth; lc.min_data_in_leaf = p.min_data_in_leaf; lc.N = N; lc.NS = (N + 255) & ~255ll; lc.NG = lc.NS;
-        lc.sib_local = (dp && g_comm.rank == 0) ? 1 : 0;
-        lc.has_mult = wm ? 1u : 0u;
-        n_hnodes = (1 << p.max_depth) - 1;
-        passes = plan_level_passes(sw, fmeta, cmeta, N, K, p.max_depth, wm, lc.lds_bytes);
+        if (st.sw.lv_lds >= 65536 && st.sw.lv_lds <= LV_LDS_BYTES) lc.lds_bytes = st.sw.lv_lds;      // testing: a smaller LDS pool forces several built-slot windows per level
+        lc.nchunk = st.h.nchunk; lc.K = st.K; lc.F = st.F; lc.totbins = st.h.tc.totbins;
+        lc.num_leaves = st.NL; lc.max_depth = st.p.max_depth; lc.min_data_in_leaf = st.p.min_data_in_leaf; lc.N = st.N; lc.NS = (st.N + 255) & ~255ll; lc.NG = lc.NS;
+        lc.sib_local = (st.dp && g_comm.rank == 0) ? 1 : 0;
+        lc.has_mult = st.tab.has_mult ? 1u : 0u;
+        passes = plan_level_passes(st.sw, st.h.fmeta, st.h.cmeta, st.N, st.K, st.p.max_depth, st.tab.has_mult, lc.lds_bytes);
         lc.gx = passes.root_gx; lc.xcd_blocks = 1; lc.max_built = 1;
-        d_node.alloc((size_t)K * lc.NS);
+        node.alloc((size_t)st.K * lc.NS);
         // the padding rows [N, NS) of every class tree stay LV_INACTIVE for the whole fit (the gradient kernels reset rows < N only): the level pass
         // routes rows by their id alone, and an id past the end of a class tree's table takes the dummy entry
-        HIPCHK(hipMemsetAsync(d_node.p, 0xFF, (size_t)K * lc.NS, s));
-        d_plan.alloc(K); d_snodes.alloc((size_t)K * 256); d_lcand.alloc((size_t)K * 256 * F);
-        d_part.alloc(passes.part_items * tc.totbins); d_lpool.alloc((size_t)K * n_hnodes * tc.totbins);
-        d_count.alloc((size_t)K * 256); use_reduce = dp || lc.gx > 4;
-        if (dp) d_count_g.alloc((size_t)K * 256);
-        const int max_built_all = 1 << std::max(0, p.max_depth - 2);
-        d_part_red.alloc((size_t)K * max_built_all * tc.totbins + (size_t)K * 128 /* K*256 int64 counts */);
-        d_leafnode.alloc((size_t)K * LV_MAX_LEAVES); d_err.alloc(1); d_err.zero(s); d_ndelta.alloc((size_t)K * 256); d_statrows.alloc(1); d_statrows.zero(s);
+        HIPCHK(hipMemsetAsync(node.p, 0xFF, (size_t)st.K * lc.NS, s));
+        plan.alloc(st.K); snodes.alloc((size_t)st.K * 256); lcand.alloc((size_t)st.K * 256 * st.F);
+        part.alloc(passes.part_items * st.h.tc.totbins); lpool.alloc((size_t)st.K * n_hnodes * st.h.tc.totbins);
+        count.alloc((size_t)st.K * 256); use_reduce = st.dp || lc.gx > 4;
+        if (st.dp) count_g.alloc((size_t)st.K * 256);
+        const int max_built_all = 1 << std::max(0, st.p.max_depth - 2);
+        part_red.alloc((size_t)st.K * max_built_all * st.h.tc.totbins + (size_t)st.K * 128 /* K*256 int64 counts */);
+        leafnode.alloc((size_t)st.K * LV_MAX_LEAVES); err.alloc(1); err.zero(s); ndelta.alloc((size_t)st.K * 256); d_statrows.alloc(1); d_statrows.zero(s);
         // Joint bins for the root pass (the tables where the root pass runs at the LDS-atomic rate); RGBM_JOINT_ROOT=0 disables it (same
         // models either way: the sums are exact integers)
-        if (sw.joint_root && ((long long)K * N >= (1ll << 21) || (wm && nchunk == 2))) {
-            const JointRootPlan jp = plan_joint_root(fmeta, tc.totbins, wm, lc.lds_bytes);
+        if (st.sw.joint_root && ((long long)st.K * st.N >= (1ll << 21) || (st.tab.has_mult && st.h.nchunk == 2))) {
+            const JointRootPlan jp = plan_joint_root(st.h.fmeta, st.h.tc.totbins, st.tab.has_mult, lc.lds_bytes);
             if (jp.on) {
                 const int VF = (int)jp.vfm.size();
                 joint_root = true; vtotbins = jp.vcm.wide_bins;
-                d_vfmeta.alloc(VF); d_vfmeta.upload(jp.vfm.data(), VF, s); d_vcmeta.alloc(1); d_vcmeta.upload(&jp.vcm, 1, s);
-                d_jf.alloc(F); d_jf.upload(jp.jf.data(), F, s); d_binfeat.alloc(jp.binfeat.size()); d_binfeat.upload(jp.binfeat.data(), jp.binfeat.size(), s);
-                d_rec_j.alloc((size_t)N);
-                hipLaunchKernelGGL(k_pack_joint, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_rec.p, (long long)N, F, d_jf.p, d_rec_j.p, wm ? nchunk - 1 : -1);
-                d_part_j.alloc((size_t)K * lc.gx * vtotbins); d_red_j.alloc((size_t)K * vtotbins + (size_t)K * 128 /* k_level_reduce parks the counts behind the bins */);
+                vfmeta.alloc(VF); vfmeta.upload(jp.vfm.data(), VF, s); vcmeta.alloc(1); vcmeta.upload(&jp.vcm, 1, s);
+                jf.alloc(st.F); jf.upload(jp.jf.data(), st.F, s); binfeat.alloc(jp.binfeat.size()); binfeat.upload(jp.binfeat.data(), jp.binfeat.size(), s);
+                rec_j.alloc((size_t)st.N);
+                hipLaunchKernelGGL(k_pack_joint, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, s, st.bins.rec.p, (long long)st.N, st.F, jf.p, rec_j.p, st.tab.has_mult ? st.h.nchunk - 1 : -1);
+                part_j.alloc((size_t)st.K * lc.gx * vtotbins); red_j.alloc((size_t)st.K * vtotbins + (size_t)st.K * 128 /* k_level_reduce parks the counts behind the bins */);
                 lcj = lc; lcj.nchunk = 1; lcj.F = VF; lcj.totbins = vtotbins; lcj.max_built = 1;
-                use_reduce = true;
+                use_reduce = true; root_feats = VF;
                 HIPCHK(hipStreamSynchronize(s));   // jp's vectors are locals
             }
         }
-        if (wm && nchunk == 2 && !joint_root)
+        if (st.tab.has_mult && st.h.nchunk == 2 && !joint_root)
             throw std::invalid_argument("a two-chunk table with row multiplicities needs the joint-bin root pass (its record carries the multiplicity); this feature set does not pack into 15 groups");
-        if (sw.timing) {
+        if (st.sw.timing) {
             fprintf(stderr, "[rgbm] root: gx %d joint %d groups %d\n", lc.gx, joint_root ? 1 : 0, joint_root ? lcj.F : 0);
-            for (int level = 1; level < p.max_depth; ++level) for (const auto& L : passes.mt[level])
+            for (int level = 1; level < st.p.max_depth; ++level) for (const auto& L : passes.mt[level])
                 fprintf(stderr, "[rgbm] level %d launch: chunk %d slots %d..%d route %d T %d G %d gx %d acc2 %d rot %d\n", level, L.ch, L.slot0, L.slot0 + L.nslots - 1, L.route, L.T, L.G, L.gx, L.acc2, L.rot);
         }
-        set_level_lds_attributes(tab.device);
+        rgh::once_per_device(st.tab.device, rgh::ONCE_LEVEL_LDS, [] {      // the level grower's kernels may use the CU's whole LDS
+            HIPCHK(hipFuncSetAttribute((const void*)rg::k_level_root, hipFuncAttributeMaxDynamicSharedMemorySize, rg::LV_LDS_BYTES));
+            for (const MtForm& f : MT_FORMS) for (int bag = 0; bag < 2; ++bag) for (int route = 0; route < 2; ++route)
+                HIPCHK(hipFuncSetAttribute((const void*)mt_kernel(f, bag != 0, route != 0), hipFuncAttributeMaxDynamicSharedMemorySize, rg::LV_LDS_BYTES));
+        });
+        if (trace.on) trace.buf.alloc(((size_t)st.K * n_hnodes * st.h.tc.totbins * 16 + (size_t)st.K * 256 * (sizeof(SNode) + 4) + (size_t)st.K * sizeof(LvPlan) + 4096) * (size_t)(st.p.max_depth + 1) * (size_t)(trace.hi - trace.lo + 1) + (size_t)st.NE * 64 + 4096);
     }
-    const size_t NT = (size_t)NE * K;
-    DevBuf<int32_t> t_L(NT), t_feat(NT * (NL - 1)), t_theta(NT * (NL - 1)), t_dleft(NT * (NL - 1)), t_left(NT * (NL - 1)), t_right(NT * (NL - 1)), t_cnt(NT * NL);
-    DevBuf<double> t_gain(NT * (NL - 1)), t_val(NT * NL);
-    t_cnt.zero(s); t_val.zero(s);
-    TreeOut to{t_L.p, t_feat.p, t_theta.p, t_dleft.p, t_left.p, t_right.p, t_gain.p, t_val.p, t_cnt.p};
-    DevBuf<double> d_cw, d_yv, d_sw;
-    if (class_weight) { d_cw.alloc(n_y); d_cw.upload(class_weight, n_y, s); }
-    if (y_value) { d_yv.alloc(n_y); d_yv.upload(y_value, n_y, s); }
-    if (sample_weight_host) { d_sw.alloc(N); d_sw.upload(sample_weight_host, N, s); }
 
-    const std::vector<uint8_t> used = make_used_masks(p, NT, F, trivial);
-    DevBuf<uint8_t> d_used(used.size()); d_used.upload(used.data(), used.size(), s);
+    void trace_level(int level) {
+        trace.copy("count", level, count.p, (size_t)st.K * 256 * 4);
+        trace.copy("plan", level, plan.p, (size_t)st.K * sizeof(rg::LvPlan));
+        trace.copy("snodes", level, snodes.p, (size_t)st.K * 256 * sizeof(rg::SNode));
+        trace.copy("lpool", level, lpool.p, (size_t)st.K * n_hnodes * st.h.tc.totbins * 16);
+    }
+    // partials of this rank -> compact buffer (-> integer all-reduce when row-sharded); the split kernel then sees ONE partial
+    std::pair<const rg::HistBin*, rg::LevelConst> exchange(bool root, int nb, const rg::LevelConst& lp) {
+        using namespace rg;
+        if (root && !use_reduce) return {part.p, lp};
+        if (root && joint_root) {   // partials -> one joint histogram per class tree (k_level_reduce in the joint bin space) -> marginals of the real features
+            hipLaunchKernelGGL(k_level_reduce, dim3((vtotbins + 63) / 64, 1, st.K), dim3(256), 0, s, part_j.p, red_j.p, plan.p, count.p, 1, 1, lcj);
+            hipLaunchKernelGGL(k_level_marginal, dim3((st.h.tc.totbins + 255) / 256, st.K), dim3(256), 0, s, red_j.p, part_red.p, plan.p, count.p, jf.p, binfeat.p, vtotbins, lc);
+        } else
+            hipLaunchKernelGGL(k_level_reduce, dim3((st.h.tc.totbins + 63) / 64, nb, st.K), dim3(256), 0, s, part.p, part_red.p, plan.p, count.p, root ? 1 : 0, nb, lp);
+        if (st.dp) {
+            const size_t nh = (size_t)st.K * nb * st.h.tc.totbins * 2;          // int64 words of histograms, then K*256 child counts
+            all_reduce(part_red.p, nh + (size_t)st.K * 256, AR_I64, s);
+            hipLaunchKernelGGL(k_counts_unpack, dim3(st.K), dim3(256), 0, s, reinterpret_cast<const long long*>(part_red.p) + nh, count_g.p);
+        }
+        LevelConst r = lp; r.gx = 1; r.max_built = nb;
+        return {part_red.p, r};
+    }
+    // one boosting iteration of the level grower after the gradients: an iteration-invariant launch sequence
+    void enqueue_iteration(int it) {
+        using namespace rg;
+        const TreeOut to = st.trees.out();
+        trace.cur_it = it;
+        trace.sum("gh", st.gh.p, (size_t)st.K * st.h.tc.NG * 8);
+        hipLaunchKernelGGL(k_level_init, dim3(st.K), dim3(64), 0, s, plan.p, snodes.p, count.p, st.n_in_ptr, (long long)st.h.n_train, st.fxq.p, st.h.tc.fx, st.fxs.p, lc);
+        int32_t* cntg = st.dp ? count_g.p : count.p;      // child row counts seen by split / leaf-count (global when row-sharded)
+        st.timers.timed(true, [&]() {
+            if (joint_root)   // the root pass over the joint record: one pair of atomics per feature GROUP and row
+                hipLaunchKernelGGL(k_level_root, dim3((unsigned)lc.gx * (unsigned)st.K, 1, 1), dim3(LV_THREADS), lc.lds_bytes, s, rec_j.p, st.gh.p, node.p, plan.p, part_j.p,
+                                   vfmeta.p, vcmeta.p, st.fxs.p, lcj);
+            else
+                hipLaunchKernelGGL(k_level_root, dim3((unsigned)lc.gx * (unsigned)st.K, 1, st.h.nchunk), dim3(LV_THREADS), lc.lds_bytes, s, st.bins.rec.p, st.gh.p, node.p, plan.p, part.p,
+                                   st.bins.fmeta.p, st.bins.cmeta.p, st.fxs.p, lc);
+        });
+        {
+            auto ex = exchange(true, 1, lc);
+            hipLaunchKernelGGL(k_level_split<true>, dim3((st.F + 3) / 4, 1, st.K), dim3(256), 0, s, ex.first, lpool.p, plan.p, snodes.p, cntg, count.p, st.bins.fmeta.p,
+                               st.used.p, lcand.p, d_statrows.p, st.it.p, n_hnodes, st.fxs.p, st.h.tc, ex.second);
+            trace_level(0);
+        }
+        for (int level = 1; level < st.p.max_depth; ++level) {
+            hipLaunchKernelGGL(k_level_plan, dim3(st.K), dim3(256), 0, s, plan.p, snodes.p, lcand.p, st.bins.fmeta.p, level, st.h.tc, lc);
+            // the k_level_mt launches of the level; lp describes the partials they write
+            LevelConst lp = lc;
+            lp.xcd_blocks = 0; lp.gx = passes.mt_gx[level]; lp.max_built = 1 << (level - 1);
+            for (const MtLaunch& L : passes.mt[level]) {
+                LevelConst l1 = lp;
+                l1.mt_T = L.T; l1.mt_G = L.G; l1.mt_ch = L.ch; l1.mt_slot0 = L.slot0; l1.mt_nslots = L.nslots; l1.mt_route = L.route; l1.mt_sparse = st.sw.mt_sparse ? 1 : 0;
+                const bool acc2 = L.acc2 != 0;
+                const MtForm form{acc2 ? 2 : (st.h.nchunk <= 2 ? st.h.nchunk : 0), acc2 ? MT_THREADS_ACC2 : LV_THREADS, acc2, acc2, L.rot != 0};
+                st.timers.timed(false, [&]() {
+                    launch_level_mt(form, st.use_bagging, L.route != 0, dim3((unsigned)L.G * (unsigned)L.gx), s, st.bins.rec.p, st.gh.p, node.p, st.bag.inbag.p,
+                                    plan.p, part.p, count.p, st.bins.fmeta.p, st.bins.cmeta.p, err.p, st.fxs.p, l1);
+                });
+            }
+            auto ex = exchange(false, 1 << (level - 1), lp);
+            hipLaunchKernelGGL(k_level_split<false>, dim3((st.F + 1) / 2, 1 << (level - 1), st.K), dim3(256), 0, s, ex.first, lpool.p, plan.p, snodes.p,
+                               cntg, count.p, st.bins.fmeta.p, st.used.p, lcand.p, d_statrows.p, st.it.p, n_hnodes, st.fxs.p, st.h.tc, ex.second);
+            trace_level(level);
+        }
+        // last level: plan -> replay (leaf values never depend on the deepest counts) -> route + count + score in one pass
+        hipLaunchKernelGGL(k_level_plan, dim3(st.K), dim3(256), 0, s, plan.p, snodes.p, lcand.p, st.bins.fmeta.p, st.p.max_depth, st.h.tc, lc);
+        hipLaunchKernelGGL(k_level_replay, dim3(st.K), dim3(64), 0, s, plan.p, snodes.p, cntg, to, st.init.p, ndelta.p, leafnode.p, st.trees.any.p, err.p, st.it.p, st.h.tc);
+        // AddScore: the pass that routes, counts and adds in one
+        hipLaunchKernelGGL(k_level_final, dim3(score_gx, st.K), dim3(256), 0, s, st.bins.rec.p, node.p, st.bag.inbag.p, plan.p, to, ndelta.p, st.score.p, count.p, st.it.p, lc);
+        if (st.dp) { hipLaunchKernelGGL(k_copy_i32, dim3(st.K), dim3(256), 0, s, count.p, count_g.p, (long long)st.K * 256); all_reduce(count_g.p, (size_t)st.K * 256, AR_I32, s); }
+        hipLaunchKernelGGL(k_level_leafcount, dim3(st.K), dim3(LV_MAX_LEAVES), 0, s, plan.p, cntg, leafnode.p, to, st.it.p, st.h.tc);
+        trace_level(st.p.max_depth);
+        trace.sum("score", st.score.p, (size_t)st.K * st.N * 8); trace.sum("node", node.p, (size_t)st.K * lc.NS);
+        hipLaunchKernelGGL(k_next_iteration, dim3(1), dim3(1), 0, s, st.it.p);
+    }
+    // behind the last iteration: what report() needs on the host; report() runs after the stream has drained and raises what the device flagged
+    void enqueue_report() { err.download(&h_err, 1, s); d_statrows.download(&statrows, 1, s); }
+    void report(int32_t target_col) {
+        trace.write(target_col);
+        if (h_err & 2) throw std::runtime_error("level grower: a level pass was launched with more built nodes / route entries than its workgroup tables hold (sizing violated)");
+        if (h_err) throw std::runtime_error("level grower: a node outside the speculative expansion was selected (expansion bound violated)");
+    }
+};
 
-    // bagging state (GBDT::Bagging): stable training-row order, one LCG per 1024 positions
-    DevBuf<int32_t> d_sorted_rows, d_oob; DevBuf<unsigned int> d_blk, d_rand, d_bagcnt, d_bagcnt_g; DevBuf<uint8_t> d_inbag;
-    long long bag_off = 0, bag_local = 0, bag_nrb = 1;
-    if (use_bagging) {
-        const long long nblk = (N + 1023) / 1024;
-        d_blk.alloc(nblk); d_sorted_rows.alloc(n_train); d_oob.alloc(n_train); d_inbag.alloc(N); d_bagcnt.alloc(2);
-        hipLaunchKernelGGL(k_block_count, dim3((unsigned)nblk), dim3(256), 0, s, d_ycol, (long long)N, d_blk.p);
-        hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, d_blk.p, nblk);
-        hipLaunchKernelGGL(k_stable_compact, dim3((unsigned)nblk), dim3(256), 0, s, d_ycol, (long long)N, d_blk.p, d_sorted_rows.p);
-        if (dp) {
+// The index-list grower (rgbm_kernels.h): leaf-wise, num_leaves - 1 rounds of hist -> split_find -> tree_step -> partition -> finish_split.
+struct LeafwiseGrower {
+    FitState& st; hipStream_t s;
+    DevBuf<int32_t> idx0, idx1, sorted; DevBuf<rg::HistBin> pool; DevBuf<rg::TreeState> state; DevBuf<rg::Leaf> leaves; DevBuf<rg::Cand> cand; DevBuf<double> upd;
+    const long long root_tiles = (st.N + rg::TILE_ROWS - 1) / rg::TILE_ROWS;
+    const int hist_gx = (int)std::max<long long>(1, std::min<long long>(root_tiles, (1536 + (long long)st.K * st.h.nchunk - 1) / ((long long)st.K * st.h.nchunk)));
+    const int part_gx = (int)std::max<long long>(1, std::min<long long>((st.h.n_train + 1023) / 1024, (1024 + st.K - 1) / st.K));
+    const int upd_gx = (int)std::max<long long>(1, std::min<long long>((st.h.n_train + 255) / 256, (2048 + st.K - 1) / st.K));
+    const size_t upd_lds = (size_t)(3 * st.NL + (st.NL & 1)) * 4 + (size_t)st.NL * 8;
+
+    explicit LeafwiseGrower(FitState& st_) : st(st_), s(st_.s) {
+        idx0.alloc((size_t)st.K * st.h.n_train); idx1.alloc((size_t)st.K * st.h.n_train);
+        pool.alloc((size_t)st.K * st.NL * st.h.tc.totbins);
+        state.alloc(st.K); leaves.alloc((size_t)st.K * st.NL); cand.alloc((size_t)st.K * 2 * st.F);
+        upd.alloc((size_t)st.K * st.NL); sorted.alloc((size_t)st.K * st.NL * 3);
+        if (st.h.lds_hist > 64 * 1024)
+            rgh::once_per_device(st.tab.device, rgh::ONCE_HIST_LDS, [] { HIPCHK(hipFuncSetAttribute((const void*)rg::k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
+        if (st.h.lds_hist > 160 * 1024) throw std::invalid_argument("histogram working set exceeds LDS");
+    }
+    void enqueue_iteration(int it) {
+        using namespace rg;
+        const TreeOut to = st.trees.out();
+        const uint8_t* usedp = st.used.p + (size_t)it * st.K * st.F;
+        hipLaunchKernelGGL(k_init_iter, dim3(st.K), dim3(64), 0, s, state.p, leaves.p, pool.p, to, st.n_in_ptr, it, st.h.tc);
+        for (int step = 0; step < st.NL - 1; ++step) {
+            st.timers.timed(step == 0, [&]() {
+                hipLaunchKernelGGL(k_hist, dim3(hist_gx, st.K, st.h.nchunk), dim3(256), st.h.lds_hist, s, st.bins.rec.p, st.gh.p, idx0.p, idx1.p, st.base.p,
+                                   state.p, pool.p, st.bins.fmeta.p, st.bins.cmeta.p, st.fxs.p, st.h.tc);
+            });
+            hipLaunchKernelGGL(k_split_find, dim3((st.F + 3) / 4, st.K), dim3(256), 0, s, pool.p, state.p, leaves.p, st.bins.fmeta.p, usedp, cand.p, st.fxs.p, st.h.tc);
+            hipLaunchKernelGGL(k_tree_step, dim3(st.K), dim3(64), 0, s, state.p, leaves.p, cand.p, pool.p, st.bins.fmeta.p, to, it, st.h.tc);
+            hipLaunchKernelGGL(k_partition, dim3(part_gx, st.K), dim3(256), 0, s, reinterpret_cast<const uint8_t*>(st.bins.rec.p), idx0.p, idx1.p, st.base.p, state.p, st.h.tc);
+            hipLaunchKernelGGL(k_finish_split, dim3(st.K), dim3(64), 0, s, state.p, leaves.p, to, it, st.h.tc);
+        }
+        hipLaunchKernelGGL(k_finalize_tree, dim3(st.K), dim3(64), 0, s, state.p, leaves.p, to, st.init.p, upd.p, sorted.p, st.trees.any.p, it, st.h.tc);
+        hipLaunchKernelGGL(k_score_update, dim3(upd_gx, st.K), dim3(256), upd_lds, s, state.p, leaves.p, sorted.p, upd.p, idx0.p, idx1.p, st.base.p, st.score.p, st.n_in_ptr, st.h.tc);
+        if (st.use_bagging)
+            hipLaunchKernelGGL(k_score_update_oob, dim3(upd_gx, st.K), dim3(256), 0, s, reinterpret_cast<const uint8_t*>(st.bins.rec.p), st.bag.oob.p, st.bag.bagcnt.p,
+                               state.p, to, st.bins.fmeta.p, upd.p, st.score.p, it, st.h.tc);
+    }
+};
+
+// ---- what an iteration enqueues before its grower
+void FitState::enqueue_grad(uint8_t* node0, long long NS) {
+    using namespace rg;
+    if (p.objective == 0) hipLaunchKernelGGL(k_grad<0>, dim3(grad_gx()), dim3(256), 0, s, score.p, d_ycol, yv.p, cw.p, sw_rows.p, bag.inbag.p, gh.p, node0, NS, qpart.p, d_mult, h.tc);
+    else if (mc_rows())
+        hipLaunchKernelGGL(k_grad_mc_rows<256>, dim3((unsigned)((N + 255) / 256)), dim3(256), (size_t)K * 256 * 8, s, score.p, d_ycol, cw.p, sw_rows.p, bag.inbag.p, gh.p, node0, NS, qpart.p, d_mult, h.tc);
+    else if (mc_tile())
+        hipLaunchKernelGGL(k_grad_mc, dim3((unsigned)((N + 63) / 64)), dim3(256), (size_t)(K * 64 + 320) * 8, s, score.p, d_ycol, cw.p, sw_rows.p, bag.inbag.p, gh.p, node0, NS, qpart.p, d_mult, h.tc);
+    else if (p.objective == 1) hipLaunchKernelGGL(k_grad<1>, dim3(grad_gx()), dim3(256), 0, s, score.p, d_ycol, yv.p, cw.p, sw_rows.p, bag.inbag.p, gh.p, node0, NS, (unsigned long long*)nullptr, d_mult, h.tc);
+    else hipLaunchKernelGGL(k_grad<2>, dim3(grad_gx()), dim3(256), 0, s, score.p, d_ycol, yv.p, cw.p, sw_rows.p, bag.inbag.p, gh.p, node0, NS, qpart.p, d_mult, h.tc);
+    if (fx_fused) {
+        const long long total = fx_parts * K * 2;
+        const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(256, (total + 8191) / 8192));
+        hipLaunchKernelGGL(k_fx_reduce, dim3(gx), dim3(256), (size_t)K * 2 * 8, s, qpart.p, fx_parts, 2 * K, fxq.p);
+    } else {
+        const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(128, (N + 4095) / 4096));
+        hipLaunchKernelGGL(k_fx_measure, dim3(gx, K), dim3(256), 0, s, gh.p, (long long)N, (long long)h.tc.NG, h.tc.fx, fxq.p, d_mult);
+    }
+    if (dp) all_reduce(fxq.p, (size_t)K * 2, AR_I64, s);
+    if (!level_mode) hipLaunchKernelGGL(k_fx_scale, dim3(1), dim3(256), 0, s, fxq.p, K, h.tc.fx, fxs.p);      // (level grower: k_level_init does it)
+}
+void FitState::enqueue_bagging() {
+    using namespace rg;
+    hipLaunchKernelGGL(k_bagging, dim3((unsigned)((bag.nrb + 63) / 64)), dim3(64), 0, s, bag.rand.p, bag.local, p.bagging_fraction, bag.sorted_rows.p, bag.inbag.p, bag.bagcnt.p,
+                       bag.off, (long long)h.n_train);
+    hipLaunchKernelGGL(k_bag_lists, dim3((unsigned)((std::max<long long>(bag.local, 1) + 255) / 256)), dim3(256), 0, s, bag.sorted_rows.p, bag.local, bag.inbag.p, base.p, bag.oob.p, bag.bagcnt.p);
+    if (dp) {
+        hipLaunchKernelGGL(k_copy_i32, dim3(1), dim3(256), 0, s, reinterpret_cast<const int32_t*>(bag.bagcnt.p), reinterpret_cast<int32_t*>(bagcnt_g.p), 2ll);
+        all_reduce(bagcnt_g.p, 2, AR_U32, s);
+    }
+}
+
+rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t* feat_cols, int32_t F,
+                       const double* y_value, const double* class_weight, const double* sample_weight_host,
+                       const HostLabelStats* hls, const rgbm_params& p, rgbm_train_stats* stats) {
+    using namespace rg;
+    check_fit_args(tab, target_col, feat_cols, F, y_value, p);
+    if (F > 65535) throw std::invalid_argument("more than 65535 feature columns");
+    StreamGuard sg_; hipStream_t s = sg_.s;
+    rgh::Event ev_begin, ev_end;
+    HIPCHK(hipEventRecord(ev_begin.e, s));
+
+    FitState st(tab, target_col, F, p, stats != nullptr, s);
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_start = now();
+    // ---- 1. prologue: code frequencies of the training rows -> bins, tables, label statistics (fit_setup) -> bin records
+    st.bins.count_codes(tab, target_col, feat_cols, F, st.h, s);
+    if (st.dp) {   // the table is one rank's row shard: the counts are summed over the ranks
+        if (g_comm.kind == 0) throw std::invalid_argument("row-sharded training requested but this thread has no communicator (rgbm_comm_init)");
+        all_reduce(st.bins.cnt.p, st.bins.cnt.n, AR_U32, s);
+    }
+    st.bins.download_counts(st.h, s);
+    if (st.dp) stream_sync_watchdog(s); else HIPCHK(hipStreamSynchronize(s));
+    fit_setup(tab, y_value, class_weight, hls, p, F, st.h);
+    if (p.objective == 2) y_value = st.h.yv32.data();          // LightGBM keeps labels as float32: the dictionary rounded once
+    const int n_y = st.h.ncod[F];
+
+    const double t_bins = now();
+    st.bins.fill(st.h, st.N, s);
+    // rows with multiplicities (rgbm_table_set_row_multiplicity): the multiplicity rides in byte 15 of the row's LAST bin record, so that chunk
+    // must leave the byte free; the level grower only (one chunk, or two chunks in one pass), no bagging (LightGBM draws per ORIGINAL row), no per-row weights
+    if (tab.has_mult && (!st.level_mode || st.h.nchunk > 2 || (F % 16) == 0 || sample_weight_host || st.use_bagging))
+        throw std::invalid_argument("a table with row multiplicities trains with the level grower (1 <= max_depth <= 7), at most 32 features of which the last 16-feature "
+                                    "chunk holds at most 15, without bagging and without per-row weights");
+    st.bins.pack(tab, s);
+    if (st.dp && (!st.level_mode || sample_weight_host))
+        throw std::invalid_argument("row-sharded training supports the level grower (1 <= max_depth <= 7) without per-row weights");
+    // ---- 2. the state both growers work on, up to the trees; then the grower with its own buffers and set-up
+    st.counter.alloc(1); st.counter.zero(s);
+    if (!st.level_mode || st.use_bagging) {
+        st.base.alloc(st.h.n_train);
+        hipLaunchKernelGGL(k_iota_train, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, s, st.d_ycol, (long long)st.N, st.base.p, st.counter.p);
+    }
+    if (st.level_mode) st.h.tc.NG = (st.N + 255) & ~255ll;            // level grower: every wave tile of a class tree's (g, h) row is in bounds and 32-byte aligned
+    st.gh.alloc((size_t)st.K * st.h.tc.NG); st.gh.zero(s);
+    st.score.alloc((size_t)st.K * st.N); st.init.alloc(st.K);
+    st.init.upload(st.h.init.data(), st.K, s);
+    st.fxq.alloc((size_t)st.K * 2); st.fxq.zero(s);
+    st.fxs.alloc(st.K);
+    hipLaunchKernelGGL(k_init_score, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, s, st.score.p, (long long)st.N, st.K, st.init.p);
+    const size_t NT = (size_t)st.NE * st.K;
+    st.trees.alloc(NT, st.NL, st.NE, s);
+    std::unique_ptr<LevelGrower> lg; std::unique_ptr<LeafwiseGrower> lw;
+    if (st.level_mode) lg.reset(new LevelGrower(st)); else lw.reset(new LeafwiseGrower(st));
+    // ---- 3. the rest of the common state: weights, feature masks, bagging
+    if (class_weight) { st.cw.alloc(n_y); st.cw.upload(class_weight, n_y, s); }
+    if (y_value) { st.yv.alloc(n_y); st.yv.upload(y_value, n_y, s); }
+    if (sample_weight_host) { st.sw_rows.alloc(st.N); st.sw_rows.upload(sample_weight_host, st.N, s); }
+
+    const std::vector<uint8_t> used = make_used_masks(p, NT, F, st.h.trivial);
+    st.used.alloc(used.size()); st.used.upload(used.data(), used.size(), s);
+
+    if (st.use_bagging) {
+        st.bag.order_rows(st.d_ycol, st.N, st.h.n_train, s);
+        long long bag_off = 0, bag_local = st.h.n_train;
+        if (st.dp) {
             // GBDT::Bagging draws per training-row POSITION (ascending row order over the whole table): this rank's rows hold the positions
             // [bag_off, bag_off + bag_local), bag_off = training rows of the ranks before it (one all-reduce of a per-rank count vector)
-            unsigned int h_local = 0; d_counter.download(&h_local, 1, s); stream_sync_watchdog(s);
+            unsigned int h_local = 0; st.counter.download(&h_local, 1, s); stream_sync_watchdog(s);
             bag_local = (long long)h_local;
             std::vector<long long> rc((size_t)g_comm.nranks, 0); rc[(size_t)g_comm.rank] = bag_local;
             DevBuf<long long> d_rc(rc.size()); d_rc.upload(rc.data(), rc.size(), s);
@@ -1366,221 +1621,47 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
             d_rc.download(rc.data(), rc.size(), s); stream_sync_watchdog(s);
             long long tot = 0;
             for (int r = 0; r < g_comm.nranks; ++r) { if (r < g_comm.rank) bag_off += rc[(size_t)r]; tot += rc[(size_t)r]; }
-            if (tot != n_train) throw std::runtime_error("row-sharded bagging: the ranks' training-row counts do not add up");
-            d_bagcnt_g.alloc(2);
-        } else bag_local = n_train;
-        bag_nrb = std::max<long long>(1, (bag_off + bag_local + 1023) / 1024 - bag_off / 1024);
-        LgbRand sr2((uint32_t)p.seed); sr2.rnd16();
-        const int bagging_seed = sr2.rnd16();
-        std::vector<unsigned int> st(bag_nrb);
-        for (long long b = 0; b < bag_nrb; ++b) st[b] = (unsigned int)(bagging_seed + bag_off / 1024 + b);
-        d_rand.alloc(bag_nrb); d_rand.upload(st.data(), bag_nrb, s);
+            if (tot != st.h.n_train) throw std::runtime_error("row-sharded bagging: the ranks' training-row counts do not add up");
+            st.bagcnt_g.alloc(2);
+        }
+        st.bag.seed(p, bag_off, bag_local, s);
         HIPCHK(hipStreamSynchronize(s));
+        st.n_in_ptr = st.dp ? st.bagcnt_g.p : st.bag.bagcnt.p;
     }
-    // rows in the bag of the current iteration, over ALL ranks when row-sharded (the root count of every tree)
-    const unsigned int* n_in_ptr = use_bagging ? (dp ? d_bagcnt_g.p : d_bagcnt.p) : nullptr;
+    st.it.alloc(1); st.it.zero(s);
+    st.alloc_fx_parts();
 
-    if (!level_mode) {
-        if (lds_hist > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hist));
-        if (lds_hist > 160 * 1024) throw std::invalid_argument("histogram working set exceeds LDS");
-    }
-
-    const long long root_tiles = (N + TILE_ROWS - 1) / TILE_ROWS;
-    const int hist_gx = (int)std::max<long long>(1, std::min<long long>(root_tiles, (1536 + (long long)K * nchunk - 1) / ((long long)K * nchunk)));
-    const int part_gx = (int)std::max<long long>(1, std::min<long long>((n_train + 1023) / 1024, (1024 + K - 1) / K));
-    const int upd_gx = (int)std::max<long long>(1, std::min<long long>((n_train + 255) / 256, (2048 + K - 1) / K));
-    const int grad_gx = (int)std::min<long long>((N + 255) / 256, 4096);
-    const size_t upd_lds = (size_t)(3 * NL + (NL & 1)) * 4 + (size_t)NL * 8;
-
-    HistTimers timers{stats != nullptr, s};
-    const int score_gx = (int)std::max<long long>(1, std::min<long long>((N + 1023) / 1024, (2048 + K - 1) / K));
-    auto launch_root = [&]() {
-        timers.timed(true, [&]() {
-            if (joint_root)   // the root pass over the joint record: one pair of atomics per feature GROUP and row
-                hipLaunchKernelGGL(k_level_root, dim3((unsigned)lc.gx * (unsigned)K, 1, 1), dim3(LV_THREADS), lc.lds_bytes, s, d_rec_j.p, d_gh.p, d_node.p, d_plan.p, d_part_j.p,
-                                   d_vfmeta.p, d_vcmeta.p, d_fxs.p, lcj);
-            else
-                hipLaunchKernelGGL(k_level_root, dim3((unsigned)lc.gx * (unsigned)K, 1, nchunk), dim3(LV_THREADS), lc.lds_bytes, s, d_rec.p, d_gh.p, d_node.p, d_plan.p, d_part.p,
-                                   d_fmeta.p, d_cmeta.p, d_fxs.p, lc);
-        });
-    };
-    // the k_level_mt launches of one level; returns the LevelConst that describes the partials they wrote
-    auto launch_level = [&](int level) -> LevelConst {
-        LevelConst ll = lc;
-        ll.xcd_blocks = 0; ll.gx = passes.mt_gx[level]; ll.max_built = 1 << (level - 1);
-        for (const MtLaunch& L : passes.mt[level]) {
-            LevelConst l1 = ll;
-            l1.mt_T = L.T; l1.mt_G = L.G; l1.mt_ch = L.ch; l1.mt_slot0 = L.slot0; l1.mt_nslots = L.nslots; l1.mt_route = L.route; l1.mt_sparse = sw.mt_sparse ? 1 : 0;
-            const bool acc2 = L.acc2 != 0;
-            const MtForm form{acc2 ? 2 : (nchunk <= 2 ? nchunk : 0), acc2 ? MT_THREADS_ACC2 : LV_THREADS, acc2, acc2, L.rot != 0};
-            timers.timed(false, [&]() {
-                launch_level_mt(form, use_bagging, L.route != 0, dim3((unsigned)L.G * (unsigned)L.gx), s, d_rec.p, d_gh.p, d_node.p, use_bagging ? d_inbag.p : nullptr,
-                                d_plan.p, d_part.p, d_count.p, d_fmeta.p, d_cmeta.p, d_err.p, d_fxs.p, l1);
-            });
-        }
-        return ll;
-    };
-
-    DevBuf<int32_t> d_it(1); d_it.zero(s);   // device-side iteration counter (k_next_iteration)
-    LevelTrace trace(level_mode, K, s);
-    if (trace.on) trace.buf.alloc(((size_t)K * n_hnodes * tc.totbins * 16 + (size_t)K * 256 * (sizeof(SNode) + 4) + (size_t)K * sizeof(LvPlan) + 4096) * (size_t)(p.max_depth + 1) * (size_t)(trace.hi - trace.lo + 1) + (size_t)NE * 64 + 4096);
-    auto trace_level = [&](int level) {
-        trace.copy("count", level, d_count.p, (size_t)K * 256 * 4);
-        trace.copy("plan", level, d_plan.p, (size_t)K * sizeof(LvPlan));
-        trace.copy("snodes", level, d_snodes.p, (size_t)K * 256 * sizeof(SNode));
-        trace.copy("lpool", level, d_lpool.p, (size_t)K * n_hnodes * tc.totbins * 16);
-    };
-    // one boosting iteration of the level grower after the gradients: an iteration-invariant launch sequence
-    auto enqueue_level_growth = [&]() {
-            hipLaunchKernelGGL(k_level_init, dim3(K), dim3(64), 0, s, d_plan.p, d_snodes.p, d_count.p, n_in_ptr, (long long)n_train, d_fxq.p, tc.fx, d_fxs.p, lc);
-            int32_t* cntg = dp ? d_count_g.p : d_count.p;      // child row counts seen by split / leaf-count (global when row-sharded)
-            // partials of this rank -> compact buffer (-> integer all-reduce when row-sharded); the split kernel then sees ONE partial
-            auto exchange = [&](bool root, int nb, const LevelConst& lp) -> std::pair<const HistBin*, LevelConst> {
-                if (root && !use_reduce) return {d_part.p, lp};
-                if (root && joint_root) {   // partials -> one joint histogram per class tree (k_level_reduce in the joint bin space) -> marginals of the real features
-                    hipLaunchKernelGGL(k_level_reduce, dim3((vtotbins + 63) / 64, 1, K), dim3(256), 0, s, d_part_j.p, d_red_j.p, d_plan.p, d_count.p, 1, 1, lcj);
-                    hipLaunchKernelGGL(k_level_marginal, dim3((tc.totbins + 255) / 256, K), dim3(256), 0, s, d_red_j.p, d_part_red.p, d_plan.p, d_count.p, d_jf.p, d_binfeat.p, vtotbins, lc);
-                } else
-                hipLaunchKernelGGL(k_level_reduce, dim3((tc.totbins + 63) / 64, nb, K), dim3(256), 0, s, d_part.p, d_part_red.p, d_plan.p, d_count.p, root ? 1 : 0, nb, lp);
-                if (dp) {
-                    const size_t nh = (size_t)K * nb * tc.totbins * 2;          // int64 words of histograms, then K*256 child counts
-                    all_reduce(d_part_red.p, nh + (size_t)K * 256, AR_I64, s);
-                    hipLaunchKernelGGL(k_counts_unpack, dim3(K), dim3(256), 0, s, reinterpret_cast<const long long*>(d_part_red.p) + nh, d_count_g.p);
-                }
-                LevelConst r = lp; r.gx = 1; r.max_built = nb;
-                return {d_part_red.p, r};
-            };
-            launch_root();
-            {
-                auto ex = exchange(true, 1, lc);
-                hipLaunchKernelGGL(k_level_split<true>, dim3((F + 3) / 4, 1, K), dim3(256), 0, s, ex.first, d_lpool.p, d_plan.p, d_snodes.p, cntg, d_count.p, d_fmeta.p,
-                                   d_used.p, d_lcand.p, d_statrows.p, d_it.p, n_hnodes, d_fxs.p, tc, ex.second);
-                trace_level(0);
-            }
-            for (int level = 1; level < p.max_depth; ++level) {
-                hipLaunchKernelGGL(k_level_plan, dim3(K), dim3(256), 0, s, d_plan.p, d_snodes.p, d_lcand.p, d_fmeta.p, level, tc, lc);
-                const LevelConst lp = launch_level(level);
-                auto ex = exchange(false, 1 << (level - 1), lp);
-                hipLaunchKernelGGL(k_level_split<false>, dim3((F + 1) / 2, 1 << (level - 1), K), dim3(256), 0, s, ex.first, d_lpool.p, d_plan.p, d_snodes.p,
-                                   cntg, d_count.p, d_fmeta.p, d_used.p, d_lcand.p, d_statrows.p, d_it.p, n_hnodes, d_fxs.p, tc, ex.second);
-                trace_level(level);
-            }
-            // last level: plan -> replay (leaf values never depend on the deepest counts) -> route + count + score in one pass
-            hipLaunchKernelGGL(k_level_plan, dim3(K), dim3(256), 0, s, d_plan.p, d_snodes.p, d_lcand.p, d_fmeta.p, p.max_depth, tc, lc);
-            hipLaunchKernelGGL(k_level_replay, dim3(K), dim3(64), 0, s, d_plan.p, d_snodes.p, cntg, to, d_init.p, d_ndelta.p, d_leafnode.p, d_any.p, d_err.p, d_it.p, tc);
-            // AddScore: the pass that routes, counts and adds in one
-            hipLaunchKernelGGL(k_level_final, dim3(score_gx, K), dim3(256), 0, s, d_rec.p, d_node.p, use_bagging ? d_inbag.p : (const uint8_t*)nullptr,
-                               d_plan.p, to, d_ndelta.p, d_score.p, d_count.p, d_it.p, lc);
-            if (dp) { hipLaunchKernelGGL(k_copy_i32, dim3(K), dim3(256), 0, s, d_count.p, d_count_g.p, (long long)K * 256); all_reduce(d_count_g.p, (size_t)K * 256, AR_I32, s); }
-            hipLaunchKernelGGL(k_level_leafcount, dim3(K), dim3(LV_MAX_LEAVES), 0, s, d_plan.p, cntg, d_leafnode.p, to, d_it.p, tc);
-            trace_level(p.max_depth);
-            trace.sum("score", d_score.p, (size_t)K * N * 8); trace.sum("node", d_node.p, (size_t)K * lc.NS);
-    };
-
-    // numerics v2.2: every class tree of an iteration gets its own fixed-point grid from the coarse sums Q_g, Q_h of its (g, h) (rgbm_numerics.h).  The
-    // gradient kernels leave the sums per workgroup / wave (d_qpart [parts][K][2]: plain stores, no atomics), k_fx_reduce adds them up into d_fxq [K][2];
-    // k_grad<1> (softmax with K > 112) and RGBM_FX_MEASURE=separate take them from a pass of their own over the (g, h) array (k_fx_measure).  Row-sharded:
-    // ONE more integer all-reduce per iteration (2 K words).  k_fx_scale turns the sums into the FxScale table every accumulating / searching kernel reads.
-    const bool mc_tile = obj == 1 && K >= 16 && K <= 112, mc_rows = obj == 1 && K < 16;
-    const bool fx_fused = !sw.fx_separate && (obj != 1 || mc_tile || mc_rows);
-    const long long fx_parts = !fx_fused ? 0 : (mc_tile ? (N + 63) / 64 : (mc_rows ? ((N + 255) / 256) * 4 : (long long)grad_gx));
-    DevBuf<unsigned long long> d_qpart; if (fx_fused) d_qpart.alloc((size_t)fx_parts * K * 2);
-    auto enqueue_grad = [&]() {
-        const double* cw = class_weight ? d_cw.p : nullptr; const double* yv = y_value ? d_yv.p : nullptr; const double* sw_ = sample_weight_host ? d_sw.p : nullptr;
-        const uint8_t* inbag = use_bagging ? d_inbag.p : nullptr;
-        uint8_t* node0 = level_mode ? d_node.p : nullptr;
-        unsigned long long* qp = fx_fused ? d_qpart.p : nullptr;
-        if (obj == 0) hipLaunchKernelGGL(k_grad<0>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
-        else if (mc_rows)
-            hipLaunchKernelGGL(k_grad_mc_rows<256>, dim3((unsigned)((N + 255) / 256)), dim3(256), (size_t)K * 256 * 8, s, d_score.p, d_ycol, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
-        else if (mc_tile)
-            hipLaunchKernelGGL(k_grad_mc, dim3((unsigned)((N + 63) / 64)), dim3(256), (size_t)(K * 64 + 320) * 8, s, d_score.p, d_ycol, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
-        else if (obj == 1) hipLaunchKernelGGL(k_grad<1>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, (unsigned long long*)nullptr, d_mult, tc);
-        else hipLaunchKernelGGL(k_grad<2>, dim3(grad_gx), dim3(256), 0, s, d_score.p, d_ycol, yv, cw, sw_, inbag, d_gh.p, node0, lc.NS, qp, d_mult, tc);
-        if (fx_fused) {
-            const long long total = fx_parts * K * 2;
-            const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(256, (total + 8191) / 8192));
-            hipLaunchKernelGGL(k_fx_reduce, dim3(gx), dim3(256), (size_t)K * 2 * 8, s, d_qpart.p, fx_parts, 2 * K, d_fxq.p);
-        } else {
-            const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(128, (N + 4095) / 4096));
-            hipLaunchKernelGGL(k_fx_measure, dim3(gx, K), dim3(256), 0, s, d_gh.p, (long long)N, (long long)tc.NG, tc.fx, d_fxq.p, d_mult);
-        }
-        if (dp) all_reduce(d_fxq.p, (size_t)K * 2, AR_I64, s);
-        if (!level_mode) hipLaunchKernelGGL(k_fx_scale, dim3(1), dim3(256), 0, s, d_fxq.p, K, tc.fx, d_fxs.p);      // (level grower: k_level_init does it)
-    };
-
-    if (timing) HIPCHK(hipStreamSynchronize(s));
+    if (st.sw.timing) HIPCHK(hipStreamSynchronize(s));
     const double t_setup = now();
-    // ---- 5. boosting iterations: everything below is enqueue-only.
+    // ---- 4. boosting iterations: everything below is enqueue-only.
     // hipGraph replay of an iteration was built and measured twice (rounds 1 and 2, MI355X / ROCm 7.2) and removed: a 10 000-row fit
     // takes the same time either way (the chain of ~30 small dependent kernels per iteration is bound by GPU-side latency, not by
     // the host launches), 24 concurrent host threads gain nothing (8.8 vs 9.2 ms per 60-iteration fit), and captures made while
     // other threads train fail or replay wrongly (20 bad models in 150) even with every graph call behind one mutex.
-    auto enqueue_bagging = [&]() {
-        hipLaunchKernelGGL(k_bagging, dim3((unsigned)((bag_nrb + 63) / 64)), dim3(64), 0, s, d_rand.p, bag_local, p.bagging_fraction, d_sorted_rows.p, d_inbag.p, d_bagcnt.p,
-                           bag_off, (long long)n_train);
-        hipLaunchKernelGGL(k_bag_lists, dim3((unsigned)((std::max<long long>(bag_local, 1) + 255) / 256)), dim3(256), 0, s, d_sorted_rows.p, bag_local, d_inbag.p, d_base.p, d_oob.p, d_bagcnt.p);
-        if (dp) {
-            hipLaunchKernelGGL(k_copy_i32, dim3(1), dim3(256), 0, s, reinterpret_cast<const int32_t*>(d_bagcnt.p), reinterpret_cast<int32_t*>(d_bagcnt_g.p), 2ll);
-            all_reduce(d_bagcnt_g.p, 2, AR_U32, s);
-        }
-    };
-    for (int it = 0; it < NE; ++it) {
-        if (use_bagging && it % p.bagging_freq == 0) enqueue_bagging();
-        trace.cur_it = it;
-        enqueue_grad();
-        trace.sum("gh", d_gh.p, (size_t)K * tc.NG * 8);
-        const uint8_t* usedp = d_used.p + (size_t)it * K * F;
-        if (level_mode) {
-            enqueue_level_growth();
-            hipLaunchKernelGGL(k_next_iteration, dim3(1), dim3(1), 0, s, d_it.p);
-            continue;
-        }
-        hipLaunchKernelGGL(k_init_iter, dim3(K), dim3(64), 0, s, d_state.p, d_leaves.p, d_pool.p, to, n_in_ptr, it, tc);
-        for (int step = 0; step < NL - 1; ++step) {
-            timers.timed(step == 0, [&]() {
-                hipLaunchKernelGGL(k_hist, dim3(hist_gx, K, nchunk), dim3(256), lds_hist, s, d_rec.p, d_gh.p, d_idx0.p, d_idx1.p, d_base.p,
-                                   d_state.p, d_pool.p, d_fmeta.p, d_cmeta.p, d_fxs.p, tc);
-            });
-            hipLaunchKernelGGL(k_split_find, dim3((F + 3) / 4, K), dim3(256), 0, s, d_pool.p, d_state.p, d_leaves.p, d_fmeta.p, usedp, d_cand.p, d_fxs.p, tc);
-            hipLaunchKernelGGL(k_tree_step, dim3(K), dim3(64), 0, s, d_state.p, d_leaves.p, d_cand.p, d_pool.p, d_fmeta.p, to, it, tc);
-            hipLaunchKernelGGL(k_partition, dim3(part_gx, K), dim3(256), 0, s, reinterpret_cast<const uint8_t*>(d_rec.p), d_idx0.p, d_idx1.p, d_base.p, d_state.p, tc);
-            hipLaunchKernelGGL(k_finish_split, dim3(K), dim3(64), 0, s, d_state.p, d_leaves.p, to, it, tc);
-        }
-        hipLaunchKernelGGL(k_finalize_tree, dim3(K), dim3(64), 0, s, d_state.p, d_leaves.p, to, d_init.p, d_upd.p, d_sorted.p, d_any.p, it, tc);
-        hipLaunchKernelGGL(k_score_update, dim3(upd_gx, K), dim3(256), upd_lds, s, d_state.p, d_leaves.p, d_sorted.p, d_upd.p, d_idx0.p, d_idx1.p, d_base.p, d_score.p, n_in_ptr, tc);
-        if (use_bagging)
-            hipLaunchKernelGGL(k_score_update_oob, dim3(upd_gx, K), dim3(256), 0, s, reinterpret_cast<const uint8_t*>(d_rec.p), d_oob.p, d_bagcnt.p,
-                               d_state.p, to, d_fmeta.p, d_upd.p, d_score.p, it, tc);
+    for (int it = 0; it < st.NE; ++it) {
+        if (st.use_bagging && it % p.bagging_freq == 0) st.enqueue_bagging();
+        st.enqueue_grad(lg ? lg->node.p : nullptr, lg ? lg->lc.NS : 0);
+        if (lg) lg->enqueue_iteration(it); else lw->enqueue_iteration(it);
     }
     HIPCHK(hipGetLastError());
 
     const double t_enq = now();
-    // ---- 6. trees back to the host
-    std::vector<int32_t> hL(NT), hfeat(NT * (NL - 1)), htheta(NT * (NL - 1)), hdleft(NT * (NL - 1)), hleft(NT * (NL - 1)), hright(NT * (NL - 1)), hcnt(NT * NL), hany(NE);
-    std::vector<double> hgain(NT * (NL - 1)), hval(NT * NL);
-    t_L.download(hL.data(), hL.size(), s); t_feat.download(hfeat.data(), hfeat.size(), s); t_theta.download(htheta.data(), htheta.size(), s);
-    t_dleft.download(hdleft.data(), hdleft.size(), s); t_left.download(hleft.data(), hleft.size(), s); t_right.download(hright.data(), hright.size(), s);
-    t_cnt.download(hcnt.data(), hcnt.size(), s); t_gain.download(hgain.data(), hgain.size(), s); t_val.download(hval.data(), hval.size(), s);
-    d_any.download(hany.data(), NE, s);
-    int32_t h_err = 0; unsigned long long h_statrows = 0;
-    if (level_mode) { d_err.download(&h_err, 1, s); d_statrows.download(&h_statrows, 1, s); }
-    HIPCHK(hipEventRecord(ev_end, s));
-    if (dp) stream_sync_watchdog(s); else HIPCHK(hipStreamSynchronize(s));
-    if (timing) fprintf(stderr, "[rgbm] target %d K=%d: count+bins %.1f ms, alloc+pack %.1f ms, enqueue %.1f ms, drain+download %.1f ms\n", target_col, K, t_bins - t_start, t_setup - t_bins, t_enq - t_setup, now() - t_enq);
-    trace.write(target_col);
-    if (h_err & 2) throw std::runtime_error("level grower: a level pass was launched with more built nodes / route entries than its workgroup tables hold (sizing violated)");
-    if (h_err) throw std::runtime_error("level grower: a node outside the speculative expansion was selected (expansion bound violated)");
+    // ---- 5. trees back to the host
+    std::vector<char> host_trees(st.trees.host_bytes());
+    const HostTrees ht = st.trees.download(host_trees.data(), s);
+    if (lg) lg->enqueue_report();
+    HIPCHK(hipEventRecord(ev_end.e, s));
+    if (st.dp) stream_sync_watchdog(s); else HIPCHK(hipStreamSynchronize(s));
+    if (st.sw.timing) fprintf(stderr, "[rgbm] target %d K=%d: count+bins %.1f ms, alloc+pack %.1f ms, enqueue %.1f ms, drain+download %.1f ms\n", target_col, st.K, t_bins - t_start, t_setup - t_bins, t_enq - t_setup, now() - t_enq);
+    if (lg) lg->report(target_col);
 
-    HostTrees ht{hL.data(), hfeat.data(), htheta.data(), hdleft.data(), hleft.data(), hright.data(), hcnt.data(), hgain.data(), hval.data(), hany.data()};
-    model_from_trees(model, ht, NE, K, NL);
+    model_from_trees(st.h.model.get(), ht, st.NE, st.K, st.NL);
     if (stats) {
-        float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
-        const int nranks = dp ? g_comm.nranks : 1;
-        fill_train_stats(stats, ms, timers, ht, p, level_mode, use_bagging, nranks, N, n_train, F, joint_root ? lcj.F : F, K, h_statrows);
+        float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev_begin.e, ev_end.e));
+        const int nranks = st.dp ? g_comm.nranks : 1;
+        fill_train_stats(stats, ms, st.timers, ht, p, st.level_mode, st.use_bagging, nranks, st.N, st.h.n_train, F, lg ? lg->root_feats : F, st.K, lg ? lg->statrows : 0);
     }
-    (void)hipEventDestroy(ev_begin); (void)hipEventDestroy(ev_end);
-    return guard.release();
+    return st.h.model.release();
 }
 
 
@@ -1595,17 +1676,15 @@ void predict_device(rgbm_model* m, int device, hipStream_t s, const int32_t* d_c
 // the models are the same bytes.
 // ---------------------------------------------------------------------------------------------
 struct SmallFitDev {   // device state of one fit of a batch
-    FitHost h; int F = 0, K = 1, NL = 0, NE = 0; size_t NT = 0; bool bag = false; long long bag_nrb = 1;
-    DevBuf<int32_t> cols, ncod; DevBuf<long long> cnt_off, lut_off; DevBuf<unsigned int> cnt, counter;
-    DevBuf<rg::FeatMeta> fmeta; DevBuf<rg::ChunkMeta> cmeta; DevBuf<uint8_t> lut, miss, used, inbag;
-    DevBuf<uint4> rec; DevBuf<float2> gh; DevBuf<double> score, init, upd, cw, yv;
-    DevBuf<int32_t> idx0, idx1, base, tree_L, any, sorted_rows, oob; DevBuf<rg::HistBin> pool;
-    DevBuf<unsigned int> blk, rand, bagcnt;
+    FitHost h; int F = 0, K = 1, NL = 0, NE = 0; bool bag = false;
+    BinRecords bins; BagState bagst; TreeBlock trees;
+    DevBuf<unsigned int> counter; DevBuf<uint8_t> used;
+    DevBuf<float2> gh; DevBuf<double> score, init, upd, cw, yv;
+    DevBuf<int32_t> idx0, idx1, base, tree_L; DevBuf<rg::HistBin> pool;
     DevBuf<rg::ScanLane> scan_map; std::vector<rg::ScanLane> h_scan; int scan_waves = 0;
     DevBuf<uint4> vrec; DevBuf<double> vscore, vtop; DevBuf<int32_t> vlabel; DevBuf<uint8_t> vlut, vmiss; std::vector<uint8_t> h_vlut, h_vmiss; long long n_valid = 0;
-    DevBuf<int32_t> t_L, t_feat, t_theta, t_dleft, t_left, t_right, t_cnt; DevBuf<double> t_gain, t_val;
-    std::vector<int32_t> hL, hfeat, htheta, hdleft, hleft, hright, hcnt, hany; std::vector<double> hgain, hval;
-    std::vector<uint8_t> h_used; std::vector<unsigned int> h_rand;      // host sources of asynchronous uploads: alive until the batch has drained
+    std::vector<char> host_trees;          // the harvest, when the page-locked block is not to be had
+    std::vector<uint8_t> h_used;           // host source of an asynchronous upload: alive until the batch has drained
 };
 
 // validation rows of a fit that trained outside the fused kernels: the predictor on its model (same labels / values)
@@ -1654,17 +1733,14 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
     if (const char* e = getenv("RGBM_SMALL_ROWS")) small_rows = atoll(e);
     const int device = specs[0].table->device;
     std::vector<int> batch;                                           // fits that go through the fused kernels
-    auto record_error = [&](int i, const std::exception& e, int code) { status[i] = code; rgh::last_error() = e.what(); };
+    auto record_error = [&](int i, const std::exception& e) { status[i] = rgh::status_of(e); rgh::last_error() = e.what(); };
     auto run_single = [&](int i) {
         const rgbm_fit_spec& sp = specs[i];
         try {
             out[i] = train_core(*sp.table, sp.target_col, sp.feat_cols, sp.n_features, sp.y_value, sp.class_weight, nullptr, nullptr, *sp.params, nullptr); status[i] = RGBM_OK;
             score_valid_with_model(sp, out[i]);
         }
-        catch (const std::invalid_argument& e) { record_error(i, e, RGBM_ERR_PARAM); }
-        catch (const std::out_of_range& e) { record_error(i, e, RGBM_ERR_LABEL); }
-        catch (const std::domain_error& e) { record_error(i, e, RGBM_ERR_NO_DEVICE); }
-        catch (const std::exception& e) { record_error(i, e, RGBM_ERR_HIP); }
+        catch (const std::exception& e) { record_error(i, e); }
     };
     for (int i = 0; i < n_fits; ++i) {
         out[i] = nullptr; status[i] = RGBM_OK;
@@ -1685,32 +1761,12 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
     std::vector<int> live;
     for (int i : batch) {
         const rgbm_fit_spec& sp = specs[i]; const rgbm_table& tab = *sp.table; const rgbm_params& p = *sp.params; const int F = sp.n_features;
-        try {
-            check_params(p);
-            if (F <= 0) throw std::invalid_argument("no feature columns");
-            if (sp.target_col < 0 || sp.target_col >= tab.c) throw std::invalid_argument("target column out of range");
-            for (int f = 0; f < F; ++f) if (sp.feat_cols[f] < 0 || sp.feat_cols[f] >= tab.c) throw std::invalid_argument("feature column out of range");
-            const int obj = p.objective, n_y = tab.n_codes[sp.target_col];
-            if (obj == 1 && n_y > p.num_class) throw std::out_of_range("target has more label codes than num_class");
-            if (obj == 0 && n_y > 2) throw std::out_of_range("binary objective with more than 2 label codes");
-            if (obj == 2 && !sp.y_value) throw std::out_of_range("regression needs the y_value dictionary");
-        }
-        catch (const std::invalid_argument& e) { record_error(i, e, RGBM_ERR_PARAM); continue; }
-        catch (const std::out_of_range& e) { record_error(i, e, RGBM_ERR_LABEL); continue; }
-        catch (const std::exception& e) { record_error(i, e, RGBM_ERR_HIP); continue; }
+        try { check_fit_args(tab, sp.target_col, sp.feat_cols, F, sp.y_value, p); }
+        catch (const std::exception& e) { record_error(i, e); continue; }
         dev[i].reset(new SmallFitDev());
-        SmallFitDev& d = *dev[i]; FitHost& h = d.h;
-        d.F = F; d.K = p.objective == 1 ? p.num_class : 1; d.NL = p.num_leaves; d.NE = p.n_estimators; d.NT = (size_t)d.NE * d.K;
-        h.cols.assign(sp.feat_cols, sp.feat_cols + F); h.cols.push_back(sp.target_col);
-        h.ncod.resize(F + 1); h.cnt_off.assign(F + 2, 0);
-        for (int f = 0; f <= F; ++f) { h.ncod[f] = tab.n_codes[h.cols[f]]; h.cnt_off[f + 1] = h.cnt_off[f] + std::max(h.ncod[f], 1); }
-        d.cols.alloc(F + 1); d.ncod.alloc(F + 1); d.cnt_off.alloc(F + 2); d.cnt.alloc(h.cnt_off[F + 1]);
-        d.cols.upload(h.cols.data(), F + 1, s); d.ncod.upload(h.ncod.data(), F + 1, s); d.cnt_off.upload(h.cnt_off.data(), F + 2, s); d.cnt.zero(s);
-        const int32_t* d_ycol = tab.codes.p + (long long)sp.target_col * tab.n;
-        const int gx = (int)std::min<int64_t>((tab.n + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_count_codes, dim3(gx, F + 1), dim3(256), 0, s, tab.codes.p, (long long)tab.n, d_ycol, d.cols.p, d.ncod.p, d.cnt_off.p, d.cnt.p);
-        h.cnt.resize(h.cnt_off[F + 1]);
-        d.cnt.download(h.cnt.data(), h.cnt.size(), s);
+        SmallFitDev& d = *dev[i];
+        d.F = F; d.K = p.objective == 1 ? p.num_class : 1; d.NL = p.num_leaves; d.NE = p.n_estimators;
+        d.bins.count_codes(tab, sp.target_col, sp.feat_cols, F, d.h, s); d.bins.download_counts(d.h, s);
         live.push_back(i);
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -1722,7 +1778,6 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
         SmallFitDev& d = *dev[i]; FitHost& h = d.h; const int F = d.F, K = d.K, NL = d.NL, NE = d.NE; const long long N = tab.n;
         // one failing fit does not fail the batch: whatever this fit's set-up throws (arguments, labels, HIP) is ITS status; uploads queued from
         // its host vectors are drained before they are destroyed
-        auto drop_fit = [&](const std::exception& e, int code) { (void)hipStreamSynchronize(s); record_error(i, e, code); dev[i].reset(); };
         try {
         fit_setup(tab, sp.y_value, sp.class_weight, nullptr, p, F, h);
         // lane map of the packed threshold scan (rgbm_small.h): a lane owns 4 bins of one feature, a feature does not straddle waves;
@@ -1744,11 +1799,8 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
         const size_t lds = sm_lds_bytes(h.lds_hist, NL, F, d.scan_waves > 0 ? h.tc.totbins : 0);
         if (lds > 160 * 1024 - 2048) { dev[i].reset(); run_single(i); continue; }          // (histogram working set of one chunk + leaves exceed the LDS)
         const int nchunk = h.nchunk; const long long n_train = h.n_train;
-        d.fmeta.alloc(F); d.cmeta.alloc(nchunk); d.lut_off.alloc(F + 1); d.lut.alloc(std::max<size_t>(h.lut.size(), 1)); d.miss.alloc(F);
-        d.fmeta.upload(h.fmeta.data(), F, s); d.cmeta.upload(h.cmeta.data(), nchunk, s); d.lut_off.upload(h.lut_off.data(), F + 1, s);
-        d.lut.upload(h.lut.data(), h.lut.size(), s); d.miss.upload(h.miss.data(), F, s);
-        d.rec.alloc((size_t)nchunk * N);
-        hipLaunchKernelGGL(k_pack_bins, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, tab.codes.p, N, 0ll, N, d.cols.p, d.ncod.p, d.lut_off.p, d.lut.p, d.miss.p, F, nchunk, d.rec.p);
+        d.bins.fill(h, N, s);
+        d.bins.pack(tab, s);
         const int32_t* d_ycol = tab.codes.p + (long long)sp.target_col * N;
         d.bag = p.bagging_freq > 0 && p.bagging_fraction < 1.0;
         d.counter.alloc(1); d.counter.zero(s);
@@ -1758,10 +1810,9 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
         d.score.alloc((size_t)K * N); d.init.alloc(K); d.init.upload(h.init.data(), K, s);
         hipLaunchKernelGGL(k_init_score, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d.score.p, N, K, d.init.p);
         d.idx0.alloc((size_t)K * n_train); d.idx1.alloc((size_t)K * n_train);
-        d.pool.alloc((size_t)K * NL * h.tc.totbins); d.upd.alloc((size_t)K * NL); d.tree_L.alloc(K); d.any.alloc(NE); d.any.zero(s);
-        const size_t NT = d.NT;
-        d.t_L.alloc(NT); d.t_feat.alloc(NT * (NL - 1)); d.t_theta.alloc(NT * (NL - 1)); d.t_dleft.alloc(NT * (NL - 1)); d.t_left.alloc(NT * (NL - 1)); d.t_right.alloc(NT * (NL - 1));
-        d.t_cnt.alloc(NT * NL); d.t_gain.alloc(NT * (NL - 1)); d.t_val.alloc(NT * NL); d.t_cnt.zero(s); d.t_val.zero(s);
+        d.pool.alloc((size_t)K * NL * h.tc.totbins); d.upd.alloc((size_t)K * NL); d.tree_L.alloc(K);
+        const size_t NT = (size_t)NE * K;
+        d.trees.alloc(NT, NL, NE, s);
         const int n_y = h.ncod[F];
         if (sp.class_weight) { d.cw.alloc(n_y); d.cw.upload(sp.class_weight, n_y, s); }
         if (p.objective == 2) { d.yv.alloc(n_y); d.yv.upload(h.yv32.data(), n_y, s); }
@@ -1779,34 +1830,22 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
             }
             d.vlut.alloc(d.h_vlut.size()); d.vlut.upload(d.h_vlut.data(), d.h_vlut.size(), s); d.vmiss.alloc(F); d.vmiss.upload(d.h_vmiss.data(), F, s);
             d.vrec.alloc((size_t)nchunk * vt.n);
-            hipLaunchKernelGGL(k_pack_bins, dim3((unsigned)((vt.n + 255) / 256)), dim3(256), 0, s, vt.codes.p, (long long)vt.n, 0ll, (long long)vt.n, d.cols.p, d.ncod.p, d.lut_off.p, d.vlut.p, d.vmiss.p, F, nchunk, d.vrec.p);
+            d.bins.pack(vt, d.vlut.p, d.vmiss.p, d.vrec.p, nullptr, s);
             d.vscore.alloc((size_t)K * vt.n); d.vlabel.alloc(vt.n); d.vtop.alloc(vt.n);
             hipLaunchKernelGGL(k_init_score, dim3((unsigned)((vt.n + 255) / 256)), dim3(256), 0, s, d.vscore.p, (long long)vt.n, K, d.init.p);
             nvalid_max = std::max<long long>(nvalid_max, vt.n);
         }
         d.h_used = make_used_masks(p, NT, F, h.trivial);
         d.used.alloc(d.h_used.size()); d.used.upload(d.h_used.data(), d.h_used.size(), s);
-        if (d.bag) {   // GBDT::Bagging state: stable training-row order, one LCG per 1024 positions
-            const long long nblk = (N + 1023) / 1024;
-            d.blk.alloc(nblk); d.sorted_rows.alloc(n_train); d.oob.alloc(n_train); d.inbag.alloc(N); d.bagcnt.alloc(2);
-            hipLaunchKernelGGL(k_block_count, dim3((unsigned)nblk), dim3(256), 0, s, d_ycol, N, d.blk.p);
-            hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, d.blk.p, nblk);
-            hipLaunchKernelGGL(k_stable_compact, dim3((unsigned)nblk), dim3(256), 0, s, d_ycol, N, d.blk.p, d.sorted_rows.p);
-            d.bag_nrb = std::max<long long>(1, (n_train + 1023) / 1024);
-            LgbRand sr2((uint32_t)p.seed); sr2.rnd16();
-            const int bagging_seed = sr2.rnd16();
-            d.h_rand.resize(d.bag_nrb);
-            for (long long b = 0; b < d.bag_nrb; ++b) d.h_rand[b] = (unsigned int)(bagging_seed + b);
-            d.rand.alloc(d.bag_nrb); d.rand.upload(d.h_rand.data(), d.bag_nrb, s);
-            any_bag = true; nrb_max = std::max(nrb_max, d.bag_nrb);
+        if (d.bag) {
+            d.bagst.order_rows(d_ycol, N, n_train, s);
+            d.bagst.seed(p, 0, n_train, s);
+            any_bag = true; nrb_max = std::max(nrb_max, d.bagst.nrb);
         }
         NE_max = std::max(NE_max, NE); lds_max = std::max(lds_max, lds); N_max = std::max(N_max, N); ntrain_max = std::max(ntrain_max, n_train);
         ok.push_back(i);
         }
-        catch (const std::invalid_argument& e) { drop_fit(e, RGBM_ERR_PARAM); continue; }
-        catch (const std::out_of_range& e) { drop_fit(e, RGBM_ERR_LABEL); continue; }
-        catch (const std::domain_error& e) { drop_fit(e, RGBM_ERR_NO_DEVICE); continue; }
-        catch (const std::exception& e) { drop_fit(e, RGBM_ERR_HIP); continue; }
+        catch (const std::exception& e) { (void)hipStreamSynchronize(s); record_error(i, e); dev[i].reset(); continue; }
     }
     if (ok.empty()) return;
     if (timing) HIPCHK(hipStreamSynchronize(s));
@@ -1816,13 +1855,13 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
     for (size_t j = 0; j < ok.size(); ++j) {
         const int i = ok[j]; const rgbm_fit_spec& sp = specs[i]; const rgbm_params& p = *sp.params; SmallFitDev& d = *dev[i]; FitHost& h = d.h;
         SmallFit& f = fits[j]; memset(&f, 0, sizeof(f));
-        f.c = h.tc; f.rec = d.rec.p; f.ycol = sp.table->codes.p + (long long)sp.target_col * sp.table->n; f.gh = d.gh.p; f.score = d.score.p;
-        f.idx0 = d.idx0.p; f.idx1 = d.idx1.p; f.base_idx = d.base.p; f.pool = d.pool.p; f.fmeta = d.fmeta.p; f.cmeta = d.cmeta.p; f.used = d.used.p;
-        f.out = TreeOut{d.t_L.p, d.t_feat.p, d.t_theta.p, d.t_dleft.p, d.t_left.p, d.t_right.p, d.t_gain.p, d.t_val.p, d.t_cnt.p};
-        f.init = d.init.p; f.upd = d.upd.p; f.tree_L = d.tree_L.p; f.any_split = d.any.p;
+        f.c = h.tc; f.rec = d.bins.rec.p; f.ycol = sp.table->codes.p + (long long)sp.target_col * sp.table->n; f.gh = d.gh.p; f.score = d.score.p;
+        f.idx0 = d.idx0.p; f.idx1 = d.idx1.p; f.base_idx = d.base.p; f.pool = d.pool.p; f.fmeta = d.bins.fmeta.p; f.cmeta = d.bins.cmeta.p; f.used = d.used.p;
+        f.out = d.trees.out();
+        f.init = d.init.p; f.upd = d.upd.p; f.tree_L = d.tree_L.p; f.any_split = d.trees.any.p;
         f.class_w = sp.class_weight ? d.cw.p : nullptr; f.y_value = p.objective == 2 ? d.yv.p : nullptr;
-        f.rand_state = d.rand.p; f.sorted_rows = d.sorted_rows.p; f.inbag = d.inbag.p; f.bagcnt = d.bagcnt.p; f.oob = d.oob.p;
-        f.bag_fraction = p.bagging_fraction; f.bag_nrb = d.bag_nrb; f.bag_freq = d.bag ? p.bagging_freq : 0;
+        f.rand_state = d.bagst.rand.p; f.sorted_rows = d.bagst.sorted_rows.p; f.inbag = d.bagst.inbag.p; f.bagcnt = d.bagst.bagcnt.p; f.oob = d.bagst.oob.p;
+        f.bag_fraction = p.bagging_fraction; f.bag_nrb = d.bagst.nrb; f.bag_freq = d.bag ? p.bagging_freq : 0;
         f.tree0 = (int32_t)tree2fit.size(); f.n_estimators = d.NE; f.lds_hist = (unsigned long long)h.lds_hist;
         f.scan_map = d.scan_map.p; f.scan_waves = d.scan_waves;
         f.vrec = d.vrec.p; f.vscore = d.vscore.p; f.n_valid = d.n_valid;
@@ -1832,11 +1871,7 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
     for (auto& f : fits) f.prof = d_prof.p;
     DevBuf<SmallFit> d_fits(fits.size()); DevBuf<int32_t> d_t2f(tree2fit.size());
     d_fits.upload(fits.data(), fits.size(), s); d_t2f.upload(tree2fit.data(), tree2fit.size(), s);
-    {
-        static std::mutex attr_mu; static std::vector<char> attr_done(64, 0);
-        std::lock_guard<std::mutex> lk(attr_mu);
-        if (!attr_done[device & 63]) { HIPCHK(hipFuncSetAttribute((const void*)k_small_tree, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048)); attr_done[device & 63] = 1; }
-    }
+    rgh::once_per_device(device, rgh::ONCE_SMALL_TREE_LDS, [] { HIPCHK(hipFuncSetAttribute((const void*)k_small_tree, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048)); });
     if (lds_max > 160 * 1024 - 2048) throw std::invalid_argument("small-table batch: histogram working set exceeds LDS");
     // ---- D. the boosting iterations of the whole batch: enqueue only
     const unsigned nf = (unsigned)fits.size(), KT = (unsigned)tree2fit.size();
@@ -1872,38 +1907,14 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
     std::vector<HostTrees> hts(n_fits);
     HarvestArena& HA = harvest_arena();
     std::unique_lock<std::mutex> ha_lock(HA.mu, std::try_to_lock);
-    {
-        size_t need = 0;
-        auto take = [&](size_t bytes) { const size_t o = need; need += (bytes + 63) & ~(size_t)63; return o; };
-        struct Off { size_t L, feat, theta, dleft, left, right, cnt, gain, val, any; };
-        std::vector<Off> offs(n_fits);
-        for (int i : want) {
-            SmallFitDev& d = *dev[i]; const size_t NT = d.NT, nn = NT * (size_t)(d.NL - 1), nl = NT * (size_t)d.NL;
-            Off& o = offs[i];
-            o.L = take(NT * 4); o.feat = take(nn * 4); o.theta = take(nn * 4); o.dleft = take(nn * 4); o.left = take(nn * 4); o.right = take(nn * 4);
-            o.cnt = take(nl * 4); o.gain = take(nn * 8); o.val = take(nl * 8); o.any = take((size_t)d.NE * 4);
-        }
-        char* base = ha_lock.owns_lock() ? (char*)HA.get(need, device) : nullptr;
-        for (int i : want) {
-            SmallFitDev& d = *dev[i]; const size_t NT = d.NT, nn = NT * (size_t)(d.NL - 1), nl = NT * (size_t)d.NL;
-            int32_t *hL, *hfeat, *htheta, *hdleft, *hleft, *hright, *hcnt, *hany; double *hgain, *hval;
-            if (base) {
-                const Off& o = offs[i];
-                hL = (int32_t*)(base + o.L); hfeat = (int32_t*)(base + o.feat); htheta = (int32_t*)(base + o.theta); hdleft = (int32_t*)(base + o.dleft);
-                hleft = (int32_t*)(base + o.left); hright = (int32_t*)(base + o.right); hcnt = (int32_t*)(base + o.cnt); hany = (int32_t*)(base + o.any);
-                hgain = (double*)(base + o.gain); hval = (double*)(base + o.val);
-            } else {
-                d.hL.resize(NT); d.hfeat.resize(nn); d.htheta.resize(nn); d.hdleft.resize(nn); d.hleft.resize(nn); d.hright.resize(nn);
-                d.hcnt.resize(nl); d.hany.resize(d.NE); d.hgain.resize(nn); d.hval.resize(nl);
-                hL = d.hL.data(); hfeat = d.hfeat.data(); htheta = d.htheta.data(); hdleft = d.hdleft.data(); hleft = d.hleft.data(); hright = d.hright.data();
-                hcnt = d.hcnt.data(); hany = d.hany.data(); hgain = d.hgain.data(); hval = d.hval.data();
-            }
-            d.t_L.download(hL, NT, s); d.t_feat.download(hfeat, nn, s); d.t_theta.download(htheta, nn, s);
-            d.t_dleft.download(hdleft, nn, s); d.t_left.download(hleft, nn, s); d.t_right.download(hright, nn, s);
-            d.t_cnt.download(hcnt, nl, s); d.t_gain.download(hgain, nn, s); d.t_val.download(hval, nl, s);
-            d.any.download(hany, d.NE, s);
-            hts[i] = HostTrees{hL, hfeat, htheta, hdleft, hleft, hright, hcnt, hgain, hval, hany};
-        }
+    size_t need = 0;
+    for (int i : want) need += dev[i]->trees.host_bytes();
+    char* base = ha_lock.owns_lock() ? (char*)HA.get(need, device) : nullptr;
+    for (int i : want) {
+        SmallFitDev& d = *dev[i];
+        const size_t bytes = d.trees.host_bytes();
+        if (base) { hts[i] = d.trees.download(base, s); base += bytes; }
+        else { d.host_trees.resize(bytes); hts[i] = d.trees.download(d.host_trees.data(), s); }
     }
     HIPCHK(hipStreamSynchronize(s));
     const double t_down = now();

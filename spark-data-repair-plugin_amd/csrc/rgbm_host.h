@@ -76,15 +76,39 @@ struct StreamGuard {
     ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
 };
 
+// a HIP event that lives as long as its scope, whatever leaves it (timing events: hipEventElapsedTime needs them)
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() { HIPCHK(hipEventCreate(&e)); }
+    Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+};
+
+// Runs fn once per process, device and tag.  For function attributes (hipFuncSetAttribute): they belong to the function, not to the
+// call, and other threads are launching the kernels while a new training call sets up.  A call that throws runs again next time.
+enum OnceTag { ONCE_LEVEL_LDS = 0, ONCE_SMALL_TREE_LDS, ONCE_HIST_LDS, ONCE_TAGS };
+inline void once_per_device(int device, OnceTag tag, void (*fn)()) {
+    static std::mutex mu; static char done[64][ONCE_TAGS] = {};
+    std::lock_guard<std::mutex> lk(mu);
+    if (done[device & 63][tag]) return;
+    fn();
+    done[device & 63][tag] = 1;
+}
+
+// the RGBM_ERR_* code an exception stands for
+inline int status_of(const std::exception& e) {
+    if (dynamic_cast<const std::invalid_argument*>(&e)) return RGBM_ERR_PARAM;
+    if (dynamic_cast<const std::out_of_range*>(&e)) return RGBM_ERR_LABEL;
+    if (dynamic_cast<const std::domain_error*>(&e)) return RGBM_ERR_NO_DEVICE;
+    if (dynamic_cast<const std::bad_alloc*>(&e)) return RGBM_ERR_NOMEM;
+    return RGBM_ERR_HIP;
+}
+
 // C++ exceptions never cross the C ABI: every entry point runs its body through this
 template <typename Fn>
 int guarded(Fn&& fn) {
     try { return fn(); }
-    catch (const std::invalid_argument& e) { return fail(RGBM_ERR_PARAM, e.what()); }
-    catch (const std::out_of_range& e) { return fail(RGBM_ERR_LABEL, e.what()); }
-    catch (const std::domain_error& e) { return fail(RGBM_ERR_NO_DEVICE, e.what()); }
-    catch (const std::bad_alloc&) { return fail(RGBM_ERR_NOMEM, "out of host memory"); }
-    catch (const std::exception& e) { return fail(RGBM_ERR_HIP, e.what()); }
+    catch (const std::exception& e) { const int code = status_of(e); return fail(code, code == RGBM_ERR_NOMEM ? "out of host memory" : e.what()); }
 }
 
 // class probabilities [n][num_class] (row-major, device) of the n rows of a device code block [c][n]; defined in rgbm.hip
