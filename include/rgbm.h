@@ -164,6 +164,23 @@ int rgbm_table_train(const rgbm_table* t, int32_t target_col, const int32_t* fea
  * integers).  NULL clears.  Level grower only (1 <= max_depth <= 7), at most 32 features with a free byte in the last 16-feature record, no
  * bagging, no per-row weights: a training call that cannot honour it fails with RGBM_ERR_PARAM. */
 int rgbm_table_set_row_multiplicity(rgbm_table* t, const uint8_t* mult /* [n] or NULL */);
+/* The multiplicities a table carries, one per row (1 everywhere when it carries none). */
+int rgbm_table_read_row_multiplicity(const rgbm_table* t, uint8_t* mult_out /* [n] */);
+/* The DISTINCT rows of a resident table, found on the device (the host statement is repair.pipeline.distinct_rows; the reference has no
+ * counterpart, see rgbm_table_set_row_multiplicity).  All c columns take part and NULL (-1, or any code outside [0, n_codes)) is a value of
+ * its own.  The result is a function of the table alone:
+ *   - `out` holds one group per distinct row, the groups in order of FIRST OCCURRENCE (ascending position of the first row of each group);
+ *   - a group of cnt rows is kept as ceil(cnt / 255) consecutive copies with the multiplicities 255, .., 255, cnt - 255 * (copies - 1),
+ *     which are attached to `out` as rgbm_table_set_row_multiplicity attaches them: rgbm_table_train on `out` returns the models of `t`;
+ *   - `out` inherits the column kinds and column values, like rgbm_table_gather_rows;
+ *   - inverse_out[i] = position in `out` of the first copy of row i's group;  *n_out = rows of `out`.
+ * RGBM_ERR_PARAM: more than 2^30 rows; a table that carries multiplicities itself; or a working set -- everything the call allocates with the
+ * output at its largest: 8 B per slot of >= 2n slots (a power of two) + (47 + 8 per key word + 4c) B per row -- above half of the device memory.
+ * The other table entries do not read multiplicities: on `out` they see its rows.
+ * What rgbm_table_train refuses on a table with multiplicities it refuses on `out`: besides the parameters named at
+ * rgbm_table_set_row_multiplicity, a table of 17 to 31 features trains only when both 16-feature chunks fit one level pass and the features pack
+ * into at most 15 joint-bin groups of at most 256 bins (about: fewer than 16 features with more than 16 bins).  Callers fall back to `t`. */
+int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, int64_t* n_out, int64_t* inverse_out /* [n] or NULL */);
 /* ---- many small fits in one go ------------------------------------------------------------------
  * Replaces the LOOP over fits of python/repair/train.py:158-209 (every hyper-parameter trial is `cross_val_score`: n_splits fits of
  * the same estimator on row subsets of one frame, train.py:171-172) and of python/repair/model.py:768-815 on the reference's default

@@ -85,7 +85,8 @@ def lib():
                      "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict",
                      "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
-                     "rgbm_nearest_values", "rgbm_table_detect_cells"):
+                     "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
+                     "rgbm_table_read_row_multiplicity"):
             getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -109,6 +110,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
+    "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity",
 ]
 
 COMM_ID_BYTES = 128
@@ -805,6 +807,22 @@ class Table:
         if m is not None and m.shape != (self.n,):
             raise ValueError("one multiplicity per row")
         _check(lib().rgbm_table_set_row_multiplicity(self.h, _p(m, C.c_uint8)), "rgbm_table_set_row_multiplicity")
+
+    def row_multiplicity(self):
+        """The multiplicities the table carries, uint8 [n] (1 everywhere when it carries none)."""
+        out = np.zeros(self.n, np.uint8)
+        _check(lib().rgbm_table_read_row_multiplicity(self.h, _p(out, C.c_uint8)), "rgbm_table_read_row_multiplicity")
+        return out
+
+    def distinct_rows(self, want_inverse=False):
+        """The distinct rows of this table as a new resident table, found on the device (rgbm_table_distinct_rows): groups in order of
+        first occurrence, a group of more than 255 rows kept as several copies, the multiplicities attached -- train() on it returns
+        the models of this table, byte for byte.  `want_inverse`: also int64 [n], the position of every row's group in the new table."""
+        h, m = C.c_void_p(), C.c_int64(0)
+        inv = np.zeros(self.n, np.int64) if want_inverse else None
+        _check(lib().rgbm_table_distinct_rows(self.h, C.byref(h), C.byref(m), _p(inv, C.c_int64)), "rgbm_table_distinct_rows")
+        d = Table._adopt(h, self.device_id)
+        return (d, inv) if want_inverse else d
 
     def repair_chain_gather(self, models, target_col, feat_cols, row_begin=0, n_rows=None):
         """The chained repair of THIS rank's rows, the outputs all-gathered over the calling thread's communicator on the device (C2):

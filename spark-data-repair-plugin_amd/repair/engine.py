@@ -187,7 +187,7 @@ def _train_concurrency(engine, table, costs, requested, search_fits=0):
 
 def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, base_params, want_stats=False, row_table=None,
             force_row_sharding=False, train_concurrency=None, y_values=None, integral=(), train_tables=None, param_search=None,
-            dirty_is_shard=False, row_shard_all=False, rule_steps=None):
+            dirty_is_shard=False, row_shard_all=False, rule_steps=None, fallback_tables=None):
     """Train + repair, sharded over the ranks of the current torch.distributed group (if any).
 
     train_table / dirty_table : engine tables (all rows with error cells NULLed / the dirty rows)
@@ -202,12 +202,17 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
                                 an L2 regressor (train.py:97-100) on those values; `integral` names the ones rounded after prediction
     rule_steps[t]             : dict(x=column or -1, lut): target t is answered by a rule (`chained_repair`), not by a model: it is not
                                 trained, has no blob and no label counts; the chain then runs through `chained_repair`
-    Returns dict(labels [T][D], probs [T][D], values [T][D] or None, models {target: bytes}, times, stats).
+    fallback_tables[t]        : the table target t trains on when the trainer REFUSES its entry of `train_tables` with RGBM_ERR_PARAM (a distinct-row
+                                table whose multiplicities this fit cannot carry: include/rgbm.h rgbm_table_distinct_rows); `fell_back` of the
+                                result holds {target: the refusal}.  Any other failure surfaces as before.
+    Returns dict(labels [T][D], probs [T][D], values [T][D] or None, models {target: bytes}, times, stats, fell_back).
     """
     y_values = dict(y_values or {})
     rule_steps = dict(rule_steps or {})
     integral = set(integral)
-    train_tables = dict(train_tables or {})     # {target: table}: that target trains on its own (sampled) table, model.py:755-766
+    # {target: table}: that target trains on its own table -- a row sample (model.py:755-766), or the distinct rows of the training table with
+    # their multiplicities (pipeline.distinct_training_tables, which only enters tables above small_rows(): the batched trainer below carries none)
+    train_tables = dict(train_tables or {})
     # param_search(target, table) -> {LightGBM core parameter: value} found by the hyper-parameter search for that target (train.py:133-209),
     # run by the rank that owns the target right before its final fit; None = the fixed parameters
     rank, ws = dist.world()
@@ -223,6 +228,8 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
     t0 = time.perf_counter()
     blobs, stats, shared, fusion_stats = {}, [], {}, {}
     trained = {}     # target -> the model object this rank trained itself (load(save(m)) is m: no need to parse its own blob again)
+    fallback_tables = dict(fallback_tables or {})
+    fell_back = {}
 
     def one(t, table, fn):
         feats = [c for c in range(n_cols) if c != t]
@@ -230,8 +237,14 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
         base = dict(base_params)
         if param_search is not None and fn == engine.train:
             base.update(param_search(t, table) or {})
-        res = fn(table, t, feats, cw, model_params(int(n_codes[t]), base, continuous=t in y_values), y_value=y_values.get(t),
-                 want_stats=want_stats)
+        params = model_params(int(n_codes[t]), base, continuous=t in y_values)
+        try:
+            res = fn(table, t, feats, cw, params, y_value=y_values.get(t), want_stats=want_stats)
+        except Exception as e:  # noqa: BLE001
+            if getattr(e, "code", None) != -2 or t not in fallback_tables or fallback_tables[t] is table:      # -2 = RGBM_ERR_PARAM
+                raise
+            fell_back[t] = str(e)
+            res = fn(fallback_tables[t], t, feats, cw, params, y_value=y_values.get(t), want_stats=want_stats)
         if want_stats:
             res, st = res
             st["target"] = t
@@ -386,4 +399,4 @@ def run_job(engine, train_table, dirty_table, n_codes, targets, label_counts, ba
             values = dist.gather_rows(val, D) if val is not None else None
         t_gather = time.perf_counter() - t0
     return dict(labels=labels, probs=probs, values=values, models=all_blobs, stats=stats, my_targets=mine, row_sharded_targets=[t for t, _ in big], fusion=fusion_stats,
-                dirty_row0=row0, times=dict(train=t_train, exchange=t_xchg, infer=t_infer, gather=t_gather))
+                dirty_row0=row0, times=dict(train=t_train, exchange=t_xchg, infer=t_infer, gather=t_gather), fell_back=fell_back)

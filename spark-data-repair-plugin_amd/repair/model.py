@@ -103,6 +103,14 @@ class RepairModel():
     # new in this engine: the value detectors (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector) as code predicates on
     # the HBM-resident table (repair.detect_codes, `Table.detect_cells`)
     _opt_value_detectors_resident = _option("error.value_detectors.resident", False, bool, None, None)
+    # new in this engine: on the HBM-resident pipeline, train every attribute's model on the DISTINCT rows of the table with their
+    # multiplicities (found on the device, `Table.distinct_rows`): the same models, bytes included, at the cost of the distinct rows.  It
+    # only matters for an attribute that `model.max_training_row_num` does not sample (a sampled attribute trains on its sample); the
+    # whole table is used wherever the variant does not apply (repair.pipeline.distinct_training_tables; `_last_resident_info` says why)
+    _opt_train_distinct_rows = _option("model.train.distinct_rows", False, bool, None, None)
+    # ... unless the table holds more than this share of distinct rows (a policy default, not a measured break-even: DESIGN 5g)
+    _opt_train_distinct_rows_max_ratio = _option("model.train.distinct_rows.max_ratio", 0.5, float, lambda v: 0.0 < v <= 1.0,
+                                                 "`{}` should be in (0.0, 1.0]")
     # new in this engine: which HIP device trains/predicts (read by repair.train.fixed_params)
     _opt_gpu_device_id = _train_opt_gpu_device_id
 
@@ -110,7 +118,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident,
-        _opt_value_detectors_resident, _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -631,7 +639,10 @@ class RepairModel():
                       max_bin=int(g(_opt_max_bin)), lambda_l1=float(g(_opt_reg_alpha)), min_gain_to_split=float(g(_opt_min_split_gain)),
                       num_leaves=31, min_data_in_leaf=20, min_sum_hessian_in_leaf=1e-3, lambda_l2=0.0, bagging_fraction=1.0, bagging_freq=0,
                       feature_fraction=1.0, seed=42)
-        return dict(engine=engine, params=params, search=int(g(_opt_max_evals)) > 1, rules=rules)
+        distinct = None
+        if bool(self._get_option_value(*self._opt_train_distinct_rows)):
+            distinct = dict(max_ratio=float(self._get_option_value(*self._opt_train_distinct_rows_max_ratio)))
+        return dict(engine=engine, params=params, search=int(g(_opt_max_evals)) > 1, rules=rules, distinct=distinct)
 
     def _resident_rules(self, input_df: DataFrame, target_columns: List[str], continous_columns: List[str], domain_stats: Dict[str, int],
                         prob_modes: bool) -> Optional[Dict[str, Any]]:
@@ -808,7 +819,7 @@ class RepairModel():
                                    detect_nulls=plan["detect_nulls"], continuous_columns=[c for c in continous_columns if c in cands],
                                    train_rows=sample, want_details=True, search_opts=dict(self.opts) if plan.get("search") else None,
                                    only_noisy_targets=True, domain_analysis=plan.get("domain_analysis"), rules=plan.get("rules"),
-                                   value_detectors=vdets)
+                                   value_detectors=vdets, distinct_training_rows=plan.get("distinct"))
         self._last_resident_info = info
         self._last_detection_on_device = True
         merged = info.get("merged_cells")              # nearest-value merges: repaired by rule, appended as `_run` appends them
@@ -878,7 +889,8 @@ class RepairModel():
         frame, info = repair_frame(plan["engine"], input_df, rid, targets=target_columns, base_params=plan["params"],
                                    error_cells=error_cells_df[[rid, "attribute"]], detect_nulls=False,
                                    continuous_columns=[c for c in continous_columns if c in target_columns], train_rows=sample,
-                                   want_details=True, search_opts=dict(self.opts) if plan.get("search") else None, rules=rules)
+                                   want_details=True, search_opts=dict(self.opts) if plan.get("search") else None, rules=rules,
+                                   distinct_training_rows=plan.get("distinct"))
         self._last_resident_info = info
         by_rules = None
         merged = info.get("merged_cells")

@@ -9,6 +9,7 @@ job logic runs on the CPU oracle engine in the tests.
 Cells are (row position, column index); values are codes (-1 = NULL).  `repair.encode` / `Table.from_dictionaries`
 map between values and codes.
 """
+import os
 import time
 
 import numpy as np
@@ -185,6 +186,79 @@ def distinct_rows(codes, n_codes, max_mult=255):
     return np.ascontiguousarray(codes[:, rows]), mult.astype(np.uint8), start[inverse].astype(np.int64)
 
 
+def distinct_training_tables(engine, table, targets, base_params, spec, train_tables, search_opts=None, continuous=()):
+    """The opt-in hook `repair_table(distinct_training_rows=dict(max_ratio=..))`: enters ONE distinct-row table of `table`
+    (`Table.distinct_rows()`: rgbm_table_distinct_rows, multiplicities attached) into `train_tables` for every target in `targets` that
+    qualifies.  A target keeps the whole table, with the reason logged and returned, when
+      - `train_rows` picked a sample for it (`train_tables` holds it already);
+      - a hyper-parameter search runs (`search_opts`): it gathers folds, and gathers drop multiplicities;
+      - the parameters are not what the multiplicity trainer honours (include/rgbm.h rgbm_table_set_row_multiplicity: the level grower,
+        1 <= max_depth <= 7, no bagging, at most 32 features with a free byte in the last 16-feature record), or the target is
+        continuous (the variant is pinned for classifiers);
+      - the table, or its distinct table, has at most `engine.small_rows()` rows: `run_job` sends such tables to the batched trainer, which
+        does not carry multiplicities;
+      - the table holds more than max_ratio * N distinct rows (M rows cost more each than N: DESIGN 5g);
+      - the engine's table has no `distinct_rows`.
+    The parameter checks restate what the trainer would refuse, to spare the `distinct_rows()` call; they are not the guard.  What only the
+    trainer can know -- a table of 17 to 31 features whose bins do not fit the one-pass forms that carry the multiplicity, a run-time switch
+    -- it refuses with RGBM_ERR_PARAM, and `run_job(fallback_tables=..)` then trains that target on the whole table (`repair_table` moves it to
+    `skipped` with the trainer's message).
+    Returns (the distinct table or None, dict(rows=N, distinct=M or None when it was not computed, used_for=[targets], skipped={target: reason})).
+    The table is freed at once when no target qualifies; the caller frees it otherwise."""
+    N = int(table.n)
+    max_ratio = float(spec.get("max_ratio", 0.5))
+    small = int(engine.small_rows()) if hasattr(engine, "small_rows") else 0
+    info = dict(rows=N, distinct=None, used_for=[], skipped={})
+    F = int(table.c) - 1
+    depth = int(base_params.get("max_depth", -1))
+    bagging = int(base_params.get("bagging_freq", 0)) > 0 and float(base_params.get("bagging_fraction", 1.0)) < 1.0
+    for_all = None
+    if not hasattr(table, "distinct_rows"):
+        for_all = "the engine's table has no distinct_rows"
+    elif search_opts is not None:
+        for_all = "a hyper-parameter search gathers folds, and gathers drop multiplicities"
+    elif not 1 <= depth <= 7 or os.environ.get("RGBM_GROWER") == "leafwise":
+        for_all = "max_depth %d: rows with multiplicities train with the level grower (1 <= max_depth <= 7)" % depth
+    elif bagging:
+        for_all = "bagging draws per original row"
+    elif F > 32 or F % 16 == 0:
+        for_all = "%d features: rows with multiplicities take at most 32 with a free byte in the last 16-feature record" % F
+    elif N <= small:
+        for_all = "%d rows: tables of up to %d rows go to the batched trainer, which carries no multiplicities" % (N, small)
+    cand = []
+    for t in targets:
+        if for_all is not None:
+            info["skipped"][t] = for_all
+        elif t in train_tables:
+            info["skipped"][t] = "trained on a row sample (train_rows)"
+        elif t in continuous:
+            info["skipped"][t] = "continuous target: rows with multiplicities are pinned for classifiers"
+        else:
+            cand.append(t)
+    dtab = None
+    if cand:
+        dtab = table.distinct_rows()
+        M = info["distinct"] = int(dtab.n)
+        why = None
+        if M <= small:
+            why = "%d distinct rows: tables of up to %d rows go to the batched trainer, which carries no multiplicities" % (M, small)
+        elif M > max_ratio * N:
+            why = "%d distinct rows of %d: more than max_ratio = %g of them" % (M, N, max_ratio)
+        if why is not None:
+            info["skipped"].update({t: why for t in cand})
+            if hasattr(dtab, "close"):
+                dtab.close()
+            dtab = None
+        else:
+            info["used_for"] = list(cand)
+            train_tables.update({t: dtab for t in cand})
+    for t, why in info["skipped"].items():
+        _logger.info("[Repair Model Training Phase] target column %d trains on the whole table, not on its distinct rows: %s" % (t, why))
+    if info["used_for"]:
+        _logger.info("[Repair Model Training Phase] target columns %s train on the %d distinct rows of %d" % (info["used_for"], info["distinct"], N))
+    return dtab, info
+
+
 class NotResidentEligible(ValueError):
     """The run is not the plain per-attribute model loop after all (only known once the error cells are NULLed): a discrete target
     is left with fewer than two classes, a continuous one with no value.  The reference short-cuts those with `PoorModel`
@@ -338,7 +412,7 @@ def rule_step_summary(table, t, step, cell_rows, dirty_rows, dirty_tab, labels):
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None):
+                 value_detectors=None, distinct_training_rows=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
@@ -374,9 +448,14 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
                  then each FD target once its source is no longer pending.
     value_detectors: per-column code predicates of the regex / value-domain / outlier detectors (`detect_error_cells`), or a callable
                  (table) -> such a list, called on the table before any cell is NULLed (autofill and quartiles need its rows per code).
+    distinct_training_rows: None (off) or dict(max_ratio=float) -- train the targets that qualify on the DISTINCT rows of the NULLed table with
+                 their multiplicities (`distinct_training_tables`: one `Table.distinct_rows()` call on the device); same models, bytes
+                 included.  Every target that does not qualify, or whose fit the trainer refuses on the distinct table, trains on the whole
+                 table; the result's `distinct_rows` says which and why.  With `want_stats` the stats of a target trained on the distinct
+                 table describe that fit (its M rows), not a fit on the N rows.
     Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
-    dirty_rows, models, times, stats[, domain][, rule_steps, merged][, value_detectors]): one entry per error cell, ordered by
-    (column, row).
+    dirty_rows, models, times, stats[, domain][, rule_steps, merged][, value_detectors][, distinct_rows]): one entry per error cell,
+    ordered by (column, row).
     """
     continuous = dict(continuous or {})
     t0 = time.perf_counter()
@@ -479,6 +558,12 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         if gone:
             raise UnseenCategories("%d (target, feature) pairs hold categories no training row has, e.g. target column %d / feature column %d"
                                    % (len(gone), gone[0][0], gone[0][1]))
+    distinct_tab = None
+    if distinct_training_rows is not None:
+        # after the error cells are NULLed, the merges written back, the label counts taken from the whole table and the unseen-category
+        # check made on it: the distinct table holds rows whose target cell is NULL too (the trainer skips them, as on the whole table)
+        distinct_tab, out["distinct_rows"] = distinct_training_tables(engine, table, [t for t in targets if t not in rule_steps], base_params,
+                                                                      distinct_training_rows, train_tables, search_opts, continuous)
     search = None
     if search_opts is not None:
         def search(t, tab):
@@ -487,8 +572,18 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         # budgets device memory with it
         from repair.train import search_fits_in_flight
         search.fits_in_flight = search_fits_in_flight(search_opts)
-    res = run_job(engine, table, dirty_tab, n_codes, targets, label_counts, base_params, want_stats=want_stats,
-                  y_values=y_values, integral=integral, train_tables=train_tables, param_search=search, rule_steps=rule_steps)
+    try:
+        res = run_job(engine, table, dirty_tab, n_codes, targets, label_counts, base_params, want_stats=want_stats,
+                      y_values=y_values, integral=integral, train_tables=train_tables, param_search=search, rule_steps=rule_steps,
+                      fallback_tables={t: table for t in out["distinct_rows"]["used_for"]} if distinct_tab is not None else None)
+    finally:
+        if distinct_tab is not None and hasattr(distinct_tab, "close"):
+            distinct_tab.close()
+    for t, why in (res.get("fell_back") or {}).items():          # the trainer refused the distinct table for this fit: it trained on the whole one
+        d = out["distinct_rows"]
+        d["used_for"] = [u for u in d["used_for"] if u != t]
+        d["skipped"][t] = "the trainer refused the distinct table: %s" % why
+        _logger.info("[Repair Model Training Phase] target column %d trained on the whole table after all: %s" % (t, why))
     # flatten + join with the error cells (RepairMiscApi.scala:41-49, model.py:1398-1401)
     t0 = time.perf_counter()
     tpos = np.full(table.c, -1, np.int64)
@@ -584,7 +679,7 @@ def encode_frame(df, columns):
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None):
+                 value_detectors=None, distinct_training_rows=None):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
@@ -615,7 +710,10 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     values) -> strings, domain_str=callable(attribute, dictionary values) -> strings[, current=callable(attribute, row positions) ->
     strings: the error cells' current values where the caller holds them already])).  The frame then lacks the merged cells; the details
     hold them as `merged_cells` (row_id, attribute, current_value, repaired: strings), their number per attribute as `nearest_values`,
-    and `rule_steps` (`rule_step_summary` with attribute names)."""
+    and `rule_steps` (`rule_step_summary` with attribute names).
+
+    distinct_training_rows: None or dict(max_ratio=float), as `repair_table` takes it; the details then hold `distinct_rows` with attribute
+    names: dict(rows, distinct, used_for=[attributes], skipped={attribute: reason})."""
     import pandas as pd
     cols = [c for c in df.columns if c != row_id]
     targets = list(targets) if targets is not None else list(cols)
@@ -744,6 +842,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                                    pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
                                    only_noisy_targets=only_noisy_targets, domain_analysis=da_spec, rules=table_rules(),
                                    value_detectors=table_detectors(detect_nulls_) if analyse else None,
+                                   distinct_training_rows=distinct_training_rows,
                                    check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
                                    train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
 
@@ -804,6 +903,10 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         if res.get("value_detectors"):
             details["value_detectors"] = [dict(attribute=cols[d["col"]], kinds=d["kinds"], codes_flagged=d["codes_flagged"], cells=d["cells"])
                                           for d in res["value_detectors"]]
+        if res.get("distinct_rows") is not None:
+            d = res["distinct_rows"]
+            details["distinct_rows"] = dict(rows=d["rows"], distinct=d["distinct"], used_for=[cols[t] for t in d["used_for"]],
+                                            skipped={cols[t]: why for t, why in d["skipped"].items()})
         if rules is not None:
             details["rule_steps"] = [dict(st, target=cols[st["target"]], x=cols[st["x"]] if st["x"] >= 0 else None) for st in res.get("rule_steps", [])]
             mg = res.get("merged")
