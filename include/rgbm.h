@@ -242,6 +242,40 @@ int rgbm_table_detect_cells(rgbm_table* t, const int32_t* cols, int32_t n_cols, 
 int rgbm_table_detect_constraint(rgbm_table* t, const int32_t* eq_cols, int32_t n_eq, int32_t iq_col,
                                  const int32_t* cell_cols, int32_t n_cell_cols,
                                  int64_t* n_rows_out /* may be NULL */, int64_t* n_cells_out);
+/* ConstraintErrorDetector for EVERY other two-tuple denial constraint the parser accepts (DenialConstraints.scala:60-95: several IQs,
+ * LT / GT, LT / GT across two attributes), 2 <= n_preds <= 16 predicates.  For row i as t1 and row j as t2 a predicate compares
+ * L = code(i, left_col) with R = code(j, right_col); a code outside [0, n_codes) is -1, and a code is mapped through left_rank /
+ * right_rank (int32 [n_codes[col]], an entry < 0 = "this value has no number") where that pointer is not NULL:
+ *   EQ  L == R (NULL equals NULL, `<=>`)      IQ  L != R (NULL is a value of its own)
+ *   LT  L >= 0 && R >= 0 && L < R             GT  L >= 0 && R >= 0 && L > R
+ * EQ / IQ take left_col == right_col and no rank arrays (RGBM_ERR_ARG otherwise; at most 12 distinct EQ attributes).  Row i violates
+ * iff SOME row j of the table -- j == i included, as in the reference's EXISTS sub-query (ErrorDetectorApi.scala:218-223) -- makes
+ * every predicate true; with EQ predicates only every row violates.  Result as for rgbm_table_detect_constraint: the ascending
+ * violating rows x cell_cols.
+ * The rows are grouped by the EQ attributes and the other predicates evaluated over the pairs of each group, so the call knows the
+ * sum of |group|^2 before it evaluates a pair: above max_pairs (<= 0: the library default) it returns RGBM_ERR_PARAM
+ * and the table's previous result stays as it was.  RGBM_ERR_PARAM also for EQ attributes that span 2^63 value combinations or more
+ * and for a table of 2^31 rows or more. */
+#define RGBM_DC_EQ 0
+#define RGBM_DC_IQ 1
+#define RGBM_DC_LT 2
+#define RGBM_DC_GT 3
+typedef struct rgbm_dc_pred {
+    int32_t op;                 /* RGBM_DC_* */
+    int32_t left_col;           /* attribute of t1 */
+    int32_t right_col;          /* attribute of t2 */
+    int32_t reserved;           /* 0 */
+    const int32_t* left_rank;   /* [n_codes[left_col]] or NULL */
+    const int32_t* right_rank;  /* [n_codes[right_col]] or NULL */
+} rgbm_dc_pred;
+int rgbm_table_detect_dc(rgbm_table* t, const rgbm_dc_pred* preds, int32_t n_preds, const int32_t* cell_cols, int32_t n_cell_cols,
+                         int64_t max_pairs, int64_t* n_rows_out /* may be NULL */, int64_t* n_cells_out);
+/* ConstraintErrorDetector for single-tuple constraints (constant predicates, e.g. t1&EQ(t1.Sex,"Female")&EQ(t1.Relationship,"Husband")):
+ * bits[k] holds n_codes[cols[k]] + 1 bits (bit v = bit v % 64 of word v / 64), bit v = "the predicates on cols[k] hold for code v",
+ * the last bit for NULL (a code outside [0, n_codes) is NULL).  A row violates iff its bit is set in every listed column; one
+ * streaming pass.  `cols`: at least one, distinct, in range, each with a bitset (RGBM_ERR_ARG).  Result as above. */
+int rgbm_table_detect_row_bits(rgbm_table* t, const int32_t* cols, int32_t n_cols, const uint64_t* const* bits /* [n_cols] */,
+                               const int32_t* cell_cols, int32_t n_cell_cols, int64_t* n_rows_out /* may be NULL */, int64_t* n_cells_out);
 /* Ascending positions of the rows that hold at least one of the given cells: the dirty rows of
  * python/repair/model.py:549-553 (left-semi join on the row id). */
 int rgbm_table_rows_of_cells(rgbm_table* t, const int64_t* rows, int64_t n_cells, int64_t* n_rows_out);

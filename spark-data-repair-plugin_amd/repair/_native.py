@@ -86,7 +86,7 @@ def lib():
                      "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
                      "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
-                     "rgbm_table_read_row_multiplicity"):
+                     "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits"):
             getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -110,7 +110,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
-    "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity",
+    "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
 ]
 
 COMM_ID_BYTES = 128
@@ -525,6 +525,12 @@ def nearest_values(a=None, b=None, cost=None, threshold=0.0, device_id=0):
     return out
 
 
+class DcPred(C.Structure):
+    """``rgbm_dc_pred`` of include/rgbm.h."""
+    _fields_ = [("op", C.c_int32), ("left_col", C.c_int32), ("right_col", C.c_int32), ("reserved", C.c_int32),
+                ("left_rank", C.POINTER(C.c_int32)), ("right_rank", C.POINTER(C.c_int32))]
+
+
 class Table:
     """An int32 code table resident in HBM (``rgbm_table``)."""
 
@@ -616,6 +622,51 @@ class Table:
         nr, nc = C.c_int64(0), C.c_int64(0)
         _check(lib().rgbm_table_detect_constraint(self.h, _p(eq, C.c_int32), C.c_int32(len(eq)), C.c_int32(iq_col),
                                                   _p(cc, C.c_int32), C.c_int32(len(cc)), C.byref(nr), C.byref(nc)), "rgbm_table_detect_constraint")
+        return self._fetch_cells(int(nc.value), len(cc) > 0)
+
+    def detect_dc(self, preds, cell_cols=(), max_pairs=0):
+        """Rows violating a two-tuple denial constraint (rgbm_table_detect_dc; repair.dc_codes lowers a parsed constraint to this).
+        ``preds``: 2 to 16 tuples (op, left_col, right_col, left_rank, right_rank) with op in 'EQ' / 'IQ' / 'LT' / 'GT' and the ranks int32
+        [n_codes[col]] arrays (an entry < 0 = the value has no number) or None.  ``max_pairs`` <= 0: the library default; a table
+        whose EQ groups hold more pairs raises RepairGbmError with code -2.  Returns as ``detect_constraint`` does."""
+        ops = dict(EQ=0, IQ=1, LT=2, GT=3)
+        arr = (DcPred * max(len(preds), 1))()
+        keep = []
+        for k, (op, lc, rc, lr, rr) in enumerate(preds):
+            arr[k].op, arr[k].left_col, arr[k].right_col, arr[k].reserved = ops[op], int(lc), int(rc), 0
+            for name, col, r in (("left_rank", lc, lr), ("right_rank", rc, rr)):
+                if r is None:
+                    continue
+                r = _i32(np.asarray(r, np.int32).reshape(-1))
+                if 0 <= int(col) < self.c and len(r) != int(self.n_codes[int(col)]):
+                    raise ValueError("detect_dc: the rank array of column %d holds %d entries, its dictionary %d" % (col, len(r), int(self.n_codes[int(col)])))
+                keep.append(r)
+                setattr(arr[k], name, r.ctypes.data_as(C.POINTER(C.c_int32)))
+        cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
+        nr, nc = C.c_int64(0), C.c_int64(0)
+        _check(lib().rgbm_table_detect_dc(self.h, arr, C.c_int32(len(preds)), _p(cc, C.c_int32), C.c_int32(len(cc)), C.c_int64(int(max_pairs)),
+                                          C.byref(nr), C.byref(nc)), "rgbm_table_detect_dc")
+        return self._fetch_cells(int(nc.value), len(cc) > 0)
+
+    def detect_row_bits(self, cols, bits, cell_cols=()):
+        """Rows whose code has its bit set in EVERY listed column (rgbm_table_detect_row_bits: single-tuple constraints).  ``bits[k]``:
+        uint64 [ceil((n_codes[cols[k]] + 1) / 64)], bit v = the predicates on the column hold for code v, the last bit for NULL."""
+        cols_ = _i32(np.asarray(cols, np.int32).reshape(-1))
+        k = len(cols_)
+        if len(bits) != k:
+            raise ValueError("detect_row_bits: one bitset per column")
+        keep, ptrs = [], (C.POINTER(C.c_uint64) * max(k, 1))()
+        for j in range(k):
+            w = np.ascontiguousarray(bits[j], np.uint64).reshape(-1)
+            if 0 <= cols_[j] < self.c and len(w) != (int(self.n_codes[cols_[j]]) + 1 + 63) // 64:
+                raise ValueError("detect_row_bits: the bitset of column %d holds %d words, its %d codes and NULL need %d"
+                                 % (cols_[j], len(w), int(self.n_codes[cols_[j]]), (int(self.n_codes[cols_[j]]) + 64) // 64))
+            keep.append(w)
+            ptrs[j] = w.ctypes.data_as(C.POINTER(C.c_uint64))
+        cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
+        nr, nc = C.c_int64(0), C.c_int64(0)
+        _check(lib().rgbm_table_detect_row_bits(self.h, _p(cols_, C.c_int32), C.c_int32(k), ptrs, _p(cc, C.c_int32), C.c_int32(len(cc)),
+                                                C.byref(nr), C.byref(nc)), "rgbm_table_detect_row_bits")
         return self._fetch_cells(int(nc.value), len(cc) > 0)
 
     def rows_of_cells(self, rows):

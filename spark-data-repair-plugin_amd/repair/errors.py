@@ -220,23 +220,27 @@ def _key(s: pd.Series) -> np.ndarray:
     return pd.factorize(s.astype(object).where(s.notna(), "\0__NULL__"), sort=False)[0]
 
 
+def _constant_predicate_holds(col: pd.Series, p: Predicate) -> np.ndarray:
+    """bool per entry of `col`: the single-tuple predicate `p` (an attribute against a constant) holds.  Shared by `_violating_rows`
+    (on the frame's column) and `repair.dc_codes` (on the column's dictionary, in the column's dtype)."""
+    const = p.constant.strip()
+    const = const[1:-1] if len(const) >= 2 and const[0] == const[-1] and const[0] in "\"'" else const
+    sv = col.astype(str).where(col.notna(), None)
+    if p.op == "EQ":
+        return (sv == const).fillna(False).to_numpy(bool)
+    if p.op == "IQ":
+        return ~((sv == const).fillna(False).to_numpy(bool))
+    num = pd.to_numeric(col, errors="coerce")
+    cv = float(const)
+    return ((num < cv) if p.op == "LT" else (num > cv)).fillna(False).to_numpy(bool)
+
+
 def _violating_rows(df: pd.DataFrame, preds: List[Predicate]) -> np.ndarray:
     n = len(df)
     if all(p.constant is not None for p in preds):   # single-tuple constraint
         ok = np.ones(n, bool)
         for p in preds:
-            const = p.constant.strip()
-            const = const[1:-1] if len(const) >= 2 and const[0] == const[-1] and const[0] in "\"'" else const
-            col = df[p.left]
-            sv = col.astype(str).where(col.notna(), None)
-            if p.op == "EQ":
-                ok &= (sv == const).fillna(False).to_numpy(bool)
-            elif p.op == "IQ":
-                ok &= ~((sv == const).fillna(False).to_numpy(bool))
-            else:
-                num = pd.to_numeric(col, errors="coerce")
-                cv = float(const)
-                ok &= ((num < cv) if p.op == "LT" else (num > cv)).fillna(False).to_numpy(bool)
+            ok &= _constant_predicate_holds(df[p.left], p)
         return ok
     eq = [p for p in preds if p.op == "EQ"]
     iq = [p for p in preds if p.op == "IQ"]

@@ -103,6 +103,9 @@ class RepairModel():
     # new in this engine: the value detectors (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector) as code predicates on
     # the HBM-resident table (repair.detect_codes, `Table.detect_cells`)
     _opt_value_detectors_resident = _option("error.value_detectors.resident", False, bool, None, None)
+    # new in this engine: every parsed denial constraint (single-tuple constants, several IQs, LT / GT) on the HBM-resident table
+    # (repair.dc_codes, `Table.detect_dc` / `Table.detect_row_bits`); `X -> Y` constraints take `Table.detect_constraint` either way
+    _opt_constraints_resident = _option("error.constraints.resident", False, bool, None, None)
     # new in this engine: on the HBM-resident pipeline, train every attribute's model on the DISTINCT rows of the table with their
     # multiplicities (found on the device, `Table.distinct_rows`): the same models, bytes included, at the cost of the distinct rows.  It
     # only matters for an attribute that `model.max_training_row_num` does not sample (a sampled attribute trains on its sample); the
@@ -118,7 +121,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident,
-        _opt_value_detectors_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_constraints_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -709,14 +712,21 @@ class RepairModel():
 
         With `error.value_detectors.resident` set, RegExErrorDetector, DomainValues and GaussianOutlierErrorDetector (exactly these
         types) qualify too: on the encoded table they are predicates on the dictionary codes (repair.detect_codes), found together
-        with the NULL cells by one `Table.detect_cells` call.  The plan then carries `value_detectors`."""
+        with the NULL cells by one `Table.detect_cells` call.  The plan then carries `value_detectors`.
+
+        With `error.constraints.resident` set, every other constraint `repair.dc_codes.check_constraint` accepts qualifies as well
+        (single-tuple constants, several IQs, LT / GT): the plan carries its parsed predicates next to the `X -> Y` tuples and
+        `pipeline.repair_frame` lowers them against the dictionaries.  A constraint that does not lower sends the run to the value-space
+        path, as before, with the reason logged."""
         from repair.pipeline import constraint_to_columns
         value_resident = bool(self._get_option_value(*self._opt_value_detectors_resident))
+        constraints_resident = bool(self._get_option_value(*self._opt_constraints_resident))
+        general: List[Any] = []      # the parsed predicates of the constraints that are not `X -> Y`
         vdets: List[Dict[str, Any]] = []
         if self.error_cells is not None or not self.error_detectors:
             return None
         cols = [c for c in input_df.columns if c != self._row_id]
-        cons: List[Tuple[List[str], str]] = []
+        cons: List[Any] = []          # ([x names], y name) of `X -> Y` constraints; the parsed predicates of any other one
         has_null = False
         for d in self.error_detectors:
             if getattr(d, "targets", None):
@@ -731,9 +741,13 @@ class RepairModel():
                     return None
                 for preds in plist:
                     cc = constraint_to_columns(preds, cols)
-                    if cc is None:
+                    if cc is not None:
+                        cons.append(([cols[i] for i in cc[0]], cols[cc[1]]))
+                    elif constraints_resident:
+                        general.append(preds)
+                        cons.append(preds)
+                    else:
                         return None
-                    cons.append(([cols[i] for i in cc[0]], cols[cc[1]]))
             elif value_resident and type(d) is RegExErrorDetector:
                 vdets.append(dict(kind="regex", attr=d.attr, regex=d.regex))
             elif value_resident and type(d) is DomainValues:
@@ -746,6 +760,13 @@ class RepairModel():
                 return None
         from repair.utils import column_nunique
         domain_stats = {c: column_nunique(input_df, c) for c in cols}
+        for preds in general:
+            from repair.dc_codes import NotLowerable, check_constraint
+            try:
+                check_constraint(preds, cols, domain_stats)
+            except NotLowerable as e:
+                _logger.info("[Error Detection Phase] constraint %s stays with the value-space detector: %s" % (preds, e))
+                return None
         discretized = [c for c in cols if c in continous_columns or 1 < domain_stats[c] <= self.discrete_thres]
         cands = [c for c in (self.targets if self.targets else cols) if c in discretized]
         if not cands:
@@ -756,7 +777,8 @@ class RepairModel():
         others = [c for c in (self.targets if self.targets else cols) if c in cols and c not in cands]
         if others and has_null and bool(input_df[others].isna().to_numpy().any()):
             return None
-        if others and any(a in others for xs, y in cons for a in list(xs) + [y]):
+        if others and any(a in others for con in cons
+                          for a in (list(con[0]) + [con[1]] if isinstance(con, tuple) else [r for p in con for r in p.references])):
             return None
         if others and any(d["kind"] != "outlier" and d["attr"] in others for d in vdets):
             return None

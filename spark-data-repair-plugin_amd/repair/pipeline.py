@@ -34,7 +34,10 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
     """Error cells of the target attributes.
 
     constraints : [(eq_cols, iq_col)] -- denial constraints  EQ(X1)..EQ(Xm) & IQ(Y)  (ErrorDetectorApi.scala:189-244); a
-                  violating row contributes the constraint's attributes that are targets (`attrs`, line 211)
+                  violating row contributes the constraint's attributes that are targets (`attrs`, line 211).  Next to them the
+                  programs of `repair.dc_codes.lower_constraint`: dict(kind="dc", preds, refs[, max_pairs]) -> `Table.detect_dc`,
+                  dict(kind="row_bits", cols, bits, refs) -> `Table.detect_row_bits`; a `max_pairs` refusal of the device
+                  (RGBM_ERR_PARAM) raises NotResidentEligible
     error_cells : (rows, cols) given by the caller (RepairModel.setErrorCells); non-target attributes are dropped
     value_detectors : per-column descriptors of the regex / value-domain / outlier detectors as code predicates
                   (`repair.detect_codes.build_descriptors`); one `Table.detect_cells` call answers them, and the NULL detector
@@ -64,7 +67,22 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
                 d["cells"] = int(found[int(d["col"])])
     elif detect_nulls and tg:
         parts.append(table.detect_nulls(tg))
-    for eq, iq in constraints:
+    for con in constraints:
+        if isinstance(con, dict):
+            attrs = [int(a) for a in con["refs"] if a in tg]
+            if not attrs:
+                continue
+            try:
+                if con["kind"] == "dc":
+                    parts.append(table.detect_dc(con["preds"], cell_cols=attrs, max_pairs=int(con.get("max_pairs", 0))))
+                else:
+                    parts.append(table.detect_row_bits(con["cols"], con["bits"], cell_cols=attrs))
+            except Exception as e:  # noqa: BLE001
+                if getattr(e, "code", None) == -2:     # RGBM_ERR_PARAM: more pairs than max_pairs, a key span beyond 2^63
+                    raise NotResidentEligible("denial constraint: %s" % e)
+                raise
+            continue
+        eq, iq = con
         attrs = []
         for a in list(eq) + [iq]:
             if a in tg and a not in attrs:
@@ -685,7 +703,8 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
 
     Columns are discrete (one class per distinct value) unless named in `continuous_columns` (numeric columns; those targets
     get regressors and `repaired` is the predicted number, rounded for integer columns); `constraints` are `X1,..,Xm -> Y`
-    dependencies given as ([x names], y name); `error_cells` is a frame with `row_id` and `attribute` columns
+    dependencies given as the tuple ([x names], y name), or any other parsed constraint as its list of `repair.errors.Predicate`
+    (`repair.dc_codes.lower_constraint` turns it into a program on the codes); `error_cells` is a frame with `row_id` and `attribute` columns
     (RepairModel.setErrorCells).  Regex / value-domain / outlier detectors come as `value_detectors`; LOF-style detectors stay with
     `repair.model.RepairModel` (the value-space API).
 
@@ -832,7 +851,16 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                 table.set_column_values(j, dicts[j])
             elif dicts[j].dtype == object:
                 table.set_column_kind(j, True)     # categories a model's training rows do not show are missing for that model
-        cons = [([pos[x] for x in xs], pos[y]) for xs, y in constraints_]
+        cons = []
+        for con in constraints_:
+            if isinstance(con, tuple):
+                cons.append(([pos[x] for x in con[0]], pos[con[1]]))
+            else:                                  # a parsed constraint: lowered against the dictionaries the table is built from
+                from repair.dc_codes import NotLowerable, lower_constraint
+                try:
+                    cons.append(lower_constraint(con, cols, dicts, {c: df[c].dtype for c in cols}))
+                except NotLowerable as e:
+                    raise NotResidentEligible("denial constraint %s: %s" % (con, e))
         cont_ = {}
         for c in continuous_columns:
             if c in pos and c in targets:
