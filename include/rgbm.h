@@ -425,6 +425,11 @@ int rgbm_model_load(const void* buf, size_t len, rgbm_model** out);
 void rgbm_model_free(rgbm_model* m);
 /* info[5] = {objective, num_class, trees_per_iteration, n_iterations, n_features} */
 int rgbm_model_info(const rgbm_model* m, int32_t* info);
+/* The kernel the predictor runs for this model: out[5] = {form, mask words per tree entry (1: <= 32 leaves, 2: <= 64), padded mask words
+ * per tree (fixed form; else 0), trees per LDS stage, LDS bytes of a workgroup}.  form 0 = fixed-stride bit-vector scorer, 1 =
+ * dynamic-stride scorer, 2 = walk over index-linked nodes (the other entries are 0).  A function of the model and of the environment
+ * switches RGBM_QS_FIXED=0 / RGBM_PREDICTOR=walk alone: it needs no device, and the predictor launches from the same rule. */
+int rgbm_model_predict_form(const rgbm_model* m, int32_t* out);
 /* LightGBM feature_importances_ (train.py:219): type 0 = split counts, 1 = total gain. */
 int rgbm_model_importance(const rgbm_model* m, int32_t type, double* out /* [n_features] */);
 

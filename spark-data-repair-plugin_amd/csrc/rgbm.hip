@@ -1990,6 +1990,40 @@ void build_walk_tables(rgbm_model* m, DeviceModel* dm, hipStream_t s) {
     HIPCHK(hipStreamSynchronize(s));     // the vectors are locals
 }
 
+// Which kernel scores a model, as a function of the model alone (and of the two test switches): the ONE copy of the rule.
+//   fixed    k_predict_qs<MW, FMAX, TW, TBN>: the model's S mask entries (per feature its value bins + the missing entry) and the
+//            all-ones pad entry fit a compile-time stride, S * MW + MW <= TW (the first such row of the table below)
+//   dynamic  k_predict_qs<MW, FMAX, 0, 0>: any larger table, with as many trees per stage (8 at most) as fit 48 KB of LDS twice
+//   walk     k_predict_raw: more than 64 leaves in a tree, more than 32 features, no trees, or not even one tree per stage fits
+// RGBM_QS_FIXED=0 skips the fixed variants and RGBM_PREDICTOR=walk forces the walk (tests).
+enum { FORM_FIXED = 0, FORM_DYNAMIC = 1, FORM_WALK = 2 };
+struct PredictForm { int form, mw, tw, tb; size_t lds; };
+PredictForm predict_form(const rgbm_model* m) {
+    PredictForm pf{FORM_WALK, 0, 0, 0, 0};
+    const char* pe = getenv("RGBM_PREDICTOR");
+    if (pe && strcmp(pe, "walk") == 0) return pf;
+    int maxLeaves = 1;
+    for (const Tree& tr : m->trees) maxLeaves = std::max(maxLeaves, tr.L);
+    const int F = m->F;
+    if (maxLeaves > 64 || F > 32 || m->trees.empty()) return pf;
+    const int MW = maxLeaves <= 32 ? 1 : 2;
+    int S = 0;
+    for (const Feat& f : m->feats) S += std::max(f.V, 1) + 1;
+    const int words = S * MW;
+    int tb = 8, tw = 0;        // trees per LDS stage; padded mask words per tree (0: the dynamic-stride kernel)
+    // compile-time strides (k_predict_qs<., ., TW, TBN>) for the table sizes that occur: the tree's offset rides in the ds_read
+    struct Fix { int mw, fmax, tw, tbn; };
+    static const Fix fixes[] = {{1, 16, 256, 8}, {1, 16, 512, 8}, {1, 32, 512, 8}, {1, 32, 1024, 4}, {2, 16, 512, 8}, {2, 16, 1024, 4}, {2, 32, 1024, 4}, {2, 32, 2048, 2}};
+    const char* qf = getenv("RGBM_QS_FIXED");
+    const bool no_fix = qf && atoi(qf) == 0;
+    for (const Fix& fx : fixes)
+        if (!no_fix && fx.mw == MW && fx.fmax == (F <= 16 ? 16 : 32) && words + MW <= fx.tw) { tw = fx.tw; tb = fx.tbn; break; }   // (+ one all-ones pad entry)
+    const size_t per_tree = (size_t)(tw ? tw : words) * 4 + (size_t)32 * MW * 8 + 4;
+    if (!tw) while (tb > 1 && 2 * tb * per_tree + 16 > 48 * 1024) --tb;
+    if (2 * tb * per_tree + 16 > 48 * 1024) return pf;
+    return PredictForm{tw ? FORM_FIXED : FORM_DYNAMIC, MW, tw, tb, 2 * tb * per_tree + 16};
+}
+
 DeviceModel* device_model(rgbm_model* m, int device, hipStream_t s) {
     std::lock_guard<std::mutex> lk(m->mu);
     auto it = m->dev.find(device);
@@ -2091,24 +2125,13 @@ void predict_device(rgbm_model* m, int device, hipStream_t s, const int32_t* d_c
     DevBuf<uint4>& rec = sc.rec; DevBuf<double>& raw = sc.raw;
     hipLaunchKernelGGL(k_pack_bins, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_codes, Ntab, row0, n,
                        d_feat_cols ? d_feat_cols : dm->ident.p, dm->n_codes.p, dm->lut_off.p, dm->lut.p, dm->miss.p, F, nchunk, rec.p);
-    const char* pe = getenv("RGBM_PREDICTOR"); const bool force_walk = pe && strcmp(pe, "walk") == 0;   // tests: the index-linked walk
-    bool qs = dm->qs_MW > 0 && !force_walk;
-    int qs_tb = 8, qs_tw = 0;        // trees per LDS stage; padded mask words per tree (0: the dynamic-stride kernel)
-    if (qs) {
-        const int words = dm->qs_S * dm->qs_MW;
-        // compile-time strides (k_predict_qs<., ., TW, TBN>) for the table sizes that occur: the tree's offset rides in the ds_read
-        struct Fix { int mw, fmax, tw, tbn; };
-        static const Fix fixes[] = {{1, 16, 256, 8}, {1, 16, 512, 8}, {1, 32, 512, 8}, {1, 32, 1024, 4}, {2, 16, 512, 8}, {2, 16, 1024, 4}, {2, 32, 1024, 4}, {2, 32, 2048, 2}};
-        const bool no_fix = getenv("RGBM_QS_FIXED") && atoi(getenv("RGBM_QS_FIXED")) == 0;
-        for (const Fix& fx : fixes)
-            if (!no_fix && fx.mw == dm->qs_MW && fx.fmax == (F <= 16 ? 16 : 32) && words + dm->qs_MW <= fx.tw) { qs_tw = fx.tw; qs_tb = fx.tbn; break; }   // (+ one all-ones pad entry)
-        const size_t per_tree = (size_t)(qs_tw ? qs_tw : words) * 4 + (size_t)32 * dm->qs_MW * 8 + 4;
-        if (!qs_tw) while (qs_tb > 1 && 2 * qs_tb * per_tree + 16 > 48 * 1024) --qs_tb;
-        if (2 * qs_tb * per_tree + 16 > 48 * 1024) qs = false;
-    }
+    const PredictForm pf = predict_form(m);
+    const bool qs = pf.form != FORM_WALK;
+    if (qs && pf.mw != dm->qs_MW) throw std::logic_error("predict: the scoring tables do not match the model's form");
+    const int qs_tb = pf.tb, qs_tw = pf.tw;
     if (!qs) { std::lock_guard<std::mutex> lk(m->mu); build_walk_tables(m, dm, s); }
     if (qs) {   // bit-vector scoring: no tree walk at all
-        const size_t lds = (size_t)2 * qs_tb * ((size_t)(qs_tw ? qs_tw : dm->qs_S * dm->qs_MW) * 4 + (size_t)32 * dm->qs_MW * 8 + 4) + 16;
+        const size_t lds = pf.lds;
         const dim3 grid((unsigned)((n + 256 * QS_ROWS - 1) / (256 * QS_ROWS)), K);
         const uint8_t* r8 = reinterpret_cast<const uint8_t*>(rec.p);
 #define RGBM_QS(MW, FM, TW, TBN) hipLaunchKernelGGL((k_predict_qs<MW, FM, TW, TBN>), grid, dim3(256), lds, s, r8, n, dm->qs_masks.p, dm->qs_leaves.p, dm->qs_used.p, dm->qs_foff.p, F, dm->qs_S, qs_tb, m->n_iter, K, raw.p)
@@ -2600,6 +2623,7 @@ RGBM_EXPORT int rgbm_model_load(const void* buf, size_t len, rgbm_model** out) {
                 }
             }
             m->trees.resize((size_t)m->n_iter * m->K);
+            std::vector<uint8_t> refs;
             for (Tree& t : m->trees) {
                 int32_t L_; need(4); memcpy(&L_, p, 4); p += 4;
                 if (L_ < 1 || L_ > 32767) return fail(RGBM_ERR_FORMAT, "rgbm_model_load: bad leaf count");
@@ -2616,6 +2640,14 @@ RGBM_EXPORT int rgbm_model_load(const void* buf, size_t len, rgbm_model** out) {
                     auto okc = [&](int ch) { return ch < 0 ? (~ch) < t.L : ch < (int)n && ch > (int)j; };
                     if (!okc(t.left[j]) || !okc(t.right[j])) return fail(RGBM_ERR_FORMAT, "rgbm_model_load: bad child link");
                 }
+                // the links must form a tree: every leaf and every node but the root referenced exactly once (a shared child would make
+                // the in-order traversal of device_model emit more than L leaves, past the tree's leaf block)
+                refs.assign(n + (size_t)t.L, 0);
+                bool tree_ok = true;
+                for (size_t j = 0; j < n; ++j)
+                    for (int ch : {t.left[j], t.right[j]}) if (++refs[ch < 0 ? n + (size_t)(~ch) : (size_t)ch] > 1) tree_ok = false;
+                for (size_t j = 1; j < refs.size(); ++j) if (refs[j] != 1) tree_ok = false;       // (entry 0: the root, or the leaf of a stump)
+                if (!tree_ok) return fail(RGBM_ERR_FORMAT, "rgbm_model_load: child links do not form a tree");
             }
             *out = m.release();
             return RGBM_OK;
@@ -2843,6 +2875,15 @@ RGBM_EXPORT int rgbm_model_info(const rgbm_model* m, int32_t* info) {
     if (!m || !info) return fail(RGBM_ERR_ARG, "rgbm_model_info: bad argument");
     info[0] = m->objective; info[1] = m->num_class; info[2] = m->K; info[3] = m->n_iter; info[4] = m->F;
     return RGBM_OK;
+}
+
+RGBM_EXPORT int rgbm_model_predict_form(const rgbm_model* m, int32_t* out) {
+    if (!m || !out) return fail(RGBM_ERR_ARG, "rgbm_model_predict_form: bad argument");
+    return guarded([&]() {
+        const PredictForm pf = predict_form(m);
+        out[0] = pf.form; out[1] = pf.mw; out[2] = pf.tw; out[3] = pf.tb; out[4] = (int32_t)pf.lds;
+        return RGBM_OK;
+    });
 }
 
 RGBM_EXPORT int rgbm_model_importance(const rgbm_model* m, int32_t type, double* out) {

@@ -78,7 +78,7 @@ def lib():
         l.rgbm_last_error.restype = C.c_char_p
         for name in ("rgbm_device_count", "rgbm_version", "rgbm_release_cache", "rgbm_train", "rgbm_predict", "rgbm_repair_chain",
                      "rgbm_table_create", "rgbm_table_train", "rgbm_table_train_batch", "rgbm_table_repair_chain", "rgbm_table_read_column",
-                     "rgbm_model_save", "rgbm_model_load", "rgbm_model_info", "rgbm_model_importance",
+                     "rgbm_model_save", "rgbm_model_load", "rgbm_model_info", "rgbm_model_importance", "rgbm_model_predict_form",
                      "rgbm_comm_unique_id", "rgbm_comm_init", "rgbm_comm_finalize", "rgbm_comm_info", "rgbm_comm_count",
                      "rgbm_local_group_create", "rgbm_comm_init_local",
                      "rgbm_table_detect_nulls", "rgbm_table_detect_constraint", "rgbm_table_rows_of_cells", "rgbm_table_cells_fetch",
@@ -110,7 +110,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
-    "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
+    "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
 ]
 
 COMM_ID_BYTES = 128
@@ -342,6 +342,13 @@ class Model:
         out = np.zeros(self.info()["F"], np.float64)
         _check(lib().rgbm_model_importance(self.h, C.c_int32(0 if kind == "split" else 1), _p(out, C.c_double)), "rgbm_model_importance")
         return out
+
+    def predict_form(self):
+        """The kernel the predictor runs for this model (rgbm_model_predict_form; needs no device): form "fixed" | "dynamic" | "walk",
+        MW mask words per table entry, TW padded mask words per tree (fixed form), tb trees per LDS stage, lds bytes per workgroup."""
+        a = np.zeros(5, np.int32)
+        _check(lib().rgbm_model_predict_form(self.h, _p(a, C.c_int32)), "rgbm_model_predict_form")
+        return dict(form=("fixed", "dynamic", "walk")[int(a[0])], MW=int(a[1]), TW=int(a[2]), tb=int(a[3]), lds=int(a[4]))
 
     def predict(self, X, device_id=0):
         """X: [F][n] int32 codes (column-major). Returns [n][ncol] float64 (regression: [n][1])."""
