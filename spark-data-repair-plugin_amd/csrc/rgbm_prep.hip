@@ -19,6 +19,9 @@
 // Result lists are ORDERED (by position in the column list, then ascending row), so the output is a deterministic
 // function of the input: the device stream compaction is two passes (coalesced flag pass that leaves 64-row ballots
 // behind, exclusive scan of the per-block counts, emit pass over the ballots) and never uses arrival order.
+// Every later section uses the ONE copy of each mechanism that this first section holds -- compaction: flags_to_ballots, scan_emit (into the
+// table's cell list: emit_to_table, compact<MODE>), rows_to_cells;  keys: key_digit / row_key, key_spec, table_capacity, ht_claim, wave_add;
+// bitsets: append_bitset, bitset_stage / bitset_test;  scratch: enum Scr, with the slots every entry point holds together.
 #include "rgbm_host.h"
 #include "rgbm_cost.h"
 
@@ -89,6 +92,25 @@ __global__ __launch_bounds__(PB) void k_flag(const int32_t* __restrict__ codes, 
 struct DetDesc { int32_t col, null_is_error, keep_lo, keep_hi; long long bit_off; int32_t n_words, pad; };   // bit_off: 64-bit words, -1 = none
 constexpr int DET_LDS_WORDS = 1024;
 
+// The bitset of a block's column, n_words 64-bit words at bits + bit_off (bit_off < 0: none, nw32 = 0): staged into LDS (in_lds, uniform over the
+// block) or read where it lies.  Every lane calls bitset_stage; a block that restages puts a __syncthreads() between the last tests and the call.
+struct BitsetView { const unsigned* g32; const unsigned* lds; unsigned nw32; bool in_lds; };
+__device__ __forceinline__ BitsetView bitset_stage(const unsigned long long* __restrict__ bits, long long bit_off, int32_t n_words) {
+    __shared__ unsigned lbits[DET_LDS_WORDS * 2];
+    const bool has_bits = bit_off >= 0 && n_words > 0;
+    const BitsetView v{reinterpret_cast<const unsigned*>(bits + (has_bits ? bit_off : 0)), lbits, has_bits ? 2u * (unsigned)n_words : 0u,
+                       has_bits && n_words <= DET_LDS_WORDS};
+    if (v.in_lds) {
+        for (unsigned i = threadIdx.x; i < v.nw32; i += PB) lbits[i] = v.g32[i];
+        __syncthreads();
+    }
+    return v;
+}
+__device__ __forceinline__ bool bitset_test(const BitsetView& v, unsigned x) {           // a code beyond the bitset has no bit
+    const unsigned w = x >> 5;
+    return w < v.nw32 && (((v.in_lds ? v.lds[w] : v.g32[w]) >> (x & 31u)) & 1u);
+}
+
 __global__ __launch_bounds__(PB) void k_detect(const int32_t* __restrict__ codes, const DetDesc* __restrict__ desc,
                                                const unsigned long long* __restrict__ bits, long long n, long long nblk,
                                                unsigned long long* __restrict__ ballots, unsigned* __restrict__ bcount) {
@@ -103,15 +125,7 @@ __global__ __launch_bounds__(PB) void k_detect(const int32_t* __restrict__ codes
         const long long r = base + (long long)s * PB + threadIdx.x;
         v[s] = r < n ? col[r] : 0;
     }
-    __shared__ unsigned lbits[DET_LDS_WORDS * 2];
-    const bool has_bits = d.bit_off >= 0 && d.n_words > 0;
-    const bool in_lds = has_bits && d.n_words <= DET_LDS_WORDS;          // uniform over the block
-    const unsigned* g32 = reinterpret_cast<const unsigned*>(bits + (has_bits ? d.bit_off : 0));
-    const unsigned nw32 = has_bits ? 2u * (unsigned)d.n_words : 0u;
-    if (in_lds) {
-        for (unsigned i = threadIdx.x; i < nw32; i += PB) lbits[i] = g32[i];
-        __syncthreads();
-    }
+    const BitsetView bv = bitset_stage(bits, d.bit_off, d.n_words);
     const bool has_range = d.keep_lo <= d.keep_hi;
     bool f[PSUB];
 #pragma unroll
@@ -120,11 +134,7 @@ __global__ __launch_bounds__(PB) void k_detect(const int32_t* __restrict__ codes
         const int32_t x = v[s];
         bool e;
         if (x < 0) e = d.null_is_error != 0;
-        else {
-            e = has_range && (x < d.keep_lo || x > d.keep_hi);
-            const unsigned w = (unsigned)x >> 5;
-            if (w < nw32) e = e || (((in_lds ? lbits[w] : g32[w]) >> (x & 31)) & 1u);     // a code beyond the bitset has no bit
-        }
+        else e = (has_range && (x < d.keep_lo || x > d.keep_hi)) || bitset_test(bv, (unsigned)x);
         f[s] = r < n && e;
     }
     flags_to_ballots(f, (long long)j * nblk + b, ballots, bcount);
@@ -215,27 +225,64 @@ constexpr unsigned long long HT_EMPTY = ~0ull;
 __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
     x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31; return x;
 }
+// digit of a code in the NULL-safe mixed-radix key: code + 1, NULL (-1) -> 0.  CLAMP: a code at or above the column's dictionary (digit >=
+// radix) or below -1 counts as NULL, so distinct keys never collide.  Neither rgbm_table_create nor rgbm_table_write_cells refuses such
+// codes, and on them the unclamped digit gives other (colliding) keys: rgbm_table_detect_constraint, which has always used it, keeps it
+// (CLAMP = false), so that its result stays what it was on every table; the two forms are the same wherever codes lie in [-1, n_codes).
+template <bool CLAMP>
+__device__ __forceinline__ unsigned long long key_digit(int32_t v, unsigned long long radix) {
+    if (!CLAMP) return (unsigned long long)(v + 1);
+    return (v < 0 || (unsigned long long)v + 1ull >= radix) ? 0ull : (unsigned long long)v + 1ull;
+}
+template <bool CLAMP>
 __device__ __forceinline__ unsigned long long row_key(const int32_t* __restrict__ codes, long long n, const KeySpec& ks, long long i) {
     unsigned long long k = 0;
-    for (int c = 0; c < ks.ncols; ++c) k = k * ks.radix[c] + (unsigned long long)(codes[(long long)ks.col[c] * n + i] + 1);   // NULL (-1) -> digit 0
+    for (int c = 0; c < ks.ncols; ++c) k = k * ks.radix[c] + key_digit<CLAMP>(codes[(long long)ks.col[c] * n + i], ks.radix[c]);
     return k;
 }
 
-__global__ __launch_bounds__(256) void k_ht_insert(const int32_t* __restrict__ codes, long long n, KeySpec ks, int iq_col,
-                                                   unsigned long long* __restrict__ keys, unsigned* __restrict__ state, unsigned long long cap_mask) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long key = row_key(codes, n, ks, i);
+// The slot of `key` in an open-addressing table of cap_mask + 1 >= 2 x (number of keys) slots, claimed if nobody has.  A slot only ever
+// goes EMPTY -> key, so a plain read that already shows the key makes the atomic unnecessary: low-cardinality keys (few groups,
+// millions of rows each) would otherwise serialise on a handful of addresses.
+__device__ __forceinline__ unsigned long long ht_claim(unsigned long long* __restrict__ keys, unsigned long long cap_mask, unsigned long long key) {
     unsigned long long slot = mix64(key) & cap_mask;
-    // A slot only ever goes EMPTY -> key, and its state only grows (0 -> first value -> | "another value"),
-    // so a plain read that already shows the final answer makes the atomic unnecessary: low-cardinality keys (few
-    // groups, millions of rows each) would otherwise serialise on a handful of addresses.
     for (;;) {
         unsigned long long prev = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read at L2, never a stale L1 line
         if (prev == key) break;
         if (prev == HT_EMPTY) { prev = atomicCAS(&keys[slot], HT_EMPTY, key); if (prev == HT_EMPTY || prev == key) break; }
         slot = (slot + 1) & cap_mask;
     }
+    return slot;
+}
+
+// count[slot] += 1 for every `active` lane, the lanes of a wave that hold the same slot adding once (one group may span the table and
+// would otherwise serialise on one address); after ROUNDS leaders the remaining lanes add on their own.  Returns the lane's arrival
+// rank in its slot.  Every lane of the wave calls it.
+template <int ROUNDS>
+__device__ __forceinline__ unsigned wave_add(unsigned* __restrict__ count, unsigned slot, bool active) {
+    const int lane = lane_id();
+    unsigned rank = 0;
+    unsigned long long pend = __ballot(active);
+    for (int round = 0; round < ROUNDS && pend; ++round) {
+        const int leader = __ffsll((long long)pend) - 1;
+        const unsigned s = (unsigned)__shfl((int)slot, leader);
+        const unsigned long long same = __ballot(active && slot == s);      // (a subset of pend: a slot leaves pend with all its lanes)
+        unsigned base = 0;
+        if (lane == leader) base = atomicAdd(&count[s], (unsigned)__popcll(same));
+        base = (unsigned)__shfl((int)base, leader);
+        if ((same >> lane) & 1ull) rank = base + (unsigned)__popcll(same & ((1ull << lane) - 1ull));
+        pend &= ~same;
+    }
+    if ((pend >> lane) & 1ull) rank = atomicAdd(&count[slot], 1u);
+    return rank;
+}
+
+__global__ __launch_bounds__(256) void k_ht_insert(const int32_t* __restrict__ codes, long long n, KeySpec ks, int iq_col,
+                                                   unsigned long long* __restrict__ keys, unsigned* __restrict__ state, unsigned long long cap_mask) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long slot = ht_claim(keys, cap_mask, row_key<false>(codes, n, ks, i));
+    // the state only grows (0 -> first value -> | "another value"): a read that already shows the final answer needs no atomic either
     const unsigned v = (unsigned)(codes[(long long)iq_col * n + i] + 1) + 1u;            // >= 1; NULL is a value of its own (<=>)
     unsigned old = __hip_atomic_load(&state[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((old >> 31) || old == v) return;
@@ -248,7 +295,7 @@ __global__ __launch_bounds__(256) void k_ht_lookup(const int32_t* __restrict__ c
                                                    unsigned long long cap_mask, uint8_t* __restrict__ mask) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const unsigned long long key = row_key(codes, n, ks, i);
+    const unsigned long long key = row_key<false>(codes, n, ks, i);
     unsigned long long slot = mix64(key) & cap_mask;
     while (keys[slot] != key) slot = (slot + 1) & cap_mask;
     const unsigned st = state[slot];
@@ -375,50 +422,164 @@ hipStream_t table_stream(const rgbm_table& t) {
     if (!t.stream) HIPCHK(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
     return t.stream;
 }
-// scratch slot `slot` of the table, at least `count` elements of T (grown, never shrunk)
+// The table's twelve scratch buffers by what they hold.  A buffer's content lives from its scr / scr_upload call to the entry point's last
+// synchronise (prep_mu is held all that time); inside one entry point no two uses may share a slot.  Slots held together, per entry:
+//   detect_nulls, repair_pmf[_weighted]   COLS | BALLOTS BCOUNT BOFF
+//   detect_cells                          COLS TABLE_A (descriptors) TABLE_B (bitsets) | BALLOTS BCOUNT BOFF
+//   detect_constraint                     TABLE_A (keys) TABLE_B (state) ROW_MASK | BALLOTS BCOUNT BOFF | COLS (the cell columns, rows_to_cells)
+//   detect_dc                             ROW_MASK | BALLOTS BCOUNT BOFF | COLS          (its hash table and operands are DevBufs)
+//   detect_row_bits                       TABLE_A (descriptors) TABLE_B (bitsets) BALLOTS BCOUNT BOFF | COLS
+//   rows_of_cells                         ROW_MASK IN_ROWS | BALLOTS BCOUNT BOFF
+//   null_cells                            COLS (is-target bytes) IN_ROWS IN_COLS
+//   write_cells, read_cells               IN_ROWS IN_COLS VALS;     gather_rows  IN_ROWS;     count_codes  VALS
+//   pair_counts                           TABLE_A (groups) TABLE_B (pairs) COLS (group columns)
+//   cell_domains                          TABLE_A (attributes) COLS (single_ok) IN_ROWS ROW_MASK (weak) IN_COLS (top) VALS (top_prob)
+//   fd_map                                TABLE_A (lo) TABLE_B (hi) VALS (map);     rule_fill  IN_COLS (lut) VALS (labels)
+// (distinct_rows works on a const table whose cell list and scratch must survive: DevBufs of its own throughout.)
+enum Scr {
+    SCR_BALLOTS = 0,      // compaction: the 64-row ballots of every (block, column)
+    SCR_BCOUNT = 1,       // compaction: flags per (block, column)
+    SCR_BOFF = 2,         // compaction: their exclusive scan, the total behind it
+    SCR_TABLE_A = 3,      // the entry's first table: column descriptors / hash keys / pair-count groups / domain attributes / fd lo
+    SCR_TABLE_B = 4,      // its second: bitset words / hash state / pair-count pairs / fd hi
+    SCR_ROW_MASK = 5,     // one byte per row (the flag of compact<1>) or per cell (weak labels)
+    SCR_COLS = 6,         // a short list per call: columns, cell columns, is-target bytes, group columns, single_ok
+    SCR_IN_ROWS = 7,      // the caller's row positions
+    SCR_IN_COLS = 8,      // int32 per cell or code: the caller's columns, a LUT, top codes
+    SCR_VALS = 9,         // values per cell or code, in or out: codes, counts, labels, probabilities, the fd map
+    SCR_FREE_10 = 10, SCR_FREE_11 = 11      // nobody's yet
+};
+
+// scratch buffer `slot` of the table, at least `count` elements of T (grown, never shrunk)
 template <typename T>
-T* scr(const rgbm_table& t, int slot, size_t count) {
+T* scr(const rgbm_table& t, Scr slot, size_t count) {
     const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
     if (t.scratch[slot].n < bytes) t.scratch[slot].alloc(bytes + bytes / 4);
     return reinterpret_cast<T*>(t.scratch[slot].p);
 }
 template <typename T>
-T* scr_upload(const rgbm_table& t, int slot, const T* host, size_t count, hipStream_t s) {
+T* scr_upload(const rgbm_table& t, Scr slot, const T* host, size_t count, hipStream_t s) {
     T* d = scr<T>(t, slot, count);
     if (count) HIPCHK(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, s));
     return d;
 }
 
-// ordered compaction of the flagged (row, column) cells into t.cell_rows / t.cell_cols; returns the cell count
-template <int MODE>
-long long compact(rgbm_table& t, const uint8_t* d_mask, const int32_t* d_cols, int ncols, bool want_cols, hipStream_t s,
-                  const DetDesc* d_desc = nullptr, const unsigned long long* d_bits = nullptr) {
-    const long long n = t.n, nblk = (n + PROWS - 1) / PROWS, m = nblk * ncols;
-    unsigned long long* ballots = scr<unsigned long long>(t, 0, (size_t)m * PBAL);
-    unsigned* bcount = scr<unsigned>(t, 1, (size_t)m);
-    long long* off = scr<long long>(t, 2, (size_t)m + 1);
-    if constexpr (MODE == 2)
-        hipLaunchKernelGGL(k_detect, dim3((unsigned)nblk, (unsigned)ncols), dim3(PB), 0, s, t.codes.p, d_desc, d_bits, n, nblk, ballots, bcount);
-    else
-        hipLaunchKernelGGL(k_flag<MODE>, dim3((unsigned)nblk, (unsigned)ncols), dim3(PB), 0, s, t.codes.p, d_mask, d_cols, n, nblk, ballots, bcount);
+// The ordered compaction behind every flag kernel.  The ballots and counts of nblk x ncols blocks are written: scan the counts, read the total (one
+// synchronise), let dest(total, &rows, &cols) size the output (cols stays null for a row list), emit (left in flight).  Returns the total.
+template <typename Dest>
+long long scan_emit(const unsigned long long* ballots, const unsigned* bcount, long long* off, long long nblk, int ncols, const int32_t* d_cols,
+                    hipStream_t s, Dest dest) {
+    const long long m = nblk * ncols;
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, bcount, m, off, off + m);
+    HIPCHK(hipGetLastError());
     long long total = 0;
     HIPCHK(hipMemcpyAsync(&total, off + m, sizeof(long long), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (t.cell_rows.n < (size_t)std::max<long long>(total, 1)) t.cell_rows.alloc((size_t)std::max<long long>(total, 1) * 5 / 4);
-    if (want_cols) { if (t.cell_cols.n < (size_t)std::max<long long>(total, 1)) t.cell_cols.alloc((size_t)std::max<long long>(total, 1) * 5 / 4); }
-    else t.cell_cols.release();
-    if (total > 0)
-        hipLaunchKernelGGL(k_emit, dim3((unsigned)nblk, (unsigned)ncols), dim3(PB), 0, s, ballots, off, want_cols ? d_cols : nullptr, nblk,
-                           t.cell_rows.p, want_cols ? t.cell_cols.p : nullptr);
+    long long* rows = nullptr; int32_t* cols = nullptr;
+    dest(total, &rows, &cols);
+    if (total > 0) hipLaunchKernelGGL(k_emit, dim3((unsigned)nblk, (unsigned)ncols), dim3(PB), 0, s, ballots, off, cols ? d_cols : nullptr, nblk, rows, cols);
     HIPCHK(hipGetLastError());
+    return total;
+}
+
+// the table's own compaction buffers (a flag kernel fills ballots and bcount) and scan_emit into its cell list: (row, column) cells when
+// d_cols is given, a row list otherwise; returns the cell count
+struct Ballots { unsigned long long* ballots; unsigned* bcount; long long* off; long long nblk; int ncols; };
+Ballots table_ballots(const rgbm_table& t, int ncols) {
+    const long long nblk = (t.n + PROWS - 1) / PROWS, m = nblk * ncols;
+    return Ballots{scr<unsigned long long>(t, SCR_BALLOTS, (size_t)m * PBAL), scr<unsigned>(t, SCR_BCOUNT, (size_t)m), scr<long long>(t, SCR_BOFF, (size_t)m + 1),
+                   nblk, ncols};
+}
+long long emit_to_table(rgbm_table& t, const Ballots& b, const int32_t* d_cols, hipStream_t s) {
+    const long long total = scan_emit(b.ballots, b.bcount, b.off, b.nblk, b.ncols, d_cols, s, [&](long long tot, long long** rows, int32_t** cols) {
+        const size_t need = (size_t)std::max<long long>(tot, 1);
+        if (t.cell_rows.n < need) t.cell_rows.alloc(need * 5 / 4);
+        if (d_cols) { if (t.cell_cols.n < need) t.cell_cols.alloc(need * 5 / 4); }
+        else t.cell_cols.release();
+        *rows = t.cell_rows.p; *cols = t.cell_cols.p;
+    });
     HIPCHK(hipStreamSynchronize(s));
     t.n_cells = total;
     return total;
 }
+// MODE 0: the NULL cells of columns d_cols (want_cols: with their columns);  MODE 1: the rows of d_mask;  MODE 2: k_detect's cells
+template <int MODE>
+long long compact(rgbm_table& t, const uint8_t* d_mask, const int32_t* d_cols, int ncols, bool want_cols, hipStream_t s,
+                  const DetDesc* d_desc = nullptr, const unsigned long long* d_bits = nullptr) {
+    const Ballots b = table_ballots(t, ncols);
+    if constexpr (MODE == 2)
+        hipLaunchKernelGGL(k_detect, dim3((unsigned)b.nblk, (unsigned)ncols), dim3(PB), 0, s, t.codes.p, d_desc, d_bits, t.n, b.nblk, b.ballots, b.bcount);
+    else
+        hipLaunchKernelGGL(k_flag<MODE>, dim3((unsigned)b.nblk, (unsigned)ncols), dim3(PB), 0, s, t.codes.p, d_mask, d_cols, t.n, b.nblk, b.ballots, b.bcount);
+    return emit_to_table(t, b, want_cols ? d_cols : nullptr, s);
+}
 
+// the m ascending violating rows in t.cell_rows -> rows x cell_cols (column-major): a constraint reports every given attribute of a row
+void rows_to_cells(rgbm_table& t, long long m, const int32_t* cell_cols, int n_cell_cols, hipStream_t s, int64_t* n_rows_out, int64_t* n_cells_out) {
+    if (n_rows_out) *n_rows_out = m;
+    if (n_cell_cols > 0) {
+        const size_t tot = (size_t)std::max<long long>(m * n_cell_cols, 1);
+        DevBuf<long long> rows_r(tot); DevBuf<int32_t> cols_r(tot);
+        const int32_t* d_cc = scr_upload<int32_t>(t, SCR_COLS, cell_cols, (size_t)n_cell_cols, s);
+        if (m > 0) hipLaunchKernelGGL(k_replicate, dim3(nblocks(m, 256)), dim3(256), 0, s, t.cell_rows.p, m, d_cc, n_cell_cols, rows_r.p, cols_r.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        t.cell_rows.swap(rows_r);
+        t.cell_cols.swap(cols_r);
+        t.n_cells = m * n_cell_cols;
+    }
+    *n_cells_out = t.n_cells;
+}
+
+// an entry point with nothing to look at: the table's cell list becomes empty (row_list: as a list without columns)
+int no_cells(rgbm_table& t, bool row_list, int64_t* n_rows_out, int64_t* n_cells_out) {
+    t.n_cells = 0; *n_cells_out = 0;
+    if (row_list) t.cell_cols.release();
+    if (n_rows_out) *n_rows_out = 0;
+    return RGBM_OK;
+}
+
+// the key of the columns `cols` (at most 12): radix = codes + 1 for NULL; a span of 2^63 combinations or more is refused under `entry`'s name
+KeySpec key_spec(const rgbm_table& t, const int32_t* cols, int ncols, const char* entry, unsigned __int128* span_out) {
+    KeySpec ks; memset(&ks, 0, sizeof(ks)); ks.ncols = ncols;
+    unsigned __int128 span = 1;
+    for (int i = 0; i < ncols; ++i) {
+        ks.col[i] = cols[i]; ks.radix[i] = (unsigned long long)std::max<int32_t>(t.n_codes[cols[i]], 0) + 1ull;
+        span *= ks.radix[i];
+        if (span >= ((unsigned __int128)1 << 63)) throw std::invalid_argument(std::string(entry) + ": the EQ attributes span more than 2^63 value combinations");
+    }
+    *span_out = span;
+    return ks;
+}
+// slots of an open-addressing table for n rows: a power of two, at least 1024 and twice the keys there can be (n, or `span` if smaller)
+unsigned long long table_capacity(long long n, unsigned __int128 span = ~(unsigned __int128)0) {
+    unsigned long long want = (unsigned long long)n * 2ull;
+    if (span < (unsigned __int128)want) want = (unsigned long long)span * 2ull;
+    unsigned long long cap = 1024; while (cap < want) cap <<= 1;
+    return cap;
+}
+// appends the first nbits bits of `src` to `words` as whole 64-bit words, the bits beyond them cleared; returns the offset, *n_words the count
+long long append_bitset(std::vector<unsigned long long>& words, const uint64_t* src, long long nbits, int32_t* n_words) {
+    const long long off = (long long)words.size(), nw = (nbits + 63) / 64;
+    words.insert(words.end(), src, src + nw);
+    if (nbits % 64) words.back() &= (1ull << (nbits % 64)) - 1ull;
+    *n_words = (int32_t)nw;
+    return off;
+}
 void check_cols(const rgbm_table& t, const int32_t* cols, int n, const char* what) {
     for (int i = 0; i < n; ++i) if (cols[i] < 0 || cols[i] >= t.c) throw std::invalid_argument(std::string(what) + ": column index out of range");
+}
+// the RGBM_ERR_ARG refusals of the detectors' column lists (check_cols throws, which gives RGBM_ERR_PARAM): every column inside the table;
+// `once`: none listed twice; `bitsets`: each with one.  RGBM_OK or the refusal.
+int refuse_cols(const rgbm_table& t, const int32_t* cols, int n, bool once, const uint64_t* const* bitsets, const char* entry) {
+    std::vector<uint8_t> seen(once ? (size_t)t.c : 0, 0);
+    for (int i = 0; i < n; ++i) {
+        if (cols[i] < 0 || cols[i] >= t.c) return fail(RGBM_ERR_ARG, std::string(entry) + ": column index out of range");
+        if (once && seen[cols[i]]) return fail(RGBM_ERR_ARG, std::string(entry) + ": a column is listed twice");
+        if (bitsets && !bitsets[i]) return fail(RGBM_ERR_ARG, std::string(entry) + ": a column without a bitset");
+        if (once) seen[cols[i]] = 1;
+    }
+    return RGBM_OK;
 }
 
 // string pool offsets: start at 0, never decrease (every read of the distance kernels stays inside [0, off[n]))
@@ -480,9 +641,9 @@ RGBM_EXPORT int rgbm_table_detect_nulls(rgbm_table* t, const int32_t* cols, int3
     return guarded([&]() {
         use_device(t->device);
         check_cols(*t, cols, n_cols, "rgbm_table_detect_nulls");
-        if (n_cols == 0) { t->n_cells = 0; *n_cells_out = 0; return RGBM_OK; }
+        if (n_cols == 0) return no_cells(*t, false, nullptr, n_cells_out);
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        const int32_t* d_cols = scr_upload<int32_t>(*t, 6, cols, (size_t)n_cols, s);
+        const int32_t* d_cols = scr_upload<int32_t>(*t, SCR_COLS, cols, (size_t)n_cols, s);
         *n_cells_out = compact<0>(*t, nullptr, d_cols, n_cols, true, s);
         return RGBM_OK;
     });
@@ -492,17 +653,10 @@ RGBM_EXPORT int rgbm_table_detect_cells(rgbm_table* t, const int32_t* cols, int3
                                         const int32_t* keep_lo, const int32_t* keep_hi, const uint64_t* const* flag_bits, int64_t* n_cells_out) {
     if (!t || !n_cells_out || n_cols < 0 || (n_cols > 0 && (!cols || !null_is_error || !keep_lo || !keep_hi)))
         return fail(RGBM_ERR_ARG, "rgbm_table_detect_cells: bad argument");
-    {
-        std::vector<uint8_t> seen((size_t)t->c, 0);
-        for (int i = 0; i < n_cols; ++i) {
-            if (cols[i] < 0 || cols[i] >= t->c) return fail(RGBM_ERR_ARG, "rgbm_table_detect_cells: column index out of range");
-            if (seen[cols[i]]) return fail(RGBM_ERR_ARG, "rgbm_table_detect_cells: a column is listed twice");
-            seen[cols[i]] = 1;
-        }
-    }
+    if (const int rc = refuse_cols(*t, cols, n_cols, true, nullptr, "rgbm_table_detect_cells")) return rc;
     return guarded([&]() {
         use_device(t->device);
-        if (n_cols == 0 || t->n == 0) { t->n_cells = 0; *n_cells_out = 0; return RGBM_OK; }
+        if (n_cols == 0 || t->n == 0) return no_cells(*t, false, nullptr, n_cells_out);
         // one descriptor per column; the bitsets one after the other, bits at and beyond n_codes cleared
         std::vector<DetDesc> desc((size_t)n_cols);
         std::vector<unsigned long long> bits;
@@ -512,15 +666,12 @@ RGBM_EXPORT int rgbm_table_detect_cells(rgbm_table* t, const int32_t* cols, int3
             d.bit_off = -1; d.n_words = 0; d.pad = 0;
             const uint64_t* fb = flag_bits ? flag_bits[i] : nullptr;
             if (!fb) continue;
-            const long long nc = std::max<long long>(t->n_codes[cols[i]], 0), nw = (nc + 63) / 64;
-            d.bit_off = (long long)bits.size(); d.n_words = (int32_t)nw;
-            bits.insert(bits.end(), fb, fb + nw);
-            if (nc % 64) bits.back() &= (1ull << (nc % 64)) - 1ull;
+            d.bit_off = append_bitset(bits, fb, std::max<long long>(t->n_codes[cols[i]], 0), &d.n_words);
         }
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        const int32_t* d_cols = scr_upload<int32_t>(*t, 6, cols, (size_t)n_cols, s);
-        const DetDesc* d_desc = scr_upload<DetDesc>(*t, 3, desc.data(), desc.size(), s);
-        const unsigned long long* d_bits = scr_upload<unsigned long long>(*t, 4, bits.data(), bits.size(), s);
+        const int32_t* d_cols = scr_upload<int32_t>(*t, SCR_COLS, cols, (size_t)n_cols, s);
+        const DetDesc* d_desc = scr_upload<DetDesc>(*t, SCR_TABLE_A, desc.data(), desc.size(), s);
+        const unsigned long long* d_bits = scr_upload<unsigned long long>(*t, SCR_TABLE_B, bits.data(), bits.size(), s);
         *n_cells_out = compact<2>(*t, nullptr, d_cols, n_cols, true, s, d_desc, d_bits);
         return RGBM_OK;
     });
@@ -535,41 +686,21 @@ RGBM_EXPORT int rgbm_table_detect_constraint(rgbm_table* t, const int32_t* eq_co
         check_cols(*t, eq_cols, n_eq, "rgbm_table_detect_constraint");
         check_cols(*t, cell_cols, n_cell_cols, "rgbm_table_detect_constraint");
         if (iq_col < 0 || iq_col >= t->c) throw std::invalid_argument("rgbm_table_detect_constraint: IQ column out of range");
-        KeySpec ks; memset(&ks, 0, sizeof(ks)); ks.ncols = n_eq;
         unsigned __int128 span = 1;
-        for (int i = 0; i < n_eq; ++i) {
-            ks.col[i] = eq_cols[i]; ks.radix[i] = (unsigned long long)t->n_codes[eq_cols[i]] + 1ull;
-            span *= ks.radix[i];
-            if (span >= ((unsigned __int128)1 << 63)) throw std::invalid_argument("rgbm_table_detect_constraint: the EQ attributes span more than 2^63 value combinations");
-        }
+        const KeySpec ks = key_spec(*t, eq_cols, n_eq, "rgbm_table_detect_constraint", &span);
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
         const long long n = t->n;
-        // the table never needs more slots than twice the number of possible keys
-        unsigned long long want = (unsigned long long)n * 2ull;
-        if (span < (unsigned __int128)want) want = (unsigned long long)span * 2ull;
-        unsigned long long cap = 1024; while (cap < want) cap <<= 1;
-        unsigned long long* keys = scr<unsigned long long>(*t, 3, (size_t)cap);
-        unsigned* state = scr<unsigned>(*t, 4, (size_t)cap);
-        uint8_t* mask = scr<uint8_t>(*t, 5, (size_t)n);
+        const unsigned long long cap = table_capacity(n, span);
+        unsigned long long* keys = scr<unsigned long long>(*t, SCR_TABLE_A, (size_t)cap);
+        unsigned* state = scr<unsigned>(*t, SCR_TABLE_B, (size_t)cap);
+        uint8_t* mask = scr<uint8_t>(*t, SCR_ROW_MASK, (size_t)n);
         HIPCHK(hipMemsetAsync(keys, 0xFF, (size_t)cap * 8, s));
         HIPCHK(hipMemsetAsync(state, 0, (size_t)cap * 4, s));
         const unsigned nb = nblocks(n, 256);
         hipLaunchKernelGGL(k_ht_insert, dim3(nb), dim3(256), 0, s, t->codes.p, n, ks, iq_col, keys, state, cap - 1);
         hipLaunchKernelGGL(k_ht_lookup, dim3(nb), dim3(256), 0, s, t->codes.p, n, ks, keys, state, cap - 1, mask);
         const long long m = compact<1>(*t, mask, nullptr, 1, false, s);     // ascending violating rows
-        if (n_rows_out) *n_rows_out = m;
-        if (n_cell_cols > 0) {
-            const size_t tot = (size_t)std::max<long long>(m * n_cell_cols, 1);
-            DevBuf<long long> rows_r(tot); DevBuf<int32_t> cols_r(tot);
-            const int32_t* d_cc = scr_upload<int32_t>(*t, 6, cell_cols, (size_t)n_cell_cols, s);
-            if (m > 0) hipLaunchKernelGGL(k_replicate, dim3(nblocks(m, 256)), dim3(256), 0, s, t->cell_rows.p, m, d_cc, n_cell_cols, rows_r.p, cols_r.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(s));
-            t->cell_rows.swap(rows_r);
-            t->cell_cols.swap(cols_r);
-            t->n_cells = m * n_cell_cols;
-        }
-        *n_cells_out = t->n_cells;
+        rows_to_cells(*t, m, cell_cols, n_cell_cols, s, n_rows_out, n_cells_out);
         return RGBM_OK;
     });
 }
@@ -579,10 +710,10 @@ RGBM_EXPORT int rgbm_table_rows_of_cells(rgbm_table* t, const int64_t* rows, int
     return guarded([&]() {
         use_device(t->device);
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        uint8_t* mask = scr<uint8_t>(*t, 5, (size_t)t->n);
+        uint8_t* mask = scr<uint8_t>(*t, SCR_ROW_MASK, (size_t)t->n);
         HIPCHK(hipMemsetAsync(mask, 0, (size_t)t->n, s));
         static_assert(sizeof(long long) == sizeof(int64_t), "row positions are 64-bit");
-        const long long* d_rows = scr_upload<long long>(*t, 7, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
+        const long long* d_rows = scr_upload<long long>(*t, SCR_IN_ROWS, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
         if (n_cells > 0) hipLaunchKernelGGL(k_mark_rows, dim3(nblocks(n_cells, 256)), dim3(256), 0, s, mask, (long long)t->n, d_rows, (long long)n_cells);
         *n_rows_out = compact<1>(*t, mask, nullptr, 1, false, s);
         return RGBM_OK;
@@ -616,9 +747,9 @@ RGBM_EXPORT int rgbm_table_null_cells(rgbm_table* t, const int64_t* rows, const 
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
         std::vector<uint8_t> is_t((size_t)t->c, 0);
         for (int i = 0; i < n_targets; ++i) is_t[target_cols[i]] = 1;
-        const uint8_t* d_t = scr_upload<uint8_t>(*t, 6, is_t.data(), is_t.size(), s);
-        const long long* d_rows = scr_upload<long long>(*t, 7, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
-        const int32_t* d_cols = scr_upload<int32_t>(*t, 8, cols, (size_t)n_cells, s);
+        const uint8_t* d_t = scr_upload<uint8_t>(*t, SCR_COLS, is_t.data(), is_t.size(), s);
+        const long long* d_rows = scr_upload<long long>(*t, SCR_IN_ROWS, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
+        const int32_t* d_cols = scr_upload<int32_t>(*t, SCR_IN_COLS, cols, (size_t)n_cells, s);
         hipLaunchKernelGGL(k_null_cells, dim3(nblocks(n_cells, 256)), dim3(256), 0, s, t->codes.p, (long long)t->n, (int)t->c, d_rows, d_cols,
                            (long long)n_cells, d_t);
         HIPCHK(hipGetLastError());
@@ -635,9 +766,9 @@ RGBM_EXPORT int rgbm_table_write_cells(rgbm_table* t, const int64_t* rows, const
         for (int64_t i = 0; i < n_cells; ++i)
             if (cols[i] >= 0 && cols[i] < t->c && codes[i] >= t->n_codes[cols[i]]) throw std::invalid_argument("rgbm_table_write_cells: code outside the column's dictionary");
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        const long long* d_rows = scr_upload<long long>(*t, 7, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
-        const int32_t* d_cols = scr_upload<int32_t>(*t, 8, cols, (size_t)n_cells, s);
-        const int32_t* d_vals = scr_upload<int32_t>(*t, 9, codes, (size_t)n_cells, s);
+        const long long* d_rows = scr_upload<long long>(*t, SCR_IN_ROWS, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
+        const int32_t* d_cols = scr_upload<int32_t>(*t, SCR_IN_COLS, cols, (size_t)n_cells, s);
+        const int32_t* d_vals = scr_upload<int32_t>(*t, SCR_VALS, codes, (size_t)n_cells, s);
         hipLaunchKernelGGL(k_write_cells, dim3(nblocks(n_cells, 256)), dim3(256), 0, s, t->codes.p, (long long)t->n, (int)t->c, d_rows, d_cols, d_vals, (long long)n_cells);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
@@ -651,9 +782,9 @@ RGBM_EXPORT int rgbm_table_read_cells(const rgbm_table* t, const int64_t* rows, 
         use_device(t->device);
         if (n_cells == 0) return RGBM_OK;
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        const long long* d_rows = scr_upload<long long>(*t, 7, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
-        const int32_t* d_cols = scr_upload<int32_t>(*t, 8, cols, (size_t)n_cells, s);
-        int32_t* d_out = scr<int32_t>(*t, 9, (size_t)n_cells);
+        const long long* d_rows = scr_upload<long long>(*t, SCR_IN_ROWS, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
+        const int32_t* d_cols = scr_upload<int32_t>(*t, SCR_IN_COLS, cols, (size_t)n_cells, s);
+        int32_t* d_out = scr<int32_t>(*t, SCR_VALS, (size_t)n_cells);
         hipLaunchKernelGGL(k_read_cells, dim3(nblocks(n_cells, 256)), dim3(256), 0, s, t->codes.p, (long long)t->n, (int)t->c, d_rows, d_cols,
                            (long long)n_cells, d_out);
         HIPCHK(hipGetLastError());
@@ -672,7 +803,7 @@ RGBM_EXPORT int rgbm_table_gather_rows(const rgbm_table* t, const int64_t* rows,
         std::unique_ptr<rgbm_table> o(new rgbm_table());
         o->device = t->device; o->n = n_rows; o->c = t->c; o->n_codes = t->n_codes; o->col_values = t->col_values; o->col_kind = t->col_kind;
         o->codes.alloc((size_t)n_rows * t->c);
-        const long long* d_rows = scr_upload<long long>(*t, 7, reinterpret_cast<const long long*>(rows), (size_t)n_rows, s);
+        const long long* d_rows = scr_upload<long long>(*t, SCR_IN_ROWS, reinterpret_cast<const long long*>(rows), (size_t)n_rows, s);
         hipLaunchKernelGGL(k_gather_rows, dim3(nblocks(n_rows, 256), (unsigned)t->c), dim3(256), 0, s, t->codes.p, (long long)t->n, o->codes.p,
                            (long long)n_rows, d_rows);
         HIPCHK(hipGetLastError());
@@ -688,7 +819,7 @@ RGBM_EXPORT int rgbm_table_count_codes(const rgbm_table* t, int32_t col, int64_t
         use_device(t->device);
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
         const int nc = t->n_codes[col];
-        unsigned long long* d_cnt = scr<unsigned long long>(*t, 9, (size_t)nc + 1);
+        unsigned long long* d_cnt = scr<unsigned long long>(*t, SCR_VALS, (size_t)nc + 1);
         HIPCHK(hipMemsetAsync(d_cnt, 0, ((size_t)nc + 1) * 8, s));
         const unsigned nb = std::min<unsigned>(nblocks(t->n, 256 * 16), 256u * 8u);
         hipLaunchKernelGGL(k_count_codes, dim3(std::max(nb, 1u)), dim3(256), 0, s, t->codes.p + (size_t)col * t->n, (long long)t->n, nc, d_cnt);
@@ -748,7 +879,7 @@ RGBM_EXPORT int rgbm_table_repair_pmf(rgbm_table* t, const rgbm_model* m, int32_
         if (obj == 2) throw std::invalid_argument("rgbm_table_repair_pmf: a regressor has no class distribution (model.py:1214-1221 handles continuous attributes)");
         if (F != f) throw std::invalid_argument("rgbm_table_repair_pmf: the model was trained on a different number of features");
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); struct { hipStream_t s; } sg{table_stream(*t)};
-        const int32_t* d_tc = scr_upload<int32_t>(*t, 6, &target_col, 1, sg.s);
+        const int32_t* d_tc = scr_upload<int32_t>(*t, SCR_COLS, &target_col, 1, sg.s);
         const long long cells = compact<0>(*t, nullptr, d_tc, 1, false, sg.s);      // ascending rows whose target cell is NULL
         *n_cells_out = cells;
         if (cells == 0) return RGBM_OK;
@@ -792,7 +923,7 @@ RGBM_EXPORT int rgbm_table_repair_pmf_weighted(rgbm_table* t, const rgbm_model* 
         if (cost && (unsigned long long)(n_cost_rows + 1) * (unsigned long long)K > (1ull << 28))
             throw std::invalid_argument("rgbm_table_repair_pmf_weighted: the cost matrix holds more than 2^28 entries");
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); struct { hipStream_t s; } sg{table_stream(*t)};
-        const int32_t* d_tc = scr_upload<int32_t>(*t, 6, &target_col, 1, sg.s);
+        const int32_t* d_tc = scr_upload<int32_t>(*t, SCR_COLS, &target_col, 1, sg.s);
         const long long cells = compact<0>(*t, nullptr, d_tc, 1, false, sg.s);      // ascending rows whose target cell is NULL
         *n_cells_out = cells;
         if (cells == 0) return RGBM_OK;
@@ -1045,9 +1176,9 @@ RGBM_EXPORT int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, 
         t->pc_lut_off.alloc(loff.size()); t->pc_lut_off.upload(loff.data(), loff.size(), s);
         t->pc_luts.alloc(std::max<size_t>(flat.size(), 1)); t->pc_luts.upload(flat.data(), flat.size(), s);
         if (!groups.empty()) {
-            const PcGroup* d_groups = scr_upload<PcGroup>(*t, 3, groups.data(), groups.size(), s);
-            const PcPair* d_pairs = scr_upload<PcPair>(*t, 4, pairs.data(), pairs.size(), s);
-            const int32_t* d_gcols = scr_upload<int32_t>(*t, 6, gcols.data(), gcols.size(), s);
+            const PcGroup* d_groups = scr_upload<PcGroup>(*t, SCR_TABLE_A, groups.data(), groups.size(), s);
+            const PcPair* d_pairs = scr_upload<PcPair>(*t, SCR_TABLE_B, pairs.data(), pairs.size(), s);
+            const int32_t* d_gcols = scr_upload<int32_t>(*t, SCR_COLS, gcols.data(), gcols.size(), s);
             unsigned max_cells = 0;
             for (const PcGroup& g : groups) max_cells = std::max(max_cells, g.cells);
             const unsigned tile_off = (max_cells * 4u + 15u) & ~15u;
@@ -1110,12 +1241,12 @@ RGBM_EXPORT int rgbm_table_cell_domains(rgbm_table* t, int32_t target_col, const
             attrs[j] = a;
         }
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        const DomAttr* d_attrs = scr_upload<DomAttr>(*t, 3, attrs.data(), attrs.size(), s);
-        const uint8_t* d_ok = scr_upload<uint8_t>(*t, 6, single_ok, (size_t)d_a, s);
-        const long long* d_rows = scr_upload<long long>(*t, 7, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
-        uint8_t* d_weak = scr<uint8_t>(*t, 5, (size_t)n_cells);
-        int32_t* d_top = scr<int32_t>(*t, 8, (size_t)n_cells);
-        double* d_tp = scr<double>(*t, 9, (size_t)n_cells);
+        const DomAttr* d_attrs = scr_upload<DomAttr>(*t, SCR_TABLE_A, attrs.data(), attrs.size(), s);
+        const uint8_t* d_ok = scr_upload<uint8_t>(*t, SCR_COLS, single_ok, (size_t)d_a, s);
+        const long long* d_rows = scr_upload<long long>(*t, SCR_IN_ROWS, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
+        uint8_t* d_weak = scr<uint8_t>(*t, SCR_ROW_MASK, (size_t)n_cells);
+        int32_t* d_top = scr<int32_t>(*t, SCR_IN_COLS, (size_t)n_cells);
+        double* d_tp = scr<double>(*t, SCR_VALS, (size_t)n_cells);
         DevBuf<double> d_probs;
         if (probs_out) d_probs.alloc((size_t)n_cells * d_a);
         hipLaunchKernelGGL(k_cell_domains, dim3(nblocks(n_cells, 256)), dim3(256), 0, s, t->codes.p, (long long)t->n, (int)target_col, d_a, d_rows,
@@ -1253,9 +1384,9 @@ RGBM_EXPORT int rgbm_table_fd_map(const rgbm_table* t, int32_t x_col, int32_t y_
         const int nx = t->n_codes[x_col], ny = t->n_codes[y_col];
         if (nx <= 0) return RGBM_OK;
         const long long n = t->n;
-        int* d_lo = scr<int>(*t, 3, (size_t)nx);
-        int* d_hi = scr<int>(*t, 4, (size_t)nx);
-        int32_t* d_map = scr<int32_t>(*t, 9, (size_t)nx);
+        int* d_lo = scr<int>(*t, SCR_TABLE_A, (size_t)nx);
+        int* d_hi = scr<int>(*t, SCR_TABLE_B, (size_t)nx);
+        int32_t* d_map = scr<int32_t>(*t, SCR_VALS, (size_t)nx);
         hipLaunchKernelGGL(k_fd_init, dim3(nblocks(nx, 256)), dim3(256), 0, s, d_lo, d_hi, nx);
         if (n > 0) {
             // enough workgroups to fill the device a few times over, each on a whole number of load tiles
@@ -1290,8 +1421,8 @@ RGBM_EXPORT int rgbm_table_rule_fill(rgbm_table* t, int32_t y_col, int32_t x_col
         for (int i = 0; i < n_lut; ++i)
             if (lut[i] >= ny) throw std::invalid_argument("rgbm_table_rule_fill: code outside the target column's dictionary");
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        const int32_t* d_lut = scr_upload<int32_t>(*t, 8, lut, (size_t)n_lut, s);
-        int32_t* d_out = out_label ? scr<int32_t>(*t, 9, (size_t)n_rows) : nullptr;
+        const int32_t* d_lut = scr_upload<int32_t>(*t, SCR_IN_COLS, lut, (size_t)n_lut, s);
+        int32_t* d_out = out_label ? scr<int32_t>(*t, SCR_VALS, (size_t)n_rows) : nullptr;
         hipLaunchKernelGGL(k_rule_fill, dim3(nblocks(n_rows, 256)), dim3(256), 0, s, t->codes.p, (long long)t->n, (int)y_col, (int)(x_col < 0 ? -1 : x_col),
                            d_lut, (int)n_lut, (long long)row_begin, (long long)n_rows, d_out);
         HIPCHK(hipGetLastError());
@@ -1349,9 +1480,8 @@ RGBM_EXPORT int rgbm_nearest_values(int32_t device_id, const int32_t* a_cp, cons
 //                 is done, the group's SMALLEST row index (integer atomicMin: order-free); count[slot] takes the group's rows (integer
 //                 atomicAdd: order-free).  An occupied slot is compared word for word with the probing row's key.  Probe reads are
 //                 agent-scope atomic loads (L2, never a stale L1 line); the probe loop ends after `cap` slots at the latest and then
-//                 raises the error flag.  Lanes of a wave that hold the same slot add their popcount with ONE atomic (a table of a
-//                 few distinct rows with millions of copies each would otherwise serialise on a few addresses); the atomicMin is
-//                 skipped by every row that already sees a smaller index in the slot.
+//                 raises the error flag.  The count goes through wave_add (a table of a few distinct rows with millions of copies each);
+//                 the atomicMin is skipped by every row that already sees a smaller index in the slot.
 //   k_dr_mark     row i is its group's representative iff slot[row_slot[i]] == i  -> mask for the ordered compaction (k_flag<1>,
 //                 k_scan_counts, k_emit: ascending representatives = groups by first occurrence)
 //   k_dr_copies   copies per group; k_scan_counts over them gives every group's first output row
@@ -1373,10 +1503,7 @@ __global__ __launch_bounds__(256) void k_dr_keys(const int32_t* __restrict__ cod
     unsigned long long k = 0; int w = 0;
     for (int cc = 0; cc < c; ++cc) {
         if (word_of[cc] != w) { keys[(long long)w * n + i] = k; k = 0; w = word_of[cc]; }
-        const unsigned long long r = radix[cc];
-        const int32_t v = codes[(long long)cc * n + i];
-        const unsigned long long d = (v < 0 || (unsigned long long)v + 1ull >= r) ? 0ull : (unsigned long long)v + 1ull;
-        k = k * r + d;
+        k = k * radix[cc] + key_digit<true>(codes[(long long)cc * n + i], radix[cc]);
     }
     keys[(long long)w * n + i] = k;
 }
@@ -1386,7 +1513,6 @@ __global__ __launch_bounds__(256) void k_dr_insert(const unsigned long long* __r
                                                    unsigned* __restrict__ err) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = i < n;                     // no early return: every lane takes part in the ballots below
-    const int lane = lane_id();
     unsigned long long slot = 0; bool found = false;
     if (valid) {
         unsigned long long h = 0;
@@ -1406,17 +1532,7 @@ __global__ __launch_bounds__(256) void k_dr_insert(const unsigned long long* __r
         row_slot[i] = found ? (unsigned)slot : DR_NO_SLOT;
         if (found && __hip_atomic_load(&slots[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (int)i) atomicMin(&slots[slot], (int)i);
     }
-    // count: the lanes of this wave that hold the same slot add once
-    const unsigned s32 = (unsigned)slot;
-    unsigned long long pend = __ballot(found);
-    for (int round = 0; round < DR_WAVE_ROUNDS && pend; ++round) {
-        const int leader = __ffsll((long long)pend) - 1;
-        const unsigned s = (unsigned)__shfl((int)s32, leader);
-        const unsigned long long same = __ballot(found && s32 == s);
-        if (lane == leader) atomicAdd(&count[s], (unsigned)__popcll(same));
-        pend &= ~same;
-    }
-    if (found && ((pend >> lane) & 1ull)) atomicAdd(&count[s32], 1u);
+    wave_add<DR_WAVE_ROUNDS>(count, (unsigned)slot, found);       // (the arrival rank is of no use here)
 }
 
 __global__ __launch_bounds__(256) void k_dr_mark(const int* __restrict__ slots, const unsigned* __restrict__ row_slot, long long n,
@@ -1488,7 +1604,7 @@ RGBM_EXPORT int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, 
             room *= radix[j];
             word_of[j] = W - 1;
         }
-        unsigned long long cap = 1024; while (cap < 2ull * (unsigned long long)n) cap <<= 1;
+        const unsigned long long cap = table_capacity(n);
         // everything the call allocates, with the output table at its largest (M <= n): slots + counts (8 B a slot); per row the slot id, the key
         // words, the compaction's mask and ballots, representative, copies, group offset, source row, first output row, inverse; the output's
         // codes and multiplicities.  Above half of the device memory the call is refused; a table that passes and still does not fit (other tables
@@ -1520,14 +1636,11 @@ RGBM_EXPORT int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, 
         const long long nblk = (n + PROWS - 1) / PROWS;
         DevBuf<unsigned long long> ballots((size_t)nblk * PBAL); DevBuf<unsigned> bcount((size_t)nblk); DevBuf<long long> boff((size_t)nblk + 1);
         hipLaunchKernelGGL(k_flag<1>, dim3((unsigned)nblk, 1u), dim3(PB), 0, s, (const int32_t*)nullptr, mask.p, (const int32_t*)nullptr, n, nblk, ballots.p, bcount.p);
-        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, bcount.p, nblk, boff.p, boff.p + nblk);
-        HIPCHK(hipGetLastError());
-        long long G = 0;
-        HIPCHK(hipMemcpyAsync(&G, boff.p + nblk, sizeof(long long), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (G < 1 || G > n) throw std::runtime_error("rgbm_table_distinct_rows: inconsistent group count");
-        DevBuf<long long> rep_rows((size_t)G);
-        hipLaunchKernelGGL(k_emit, dim3((unsigned)nblk, 1u), dim3(PB), 0, s, ballots.p, boff.p, (const int32_t*)nullptr, nblk, rep_rows.p, (int32_t*)nullptr);
+        DevBuf<long long> rep_rows;
+        const long long G = scan_emit(ballots.p, bcount.p, boff.p, nblk, 1, nullptr, s, [&](long long g, long long** rows, int32_t**) {
+            if (g < 1 || g > n) throw std::runtime_error("rgbm_table_distinct_rows: inconsistent group count");
+            rep_rows.alloc((size_t)g); *rows = rep_rows.p;
+        });
         // output rows per group (the 255 split) and every group's first output row
         DevBuf<unsigned> copies((size_t)G); DevBuf<long long> goff((size_t)G + 1);
         hipLaunchKernelGGL(k_dr_copies, dim3(nblocks(G, 256)), dim3(256), 0, s, rep_rows.p, G, n, row_slot.p, count.p, cap, copies.p);
@@ -1580,8 +1693,7 @@ RGBM_EXPORT int rgbm_table_read_row_multiplicity(const rgbm_table* t, uint8_t* m
 // Two tuples: row i violates iff SOME row j (j == i included, the reference's EXISTS sub-query) makes every predicate true.  The EQ
 // predicates group the rows (NULL-safe mixed-radix key, as rgbm_table_detect_constraint); the other predicates are evaluated over the
 // pairs of each group.  The answer is an existence mask, so no step depends on an order:
-//   k_dc_slots    open-addressing slot of every row's key; count[slot] takes the group's rows and hands every row its arrival rank
-//                 (lanes of a wave that hold the same slot add once: one group may span the table)
+//   k_dc_slots    open-addressing slot of every row's key (ht_claim); count[slot] takes the group's rows and hands every row its arrival rank (wave_add)
 //   k_dc_stats    sum of |g|^2 and max |g| over the slots -- the exact pair count, known BEFORE any pair is evaluated
 //   k_scan_counts exclusive scan of the slot counts = first position of every group
 //   k_dc_scatter  the rows laid out by group: position -> row, its group's [begin, end), and per predicate the left and the right
@@ -1619,37 +1731,8 @@ __global__ __launch_bounds__(256) void k_dc_slots(const int32_t* __restrict__ co
                                                   unsigned* __restrict__ row_rank) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = i < n;                     // no early return: every lane takes part in the ballots below
-    const int lane = lane_id();
-    unsigned long long slot = 0;
-    if (valid) {
-        unsigned long long key = 0;
-        for (int c = 0; c < ks.ncols; ++c) {
-            const int32_t v = codes[(long long)ks.col[c] * n + i];
-            const unsigned long long d = (v < 0 || (unsigned long long)v + 1ull >= ks.radix[c]) ? 0ull : (unsigned long long)v + 1ull;
-            key = key * ks.radix[c] + d;
-        }
-        slot = mix64(key) & cap_mask;
-        for (;;) {                                // as k_ht_insert: a slot only ever goes EMPTY -> key; the table has >= 2n slots
-            unsigned long long prev = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev == key) break;
-            if (prev == HT_EMPTY) { prev = atomicCAS(&keys[slot], HT_EMPTY, key); if (prev == HT_EMPTY || prev == key) break; }
-            slot = (slot + 1) & cap_mask;
-        }
-    }
-    const unsigned s32 = (unsigned)slot;
-    unsigned rank = 0;
-    unsigned long long pend = __ballot(valid);
-    for (int round = 0; round < DC_WAVE_ROUNDS && pend; ++round) {
-        const int leader = __ffsll((long long)pend) - 1;
-        const unsigned s = (unsigned)__shfl((int)s32, leader);
-        const unsigned long long same = __ballot(valid && s32 == s) & pend;
-        unsigned base = 0;
-        if (lane == leader) base = atomicAdd(&count[s], (unsigned)__popcll(same));
-        base = (unsigned)__shfl((int)base, leader);
-        if ((same >> lane) & 1ull) rank = base + (unsigned)__popcll(same & ((1ull << lane) - 1ull));
-        pend &= ~same;
-    }
-    if ((pend >> lane) & 1ull) rank = atomicAdd(&count[s32], 1u);
+    const unsigned s32 = valid ? (unsigned)ht_claim(keys, cap_mask, row_key<true>(codes, n, ks, i)) : 0u;
+    const unsigned rank = wave_add<DC_WAVE_ROUNDS>(count, s32, valid);
     if (valid) { row_slot[i] = s32; row_rank[i] = rank; }
 }
 
@@ -1762,7 +1845,6 @@ __global__ __launch_bounds__(PB) void k_row_bits(const int32_t* __restrict__ cod
                                                  unsigned* __restrict__ bcount) {
     const long long b = blockIdx.x;
     const long long base = b * PROWS;
-    __shared__ unsigned lbits[DET_LDS_WORDS * 2];
     bool f[PSUB];
 #pragma unroll
     for (int s = 0; s < PSUB; ++s) f[s] = base + (long long)s * PB + threadIdx.x < n;
@@ -1775,56 +1857,15 @@ __global__ __launch_bounds__(PB) void k_row_bits(const int32_t* __restrict__ cod
             const long long r = base + (long long)s * PB + threadIdx.x;
             v[s] = r < n ? col[r] : -1;
         }
-        const bool in_lds = d.n_words <= DET_LDS_WORDS;                    // uniform over the block
-        const unsigned* g32 = reinterpret_cast<const unsigned*>(bits + d.bit_off);
-        const unsigned nw32 = 2u * (unsigned)d.n_words;
-        __syncthreads();                             // the last column's tests are done with lbits
-        if (in_lds) {
-            for (unsigned i = threadIdx.x; i < nw32; i += PB) lbits[i] = g32[i];
-            __syncthreads();
-        }
+        __syncthreads();                             // the last column's tests are done with the staged bitset
+        const BitsetView bv = bitset_stage(bits, d.bit_off, d.n_words);
 #pragma unroll
         for (int s = 0; s < PSUB; ++s) {
             const unsigned x = (v[s] < 0 || v[s] >= d.n_codes) ? (unsigned)d.n_codes : (unsigned)v[s];     // NULL: the last bit
-            const unsigned w = x >> 5;
-            f[s] = f[s] && w < nw32 && (((in_lds ? lbits[w] : g32[w]) >> (x & 31u)) & 1u);
+            f[s] = f[s] && bitset_test(bv, x);
         }
     }
     flags_to_ballots(f, b, ballots, bcount);
-}
-
-// ballots + block counts of one flag per row (already written by the caller's kernel) -> ascending rows in t.cell_rows
-long long emit_rows(rgbm_table& t, unsigned long long* ballots, unsigned* bcount, long long* off, hipStream_t s) {
-    const long long nblk = (t.n + PROWS - 1) / PROWS;
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, bcount, nblk, off, off + nblk);
-    long long total = 0;
-    HIPCHK(hipMemcpyAsync(&total, off + nblk, sizeof(long long), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (t.cell_rows.n < (size_t)std::max<long long>(total, 1)) t.cell_rows.alloc((size_t)std::max<long long>(total, 1) * 5 / 4);
-    t.cell_cols.release();
-    if (total > 0)
-        hipLaunchKernelGGL(k_emit, dim3((unsigned)nblk, 1u), dim3(PB), 0, s, ballots, off, (const int32_t*)nullptr, nblk, t.cell_rows.p, (int32_t*)nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    t.n_cells = total;
-    return total;
-}
-
-// the m ascending violating rows in t.cell_rows -> rows x cell_cols (column-major), as rgbm_table_detect_constraint leaves them
-void rows_to_cells(rgbm_table& t, long long m, const int32_t* cell_cols, int n_cell_cols, hipStream_t s, int64_t* n_rows_out, int64_t* n_cells_out) {
-    if (n_rows_out) *n_rows_out = m;
-    if (n_cell_cols > 0) {
-        const size_t tot = (size_t)std::max<long long>(m * n_cell_cols, 1);
-        DevBuf<long long> rows_r(tot); DevBuf<int32_t> cols_r(tot);
-        const int32_t* d_cc = scr_upload<int32_t>(t, 6, cell_cols, (size_t)n_cell_cols, s);
-        if (m > 0) hipLaunchKernelGGL(k_replicate, dim3(nblocks(m, 256)), dim3(256), 0, s, t.cell_rows.p, m, d_cc, n_cell_cols, rows_r.p, cols_r.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        t.cell_rows.swap(rows_r);
-        t.cell_cols.swap(cols_r);
-        t.n_cells = m * n_cell_cols;
-    }
-    *n_cells_out = t.n_cells;
 }
 
 template <int NP>
@@ -1855,18 +1896,12 @@ RGBM_EXPORT int rgbm_table_detect_dc(rgbm_table* t, const rgbm_dc_pred* preds, i
         else if (std::find(eq.begin(), eq.end(), p.left_col) == eq.end()) eq.push_back(p.left_col);
     }
     if (eq.size() > 12) return fail(RGBM_ERR_ARG, "rgbm_table_detect_dc: at most 12 EQ attributes");
-    for (int i = 0; i < n_cell_cols; ++i)
-        if (cell_cols[i] < 0 || cell_cols[i] >= t->c) return fail(RGBM_ERR_ARG, "rgbm_table_detect_dc: column index out of range");
+    if (const int rc = refuse_cols(*t, cell_cols, n_cell_cols, false, nullptr, "rgbm_table_detect_dc")) return rc;
     if (t->n >= (1ll << 31)) return fail(RGBM_ERR_PARAM, "rgbm_table_detect_dc: 2^31 rows or more");
     return guarded([&]() {
         use_device(t->device);
-        KeySpec ks; memset(&ks, 0, sizeof(ks)); ks.ncols = (int32_t)eq.size();
         unsigned __int128 span = 1;
-        for (size_t i = 0; i < eq.size(); ++i) {
-            ks.col[i] = eq[i]; ks.radix[i] = (unsigned long long)std::max<int32_t>(t->n_codes[eq[i]], 0) + 1ull;
-            span *= ks.radix[i];
-            if (span >= ((unsigned __int128)1 << 63)) throw std::invalid_argument("rgbm_table_detect_dc: the EQ attributes span more than 2^63 value combinations");
-        }
+        const KeySpec ks = key_spec(*t, eq.data(), (int)eq.size(), "rgbm_table_detect_dc", &span);
         const long long n = t->n;
         const long long limit = max_pairs > 0 ? (long long)max_pairs : DC_DEFAULT_MAX_PAIRS;
         // the program: operands per pair predicate, the rank arrays one after the other
@@ -1886,15 +1921,13 @@ RGBM_EXPORT int rgbm_table_detect_dc(rgbm_table* t, const rgbm_dc_pred* preds, i
         }
         for (int32_t& v : ranks) if (v < 0) v = -1;
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        uint8_t* mask = scr<uint8_t>(*t, 5, (size_t)std::max<long long>(n, 1));
-        if (n == 0) { t->n_cells = 0; t->cell_cols.release(); if (n_rows_out) *n_rows_out = 0; *n_cells_out = 0; return RGBM_OK; }
+        uint8_t* mask = scr<uint8_t>(*t, SCR_ROW_MASK, (size_t)std::max<long long>(n, 1));
+        if (n == 0) return no_cells(*t, true, n_rows_out, n_cells_out);
         if (pg.np == 0) {
             // EQ predicates only: t2 = t1 satisfies them, every row violates
             HIPCHK(hipMemsetAsync(mask, 1, (size_t)n, s));
         } else {
-            unsigned long long want = (unsigned long long)n * 2ull;
-            if (span < (unsigned __int128)want) want = (unsigned long long)span * 2ull;
-            unsigned long long cap = 1024; while (cap < want) cap <<= 1;
+            const unsigned long long cap = table_capacity(n, span);
             DevBuf<unsigned long long> keys((size_t)cap), stats(2);
             DevBuf<unsigned> count((size_t)cap), row_slot((size_t)n), row_rank((size_t)n);
             DevBuf<long long> goff((size_t)cap + 1);
@@ -1944,17 +1977,8 @@ RGBM_EXPORT int rgbm_table_detect_row_bits(rgbm_table* t, const int32_t* cols, i
                                            int32_t n_cell_cols, int64_t* n_rows_out, int64_t* n_cells_out) {
     if (!t || n_cols < 1 || !cols || !bits || n_cell_cols < 0 || (n_cell_cols > 0 && !cell_cols) || !n_cells_out)
         return fail(RGBM_ERR_ARG, "rgbm_table_detect_row_bits: bad argument (at least one column)");
-    {
-        std::vector<uint8_t> seen((size_t)t->c, 0);
-        for (int i = 0; i < n_cols; ++i) {
-            if (cols[i] < 0 || cols[i] >= t->c) return fail(RGBM_ERR_ARG, "rgbm_table_detect_row_bits: column index out of range");
-            if (seen[cols[i]]) return fail(RGBM_ERR_ARG, "rgbm_table_detect_row_bits: a column is listed twice");
-            if (!bits[i]) return fail(RGBM_ERR_ARG, "rgbm_table_detect_row_bits: a column without a bitset");
-            seen[cols[i]] = 1;
-        }
-        for (int i = 0; i < n_cell_cols; ++i)
-            if (cell_cols[i] < 0 || cell_cols[i] >= t->c) return fail(RGBM_ERR_ARG, "rgbm_table_detect_row_bits: column index out of range");
-    }
+    if (const int rc = refuse_cols(*t, cols, n_cols, true, bits, "rgbm_table_detect_row_bits")) return rc;
+    if (const int rc = refuse_cols(*t, cell_cols, n_cell_cols, false, nullptr, "rgbm_table_detect_row_bits")) return rc;
     return guarded([&]() {
         use_device(t->device);
         // one descriptor per column; the bitsets one after the other, bits beyond the NULL bit cleared
@@ -1963,21 +1987,15 @@ RGBM_EXPORT int rgbm_table_detect_row_bits(rgbm_table* t, const int32_t* cols, i
         for (int i = 0; i < n_cols; ++i) {
             RowBitDesc& d = desc[i];
             d.col = cols[i]; d.n_codes = std::max<int32_t>(t->n_codes[cols[i]], 0); d.pad = 0;
-            const long long nbits = (long long)d.n_codes + 1, nw = (nbits + 63) / 64;
-            d.bit_off = (long long)words.size(); d.n_words = (int32_t)nw;
-            words.insert(words.end(), bits[i], bits[i] + nw);
-            if (nbits % 64) words.back() &= (1ull << (nbits % 64)) - 1ull;
+            d.bit_off = append_bitset(words, bits[i], (long long)d.n_codes + 1, &d.n_words);
         }
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
-        if (t->n == 0) { t->n_cells = 0; t->cell_cols.release(); if (n_rows_out) *n_rows_out = 0; *n_cells_out = 0; return RGBM_OK; }
-        const long long nblk = (t->n + PROWS - 1) / PROWS;
-        unsigned long long* ballots = scr<unsigned long long>(*t, 0, (size_t)nblk * PBAL);
-        unsigned* bcount = scr<unsigned>(*t, 1, (size_t)nblk);
-        long long* off = scr<long long>(*t, 2, (size_t)nblk + 1);
-        const RowBitDesc* d_desc = scr_upload<RowBitDesc>(*t, 3, desc.data(), desc.size(), s);
-        const unsigned long long* d_bits = scr_upload<unsigned long long>(*t, 4, words.data(), words.size(), s);
-        hipLaunchKernelGGL(k_row_bits, dim3((unsigned)nblk, 1u), dim3(PB), 0, s, t->codes.p, d_desc, (int)n_cols, d_bits, (long long)t->n, ballots, bcount);
-        const long long m = emit_rows(*t, ballots, bcount, off, s);
+        if (t->n == 0) return no_cells(*t, true, n_rows_out, n_cells_out);
+        const Ballots b = table_ballots(*t, 1);
+        const RowBitDesc* d_desc = scr_upload<RowBitDesc>(*t, SCR_TABLE_A, desc.data(), desc.size(), s);
+        const unsigned long long* d_bits = scr_upload<unsigned long long>(*t, SCR_TABLE_B, words.data(), words.size(), s);
+        hipLaunchKernelGGL(k_row_bits, dim3((unsigned)b.nblk, 1u), dim3(PB), 0, s, t->codes.p, d_desc, (int)n_cols, d_bits, (long long)t->n, b.ballots, b.bcount);
+        const long long m = emit_to_table(*t, b, nullptr, s);
         rows_to_cells(*t, m, cell_cols, n_cell_cols, s, n_rows_out, n_cells_out);
         return RGBM_OK;
     });

@@ -228,6 +228,35 @@ def test_detect_row_bits_equals_the_restatement(n):
         assert e.value.code == -1
 
 
+def _lds_bits():
+    """The most bits of a bitset that is staged into LDS: the constant of the source, not a copy of it."""
+    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
+    return int(re.search(r"constexpr int DET_LDS_WORDS = (\d+);", src).group(1)) * 64
+
+
+def test_row_bits_bitset_either_side_of_the_lds_bound():
+    """One column whose bitset (codes + the NULL bit) just fits the LDS stage and one a bit beyond it (read from global memory): each
+    alone and both in one call, the NULL bit on and off."""
+    from repair import _native as N
+    n = 4097
+    ks = [_lds_bits() - 1, _lds_bits()]                  # 65 535 and 65 536 codes: 65 536 bits (staged), 65 537 bits (global)
+    rng = np.random.default_rng(ks[1])
+    codes = np.stack([rng.integers(0, k, n) for k in ks]).astype(np.int32)
+    for j, k in enumerate(ks):
+        must = [0, 63, 64, 65534, k - 1, -1]             # both ends of the first words, the last words' last bits, NULL
+        codes[j, rng.permutation(n)[:2 * len(must)]] = must + must
+        assert set(must) <= set(codes[j].tolist())
+    tab = N.Table(codes, ks)
+    for null in (0, 1):
+        bs = [DC.pack_bits(np.r_[rng.random(k) < 0.5, bool(null)]) for k in ks]
+        assert [len(b) for b in bs] == [(k + 1 + 63) // 64 for k in ks]
+        for cols in ([0], [1], [0, 1], [1, 0]):
+            want = R.detect_row_bits(codes, ks, cols, [bs[c] for c in cols])
+            got = tab.detect_row_bits(cols, [bs[c] for c in cols])
+            assert got.dtype == np.int64 and np.array_equal(got, want)
+            assert 0 < len(want) < n
+
+
 # ---------------------------------------------------------------------------------------------- the gap this closes
 def test_a_table_the_host_detector_refuses():
     """20 001 rows, EQ(State) & GT(Salary) & LT(Tax) with groups of at most 64 rows: `_violating_rows` refuses the table, the device

@@ -1,9 +1,13 @@
 """Register / scratch / occupancy table of the library's kernels (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel.
-    python tools/kernel_resources.py [name filter]      (cross-compiles rgbm.hip for gfx950; no GPU needed)"""
+    python tools/kernel_resources.py [--src rgbm_prep.hip] [name filter [hipcc flags]]
+(cross-compiles one source file of csrc/ for gfx950, rgbm.hip unless --src names another; no GPU needed)"""
 import re, subprocess, sys, os
+source = "rgbm.hip"
+if "--src" in sys.argv:
+    i = sys.argv.index("--src"); source = sys.argv[i + 1]; del sys.argv[i:i + 2]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc")
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-c", "rgbm.hip", "-o", "/dev/null",
+cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-c", source, "-o", "/dev/null",
        "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
 out = subprocess.run(cmd, cwd=src, capture_output=True, text=True).stderr
 cur = None; rows = []
@@ -11,7 +15,7 @@ for line in out.splitlines():
     m = re.search(r"remark: +Function Name: (\S+)", line)
     if m:
         name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-        cur = {"name": re.sub(r"\(.*", "", name)}; rows.append(cur); continue
+        cur = {"name": re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", ""))}; rows.append(cur); continue
     m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
     if m and cur is not None:
         cur[m.group(1).strip()] = int(m.group(2))
