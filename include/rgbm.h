@@ -368,6 +368,20 @@ int rgbm_table_rule_fill(rgbm_table* t, int32_t y_col, int32_t x_col /* -1: cons
  * -1 everywhere. */
 int rgbm_nearest_values(int32_t device_id, const int32_t* a_cp, const int64_t* a_off, int64_t n_a, const int32_t* b_cp, const int64_t* b_off,
                         int64_t n_b, const double* cost /* [n_a][n_b] or NULL */, double threshold, int32_t* nearest_out /* [n_a] */);
+/* ---- q-gram k-means in code space (RepairMisc.splitInputTable; reference RepairMiscApi.scala:52-153; repair/qgram_kmeans.py) ----
+ * One Lloyd assignment step over the resident table.  cols [n_cols <= 1024]: the attributes, code_off[j]: where the dictionary of cols[j]
+ * starts among the d_tot dictionary entries of all of them.  p: [d_tot][k] row-major float64 (-2 E C^T), h: [k] (|C_k|^2).  The score of
+ * a row for cluster kk is the float64 sum, in this order,  h[kk] + p[code_off[0] + code_0][kk] + p[code_off[1] + code_1][kk] + ...  (a code
+ * outside [0, n_codes) is NULL and adds nothing); its label is the lowest kk with the least score.  counts_out[kk][e] = rows of cluster kk
+ * holding dictionary entry e, sizes_out[kk] = rows of cluster kk, n_changed_out = rows whose label differs from the previous call's (all
+ * rows with first != 0).  The labels (int32 per row) stay with the table on the device; rgbm_table_kmeans_read copies them out.
+ * RGBM_ERR_PARAM, the previous labels untouched: k outside 2 .. 64, n_cols outside 1 .. 1024, a column outside the table, d_tot * k outside
+ * 1 .. 2^27, code_off[j] < 0 or code_off[j] + n_codes[cols[j]] > d_tot, first == 0 without previous labels (rgbm_table_kmeans_read: no labels). */
+int rgbm_table_kmeans_assign(rgbm_table* t, const int32_t* cols, int32_t n_cols, const int64_t* code_off /* [n_cols] */,
+                             int32_t k, const double* p /* [d_tot][k] */, int64_t d_tot, const double* h /* [k] */,
+                             int32_t first /* 1: there is no previous assignment */,
+                             int64_t* counts_out /* [k][d_tot] */, int64_t* sizes_out /* [k] */, int64_t* n_changed_out);
+int rgbm_table_kmeans_read(const rgbm_table* t, int32_t* assign_out /* [n] */);
 int rgbm_table_shape(const rgbm_table* t, int64_t* n_out, int32_t* c_out, int32_t* n_codes_out /* [c] or NULL */);
 
 /* ---- row-sharded multi-GPU training ------------------------------------------------------------

@@ -142,5 +142,7 @@ struct rgbm_table {
     mutable rgh::DevBuf<unsigned long long> pc_counts; mutable rgh::DevBuf<int32_t> pc_luts; mutable rgh::DevBuf<long long> pc_lut_off;
     mutable rgh::DevBuf<int32_t> pc_bins;
     mutable std::vector<int32_t> pc_x, pc_y, pc_dx, pc_dy, pc_nbins; mutable std::vector<long long> pc_off; mutable std::vector<uint8_t> pc_has_lut;
+    // the cluster of every row after the last rgbm_table_kmeans_assign call (int32 [n]); it leaves the device through rgbm_table_kmeans_read
+    mutable rgh::DevBuf<int32_t> km_assign; mutable bool km_valid = false;
     ~rgbm_table() { if (stream) (void)hipStreamDestroy(stream); }
 };

@@ -86,7 +86,8 @@ def lib():
                      "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
                      "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
-                     "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits"):
+                     "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
+                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read"):
             getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -111,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
+    "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read",
 ]
 
 COMM_ID_BYTES = 128
@@ -826,6 +828,28 @@ class Table:
                                              _p(mc, C.c_int64), _p(ok, C.c_uint8), C.c_double(beta), C.c_int64(row_count), _p(weak, C.c_uint8),
                                              _p(top, C.c_int32), _p(tp, C.c_double), _p(probs, C.c_double)), "rgbm_table_cell_domains")
         return weak, top, tp, probs
+
+    def kmeans_assign(self, cols, code_off, p, h, first):
+        """One Lloyd assignment step of the q-gram k-means in code space (include/rgbm.h rgbm_table_kmeans_assign; the statement is
+        repair.qgram_kmeans.assign_step).  ``p`` float64 [d_tot][k], ``h`` float64 [k], ``code_off[j]`` = start of column cols[j]'s dictionary
+        among the d_tot entries.  Returns (counts int64 [k][d_tot], sizes int64 [k], n_changed); the labels stay on the device (``kmeans_read``)."""
+        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
+        off = np.ascontiguousarray(code_off, np.int64).reshape(-1)
+        pp, hh = np.ascontiguousarray(p, np.float64), np.ascontiguousarray(h, np.float64).reshape(-1)
+        if pp.ndim != 2 or pp.shape[1] != len(hh) or len(off) != len(cc):
+            raise ValueError("kmeans_assign: p must be [d_tot][k], h [k], one offset per column")
+        d_tot, k = pp.shape
+        counts, sizes, nch = np.zeros((k, d_tot), np.int64), np.zeros(k, np.int64), C.c_int64(0)
+        _check(lib().rgbm_table_kmeans_assign(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), _p(off, C.c_int64), C.c_int32(k), _p(pp, C.c_double),
+                                              C.c_int64(d_tot), _p(hh, C.c_double), C.c_int32(1 if first else 0), _p(counts, C.c_int64),
+                                              _p(sizes, C.c_int64), C.byref(nch)), "rgbm_table_kmeans_assign")
+        return counts, sizes, int(nch.value)
+
+    def kmeans_read(self):
+        """The labels the last ``kmeans_assign`` left on the device, int32 [n]."""
+        out = np.zeros(self.n, np.int32)
+        _check(lib().rgbm_table_kmeans_read(self.h, _p(out, C.c_int32)), "rgbm_table_kmeans_read")
+        return out
 
     def close(self):
         h, self.h = getattr(self, "h", None), None

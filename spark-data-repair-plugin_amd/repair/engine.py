@@ -91,6 +91,14 @@ class HipEngine:
             return _native.nearest_values(cost=cost, threshold=threshold, device_id=self.device_id)
         return _native.nearest_values(a, b, threshold=threshold, device_id=self.device_id)
 
+    def kmeans_assign(self, table, cols, code_off, p, h, first):
+        """One assignment step of the q-gram k-means on a resident table (rgbm_table_kmeans_assign) -> (counts, sizes, n_changed)."""
+        return table.kmeans_assign(cols, code_off, p, h, first)
+
+    def kmeans_read(self, table):
+        """The labels of the last `kmeans_assign` on this table (rgbm_table_kmeans_read)."""
+        return table.kmeans_read()
+
     def repair_chain_gather(self, table, models, targets, feats, row_begin, n_rows):
         """C2 on device buffers: the chain over this rank's rows, labels / probabilities all-gathered over the rank's communicator before
         they leave the device (include/rgbm.h rgbm_table_repair_chain_gather) -> (labels, probs of ALL ranks' rows in rank order, first row of this rank)."""

@@ -1,11 +1,11 @@
 """`RepairMisc` (reference python/repair/misc.py:27-131,159-260): the helper API around the repair path, on pandas frames.
 
-Only the helpers that touch the path's inputs and outputs are here -- `repair` (apply predicted updates,
-RepairMiscApi.repairAttrsFrom), `flatten` (RepairMiscApi.flattenTable), `injectNull` (RepairMiscApi.injectNullAt, the error
-injector the synthetic benchmark tables use) and `splitInputTable`'s argument checks; `describe`, `toHistogram`,
-`toErrorMap` and `generateDepGraph` are analysis / plotting utilities outside the rebuilt path.
+`repair` (apply predicted updates, RepairMiscApi.repairAttrsFrom), `flatten` (RepairMiscApi.flattenTable), `injectNull`
+(RepairMiscApi.injectNullAt, the error injector the synthetic benchmark tables use), `splitInputTable` (k-means over q-gram
+features, on the resident code table when a device is present: repair/qgram_kmeans.py), `toHistogram` and
+`toErrorMap`; `describe` (Spark's ANALYZE statistics) and `generateDepGraph` (graphviz output) stay unimplemented.
 """
-from typing import Dict, List
+from typing import Any, Dict, List
 
 import numpy as np
 import pandas as pd
@@ -79,11 +79,53 @@ class RepairMisc():
             vals[j::len(cols)] = [None if pd.isna(v) else _to_sql_string(v) for v in df[c].to_numpy(dtype=object)]
         return pd.DataFrame({rid: ids, "attribute": attrs, "value": vals})
 
+    def _resident_engine(self) -> Any:
+        """A HIP engine when a device is present and REPAIR_RESIDENT is not 0, else None (as `RepairModel._resident_engine`); tests
+        inject one through `_engine_override`."""
+        import os
+        hook = getattr(self, "_engine_override", None)
+        if hook is not None:
+            return hook
+        if os.environ.get("REPAIR_RESIDENT", "1") == "0":
+            return None
+        try:
+            from repair import _native
+            if _native.device_count() < 1:
+                return None
+            from repair.engine import HipEngine
+            return HipEngine(int(self.opts.get("gpu_device_id", "0")))
+        except Exception:  # noqa: BLE001 - any doubt: the numpy step
+            return None
+
     def splitInputTable(self) -> DataFrame:
+        """Splits an input table into `k` groups of similar rows: k-means over the bag-of-q-gram features of the target attributes
+        (RepairMiscApi.scala:74-153) -> [row_id, "k"] in frame order.  Options: `target_attr_list` (default: every column but the row
+        id), `q` (2), `clustering_alg` ("bisect-kmeans" or "kmeans++"), `seed` (0), `max_iter` (20), `tol` (1e-4).  Both algorithm names
+        run the ONE loop of repair.qgram_kmeans (k-means++ seeding, Lloyd iterations in code space); Spark's bisecting k-means and
+        k-means|| seeding are not restated, so the labels are not Spark's -- the reference's own test pins only the set of ids."""
         self._check_required_options(["table_name", "row_id", "k"])
         if not self.opts["k"].isdigit():
             raise ValueError("Option 'k' must be an integer, but '%s' found" % self.opts["k"])
-        raise NotImplementedError("splitInputTable (k-means over q-gram features) is outside the rebuilt path")
+        k = int(self.opts["k"])
+        if k < 2:
+            raise ValueError("Option 'k' must be 2 or more, but '%s' found" % self.opts["k"])
+        alg = self.opts.get("clustering_alg", "bisect-kmeans")
+        if alg not in ("bisect-kmeans", "kmeans++"):
+            raise ValueError("Unknown clustering algorithm found: %s" % alg)
+        try:
+            q = int(self.opts.get("q", "2"))          # (the reference: `Try(optionMap("q").toInt).getOrElse(2)`)
+        except ValueError:
+            q = 2
+        df, rid = self._input(), self.opts["row_id"]
+        self._check_attrs(df, [rid])
+        attrs = [a.strip() for a in self._target_attr_list.split(",") if a.strip()]
+        if attrs:
+            self._check_attrs(df, attrs)
+        else:
+            attrs = [c for c in df.columns if c != rid]
+        from repair import qgram_kmeans
+        return qgram_kmeans.split_rows(df, rid, attrs, k, q=q, seed=int(self.opts.get("seed", "0")), max_iter=int(self.opts.get("max_iter", "20")),
+                                       tol=float(self.opts.get("tol", "1e-4")), engine=self._resident_engine())
 
     def injectNull(self) -> DataFrame:
         """Randomly injects NULL into the given attributes: `IF(rand() > ratio, col, NULL)` per cell
@@ -112,13 +154,43 @@ class RepairMisc():
         return df
 
     def describe(self) -> DataFrame:
-        raise NotImplementedError("describe (column statistics) is outside the rebuilt path")
+        raise NotImplementedError("describe (Spark's ANALYZE column statistics) is outside the rebuilt path")
 
     def toHistogram(self) -> DataFrame:
-        raise NotImplementedError("toHistogram is outside the rebuilt path")
+        """The value counts of the listed attributes (RepairMiscApi.convertToHistogram, :276-301): one row [attribute, histogram] per
+        attribute of `targets` that exists and is not continuous (numeric), histogram = [{"value", "cnt"}] over its non-NULL values."""
+        self._check_required_options(["table_name", "targets"])
+        from repair.encode import is_numeric_column
+        df = self._input()
+        targets = {a.strip() for a in self.opts["targets"].split(",") if a.strip()}
+        rows = []
+        for c in df.columns:
+            if c not in targets or is_numeric_column(df[c]):
+                continue
+            cnt = df[c].dropna().value_counts(sort=False)
+            rows.append((c, [{"value": v, "cnt": int(n)} for v, n in cnt.items()]))
+        return pd.DataFrame(rows, columns=["attribute", "histogram"])
 
     def toErrorMap(self) -> DataFrame:
-        raise NotImplementedError("toErrorMap is outside the rebuilt path")
+        """[row_id, error_map]: one character per non-row-id column in frame order, `*` for a cell the error-cell table lists, `-`
+        otherwise (RepairMiscApi.toErrorMap, :303-345)."""
+        self._check_required_options(["table_name", "row_id", "error_cells"])
+        rid = self.opts["row_id"]
+        cells = session.resolve(self.opts["error_cells"])
+        if not {rid, "attribute"} <= set(cells.columns):
+            raise ValueError("Table '%s' must have '%s' and 'attribute' columns" % (self.opts["error_cells"], rid))
+        df = self._input()
+        self._check_attrs(df, [rid])
+        cols = [c for c in df.columns if c != rid]
+        marks = np.full((len(df), len(cols)), "-", dtype="<U1")
+        row_of = pd.Series(np.arange(len(df)), index=pd.Index(df[rid].to_numpy()))
+        row_of = row_of[~row_of.index.duplicated()]
+        col_of = {c: j for j, c in enumerate(cols)}
+        r = row_of.reindex(cells[rid].to_numpy()).to_numpy()
+        c = cells["attribute"].map(col_of).to_numpy(dtype=np.float64, na_value=np.nan)
+        ok = ~(np.isnan(r.astype(np.float64)) | np.isnan(c))
+        marks[r[ok].astype(np.int64), c[ok].astype(np.int64)] = "*"
+        return pd.DataFrame({rid: df[rid].to_numpy(), "error_map": ["".join(m) for m in marks]})
 
     def generateDepGraph(self) -> None:
         raise NotImplementedError("generateDepGraph is outside the rebuilt path")
