@@ -106,6 +106,20 @@ class HipEngine:
         return lab, prob, row0
 
 
+def resident_engine(device_id):
+    """The engine of the HBM-resident steps on HIP device `device_id`, or None: REPAIR_RESIDENT=0, no HIP device, or any failure to
+    reach one (the callers then keep their host path).  `RepairModel` / `RepairMisc._resident_engine` add their test hook to it."""
+    import os
+    if os.environ.get("REPAIR_RESIDENT", "1") == "0":
+        return None
+    try:
+        if _native.device_count() < 1:
+            return None
+        return HipEngine(int(device_id))
+    except Exception:  # noqa: BLE001 - any doubt: the host path
+        return None
+
+
 def model_params(n_classes, base, continuous=False):
     """objective pick of the reference (train.py:97-100): regression for continuous targets, else binary / multiclass."""
     p = dict(base)

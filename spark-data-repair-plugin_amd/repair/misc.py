@@ -82,20 +82,11 @@ class RepairMisc():
     def _resident_engine(self) -> Any:
         """A HIP engine when a device is present and REPAIR_RESIDENT is not 0, else None (as `RepairModel._resident_engine`); tests
         inject one through `_engine_override`."""
-        import os
         hook = getattr(self, "_engine_override", None)
         if hook is not None:
             return hook
-        if os.environ.get("REPAIR_RESIDENT", "1") == "0":
-            return None
-        try:
-            from repair import _native
-            if _native.device_count() < 1:
-                return None
-            from repair.engine import HipEngine
-            return HipEngine(int(self.opts.get("gpu_device_id", "0")))
-        except Exception:  # noqa: BLE001 - any doubt: the numpy step
-            return None
+        from repair.engine import resident_engine
+        return resident_engine(self.opts.get("gpu_device_id", "0"))
 
     def splitInputTable(self) -> DataFrame:
         """Splits an input table into `k` groups of similar rows: k-means over the bag-of-q-gram features of the target attributes

@@ -22,7 +22,7 @@ from repair import session
 from repair.costs import UpdateCostFunction
 from repair.encode import is_integral_column, is_numeric_column
 from repair.errors import (ConstraintErrorDetector, DomainValues, ErrorDetector, ErrorModel, GaussianOutlierErrorDetector, NullErrorDetector,
-                           RegExErrorDetector, parse_constraint, load_constraints, parse_and_verify_constraints)
+                           RegExErrorDetector, parse_constraint, load_constraints, parse_and_verify_constraints, _to_sql_string)
 from repair.train import build_model, compute_class_nrow_stdv, rebalance_training_data, train_option_keys
 from repair.train import _opt_gpu_device_id as _train_opt_gpu_device_id
 from repair.utils import argtype_check, elapsed_time, get_option_value, job_group, setup_logger, to_list_str
@@ -326,6 +326,13 @@ class RepairModel():
                 deps.setdefault(ps[1].left, []).append(ps[0].left)
         return deps or None
 
+    def _fd_source(self, functional_deps: Optional[Dict[str, List[str]]], y: str, domain_stats: Dict[str, int]) -> Optional[str]:
+        """The attribute whose functional dependency answers target `y`: the first listed source with a domain below
+        `model.rule.max_domain_size`, or None.  Asked by `_build_repair_models` and by `_resident_rules`."""
+        max_dom = int(self._get_option_value(*self._opt_max_domain_size))
+        fx = [x for x in (functional_deps or {}).get(y, []) if x in domain_stats and int(domain_stats[x]) < max_dom]
+        return fx[0] if fx else None
+
     def _build_rule_model(self, train_df: DataFrame, x: str, y: str) -> Any:
         sub = train_df[[x, y]].dropna()
         g = sub.groupby(x)[y].agg(lambda s: s.iloc[0] if s.nunique() == 1 else None).dropna()
@@ -353,6 +360,20 @@ class RepairModel():
             _logger.info("To reduce training data, extracts %s%% samples from %d rows" % (100.0 * max_rows / len(df), len(df)))
             return df.sample(n=max_rows, random_state=42)
         return df
+
+    def _training_row_sampler(self) -> Any:
+        """`_sample_training_data_from` as the `train_rows` of `repair.pipeline.repair_frame` take it: (attribute, positions of its
+        non-NULL rows) -> the positions to train on, or None for all of them.  It must stay the same seeded sample as
+        `DataFrame.sample(n, random_state=42)` above draws from the attribute's non-NULL rows."""
+        max_rows = int(self._get_option_value(*self._opt_max_training_row_num))
+
+        def sample(_attr: str, rows: np.ndarray) -> Optional[np.ndarray]:
+            if len(rows) <= max_rows:
+                return None
+            _logger.info("To reduce training data, extracts %s%% samples from %d rows" % (100.0 * max_rows / len(rows), len(rows)))
+            return rows[np.random.RandomState(42).choice(len(rows), max_rows, replace=False)]
+
+        return sample
 
     def _build_repair_stat_models_in_series(self, models: Dict[str, Any], train_df: DataFrame, target_columns: List[str],
                                             continous_columns: List[str], num_class_map: Dict[str, int],
@@ -408,11 +429,9 @@ class RepairModel():
             if is_discrete and num_class_map[y] <= 1:
                 v = train_df[y].dropna().iloc[0] if num_class_map[y] == 1 else None
                 models[y] = (PoorModel(v), input_columns, None)
-            if y not in models and functional_deps is not None and y in functional_deps:
-                max_dom = int(self._get_option_value(*self._opt_max_domain_size))
-                fx = [x for x in functional_deps[y] if x in domain_stats and int(domain_stats[x]) < max_dom]
-                if fx:
-                    models[y] = (self._build_rule_model(train_df, fx[0], y), [fx[0]], None)
+            x = self._fd_source(functional_deps, y, domain_stats) if y not in models else None
+            if x is not None:
+                models[y] = (self._build_rule_model(train_df, x, y), [x], None)
         if len(models) != len(target_columns):
             feature_map = {y: self._select_features(pairwise_attr_stats, y, [c for c in train_df.columns if c != y])
                            for y in target_columns if y not in models}
@@ -578,27 +597,19 @@ class RepairModel():
     def _resident_engine(self) -> Any:
         """The engine of the HBM-resident path, or None: no HIP device, the estimator backend was swapped (CPU tests), or
         REPAIR_RESIDENT=0.  Tests inject one through `_engine_override`."""
-        import os
         hook = getattr(self, "_engine_override", None)
         if hook is not None:
             return hook
-        if os.environ.get("REPAIR_RESIDENT", "1") == "0":
-            return None
         from repair import _native, gbm
+        from repair.engine import resident_engine
         if gbm.get_backend() is not _native:
             return None
-        try:
-            if _native.device_count() < 1:
-                return None
-            from repair.engine import HipEngine
-            return HipEngine(int(self._get_option_value(*self._opt_gpu_device_id)))
-        except Exception:  # noqa: BLE001 - any doubt: the value-space path
-            return None
+        return resident_engine(self._get_option_value(*self._opt_gpu_device_id))
 
     def _resident_plan(self, input_df: DataFrame, target_columns: List[str], continous_columns: List[str], domain_stats: Dict[str, int],
                        compute_repair_candidate_prob: bool, maximal_likelihood_repair: bool, prob_modes: bool = False) -> Optional[Dict[str, Any]]:
         """Decides whether this run can take the HBM-resident pipeline (repair.pipeline) and with which parameters.
-        `prob_modes`: the caller shapes the probability modes itself (`_run_resident_prob`), so they and a cost function qualify.
+        `prob_modes`: the caller shapes the probability modes itself (`_resident_result`), so they and a cost function qualify.
 
         It can when everything between error detection and the result frame is the per-attribute model loop itself:
         no rule-based repairs, no functional-dependency rule models, no rebalancing, no cost function, plain repair output
@@ -649,12 +660,11 @@ class RepairModel():
 
     def _resident_rules(self, input_df: DataFrame, target_columns: List[str], continous_columns: List[str], domain_stats: Dict[str, int],
                         prob_modes: bool) -> Optional[Dict[str, Any]]:
-        """The rule-based repairs of this run as `repair.pipeline.repair_frame(rules=...)` takes them, or None (with the reason in the
+        """The rule-based repairs of this run as the `rules` of `repair.pipeline.repair_frame` take them, or None (with the reason in the
         log) where the resident pipeline does not restate them: the probability modes, regex-structure repair, an FD model for a
         continuous attribute or from a continuous target (its chain value is the raw prediction, not a dictionary entry), a cycle
-        among the FD sources.  The FD attributes are selected as `_build_repair_models` selects them."""
+        among the FD sources."""
         from repair.costs import Levenshtein
-        from repair.errors import _to_sql_string
 
         def no(reason: str) -> None:
             _logger.info("rule-based repairs stay on the value-space path: %s" % reason)
@@ -665,16 +675,15 @@ class RepairModel():
             return no("regex-structure repair is enabled")
         fd: Dict[str, str] = {}
         deps = self._get_functional_deps(target_columns) if self._repair_by_functional_deps_enabled else None
-        max_dom = int(self._get_option_value(*self._opt_max_domain_size))
         for y in target_columns:
-            fx = [x for x in (deps or {}).get(y, []) if x in domain_stats and int(domain_stats[x]) < max_dom]
-            if not fx:
+            x = self._fd_source(deps, y, domain_stats)
+            if x is None:
                 continue
             if y in continous_columns:
                 return no("an FD model for the continuous attribute `%s`" % y)
-            if fx[0] in continous_columns and fx[0] in target_columns:
-                return no("the FD source `%s` of `%s` is a continuous target" % (fx[0], y))
-            fd[y] = fx[0]
+            if x in continous_columns and x in target_columns:
+                return no("the FD source `%s` of `%s` is a continuous target" % (x, y))
+            fd[y] = x
         for y in fd:
             seen, x = {y}, fd[y]
             while x in fd:
@@ -689,9 +698,7 @@ class RepairModel():
             integral = {c for c in input_df.columns if is_numeric_column(input_df[c]) and is_integral_column(input_df[c])}
 
             def current_str(attr: str, values: List[Any]) -> List[Any]:
-                # CAST(value AS STRING) of the error cells (ErrorModel.detect): integral attributes print as '2', never '2.0'
-                out = [None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_sql_string(v) for v in values]
-                return [v if v is None or attr not in integral else str(int(float(v))) for v in out]
+                return _sql_strs(values, attr in integral)
 
             def domain_str(attr: str, values: List[Any]) -> List[Any]:
                 # `_to_str` of the column's values as `_repair_by_nearest_values` reads them from the frame
@@ -807,140 +814,6 @@ class RepairModel():
             plan.update(domain_analysis=dict(options=eopts, discrete_thres=self.discrete_thres, continuous_columns=list(continous_columns)))
         return plan
 
-    def _run_resident_detect(self, plan: Dict[str, Any], input_df: DataFrame, continous_columns: List[str], repair_data: bool) -> DataFrame:
-        """`_run` with detection, NULLing, training and repair on the resident table (`_device_detection_plan`)."""
-        from repair.pipeline import NotResidentEligible, repair_frame
-        from repair.errors import _to_sql_string
-        rid = self._row_id
-        cands = plan["candidates"]
-        if repair_data and not plan["detect_nulls"]:
-            raise NotResidentEligible("repair_data without a NULL detector: NULL target cells of dirty rows would stay NULL")
-        max_rows = int(self._get_option_value(*self._opt_max_training_row_num))
-
-        def sample(_attr: str, rows: np.ndarray) -> Optional[np.ndarray]:
-            if len(rows) <= max_rows:
-                return None
-            _logger.info("To reduce training data, extracts %s%% samples from %d rows" % (100.0 * max_rows / len(rows), len(rows)))
-            return rows[np.random.RandomState(42).choice(len(rows), max_rows, replace=False)]
-
-        _logger.info("[Error Detection + Repair Model Training Phase] on the HBM-resident table, candidate attributes %s" % to_list_str(cands))
-        vdets = None
-        if plan.get("value_detectors"):
-            from repair.detect_codes import build_descriptors
-
-            def build(*a: Any, **kw: Any) -> Any:
-                # whatever stops the restatement (a malformed pattern, a dictionary that does not cast back to the column's dtype)
-                # is the value-space detector's to report
-                try:
-                    return build_descriptors(*a, **kw)
-                except Exception as e:  # noqa: BLE001
-                    raise NotResidentEligible("value detectors: %s" % e)
-
-            vdets = dict(detectors=plan["value_detectors"], build=build)
-        frame, info = repair_frame(plan["engine"], input_df, rid, targets=cands, base_params=plan["params"], constraints=plan["constraints"],
-                                   detect_nulls=plan["detect_nulls"], continuous_columns=[c for c in continous_columns if c in cands],
-                                   train_rows=sample, want_details=True, search_opts=dict(self.opts) if plan.get("search") else None,
-                                   only_noisy_targets=True, domain_analysis=plan.get("domain_analysis"), rules=plan.get("rules"),
-                                   value_detectors=vdets, distinct_training_rows=plan.get("distinct"))
-        self._last_resident_info = info
-        self._last_detection_on_device = True
-        merged = info.get("merged_cells")              # nearest-value merges: repaired by rule, appended as `_run` appends them
-        if merged is not None and len(merged) == 0:
-            merged = None
-        if len(frame) == 0 and merged is None:
-            _logger.info("Any error cell not found, so the input data is already clean")
-            return input_df if repair_data else pd.DataFrame({rid: pd.Series([], dtype=input_df[rid].dtype), "attribute": pd.Series([], dtype=object),
-                                                              "current_value": pd.Series([], dtype=object), "repaired": pd.Series([], dtype=object)})
-        cur = [None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_sql_string(v) for v in frame["current_value"].tolist()]
-        rep = [None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_str(v) for v in frame["repaired"].tolist()]
-        cand = pd.DataFrame({rid: frame[rid].to_numpy(), "attribute": frame["attribute"].to_numpy(), "current_value": np.asarray(cur, object),
-                             "repaired": np.asarray(rep, object)})
-        # integral attributes: CAST(int AS STRING) of the current value is '2', never '2.0' (ErrorModel.detect keeps nullable ints integral)
-        for a in set(cand["attribute"]):
-            if is_integral_column(input_df[a]):
-                m = (cand["attribute"] == a).to_numpy() & cand["current_value"].notna().to_numpy()
-                cand.loc[m, "current_value"] = [str(int(float(v))) for v in cand.loc[m, "current_value"]]
-        if repair_data:
-            cells = cand if merged is None else pd.concat([cand, merged], ignore_index=True)
-            base = self._prepare_repair_base_cells(input_df, cells, sorted(set(cells["attribute"])))
-            if merged is not None:
-                base = self._repair_attrs(merged, base)
-            is_dirty = base[rid].isin(set(cand[rid].tolist())).to_numpy()
-            dirty = self._repair_attrs(cand[[rid, "attribute", "repaired"]], base[is_dirty].reset_index(drop=True))
-            return pd.concat([base[~is_dirty], dirty], ignore_index=True)
-        keep = cand["repaired"].isna() | ~((cand["current_value"] == cand["repaired"]) | (cand["current_value"].isna() & cand["repaired"].isna()))
-        cand = cand[keep.to_numpy()].reset_index(drop=True)
-        return cand if merged is None else pd.concat([cand, merged], ignore_index=True)
-
-    def _run_resident(self, plan: Dict[str, Any], input_df: DataFrame, error_cells_df: DataFrame, target_columns: List[str],
-                      continous_columns: List[str], repair_data: bool) -> DataFrame:
-        """Steps 2 and 3 of `_run` on the device: the table is encoded once (dictionary indices -> codes, on the device), error
-        cells are NULLed, the dirty rows split off, one model per target attribute trained and the chained repair run without
-        the table leaving HBM (repair.pipeline.repair_frame); the host only shapes the (small) list of repaired cells."""
-        from repair.pipeline import NotResidentEligible, repair_frame
-        rid = self._row_id
-        max_rows = int(self._get_option_value(*self._opt_max_training_row_num))
-        if repair_data:
-            # The repair UDF fills EVERY NULL target cell of a dirty row (model.py:1128,1133), the cell list below only the error
-            # cells: with setErrorCells / non-NULL detectors a dirty row may hold further NULLs -- those runs keep the value-space path.
-            dirty = input_df[rid].isin(set(error_cells_df[rid].tolist())).to_numpy()
-            nulls_in_dirty = int(input_df.loc[dirty, target_columns].isna().to_numpy().sum())
-            null_error_cells = int(error_cells_df["current_value"].isna().to_numpy().sum())
-            if nulls_in_dirty > null_error_cells:
-                raise NotResidentEligible("%d NULL target cells of dirty rows are not error cells" % (nulls_in_dirty - null_error_cells))
-
-        def sample(_attr: str, rows: np.ndarray) -> Optional[np.ndarray]:
-            # `_sample_training_data_from`: the same seeded sample as DataFrame.sample(n, random_state=42) on the attribute's non-NULL rows
-            if len(rows) <= max_rows:
-                return None
-            _logger.info("To reduce training data, extracts %s%% samples from %d rows" % (100.0 * max_rows / len(rows), len(rows)))
-            return rows[np.random.RandomState(42).choice(len(rows), max_rows, replace=False)]
-
-        rules = plan.get("rules")
-        if rules is not None and rules.get("nearest") is not None:
-            # the cost functions see the error cells' current values as `error_cells_df` holds them
-            rpos = pd.Series(np.arange(len(input_df)), index=input_df[rid].to_numpy()).reindex(error_cells_df[rid].to_numpy()).to_numpy(np.int64)
-            curv = error_cells_df["current_value"].to_numpy(dtype=object)
-            by_attr = {}
-            for a, idx in error_cells_df.groupby("attribute").indices.items():
-                o = np.argsort(rpos[idx], kind="stable")
-                by_attr[a] = (rpos[idx][o], curv[idx][o])
-            rules = dict(rules, nearest=dict(rules["nearest"], current=lambda a, rows: list(by_attr[a][1][np.searchsorted(by_attr[a][0], rows)])))
-        _logger.info("[Repair Model Training Phase] Building %d models on the HBM-resident table to repair the cells in %s" % (
-            len(target_columns), to_list_str(target_columns)))
-        frame, info = repair_frame(plan["engine"], input_df, rid, targets=target_columns, base_params=plan["params"],
-                                   error_cells=error_cells_df[[rid, "attribute"]], detect_nulls=False,
-                                   continuous_columns=[c for c in continous_columns if c in target_columns], train_rows=sample,
-                                   want_details=True, search_opts=dict(self.opts) if plan.get("search") else None, rules=rules,
-                                   distinct_training_rows=plan.get("distinct"))
-        self._last_resident_info = info
-        by_rules = None
-        merged = info.get("merged_cells")
-        if merged is not None and len(merged):
-            # nearest-value merges: they leave the error cells and are appended as `_run` appends `repaired_by_rules_df`
-            mrep = pd.Series(merged["repaired"].to_numpy(dtype=object),
-                             index=pd.MultiIndex.from_arrays([merged[rid].to_numpy(), merged["attribute"].to_numpy()]))
-            mkey = pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()])
-            is_merged = mkey.isin(mrep.index)
-            by_rules = error_cells_df[is_merged].assign(repaired=mrep.reindex(mkey[is_merged]).to_numpy(dtype=object))
-            all_cells_df, error_cells_df = error_cells_df, error_cells_df[~is_merged].reset_index(drop=True)
-        rep = pd.Series(frame["repaired"].to_numpy(dtype=object),
-                        index=pd.MultiIndex.from_arrays([frame[rid].to_numpy(), frame["attribute"].to_numpy()]))
-        key = pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()])
-        values = rep.reindex(key).to_numpy(dtype=object)
-        if repair_data:
-            base = self._prepare_repair_base_cells(input_df, error_cells_df if by_rules is None else all_cells_df, target_columns)
-            if by_rules is not None:
-                base = self._repair_attrs(by_rules, base)
-            is_dirty = base[rid].isin(set(error_cells_df[rid].tolist())).to_numpy()
-            upd = error_cells_df[[rid, "attribute"]].assign(repaired=[None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_str(v) for v in values])
-            dirty = self._repair_attrs(upd, base[is_dirty].reset_index(drop=True))
-            return pd.concat([base[~is_dirty], dirty], ignore_index=True)
-        cand = error_cells_df.assign(repaired=[None if v is None or (isinstance(v, float) and np.isnan(v)) else _to_str(v) for v in values])
-        keep = cand["repaired"].isna() | ~((cand["current_value"] == cand["repaired"]) | (cand["current_value"].isna() & cand["repaired"].isna()))
-        cand = cand[keep.to_numpy()].reset_index(drop=True)
-        return cand if by_rules is None else pd.concat([cand, by_rules], ignore_index=True)
-
     def _cost_spec(self, engine: Any, attr: str, classes: Any, cur: List[Any], ml: bool) -> Dict[str, Any]:
         """The update costs of one target's cells as `repair.pipeline.repair_table(pmf_costs=...)` takes them, from the values
         `_compute_repair_pmf` / `_compute_score` see: the error cells' current values and `_to_str` of the classes.  One cost row per
@@ -992,53 +865,132 @@ class RepairModel():
         cost_row = np.array([row_of[v] if v is not None else -1 for v in cur], np.int32)
         return dict(cost=cost, cost_row=cost_row, cur_code=cur_code, weight=weight, renormalise=True)
 
-    def _run_resident_prob(self, plan: Dict[str, Any], input_df: DataFrame, error_cells_df: DataFrame, target_columns: List[str],
-                           continous_columns: List[str], compute_repair_candidate_prob: bool, compute_repair_prob: bool,
-                           compute_repair_score: bool, repair_data: bool, maximal_likelihood_repair: bool) -> DataFrame:
-        """Steps 2 and 3 of `_run` for the probability modes (option `repair.pmf.resident`): the models, the candidate
-        distributions, the update-cost re-weighting and the score inputs come from the resident pipeline (rgbm_table_repair_pmf_weighted,
-        rgbm_edit_distance); the host shapes the frames of the value-space branch below (`_compute_repair_pmf`, `_compute_score`,
-        `_maximal_likelihood_repair`), the score's log and percentile vectorised."""
-        import time
-        from repair.pipeline import repair_frame
+    def _current_values_by_position(self, input_df: DataFrame, error_cells_df: DataFrame) -> Any:
+        """(attribute, ascending row positions) -> the current values of those error cells as `error_cells_df` holds them: what the cost
+        functions see on the value-space path (`_repair_by_nearest_values`, `_compute_repair_pmf`)."""
         rid = self._row_id
-        max_rows = int(self._get_option_value(*self._opt_max_training_row_num))
-        thres = float(self._get_option_value(*self._opt_prob_threshold))
-        top_k = int(self._get_option_value(*self._opt_prob_top_k))
-        engine = plan["engine"]
-        ml = maximal_likelihood_repair
-
-        def sample(_attr: str, rows: np.ndarray) -> Optional[np.ndarray]:
-            if len(rows) <= max_rows:
-                return None
-            _logger.info("To reduce training data, extracts %s%% samples from %d rows" % (100.0 * max_rows / len(rows), len(rows)))
-            return rows[np.random.RandomState(42).choice(len(rows), max_rows, replace=False)]
-
-        # the error cells' current values by attribute and row position (what `_compute_repair_pmf` reads from `error_cells_df`)
         rpos = pd.Series(np.arange(len(input_df)), index=input_df[rid].to_numpy()).reindex(error_cells_df[rid].to_numpy()).to_numpy(np.int64)
         curv = error_cells_df["current_value"].to_numpy(dtype=object)
         by_attr = {}
         for a, idx in error_cells_df.groupby("attribute").indices.items():
             o = np.argsort(rpos[idx], kind="stable")
             by_attr[a] = (rpos[idx][o], curv[idx][o])
+        return lambda a, rows: list(by_attr[a][1][np.searchsorted(by_attr[a][0], rows)])
 
-        def costs(attr: str, classes: Any, rows: np.ndarray) -> Dict[str, Any]:
-            pos, cur = by_attr[attr]
-            return self._cost_spec(engine, attr, classes, list(cur[np.searchsorted(pos, rows)]), ml)
+    def _resident_run(self, plan: Dict[str, Any], input_df: DataFrame, target_columns: List[str], continous_columns: List[str],
+                      error_cells_df: Optional[DataFrame], compute_repair_candidate_prob: bool, compute_repair_prob: bool,
+                      compute_repair_score: bool, repair_data: bool, maximal_likelihood_repair: bool) -> DataFrame:
+        """Steps 2 and 3 of `_run` on the device: the table is encoded once (dictionary indices -> codes, on the device), error
+        cells are NULLed, the dirty rows split off, one model per target attribute trained and the chained repair run without
+        the table leaving HBM (repair.pipeline.repair_frame); the host only shapes the (small) list of repaired cells.
 
-        _logger.info("[Repair Model Training Phase] Building %d models on the HBM-resident table to compute the repair distributions of %s" % (
-            len(target_columns), to_list_str(target_columns)))
+        `error_cells_df` None: detection runs on the resident table as well (`_device_detection_plan`; `target_columns` are its
+        candidates), so no `error_cells_df` is ever built in pandas.
+
+        The probability modes (option `repair.pmf.resident`): the candidate distributions, the update-cost re-weighting and the score
+        inputs come from the resident pipeline too (rgbm_table_repair_pmf_weighted, rgbm_edit_distance); the host shapes the frames of
+        the value-space branch (`_compute_repair_pmf`, `_compute_score`, `_maximal_likelihood_repair`), the score's log vectorised."""
+        import time
+        from repair.pipeline import NotResidentEligible, repair_frame
+        rid = self._row_id
+        detect = error_cells_df is None
+        prob = compute_repair_candidate_prob or maximal_likelihood_repair       # `_resident_plan` admits them with given cells only
+        rules = plan.get("rules")
+        if detect:
+            if repair_data and not plan["detect_nulls"]:
+                raise NotResidentEligible("repair_data without a NULL detector: NULL target cells of dirty rows would stay NULL")
+            vdets = None
+            if plan.get("value_detectors"):
+                from repair.detect_codes import build_descriptors
+
+                def build(*a: Any, **kw: Any) -> Any:
+                    # whatever stops the restatement (a malformed pattern, a dictionary that does not cast back to the column's dtype)
+                    # is the value-space detector's to report
+                    try:
+                        return build_descriptors(*a, **kw)
+                    except Exception as e:  # noqa: BLE001
+                        raise NotResidentEligible("value detectors: %s" % e)
+
+                vdets = dict(detectors=plan["value_detectors"], build=build)
+            cells = dict(constraints=plan["constraints"], detect_nulls=plan["detect_nulls"], only_noisy_targets=True,
+                         domain_analysis=plan.get("domain_analysis"), value_detectors=vdets)
+            _logger.info("[Error Detection + Repair Model Training Phase] on the HBM-resident table, candidate attributes %s" % to_list_str(target_columns))
+        else:
+            if repair_data and not prob:
+                # The repair UDF fills EVERY NULL target cell of a dirty row (model.py:1128,1133), the cell list below only the error
+                # cells: with setErrorCells / non-NULL detectors a dirty row may hold further NULLs -- those runs keep the value-space path.
+                dirty = input_df[rid].isin(set(error_cells_df[rid].tolist())).to_numpy()
+                nulls_in_dirty = int(input_df.loc[dirty, target_columns].isna().to_numpy().sum())
+                null_error_cells = int(error_cells_df["current_value"].isna().to_numpy().sum())
+                if nulls_in_dirty > null_error_cells:
+                    raise NotResidentEligible("%d NULL target cells of dirty rows are not error cells" % (nulls_in_dirty - null_error_cells))
+            cells = dict(error_cells=error_cells_df[[rid, "attribute"]], detect_nulls=False)
+            nearest = rules is not None and rules.get("nearest") is not None
+            if prob or nearest:
+                # the cost functions see the error cells' current values as `error_cells_df` holds them
+                current = self._current_values_by_position(input_df, error_cells_df)
+            if nearest:
+                rules = dict(rules, nearest=dict(rules["nearest"], current=current))
+            _logger.info("[Repair Model Training Phase] Building %d models on the HBM-resident table to %s %s" % (
+                len(target_columns), "compute the repair distributions of" if prob else "repair the cells in", to_list_str(target_columns)))
+        if prob:
+            cells.update(want_pmf=True, top_k=int(self._get_option_value(*self._opt_prob_top_k)),
+                         threshold=float(self._get_option_value(*self._opt_prob_threshold)),
+                         pmf_costs=lambda attr, classes, rows: self._cost_spec(plan["engine"], attr, classes, current(attr, rows),
+                                                                               maximal_likelihood_repair))
         t0 = time.perf_counter()
-        frame, info = repair_frame(engine, input_df, rid, targets=target_columns, base_params=plan["params"],
-                                   error_cells=error_cells_df[[rid, "attribute"]], detect_nulls=False,
-                                   continuous_columns=[c for c in continous_columns if c in target_columns], train_rows=sample,
-                                   want_details=True, search_opts=dict(self.opts) if plan.get("search") else None,
-                                   want_pmf=True, top_k=top_k, threshold=thres, pmf_costs=costs)
+        # (the probability modes train on the whole table: `model.train.distinct_rows` is not wired to them)
+        frame, info = repair_frame(plan["engine"], input_df, rid, targets=target_columns, base_params=plan["params"],
+                                   continuous_columns=[c for c in continous_columns if c in target_columns],
+                                   train_rows=self._training_row_sampler(), want_details=True,
+                                   search_opts=dict(self.opts) if plan.get("search") else None, rules=rules,
+                                   distinct_training_rows=None if prob else plan.get("distinct"), **cells)
         info["times"]["pipeline_wall"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         self._last_resident_info = info
-        key = pd.MultiIndex.from_arrays([frame[rid].to_numpy(), frame["attribute"].to_numpy()])
-        at = key.get_indexer(pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()]))
+        self._last_detection_on_device = detect
+        try:
+            return self._resident_result(input_df, frame, info.get("merged_cells"), error_cells_df, continous_columns, compute_repair_prob,
+                                         compute_repair_score, repair_data, maximal_likelihood_repair, prob)
+        finally:
+            info["times"]["host_shape"] = time.perf_counter() - t0
+
+    def _resident_result(self, input_df: DataFrame, frame: DataFrame, merged: Optional[DataFrame], error_cells_df: Optional[DataFrame],
+                         continous_columns: List[str], compute_repair_prob: bool, compute_repair_score: bool, repair_data: bool,
+                         maximal_likelihood_repair: bool, prob: bool) -> DataFrame:
+        """The result of `_run` from what `repair_frame` returned: its frame (one row per repaired cell, raw values) and the
+        nearest-value merges (`merged_cells`: repaired by rule, so they leave the error cells and are appended as `_run` appends
+        `repaired_by_rules_df`)."""
+        rid = self._row_id
+        by_rules = None
+        if error_cells_df is None:
+            # the cells were detected on the table: the frame holds them, with their current values
+            if merged is not None and len(merged):
+                by_rules = merged
+            if len(frame) == 0 and by_rules is None:
+                _logger.info("Any error cell not found, so the input data is already clean")
+                return input_df if repair_data else pd.DataFrame({rid: pd.Series([], dtype=input_df[rid].dtype), "attribute": pd.Series([], dtype=object),
+                                                                  "current_value": pd.Series([], dtype=object), "repaired": pd.Series([], dtype=object)})
+            attrs, raw = frame["attribute"].to_numpy(), frame["current_value"].to_numpy(dtype=object)
+            cur = np.empty(len(frame), object)
+            for a in set(attrs):
+                cur[attrs == a] = _sql_strs(raw[attrs == a], is_integral_column(input_df[a]))
+            cand = pd.DataFrame({rid: frame[rid].to_numpy(), "attribute": attrs, "current_value": cur,
+                                 "repaired": np.asarray(_strs(frame["repaired"].tolist()), object)})
+            return self._repair_result(input_df, cand, by_rules, repair_data)
+        if merged is not None and len(merged):
+            mrep = pd.Series(merged["repaired"].to_numpy(dtype=object),
+                             index=pd.MultiIndex.from_arrays([merged[rid].to_numpy(), merged["attribute"].to_numpy()]))
+            mkey = pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()])
+            is_merged = mkey.isin(mrep.index)
+            by_rules = error_cells_df[is_merged].assign(repaired=mrep.reindex(mkey[is_merged]).to_numpy(dtype=object))
+            error_cells_df = error_cells_df[~is_merged].reset_index(drop=True)
+        # the frame is ordered by (column, row): back onto the order of `error_cells_df`
+        at = pd.MultiIndex.from_arrays([frame[rid].to_numpy(), frame["attribute"].to_numpy()]).get_indexer(
+            pd.MultiIndex.from_arrays([error_cells_df[rid].to_numpy(), error_cells_df["attribute"].to_numpy()]))
+        if not prob:
+            values = pd.api.extensions.take(frame["repaired"].to_numpy(dtype=object), at, allow_fill=True, fill_value=None)
+            return self._repair_result(input_df, error_cells_df.assign(repaired=_strs(values)), by_rules, repair_data)
         assert (at >= 0).all()
         pmf_l = frame["pmf"].to_numpy(dtype=object)[at]
         cp = frame["current_prob"].to_numpy(np.float64)[at]
@@ -1053,53 +1005,91 @@ class RepairModel():
                 rows.append((rowid, attr, {"value": cur, "prob": 0.0}, [{"class": None if v is None else _to_str(v), "prob": 1.0}]))
             else:
                 rows.append((rowid, attr, {"value": cur, "prob": float(cp[i])}, [{"class": _to_str(d["class"]), "prob": d["prob"]} for d in pmf_l[i]]))
-        pmf_df = pd.DataFrame(rows, columns=[rid, "attribute", "current_value", "pmf"])
-        try:
-            if compute_repair_candidate_prob and not maximal_likelihood_repair:
-                pmf_df = pmf_df.assign(current_value=[c["value"] for c in pmf_df["current_value"]])
-                if compute_repair_prob:
-                    return pd.DataFrame({rid: pmf_df[rid], "attribute": pmf_df["attribute"], "current_value": pmf_df["current_value"],
-                                         "repaired": [p[0]["class"] if p else None for p in pmf_df["pmf"]],
-                                         "prob": [p[0]["prob"] if p else None for p in pmf_df["pmf"]]})
-                return pmf_df
+
+        def score_df() -> DataFrame:
             # _compute_score, vectorised: log(p_top1 / max(p_cur, 1e-6)) / (1 + cost(base, top-1)), None cost = 256
             top_p = np.array([p[0]["prob"] if p else 0.0 for p in pmf_l], np.float64)
             p_cur = np.where(cp > 0.0, cp, 1e-6)
             cost = np.where(np.isnan(tc), 256.0, tc)
             with np.errstate(divide="ignore", invalid="ignore"):
                 score = np.where(top_p > 0, np.log(top_p / p_cur) * (1.0 / (1.0 + cost)), -np.inf)
-            score_df = pd.DataFrame([(r[0], r[1], r[2]["value"], r[3][0]["class"] if r[3] else None, float(sc))
-                                     for r, sc in zip(rows, score)], columns=[rid, "attribute", "current_value", "repaired", "score"])
-            if compute_repair_score:
-                return score_df
-            top = self._maximal_likelihood_repair(score_df, error_cells_df)
-            if not repair_data:
-                return top
-            base = self._prepare_repair_base_cells(input_df, error_cells_df, target_columns)
-            is_dirty = base[rid].isin(set(error_cells_df[rid].tolist())).to_numpy()
-            dirty = self._repair_attrs(top, base[is_dirty].reset_index(drop=True))
-            return pd.concat([base[~is_dirty], dirty], ignore_index=True)
-        finally:
-            info["times"]["host_shape"] = time.perf_counter() - t0
+            return pd.DataFrame([(r[0], r[1], r[2]["value"], r[3][0]["class"] if r[3] else None, float(sc))
+                                 for r, sc in zip(rows, score)], columns=[rid, "attribute", "current_value", "repaired", "score"])
+
+        return self._probability_result(input_df, error_cells_df, pd.DataFrame(rows, columns=[rid, "attribute", "current_value", "pmf"]), score_df,
+                                        compute_repair_prob, compute_repair_score, repair_data, maximal_likelihood_repair)
+
+    # ------------------------------------------------------------------ the result of a run, resident or value-space
+    def _repaired_table(self, input_df: DataFrame, error_cells_df: DataFrame, updates: DataFrame, by_rules: Optional[DataFrame] = None) -> DataFrame:
+        """`repair_data`: the input with the error cells (and the cells repaired by rule) NULLed, the rule repairs applied, and
+        `updates` applied to the dirty rows, which follow the clean ones."""
+        rid = self._row_id
+        cells = error_cells_df if by_rules is None else pd.concat([error_cells_df, by_rules], ignore_index=True)
+        base = self._prepare_repair_base_cells(input_df, cells, sorted(set(cells["attribute"])))
+        if by_rules is not None:
+            base = self._repair_attrs(by_rules, base)
+        is_dirty = base[rid].isin(set(error_cells_df[rid].tolist())).to_numpy()
+        dirty = self._repair_attrs(updates[[rid, "attribute", "repaired"]], base[is_dirty].reset_index(drop=True))
+        return pd.concat([base[~is_dirty], dirty], ignore_index=True)
+
+    def _repair_result(self, input_df: DataFrame, cand: DataFrame, by_rules: Optional[DataFrame], repair_data: bool) -> DataFrame:
+        """The plain result: `cand` (row_id, attribute, current_value, repaired: one row per error cell a model repaired) and the
+        cells repaired by rule, as the repaired table (`repair_data`) or as the list of cells whose value changes."""
+        if repair_data:
+            return self._repaired_table(input_df, cand, cand, by_rules)
+        keep = cand["repaired"].isna() | ~((cand["current_value"] == cand["repaired"]) | (cand["current_value"].isna() & cand["repaired"].isna()))
+        cand = cand[keep.to_numpy()].reset_index(drop=True)
+        return cand if by_rules is None else pd.concat([cand, by_rules], ignore_index=True)
+
+    def _probability_result(self, input_df: DataFrame, error_cells_df: DataFrame, pmf_df: DataFrame, score_df: Any, compute_repair_prob: bool,
+                            compute_repair_score: bool, repair_data: bool, maximal_likelihood_repair: bool) -> DataFrame:
+        """The probability modes' outputs from the candidate distributions `pmf_df` (`_compute_repair_pmf`'s frame): the pmf itself, its
+        top-1 (`compute_repair_prob`), or -- maximal likelihood -- the scores (`score_df()`: how they are computed is the caller's),
+        the `repair_delta` best of them, or those applied to the data."""
+        rid = self._row_id
+        if not maximal_likelihood_repair:
+            pmf_df = pmf_df.assign(current_value=[c["value"] for c in pmf_df["current_value"]])
+            if compute_repair_prob:
+                return pd.DataFrame({rid: pmf_df[rid], "attribute": pmf_df["attribute"], "current_value": pmf_df["current_value"],
+                                     "repaired": [p[0]["class"] if p else None for p in pmf_df["pmf"]],
+                                     "prob": [p[0]["prob"] if p else None for p in pmf_df["pmf"]]})
+            return pmf_df
+        scores = score_df()
+        if compute_repair_score:
+            return scores
+        top = self._maximal_likelihood_repair(scores, error_cells_df)
+        return self._repaired_table(input_df, error_cells_df, top) if repair_data else top
 
     # ------------------------------------------------------------------ pipeline
+    def _resident_attempt(self, what: str, plan: Dict[str, Any], *args: Any) -> Optional[DataFrame]:
+        """`_resident_run`, or None (with `what` and the reason in the log) when the run turns out not to qualify."""
+        from repair.pipeline import NotResidentEligible
+        try:
+            return self._resident_run(plan, *args)
+        except NotResidentEligible as e:
+            # only known once the table is built and the error cells are NULLed, e.g.: a target left with a single class / no value (the
+            # reference's PoorModel short-cut, model.py:1008-1017), or NULL target cells in dirty rows that are not error cells under
+            # repair_data.  (Unseen categories of a dirty row need no fallback: the table marks categorical columns, so a model treats
+            # a category its training rows do not show as missing, like the reference's per-model encoders.)
+            self._last_resident_info = None
+            self._last_detection_on_device = False
+            _logger.info("%s not taken: %s" % (what, e))
+            return None
+
     @elapsed_time  # type: ignore
     def _run(self, input_df: DataFrame, continous_columns: List[str], detect_errors_only: bool,
              compute_repair_candidate_prob: bool, compute_repair_prob: bool, compute_repair_score: bool,
              repair_data: bool, maximal_likelihood_repair: bool) -> DataFrame:
         rid = self._row_id
+        flags = (compute_repair_candidate_prob, compute_repair_prob, compute_repair_score, repair_data, maximal_likelihood_repair)
         self._last_detection_on_device = False
         # 0. Everything on the HBM-resident table, detection included, when the detectors and the run allow it
-        if not detect_errors_only:
-            dplan = self._device_detection_plan(input_df, continous_columns, compute_repair_candidate_prob, maximal_likelihood_repair)
-            if dplan is not None:
-                from repair.pipeline import NotResidentEligible
-                try:
-                    return self._run_resident_detect(dplan, input_df, continous_columns, repair_data)
-                except NotResidentEligible as e:
-                    self._last_resident_info = None
-                    self._last_detection_on_device = False
-                    _logger.info("device-side detection not taken: %s" % e)
+        dplan = None if detect_errors_only else self._device_detection_plan(input_df, continous_columns, compute_repair_candidate_prob,
+                                                                            maximal_likelihood_repair)
+        if dplan is not None:
+            out = self._resident_attempt("device-side detection", dplan, input_df, dplan["candidates"], continous_columns, None, *flags)
+            if out is not None:
+                return out
         # 1. Error Detection Phase
         _logger.info("[Error Detection Phase] Detecting errors in a table... ")
         error_cells_df, target_columns, pairwise_attr_stats, domain_stats = self._detect_errors(input_df, continous_columns)
@@ -1117,25 +1107,10 @@ class RepairModel():
         prob_modes = (compute_repair_candidate_prob or maximal_likelihood_repair) and bool(self._get_option_value(*self._opt_pmf_resident))
         plan = self._resident_plan(input_df, target_columns, continous_columns, domain_stats, compute_repair_candidate_prob,
                                    maximal_likelihood_repair, prob_modes=prob_modes)
-        if plan is not None and prob_modes:
-            from repair.pipeline import NotResidentEligible
-            try:
-                return self._run_resident_prob(plan, input_df, error_cells_df, target_columns, continous_columns, compute_repair_candidate_prob,
-                                               compute_repair_prob, compute_repair_score, repair_data, maximal_likelihood_repair)
-            except NotResidentEligible as e:
-                self._last_resident_info = None
-                _logger.info("resident path not taken: %s" % e)
-        elif plan is not None:
-            from repair.pipeline import NotResidentEligible
-            try:
-                return self._run_resident(plan, input_df, error_cells_df, target_columns, continous_columns, repair_data)
-            except NotResidentEligible as e:
-                # only known once the error cells are NULLed: a target left with a single class / no value (the reference's PoorModel
-                # short-cut, model.py:1008-1017), or NULL target cells in dirty rows that are not error cells under repair_data.
-                # (Unseen categories of a dirty row need no fallback: the table marks categorical columns, so a model treats a
-                # category its training rows do not show as missing, like the reference's per-model encoders.)
-                self._last_resident_info = None
-                _logger.info("resident path not taken: %s" % e)
+        if plan is not None:
+            out = self._resident_attempt("resident path", plan, input_df, target_columns, continous_columns, error_cells_df, *flags)
+            if out is not None:
+                return out
 
         # 2. Repair Model Training Phase
         repair_base_df = self._prepare_repair_base_cells(input_df, error_cells_df, target_columns)
@@ -1156,35 +1131,20 @@ class RepairModel():
         # 3. Repair Phase
         repaired_rows_df, pmfs = self._repair(models, continous_columns, dirty_rows_df, error_cells_df,
                                               compute_repair_candidate_prob, maximal_likelihood_repair)
-        if compute_repair_candidate_prob and not maximal_likelihood_repair:
-            assert not self._repair_by_nearest_values_enabled, "repairing data by nearest values not supported in this path"
+        if compute_repair_candidate_prob or maximal_likelihood_repair:
+            if maximal_likelihood_repair:
+                assert len(continous_columns) == 0
+            else:
+                assert not self._repair_by_nearest_values_enabled, "repairing data by nearest values not supported in this path"
             pmf_df = self._compute_repair_pmf(pmfs, repaired_rows_df, dirty_rows_df, error_cells_df, continous_columns)
-            pmf_df = pmf_df.assign(current_value=[c["value"] for c in pmf_df["current_value"]])
-            if compute_repair_prob:
-                return pd.DataFrame({rid: pmf_df[rid], "attribute": pmf_df["attribute"], "current_value": pmf_df["current_value"],
-                                     "repaired": [p[0]["class"] if p else None for p in pmf_df["pmf"]],
-                                     "prob": [p[0]["prob"] if p else None for p in pmf_df["pmf"]]})
-            return pmf_df
-        if maximal_likelihood_repair:
-            assert len(continous_columns) == 0
-            pmf_df = self._compute_repair_pmf(pmfs, repaired_rows_df, dirty_rows_df, error_cells_df, [])
-            score_df = self._compute_score(pmf_df)
-            if compute_repair_score:
-                return score_df
-            top = self._maximal_likelihood_repair(score_df, error_cells_df)
-            if not repair_data:
-                return top
-            repaired_rows_df = self._repair_attrs(top, dirty_rows_df)
+            return self._probability_result(input_df, error_cells_df, pmf_df, lambda: self._compute_score(pmf_df), compute_repair_prob,
+                                            compute_repair_score, repair_data, maximal_likelihood_repair)
         if repair_data:
+            # every NULL target cell of a dirty row is filled (`_repair`), not the error cells alone: the rows are taken as they are
             clean_df = pd.concat([clean_rows_df, repaired_rows_df], ignore_index=True)
             assert len(clean_df) == len(input_df)
             return clean_df
-        cand = self._flatten_join(repaired_rows_df, error_cells_df)
-        keep = cand["repaired"].isna() | ~((cand["current_value"] == cand["repaired"]) | (cand["current_value"].isna() & cand["repaired"].isna()))
-        cand = cand[keep.to_numpy()].reset_index(drop=True)
-        if self.repair_by_rules and repaired_by_rules_df is not None:
-            cand = pd.concat([cand, repaired_by_rules_df], ignore_index=True)
-        return cand
+        return self._repair_result(input_df, self._flatten_join(repaired_rows_df, error_cells_df), repaired_by_rules_df, False)
 
     def run(self, detect_errors_only: bool = False, compute_repair_candidate_prob: bool = False,
             compute_repair_prob: bool = False, compute_repair_score: bool = False, repair_data: bool = False,
@@ -1282,3 +1242,20 @@ def _to_str(v: Any) -> str:
     if isinstance(v, (np.integer,)):
         return str(int(v))
     return str(v)
+
+
+def _is_null(v: Any) -> bool:
+    return v is None or (isinstance(v, float) and np.isnan(v))
+
+
+def _strs(values: Any) -> List[Optional[str]]:
+    """`_to_str` of repaired values as the resident pipeline decodes them; None / NaN stays None."""
+    return [None if _is_null(v) else _to_str(v) for v in values]
+
+
+def _sql_strs(values: Any, integral: bool) -> List[Optional[str]]:
+    """CAST(value AS STRING) of the error cells' current values (ErrorModel.detect); None / NaN stays None.  The resident pipeline
+    decodes numeric dictionaries as float64, so the values of an integral attribute print as '2', never '2.0' (ErrorModel.detect
+    keeps nullable ints integral)."""
+    out = [None if _is_null(v) else _to_sql_string(v) for v in values]
+    return [v if v is None else str(int(float(v))) for v in out] if integral else out

@@ -427,6 +427,56 @@ def rule_step_summary(table, t, step, cell_rows, dirty_rows, dirty_tab, labels):
     return info
 
 
+def cell_pmfs(engine, table, pmf_tab, targets, models, rows, cols, current, dirty_rows, continuous, y_values, integral, top_k, threshold,
+              pmf_costs):
+    """The candidate distributions of the error cells (rows, cols, current) for `repair_table(want_pmf=True)`, whose arguments these
+    are: `pmf_tab` holds the dirty rows un-repaired, `models` the trained models by target.  Returns dict(pmf_class, pmf_prob,
+    current_prob[, top1_cost, pmf_value])."""
+    pc = np.full((len(rows), top_k), -1, np.int32)
+    pp = np.zeros((len(rows), top_k), np.float64)
+    cp = np.zeros(len(rows), np.float64)
+    tc = np.full(len(rows), np.nan, np.float64)
+    pv = np.full(len(rows), np.nan, np.float64)
+    for t in targets:
+        sel = np.flatnonzero(cols == t)
+        feats = [c for c in range(table.c) if c != t]
+        if t in continuous:       # continuous attributes have no pmf (model.py:1215-1222: the value with prob 1.0)
+            if pmf_costs is not None and t in models:
+                from repair.engine import chained_repair
+                _, _, v = chained_repair(engine, pmf_tab, [engine.load_model(models[t])], [t], [feats], 0, pmf_tab.n, y_values, integral)
+                pv[sel] = v[0][np.searchsorted(dirty_rows, rows[sel])]
+            continue
+        if len(sel) == 0:
+            continue
+        model = engine.load_model(models[t])
+        # NULL cells of t in the dirty frame: a superset of this target's error cells when NULL detection is off
+        drows, _ = pmf_tab.detect_nulls([t])
+        j = np.searchsorted(dirty_rows[drows], rows[sel])
+        cur_for = np.full(len(drows), -1, np.int32)
+        cur_for[j] = current[sel]                          # the value the cell held (model.py:1196-1199: its probability)
+        spec = pmf_costs(t, rows[sel]) if pmf_costs is not None else None
+        if pmf_costs is None:
+            _, dcls, dpr, dcp = pmf_tab.repair_pmf(model, t, feats, top_k=top_k, threshold=threshold, cur_codes=cur_for)
+        else:
+            spec = dict(spec or {})
+            if spec.get("cur_code") is not None:
+                cur_for[j] = spec["cur_code"]
+            crow = None
+            if spec.get("cost") is not None:
+                crow = np.full(len(drows), -1, np.int32)
+                if spec.get("cost_row") is not None:
+                    crow[j] = spec["cost_row"]
+            _, dcls, dpr, dcp, dtc = pmf_tab.repair_pmf_weighted(model, t, feats, top_k=top_k, threshold=threshold, cur_codes=cur_for,
+                                                                 cost_rows=crow, cost=spec.get("cost"), weight=float(spec.get("weight", 0.0)),
+                                                                 renormalise=bool(spec.get("renormalise", False)))
+            tc[sel] = dtc[j]
+        pc[sel], pp[sel], cp[sel] = dcls[j], dpr[j], dcp[j]
+    out = dict(pmf_class=pc, pmf_prob=pp, current_prob=cp)
+    if pmf_costs is not None:
+        out.update(top1_cost=tc, pmf_value=pv)
+    return out
+
+
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
@@ -482,12 +532,11 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     if callable(value_detectors):
         value_detectors = value_detectors(table)
     rows, cols = detect_error_cells(table, targets, constraints, detect_nulls, error_cells, value_detectors=value_detectors)
+    noisy = set(int(c) for c in np.unique(cols))
     if only_noisy_targets:
-        noisy = set(int(c) for c in np.unique(cols))
         targets = [t for t in targets if t in noisy]
     domain_info = None
     if domain_analysis is not None and len(rows):
-        noisy = set(int(c) for c in np.unique(cols))
         da = analyse_cell_domains(table, [t for t in targets if t in noisy], rows, cols, domain_analysis)
         domain_info = dict(pairwise=da["pairwise"], noisy_cells=int(len(rows)), weak_cells=int(da["weak"].sum()))
         _logger.info("[Error Detection Phase] %d noisy cells fixed and %d error cells remaining..." % (domain_info["weak_cells"],
@@ -525,24 +574,24 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     fd = dict(rules.get("fd") or {}) if rules is not None else {}
     for t in targets:
         cnt, _ = table.count_codes(t)
+        live = np.flatnonzero(cnt > 0)
         if t in continuous:
-            if int((cnt > 0).sum()) < 1:
+            if len(live) < 1:
                 raise NotResidentEligible("continuous target column %d has no non-NULL row to learn from" % t)
-        elif t in fd and int((cnt > 0).sum()) >= 2:
+        elif t in fd and len(live) >= 2:
             # FunctionalDepModel (model.py `_build_rule_model`): the map of the whole NULLed table; no model, so no label-count checks
             rule_steps[t] = dict(x=int(fd[t]), lut=np.asarray(table.fd_map(int(fd[t]), t), np.int32), kind="fd")
             continue
-        elif only_noisy_targets and int((cnt > 0).sum()) < len(cnt):
-            e = DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, int((cnt <= 0).sum()), len(cnt)), *detected)
+        elif only_noisy_targets and len(live) < len(cnt):
+            e = DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, len(cnt) - len(live), len(cnt)), *detected)
             e.domain_info = domain_info          # the cells it carries are the pruned ones: the second pass does not analyse again
             e.value_detectors = out.get("value_detectors")
             raise e
-        elif int((cnt > 0).sum()) < 2 and rules is not None:
+        elif len(live) < 2 and rules is not None:
             # PoorModel (model.py:1008-1017): the one live class, or NULL when the column has no value left
-            live = np.flatnonzero(cnt > 0)
             rule_steps[t] = dict(x=-1, lut=np.array([live[0] if len(live) else -1], np.int32), kind="constant")
             continue
-        elif int((cnt > 0).sum()) < 2:
+        elif len(live) < 2:
             raise NotResidentEligible("target column %d has fewer than two classes among its non-NULL rows; the reference short-cuts such "
                              "attributes with a constant model (model.py:1008-1017) -- drop it from `targets`" % t)
         label_counts[t] = cnt
@@ -615,48 +664,8 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         out["rule_steps"] = [rule_step_summary(table, t, rule_steps[t], rows[cols == t], dirty_rows, dirty_tab, repaired[cols == t])
                              for t in targets if t in rule_steps]
     if want_pmf:
-        pc = np.full((len(rows), top_k), -1, np.int32)
-        pp = np.zeros((len(rows), top_k), np.float64)
-        cp = np.zeros(len(rows), np.float64)
-        tc = np.full(len(rows), np.nan, np.float64)
-        pv = np.full(len(rows), np.nan, np.float64)
-        for t in targets:
-            sel = np.flatnonzero(cols == t)
-            feats = [c for c in range(table.c) if c != t]
-            if t in continuous:       # continuous attributes have no pmf (model.py:1215-1222: the value with prob 1.0)
-                if pmf_costs is not None and t in res["models"]:
-                    from repair.engine import chained_repair
-                    _, _, v = chained_repair(engine, pmf_tab, [engine.load_model(res["models"][t])], [t], [feats], 0, pmf_tab.n, y_values, integral)
-                    pv[sel] = v[0][np.searchsorted(dirty_rows, rows[sel])]
-                continue
-            if len(sel) == 0:
-                continue
-            model = engine.load_model(res["models"][t])
-            # NULL cells of t in the dirty frame: a superset of this target's error cells when NULL detection is off
-            drows, _ = pmf_tab.detect_nulls([t])
-            j = np.searchsorted(dirty_rows[drows], rows[sel])
-            cur_for = np.full(len(drows), -1, np.int32)
-            cur_for[j] = current[sel]                          # the value the cell held (model.py:1196-1199: its probability)
-            spec = pmf_costs(t, rows[sel]) if pmf_costs is not None else None
-            if pmf_costs is None:
-                _, dcls, dpr, dcp = pmf_tab.repair_pmf(model, t, feats, top_k=top_k, threshold=threshold, cur_codes=cur_for)
-            else:
-                spec = dict(spec or {})
-                if spec.get("cur_code") is not None:
-                    cur_for[j] = spec["cur_code"]
-                crow = None
-                if spec.get("cost") is not None:
-                    crow = np.full(len(drows), -1, np.int32)
-                    if spec.get("cost_row") is not None:
-                        crow[j] = spec["cost_row"]
-                _, dcls, dpr, dcp, dtc = pmf_tab.repair_pmf_weighted(model, t, feats, top_k=top_k, threshold=threshold, cur_codes=cur_for,
-                                                                     cost_rows=crow, cost=spec.get("cost"), weight=float(spec.get("weight", 0.0)),
-                                                                     renormalise=bool(spec.get("renormalise", False)))
-                tc[sel] = dtc[j]
-            pc[sel], pp[sel], cp[sel] = dcls[j], dpr[j], dcp[j]
-        out.update(pmf_class=pc, pmf_prob=pp, current_prob=cp)
-        if pmf_costs is not None:
-            out.update(top1_cost=tc, pmf_value=pv)
+        out.update(cell_pmfs(engine, table, pmf_tab, targets, res["models"], rows, cols, current, dirty_rows, continuous, y_values, integral,
+                             top_k, threshold, pmf_costs))
     t_shape = time.perf_counter() - t0
     times = dict(res["times"])
     times.update(detect=t_detect, prepare=t_prep, shape=t_shape)
@@ -741,6 +750,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         raise ValueError("Target attributes not found in the input: %s" % ",".join(unknown))
     indices, remaps, dicts = encode_frame(df, cols)
     pos = {c: i for i, c in enumerate(cols)}
+    dtypes = {c: df[c].dtype for c in cols}
     cells, given_current = None, None
 
     def null_known_cells(kr, kc):
@@ -812,16 +822,19 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             current[hit] = given_current[1][order][at[hit]]
         return current
 
+    def cur_strings(t, rows_, codes_):
+        """The current-value strings of cells of column t for the nearest-value rule: the caller's where it holds them already."""
+        nv = rules["nearest"]
+        if nv.get("current") is not None:
+            return nv["current"](cols[t], rows_)
+        return nv["current_str"](cols[t], list(current_values(rows_, np.full(len(rows_), t, np.int32), codes_)))
+
     def table_rules():
         if rules is None:
             return None
         spec = dict(fd={pos[y]: pos[x] for y, x in dict(rules.get("fd") or {}).items()}, nearest=None)
         nv = rules.get("nearest")
         if nv is not None:
-            def cur_strings(t, rows_, codes_):
-                if nv.get("current") is not None:
-                    return nv["current"](cols[t], rows_)
-                return nv["current_str"](cols[t], list(current_values(rows_, np.full(len(rows_), t, np.int32), codes_)))
             spec["nearest"] = dict(targets=[pos[a] for a in nv["targets"] if a in pos], threshold=nv["threshold"], cost=nv.get("cost"),
                                    current=cur_strings, domain=lambda t, live: nv["domain_str"](cols[t], list(dicts[t][live])))
         return spec
@@ -833,7 +846,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         if build is None:
             from repair.detect_codes import build_descriptors as build
         dets = list(value_detectors["detectors"])
-        return lambda table: build(dets, cols, dicts, {c: df[c].dtype for c in cols}, lambda j: table.count_codes(j)[0], list(targets),
+        return lambda table: build(dets, cols, dicts, dtypes, lambda j: table.count_codes(j)[0], list(targets),
                                    null_all=bool(detect_nulls_))
 
     def build_and_run(cells_, detect_nulls_, constraints_, analyse=True):
@@ -858,7 +871,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             else:                                  # a parsed constraint: lowered against the dictionaries the table is built from
                 from repair.dc_codes import NotLowerable, lower_constraint
                 try:
-                    cons.append(lower_constraint(con, cols, dicts, {c: df[c].dtype for c in cols}))
+                    cons.append(lower_constraint(con, cols, dicts, dtypes))
                 except NotLowerable as e:
                     raise NotResidentEligible("denial constraint %s: %s" % (con, e))
         cont_ = {}
@@ -942,11 +955,11 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             if mg is not None and len(mg["rows"]):
                 nv = rules["nearest"]
                 mrows, mcols = mg["rows"], mg["cols"]
-                raw_cur, raw_rep = current_values(mrows, mcols, mg["current"]), decode(mg["repaired"], mcols)
+                raw_rep = decode(mg["repaired"], mcols)
                 mcur, mrep = np.empty(len(mrows), object), np.empty(len(mrows), object)
                 for j in np.unique(mcols):
                     sel = np.flatnonzero(mcols == j)
-                    mcur[sel] = nv["current"](cols[j], mrows[sel]) if nv.get("current") is not None else nv["current_str"](cols[j], list(raw_cur[sel]))
+                    mcur[sel] = cur_strings(j, mrows[sel], mg["current"][sel])
                     mrep[sel] = nv["domain_str"](cols[j], list(raw_rep[sel]))
             details["merged_cells"] = pd.DataFrame({row_id: df[row_id].to_numpy()[mrows], "attribute": np.asarray(cols, object)[mcols],
                                                     "current_value": np.asarray(mcur, object), "repaired": np.asarray(mrep, object)})

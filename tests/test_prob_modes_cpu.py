@@ -177,16 +177,22 @@ def test_without_the_option_the_probability_modes_keep_the_value_space_path(orac
 # maximal likelihood (and the score) needs a cost function without targets: run() rejects the other combinations
 CASES = [(cf, f) for cf in (None, "lev", "lev_one", "user") for f in MODES
          if cf in ("lev", "user") or not ("compute_repair_score" in f or "maximal_likelihood_repair" in f)]
+# the training-row sample and the hyper-parameter search reach the probability modes through the same runner as the plain run: both
+# option sets with Levenshtein(), for the top-1 frame and for maximal likelihood + repair_data (appended, so the ids above keep)
+OPTION_SETS = {"lev_sampled": {"model.max_training_row_num": "700"},
+               "lev_search": {"model.hp.max_evals": "3", "model.hp.no_progress_loss": "2"}}
+CASES += [(cf, f) for cf in OPTION_SETS for f in (MODES[1], MODES[4])]
 
 
 @pytest.mark.parametrize("cells", [False, True])
 @pytest.mark.parametrize("cf,flags", CASES)
 def test_synthetic_frames_equal_the_value_space_path(oracle_backend, cf, flags, cells):
     df = _synthetic_frame(1500, 5, seed=21)
-    make_cf = {None: lambda: None, "lev": Levenshtein, "lev_one": lambda: Levenshtein(targets=["c2"]),
+    make_cf = {None: lambda: None, "lev": Levenshtein, "lev_sampled": Levenshtein, "lev_search": Levenshtein,
+               "lev_one": lambda: Levenshtein(targets=["c2"]),
                "user": lambda: UserDefinedUpdateCostFunction(lambda x, y: float(abs(len(x) - len(y)) + (x[-1] != y[-1])))}[cf]
     ec = _error_cells(df, seed=22) if cells else None
-    a, b, fast = _both_paths(lambda: _model(df, cf=make_cf(), delta=40, cells=ec), CostOracleEngine(), **flags)
+    a, b, fast = _both_paths(lambda: _model(df, cf=make_cf(), delta=40, cells=ec, **OPTION_SETS.get(cf, {})), CostOracleEngine(), **flags)
     assert fast._last_resident_info is not None, "the run did not take the resident path"
     assert len(a) > 0 and list(a.columns) == list(b.columns)
     if flags.get("repair_data"):
