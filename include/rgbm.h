@@ -60,7 +60,7 @@ typedef struct {
     int32_t bagging_freq;     /* subsample_freq, train.py:151 */
     int32_t seed;             /* random_state=42, train.py:113 */
     int32_t device_id;        /* HIP device ordinal */
-    int32_t reserved;         /* flags: RGBM_FLAG_ROW_SHARDED */
+    int32_t reserved;         /* flags: RGBM_FLAG_ROW_SHARDED, RGBM_FLAG_NO_MODEL, RGBM_FLAG_WHOLE_TABLE */
     double learning_rate;           /* model.lgb.learning_rate, train.py:41-42 */
     double lambda_l1;               /* reg_alpha, train.py:47-49 */
     double lambda_l2;               /* reg_lambda, train.py:155 */
@@ -75,7 +75,7 @@ typedef struct {
     double hist_ms;          /* sum of hist_build kernel time (HIP events on the launch stream) */
     double total_ms;         /* whole training call, device side */
     int64_t hist_launches;   /* number of hist_build launches */
-    int64_t hist_rows;       /* rows scanned by hist_build over all launches and class trees */
+    int64_t hist_rows;       /* rows scanned by hist_build over all launches and class trees (a fit on the distinct-row view: rows STREAMED, see rgbm_table_distinct_view_info) */
     int64_t hist_bytes;      /* algorithmic bytes: rows * (F + 8) (+4 per row via an index list) */
     int64_t root_rows;       /* of which full-table (root) scans */
     double root_ms;          /* hist_build time spent in root scans */
@@ -162,7 +162,8 @@ int rgbm_table_train(const rgbm_table* t, int32_t target_col, const int32_t* fea
  * categorical tables it repairs a quarter of the rows are distinct -- but the result is defined by it: every later rgbm_table_train on this
  * table returns byte for byte the model the EXPANDED table gives (identical rows take identical paths and gradients; all sums are exact
  * integers).  NULL clears.  Level grower only (1 <= max_depth <= 7), at most 32 features with a free byte in the last 16-feature record, no
- * bagging, no per-row weights: a training call that cannot honour it fails with RGBM_ERR_PARAM. */
+ * bagging, no per-row weights: a training call that cannot honour it fails with RGBM_ERR_PARAM.  A table that carries multiplicities never
+ * gets a distinct-row view (rgbm_table_distinct_view_info); setting or clearing them drops the view. */
 int rgbm_table_set_row_multiplicity(rgbm_table* t, const uint8_t* mult /* [n] or NULL */);
 /* The multiplicities a table carries, one per row (1 everywhere when it carries none). */
 int rgbm_table_read_row_multiplicity(const rgbm_table* t, uint8_t* mult_out /* [n] */);
@@ -181,6 +182,22 @@ int rgbm_table_read_row_multiplicity(const rgbm_table* t, uint8_t* mult_out /* [
  * rgbm_table_set_row_multiplicity, a table of 17 to 31 features trains only when both 16-feature chunks fit one level pass and the features pack
  * into at most 15 joint-bin groups of at most 256 bins (about: fewer than 16 features with more than 16 bins).  Callers fall back to `t`. */
 int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, int64_t* n_out, int64_t* inverse_out /* [n] or NULL */);
+/* The DISTINCT-ROW VIEW.  rgbm_table_train deduplicates a table by itself: the first training call that can use it builds, once per table
+ * and version of its contents, the table rgbm_table_distinct_rows makes (concurrent callers wait for that one build), and every fit whose
+ * model comes out the same bytes trains on it -- level grower (1 <= max_depth <= 7), classifier objective, no bagging, not row-sharded, at most
+ * 32 features with a free byte in the last 16-feature record, a table without multiplicities of its own and of at least RGBM_DISTINCT_MIN_ROWS
+ * rows (default 2^20), whose distinct rows are at most RGBM_DISTINCT_MAX_RATIO (default 0.5) of its rows.  What the multiplicity trainer refuses
+ * on the view (see rgbm_table_distinct_rows) trains on the whole table inside the same call: no error reaches the caller for it.  Every entry
+ * point that writes cells, column kinds, column values or multiplicities drops the view; rgbm_table_free frees it.  RGBM_DISTINCT=0 (read at
+ * every training call) and RGBM_FLAG_WHOLE_TABLE (per call) switch it off.  A fit that trained on the view reports in rgbm_train_stats the rows
+ * its kernels streamed (root_rows exactly; the level passes' share of hist_rows / hist_bytes pro rata), not rows weighted by multiplicity.
+ *   state: 0 no pass yet (or dropped), 1 built (*rows = its rows), 2 not worth it (*rows = the distinct rows; no table kept),
+ *          3 cannot (more than 2^30 rows, working set above half of the device memory, or the allocator refused; the reason goes to stderr
+ *          under RGBM_TIMING).  *builds = distinct passes run for this table object.  Any of the three outputs may be NULL. */
+int rgbm_table_distinct_view_info(const rgbm_table* t, int32_t* state, int64_t* rows, int64_t* builds);
+/* Whether a fit of this shape MAY train on the view: a function of its arguments alone (no device), 1 or 0.  rows, f = rows and features of the
+ * fit; table_has_mult = the table carries multiplicities of its own; min_rows <= 0 takes the built-in default. */
+int rgbm_distinct_view_eligible(int64_t rows, int32_t f, const rgbm_params* p, int32_t table_has_mult, int64_t min_rows);
 /* ---- many small fits in one go ------------------------------------------------------------------
  * Replaces the LOOP over fits of python/repair/train.py:158-209 (every hyper-parameter trial is `cross_val_score`: n_splits fits of
  * the same estimator on row subsets of one frame, train.py:171-172) and of python/repair/model.py:768-815 on the reference's default
@@ -395,6 +412,7 @@ int rgbm_table_shape(const rgbm_table* t, int64_t* n_out, int32_t* c_out, int32_
  * position (the shards must hold consecutive row ranges in rank order), so the model is the single-device one. */
 #define RGBM_COMM_ID_BYTES 128
 #define RGBM_FLAG_ROW_SHARDED 1 /* rgbm_params.reserved: this call is one rank of a row-sharded training */
+#define RGBM_FLAG_WHOLE_TABLE 4 /* rgbm_params.reserved, rgbm_table_train: train on every row, never on the table's distinct-row view (same model) */
 #define RGBM_FLAG_NO_MODEL 2    /* rgbm_params.reserved, rgbm_table_train_batch only: the fit is wanted for its validation scores (a CV fold); no model
                                    is built, out_models[i] stays NULL with status RGBM_OK */
 int rgbm_comm_unique_id(void* id_out /* [RGBM_COMM_ID_BYTES], call on one rank, hand to all */);

@@ -151,7 +151,7 @@ void* pool_alloc_raw(size_t bytes, size_t* block_bytes, int* device) {
         { std::lock_guard<std::mutex> lk(P.mu); P.trim_locked(0); }
         e = hipMalloc(&p, want);
     }
-    if (e != hipSuccess) { (void)hipGetLastError(); char b[256]; snprintf(b, sizeof(b), "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e)); throw std::runtime_error(b); }
+    if (e != hipSuccess) { (void)hipGetLastError(); char b[256]; snprintf(b, sizeof(b), "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e)); throw rgh::device_oom(b); }
     *block_bytes = want;
     return p;
 }
@@ -583,6 +583,14 @@ void find_bin(const unsigned int* cnt, int32_t n_codes, int64_t n_train, const r
 //   wave-specialised pass as a switch                                  one chunk: 3 % slower; two chunks: the measured default, now the only form
 //   partial-T rotation (two switches)                                  81.8 -> 86.1 -> 89.6 ms
 //   compile-time: rotate every level pass / 64-entry rings             loses 35-60 % at levels 1-4 / neutral
+// The distinct-row view (rgbm_table_train): a table is trained through its distinct rows when they are at most
+// DISTINCT_MAX_RATIO of its rows (the policy default of model.train.distinct_rows.max_ratio) and it has at least DISTINCT_MIN_ROWS rows.
+// The floor is measured (profiles/EXPERIMENTS.md, "distinct-row view"): a K = 24 fit of 20 iterations on a fresh table with M = N / 4, view build
+// included, parent library / this one alternating, three runs each, ms:   N = 2^18  23.8-25.4 / 23.7-29.3 (a fit that small is the latency of its
+// chain of kernels);   2^20  39.8-41.5 / 28.2-31.0;   2^22  96.9-98.0 / 42.7-43.3.  2^20 is the smallest of the three N at which the slowest run
+// with the view is below the fastest without.  M = N / 2 at N = 2^20: 39.0-40.2 / 33.6-34.0, so the 0.5 ratio is still ahead.
+constexpr double DISTINCT_MAX_RATIO = 0.5;
+constexpr long long DISTINCT_MIN_ROWS = 1ll << 20;
 struct RunSwitches {
     int grower = 0;                // RGBM_GROWER=level|leafwise (1 | 2): 0 picks the level grower wherever it applies; both give the same models
     bool timing = false;           // RGBM_TIMING: host wall-clock of the phases and the launch plan, to stderr
@@ -602,6 +610,9 @@ struct RunSwitches {
                                    // holds twice as many (0 = off).  0 / 2 / 4: bench step 80.4-80.8 / 80.0-80.1 / 80.8-81.2 ms (profiles/EXPERIMENTS.md, r7m / r7n)
     bool fx_separate = false;      // RGBM_FX_MEASURE=separate: the coarse gradient sums of numerics v2.2 from a pass of their own (k_fx_measure, the
                                    // live path for K > 112) instead of out of the gradient kernels; same sums, same models
+    bool distinct = true;          // RGBM_DISTINCT=0: rgbm_table_train never trains on the table's distinct-row view (the row-for-row figures)
+    double distinct_max_ratio = DISTINCT_MAX_RATIO;      // RGBM_DISTINCT_MAX_RATIO
+    long long distinct_min_rows = DISTINCT_MIN_ROWS;     // RGBM_DISTINCT_MIN_ROWS
 };
 RunSwitches read_switches() {
     RunSwitches w;
@@ -618,6 +629,9 @@ RunSwitches read_switches() {
     if (const char* e = getenv("RGBM_MT_ROT")) w.mt_rot = atoi(e);
     if (const char* e = getenv("RGBM_MT_ROT_COPIES2")) w.mt_rot_copies2 = atoi(e);
     if (const char* e = getenv("RGBM_MT_ROT_TMIN")) w.mt_rot_tmin = atoi(e);
+    if (const char* e = getenv("RGBM_DISTINCT")) w.distinct = atoi(e) != 0;
+    if (const char* e = getenv("RGBM_DISTINCT_MAX_RATIO")) { const double r = atof(e); if (r >= 0.0 && r <= 1.0) w.distinct_max_ratio = r; }
+    if (const char* e = getenv("RGBM_DISTINCT_MIN_ROWS")) w.distinct_min_rows = std::max(1ll, atoll(e));
     w.timing = getenv("RGBM_TIMING") != nullptr;
     return w;
 }
@@ -1549,7 +1563,7 @@ void FitState::enqueue_bagging() {
 
 rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t* feat_cols, int32_t F,
                        const double* y_value, const double* class_weight, const double* sample_weight_host,
-                       const HostLabelStats* hls, const rgbm_params& p, rgbm_train_stats* stats) {
+                       const HostLabelStats* hls, const rgbm_params& p, rgbm_train_stats* stats, bool view_stats = false) {
     using namespace rg;
     check_fit_args(tab, target_col, feat_cols, F, y_value, p);
     if (F > 65535) throw std::invalid_argument("more than 65535 feature columns");
@@ -1630,6 +1644,12 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     }
     st.it.alloc(1); st.it.zero(s);
     st.alloc_fx_parts();
+    // the distinct-row view: the statistics count the rows the kernels stream, so the view's own training rows are counted once
+    unsigned int view_train_rows = 0;
+    if (view_stats && stats) {
+        hipLaunchKernelGGL(k_count_train, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, s, st.d_ycol, (long long)st.N, st.counter.p);
+        st.counter.download(&view_train_rows, 1, s);      // (read after the final synchronise; the level grower does not use the counter)
+    }
 
     if (st.sw.timing) HIPCHK(hipStreamSynchronize(s));
     const double t_setup = now();
@@ -1660,6 +1680,14 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
         float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev_begin.e, ev_end.e));
         const int nranks = st.dp ? g_comm.nranks : 1;
         fill_train_stats(stats, ms, st.timers, ht, p, st.level_mode, st.use_bagging, nranks, st.N, st.h.n_train, F, lg ? lg->root_feats : F, st.K, lg ? lg->statrows : 0);
+        if (view_stats && st.level_mode && st.h.n_train > 0) {
+            // n_train and the device's counter weigh a row by its multiplicity.  Streamed rows: the root passes exactly (every training row of the
+            // view, once per tree); the level passes pro rata (a built child's share of distinct rows is not counted on the device)
+            const int64_t root_w = stats->root_rows, level_w = std::max<int64_t>(0, stats->hist_rows - root_w);
+            stats->root_rows = root_w > 0 ? (int64_t)st.NE * st.K * (int64_t)view_train_rows : 0;
+            stats->hist_rows = stats->root_rows + (int64_t)((double)level_w * (double)view_train_rows / (double)st.h.n_train + 0.5);
+            stats->hist_bytes = stats->hist_rows * ((int64_t)F + 8);
+        }
     }
     return st.h.model.release();
 }
@@ -2273,6 +2301,67 @@ ChainStage& chain_stage() { static ChainStage* c = new ChainStage(); return *c; 
 struct ThreadJoiner { std::vector<std::thread> th; ~ThreadJoiner() { for (auto& t : th) if (t.joinable()) t.join(); } };
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------
+// The distinct-row view of rgbm_table_train.  Three quarters of the rows of the tables this library repairs are exact copies of
+// another row, and a row with a multiplicity gives the expanded table's model byte for byte (rgbm_table_set_row_multiplicity): the table is
+// deduplicated ONCE (rgbm_host.h: rgbm_distinct_view) and every target is trained on the result.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// May a fit of this shape use the view at all?  No device, no table: exactly what the multiplicity trainer honours (train_core), plus the
+// row-count floor.  rgbm_table_train takes no per-row weights, so that condition of train_core is always met here.
+bool distinct_view_may(int64_t rows, int32_t f, const rgbm_params& p, bool table_has_mult, int64_t min_rows) {
+    if (table_has_mult) return false;                                             // multiplicities of its own: never a view
+    if (p.reserved & (RGBM_FLAG_ROW_SHARDED | RGBM_FLAG_WHOLE_TABLE)) return false;
+    if (p.max_depth < 1 || p.max_depth > rg::LV_MAX_DEPTH) return false;          // the level grower
+    if (p.bagging_freq > 0 && p.bagging_fraction < 1.0) return false;             // LightGBM draws the bag per ORIGINAL row
+    if (p.objective != 0 && p.objective != 1) return false;                       // classifiers
+    if (f < 1 || f > 32 || f % 16 == 0) return false;                             // byte 15 of the last 16-feature record carries the multiplicity
+    return rows >= min_rows;
+}
+
+// the shapes the trainer refused on a table version are remembered by this key: what its refusals depend on besides the bin counts
+uint64_t view_shape_key(const rgbm_table& t, const int32_t* feat_cols, int32_t f, const rgbm_params& p, const RunSwitches& sw) {
+    std::vector<int32_t> nc((size_t)f);
+    for (int i = 0; i < f; ++i) nc[(size_t)i] = (feat_cols[i] >= 0 && feat_cols[i] < t.c) ? t.n_codes[(size_t)feat_cols[i]] : -1;
+    std::sort(nc.begin(), nc.end());
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto mix = [&](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; };
+    mix((uint64_t)f); mix((uint64_t)p.max_depth); mix((uint64_t)p.max_bin); mix(sw.joint_root ? 1 : 0); mix(sw.mt_acc2 ? 1 : 0);
+    for (int32_t v : nc) mix((uint64_t)(uint32_t)v);
+    return h;
+}
+
+// The view of `t` for a fit of shape `key`, or null: built by the first caller (the others wait on view.mu), one pass per table version.
+std::shared_ptr<const rgbm_table> acquire_view(const rgbm_table& t, uint64_t key, const RunSwitches& sw, uint64_t* version) {
+    rgbm_distinct_view& v = t.view;
+    std::lock_guard<std::mutex> lk(v.mu);
+    *version = v.version;
+    if (std::find(v.refused.begin(), v.refused.end(), key) != v.refused.end()) return nullptr;
+    const int64_t max_rows = (int64_t)std::floor(sw.distinct_max_ratio * (double)t.n);
+    if (v.state == RGBM_VIEW_NOT_WORTH && v.rows <= max_rows) v.state = RGBM_VIEW_NONE;      // (the ratio was raised since)
+    if (v.state == RGBM_VIEW_NONE) {
+        const auto t0 = std::chrono::steady_clock::now();
+        try {
+            rgh::DistinctOut r = rgh::distinct_rows_device(t, nullptr, max_rows);
+            ++v.builds; v.rows = r.rows;
+            if (r.tab) { v.tab = std::shared_ptr<const rgbm_table>(r.tab.release()); v.state = RGBM_VIEW_BUILT; }
+            else v.state = RGBM_VIEW_NOT_WORTH;
+        } catch (const rgh::distinct_cannot& e) {
+            v.state = RGBM_VIEW_CANNOT; v.rows = 0;
+            if (sw.timing) fprintf(stderr, "[rgbm] distinct view: cannot (%s)\n", e.what());
+        } catch (const rgh::device_oom& e) {
+            v.state = RGBM_VIEW_CANNOT; v.rows = 0;
+            if (sw.timing) fprintf(stderr, "[rgbm] distinct view: cannot (%s)\n", e.what());
+        }
+        if (sw.timing && v.state != RGBM_VIEW_CANNOT)
+            fprintf(stderr, "[rgbm] distinct view: %lld of %lld rows, %s, build %.1f ms\n", (long long)v.rows, (long long)t.n, v.state == RGBM_VIEW_BUILT ? "built" : "not worth it",
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    if (v.state != RGBM_VIEW_BUILT || v.rows > max_rows) return nullptr;
+    return v.tab;
+}
+}  // namespace
+
 // =============================================================================================
 // C-ABI
 // =============================================================================================
@@ -2327,6 +2416,7 @@ RGBM_EXPORT void rgbm_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
 RGBM_EXPORT int rgbm_table_set_column_kind(rgbm_table* t, int32_t col, int32_t kind) {
     if (!t || col < 0 || col >= t->c || kind < 0 || kind > 1) return fail(RGBM_ERR_ARG, "rgbm_table_set_column_kind: bad argument");
+    rgh::ViewWrite view_wr(t);
     if (t->col_kind.size() < (size_t)t->c) t->col_kind.resize(t->c, 0);
     t->col_kind[col] = (uint8_t)kind;
     return RGBM_OK;
@@ -2335,6 +2425,7 @@ RGBM_EXPORT int rgbm_table_set_column_kind(rgbm_table* t, int32_t col, int32_t k
 RGBM_EXPORT int rgbm_table_set_column_values(rgbm_table* t, int32_t col, const double* values, int32_t n) {
     if (!t || col < 0 || col >= t->c || n < 0 || (n > 0 && !values)) return fail(RGBM_ERR_ARG, "rgbm_table_set_column_values: bad argument");
     return guarded([&]() {
+        rgh::ViewWrite view_wr(t);
         if (n != 0 && n != t->n_codes[col]) throw std::invalid_argument("rgbm_table_set_column_values: one value per code of the column is needed");
         for (int i = 1; i < n; ++i) if (!(values[i - 1] < values[i])) throw std::invalid_argument("rgbm_table_set_column_values: values must be strictly ascending");
         if (t->col_values.size() < (size_t)t->c) t->col_values.resize(t->c);
@@ -2359,6 +2450,23 @@ RGBM_EXPORT int rgbm_table_train(const rgbm_table* t, int32_t target_col, const 
     if (!t || !feat_cols || !p || !out) return fail(RGBM_ERR_ARG, "rgbm_table_train: bad argument");
     return guarded([&]() {
         use_device(t->device);
+        // the distinct-row view: same model, a fraction of the rows.  The guard stays the trainer: what it refuses on the view (RGBM_ERR_PARAM:
+        // a two-chunk shape outside the one-pass form or the 15 joint-bin groups, RGBM_MT_ACC2=0, RGBM_JOINT_ROOT=0) trains on the whole table below
+        const RunSwitches sw = read_switches();
+        if (sw.distinct && sw.grower != 2 && distinct_view_may(t->n, f, *p, t->has_mult, sw.distinct_min_rows)) {
+            const uint64_t key = view_shape_key(*t, feat_cols, f, *p, sw);
+            uint64_t version = 0;
+            if (std::shared_ptr<const rgbm_table> view = acquire_view(*t, key, sw, &version)) {
+                try {
+                    *out = train_core(*view, target_col, feat_cols, f, y_value, class_weight, nullptr, nullptr, *p, stats, true);
+                    return RGBM_OK;
+                } catch (const std::invalid_argument& e) {
+                    if (sw.timing) fprintf(stderr, "[rgbm] distinct view: target %d refused (%s), training the whole table\n", target_col, e.what());
+                    std::lock_guard<std::mutex> lk(t->view.mu);
+                    if (t->view.version == version) t->view.refused.push_back(key);
+                }
+            }
+        }
         try {
             *out = train_core(*t, target_col, feat_cols, f, y_value, class_weight, nullptr, nullptr, *p, stats);
         } catch (...) {
@@ -2368,6 +2476,20 @@ RGBM_EXPORT int rgbm_table_train(const rgbm_table* t, int32_t target_col, const 
         }
         return RGBM_OK;
     });
+}
+
+RGBM_EXPORT int rgbm_distinct_view_eligible(int64_t rows, int32_t f, const rgbm_params* p, int32_t table_has_mult, int64_t min_rows) {
+    if (!p) return fail(RGBM_ERR_ARG, "rgbm_distinct_view_eligible: bad argument");
+    return distinct_view_may(rows, f, *p, table_has_mult != 0, min_rows > 0 ? min_rows : DISTINCT_MIN_ROWS) ? 1 : 0;
+}
+
+RGBM_EXPORT int rgbm_table_distinct_view_info(const rgbm_table* t, int32_t* state, int64_t* rows, int64_t* builds) {
+    if (!t) return fail(RGBM_ERR_ARG, "rgbm_table_distinct_view_info: bad argument");
+    std::lock_guard<std::mutex> lk(t->view.mu);
+    if (state) *state = t->view.state;
+    if (rows) *rows = t->view.rows;
+    if (builds) *builds = t->view.builds;
+    return RGBM_OK;
 }
 
 RGBM_EXPORT int rgbm_table_train_batch(const rgbm_fit_spec* fits, int32_t n_fits, rgbm_model** out_models, int32_t* out_status) {
@@ -2555,6 +2677,7 @@ RGBM_EXPORT int rgbm_table_set_row_multiplicity(rgbm_table* t, const uint8_t* mu
     if (!t) return fail(RGBM_ERR_ARG, "rgbm_table_set_row_multiplicity: bad argument");
     return guarded([&]() {
         use_device(t->device);
+        rgh::ViewWrite view_wr(t);
         if (!mult) { t->has_mult = false; t->mult_total = 0; return RGBM_OK; }
         int64_t tot = 0;
         for (int64_t i = 0; i < t->n; ++i) { if (mult[i] == 0) throw std::invalid_argument("rgbm_table_set_row_multiplicity: a multiplicity of 0"); tot += mult[i]; }
@@ -2576,6 +2699,7 @@ RGBM_EXPORT int rgbm_table_repair_chain(rgbm_table* t, const rgbm_model* const* 
     if (n_rows == 0 || T == 0) return RGBM_OK;
     return guarded([&]() {
         use_device(t->device);
+        rgh::ViewWrite view_wr(t);
         StreamGuard sg;
         return chain_device(const_cast<rgbm_model* const*>(models), T, target_col, feat_cols, feat_off, nullptr, nullptr, t->codes.p, t->n, row_begin, n_rows,
                             t->device, sg.s, out_label, out_prob);
@@ -2816,6 +2940,7 @@ RGBM_EXPORT int rgbm_table_repair_chain_gather(rgbm_table* t, const rgbm_model* 
         return fail(RGBM_ERR_ARG, "rgbm_table_repair_chain_gather: bad argument");
     return guarded([&]() {
         use_device(t->device);
+        rgh::ViewWrite view_wr(t);
         Comm& c = g_comm;
         const int nr = std::max(1, c.nranks);
         StreamGuard sg; hipStream_t s = sg.s;

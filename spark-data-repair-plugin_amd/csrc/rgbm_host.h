@@ -116,7 +116,28 @@ void predict_proba_device(const rgbm_model* m, int device, hipStream_t s, const 
                           double* d_proba);
 void model_shape(const rgbm_model* m, int32_t* objective, int32_t* num_class, int32_t* n_features);
 
+// what the distinct-row view remembers as "cannot": the two refusals of the distinct pass that depend on the table's size alone, and a refused allocation
+struct distinct_cannot : std::invalid_argument { using std::invalid_argument::invalid_argument; };
+struct device_oom : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// the body of rgbm_table_distinct_rows (rgbm_prep.hip), shared with the distinct-row view; throws.  inverse_host_out [n] may be null: then no
+// inverse is computed and nothing but two counters leaves the device.  max_rows >= 0: a result of more rows is counted (rows) but not made (tab stays null)
+struct DistinctOut { std::unique_ptr<rgbm_table> tab; int64_t rows = 0; };
+DistinctOut distinct_rows_device(const rgbm_table& t, int64_t* inverse_host_out, int64_t max_rows);
+
 }  // namespace rgh
+
+// The DISTINCT-ROW VIEW of a table (rgbm_table_train trains on it wherever the model is the same bytes and it pays): the table that
+// rgbm_table_distinct_rows makes, built lazily by the first training call that wants it, and the outcome of that build.
+enum { RGBM_VIEW_NONE = 0, RGBM_VIEW_BUILT = 1, RGBM_VIEW_NOT_WORTH = 2, RGBM_VIEW_CANNOT = 3 };
+struct rgbm_distinct_view {
+    std::mutex mu;                               // its own mutex, never prep_mu (the distinct pass takes prep_mu itself); held for the whole build: concurrent callers wait
+    uint64_t version = 0;                        // of the table's contents; every writing entry point bumps it (rgh::ViewWrite)
+    int state = RGBM_VIEW_NONE; int64_t rows = 0; int64_t builds = 0;
+    std::shared_ptr<const rgbm_table> tab;       // state BUILT only; a fit in flight holds its own reference
+    std::vector<uint64_t> refused;               // fit shapes the multiplicity trainer refused on this version (rgbm.hip: view_shape_key)
+    void drop() { ++version; state = RGBM_VIEW_NONE; rows = 0; tab.reset(); refused.clear(); }
+};
 
 // the label-encoded table, resident in HBM: int32 codes [c][n], column-major, -1 = NULL
 struct rgbm_table {
@@ -144,5 +165,23 @@ struct rgbm_table {
     mutable std::vector<int32_t> pc_x, pc_y, pc_dx, pc_dy, pc_nbins; mutable std::vector<long long> pc_off; mutable std::vector<uint8_t> pc_has_lut;
     // the cluster of every row after the last rgbm_table_kmeans_assign call (int32 [n]); it leaves the device through rgbm_table_kmeans_read
     mutable rgh::DevBuf<int32_t> km_assign; mutable bool km_valid = false;
+    mutable rgbm_distinct_view view;
     ~rgbm_table() { if (stream) (void)hipStreamDestroy(stream); }
 };
+
+namespace rgh {
+// Every entry point that can write what the distinct-row view was made from -- codes, n_codes, column kinds or values, multiplicities --
+// holds one of these for the length of the call: the view is dropped and the version bumped when the call begins and again when it ends,
+// so a fit that starts in between (which the caller must not do anyway) never leaves a view of half-written codes behind.  Declared BEFORE
+// the call takes prep_mu: view.mu is never taken under prep_mu.  The entry points:
+//   rgbm_table_repair_chain, rgbm_table_repair_chain_gather, rgbm_table_null_cells, rgbm_table_write_cells, rgbm_table_rule_fill,
+//   rgbm_table_set_column_kind, rgbm_table_set_column_values, rgbm_table_set_row_multiplicity.
+// (rgbm_table_repair_pmf and rgbm_table_repair_pmf_weighted return candidates and write no cell: they are not in the list.)
+struct ViewWrite {
+    const rgbm_table* t;
+    static void drop(const rgbm_table* t) { if (t) { std::lock_guard<std::mutex> lk(t->view.mu); t->view.drop(); } }
+    explicit ViewWrite(const rgbm_table* t_) : t(t_) { drop(t); }
+    ViewWrite(const ViewWrite&) = delete; ViewWrite& operator=(const ViewWrite&) = delete;
+    ~ViewWrite() { drop(t); }
+};
+}  // namespace rgh

@@ -112,6 +112,13 @@ __global__ void k_iota_train(const int32_t* __restrict__ ycol, long long N, int3
     if (on) out[base + __popcll(m & ((1ull << lane) - 1))] = (int32_t)r;
 }
 
+// training rows of a table, counted only (the distinct-row view's statistics)
+__global__ __launch_bounds__(256) void k_count_train(const int32_t* __restrict__ ycol, long long N, unsigned int* __restrict__ counter) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long m = __ballot(r < N && ycol[r] >= 0);
+    if (lane_id() == 0 && m) atomicAdd(counter, (unsigned)__popcll(m));
+}
+
 // ------------------------------------------------------------------------------------------------
 // K2: gradients.  thread per row (grid-stride); scores read coalesced per class.
 // ------------------------------------------------------------------------------------------------

@@ -744,6 +744,7 @@ RGBM_EXPORT int rgbm_table_null_cells(rgbm_table* t, const int64_t* rows, const 
         return fail(RGBM_ERR_ARG, "rgbm_table_null_cells: bad argument");
     return guarded([&]() {
         use_device(t->device);
+        rgh::ViewWrite view_wr(t);
         check_cols(*t, target_cols, n_targets, "rgbm_table_null_cells");
         if (n_cells == 0 || n_targets == 0) return RGBM_OK;
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
@@ -764,6 +765,7 @@ RGBM_EXPORT int rgbm_table_write_cells(rgbm_table* t, const int64_t* rows, const
     if (!t || n_cells < 0 || (n_cells > 0 && (!rows || !cols || !codes))) return fail(RGBM_ERR_ARG, "rgbm_table_write_cells: bad argument");
     return guarded([&]() {
         use_device(t->device);
+        rgh::ViewWrite view_wr(t);
         if (n_cells == 0) return RGBM_OK;
         for (int64_t i = 0; i < n_cells; ++i)
             if (cols[i] >= 0 && cols[i] < t->c && codes[i] >= t->n_codes[cols[i]]) throw std::invalid_argument("rgbm_table_write_cells: code outside the column's dictionary");
@@ -1418,6 +1420,7 @@ RGBM_EXPORT int rgbm_table_rule_fill(rgbm_table* t, int32_t y_col, int32_t x_col
         return fail(RGBM_ERR_ARG, "rgbm_table_rule_fill: bad argument");
     return guarded([&]() {
         use_device(t->device);
+        rgh::ViewWrite view_wr(t);
         if (n_rows == 0) return RGBM_OK;
         const int ny = t->n_codes[y_col];
         for (int i = 0; i < n_lut; ++i)
@@ -1796,13 +1799,12 @@ __global__ __launch_bounds__(256) void k_dr_inverse(const int* __restrict__ slot
 
 }  // namespace
 
-extern "C" {
-
-RGBM_EXPORT int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, int64_t* n_out, int64_t* inverse_out) {
-    if (!t || !out || !n_out || t->n <= 0 || t->c <= 0) return fail(RGBM_ERR_ARG, "rgbm_table_distinct_rows: bad argument");
-    if (t->n > (1ll << 30)) return fail(RGBM_ERR_PARAM, "rgbm_table_distinct_rows: more than 2^30 rows");
-    if (t->has_mult) return fail(RGBM_ERR_PARAM, "rgbm_table_distinct_rows: the table carries row multiplicities itself (clear them first)");
-    return guarded([&]() {
+// the one copy of the pass: rgbm_table_distinct_rows and the distinct-row view of rgbm_table_train (rgbm.hip) both run it
+rgh::DistinctOut rgh::distinct_rows_device(const rgbm_table& tab, int64_t* inverse_out, int64_t max_rows) {
+    const rgbm_table* t = &tab;
+    if (t->n > (1ll << 30)) throw distinct_cannot("rgbm_table_distinct_rows: more than 2^30 rows");
+    if (t->has_mult) throw std::invalid_argument("rgbm_table_distinct_rows: the table carries row multiplicities itself (clear them first)");
+    {
         use_device(t->device);
         const long long n = t->n; const int c = t->c;
         // the key words: as few as the radices need (pipeline.distinct_rows: a new word where the next radix would pass 2^63)
@@ -1823,7 +1825,7 @@ RGBM_EXPORT int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, 
         size_t mem_free = 0, mem_total = 0;
         HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
         if (work > mem_total / 2)
-            throw std::invalid_argument("rgbm_table_distinct_rows: the working set (" + std::to_string(work >> 20) + " MB) exceeds half of the device memory");
+            throw distinct_cannot("rgbm_table_distinct_rows: the working set (" + std::to_string(work >> 20) + " MB) exceeds half of the device memory");
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
         DevBuf<unsigned long long> d_radix((size_t)c), keys((size_t)W * n);
         DevBuf<int32_t> d_word((size_t)c);
@@ -1860,6 +1862,7 @@ RGBM_EXPORT int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, 
         HIPCHK(hipMemcpyAsync(&M, goff.p + G, sizeof(long long), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (M < G || M > n) throw std::runtime_error("rgbm_table_distinct_rows: inconsistent output row count");
+        if (max_rows >= 0 && M > max_rows) { DistinctOut res; res.rows = M; return res; }      // (the view: not worth a table)
         std::unique_ptr<rgbm_table> o(new rgbm_table());
         o->device = t->device; o->n = M; o->c = c; o->n_codes = t->n_codes; o->col_values = t->col_values; o->col_kind = t->col_kind;
         o->codes.alloc((size_t)M * c); o->mult.alloc((size_t)M);
@@ -1878,8 +1881,19 @@ RGBM_EXPORT int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, 
         }
         HIPCHK(hipStreamSynchronize(s));
         o->has_mult = true; o->mult_total = n;
-        *n_out = M;
-        *out = o.release();
+        DistinctOut res; res.rows = M; res.tab = std::move(o);
+        return res;
+    }
+}
+
+extern "C" {
+
+RGBM_EXPORT int rgbm_table_distinct_rows(const rgbm_table* t, rgbm_table** out, int64_t* n_out, int64_t* inverse_out) {
+    if (!t || !out || !n_out || t->n <= 0 || t->c <= 0) return fail(RGBM_ERR_ARG, "rgbm_table_distinct_rows: bad argument");
+    return guarded([&]() {
+        DistinctOut res = distinct_rows_device(*t, inverse_out, -1);
+        *n_out = res.rows;
+        *out = res.tab.release();
         return RGBM_OK;
     });
 }

@@ -47,6 +47,8 @@ PARAM_DEFAULTS = dict(objective=1, num_class=2, n_estimators=300, num_leaves=31,
 
 FLAG_ROW_SHARDED = 1
 FLAG_NO_MODEL = 2
+FLAG_WHOLE_TABLE = 4
+VIEW_STATES = ("none", "built", "not worth it", "cannot")
 
 
 def make_params(**kw):
@@ -54,6 +56,8 @@ def make_params(**kw):
     kw = dict(kw)
     if kw.pop("row_sharded", False):
         d["reserved"] = d.get("reserved", 0) | FLAG_ROW_SHARDED
+    if kw.pop("whole_table", False):
+        d["reserved"] = d.get("reserved", 0) | FLAG_WHOLE_TABLE
     if not kw.pop("want_model", True):
         d["reserved"] = d.get("reserved", 0) | FLAG_NO_MODEL
     for k, v in kw.items():
@@ -89,6 +93,9 @@ def lib():
                      "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
                      "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read"):
             getattr(l, name).restype = C.c_int
+        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible"):
+            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view)
+                getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
         l.rgbm_model_free.restype = None
@@ -112,7 +119,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
-    "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read",
+    "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
 ]
 
 COMM_ID_BYTES = 128
@@ -383,6 +390,15 @@ class RgbmFitSpec(C.Structure):
     _fields_ = [("table", C.c_void_p), ("target_col", C.c_int32), ("n_features", C.c_int32), ("feat_cols", C.POINTER(C.c_int32)),
                 ("y_value", C.POINTER(C.c_double)), ("class_weight", C.POINTER(C.c_double)), ("params", C.POINTER(RgbmParams)),
                 ("valid_table", C.c_void_p), ("valid_label_out", C.POINTER(C.c_int32)), ("valid_value_out", C.POINTER(C.c_double))]
+
+
+def distinct_view_eligible(rows, f, table_has_mult=False, min_rows=0, **params):
+    """Whether a Table.train of this shape MAY use the table's distinct-row view (rgbm_distinct_view_eligible; no device needed)."""
+    p = make_params(**params)
+    r = lib().rgbm_distinct_view_eligible(C.c_int64(rows), C.c_int32(f), C.byref(p), C.c_int32(1 if table_has_mult else 0), C.c_int64(min_rows))
+    if r < 0:
+        _check(r, "rgbm_distinct_view_eligible")
+    return bool(r)
 
 
 def train_batch(fits):
@@ -905,6 +921,13 @@ class Table:
         _check(lib().rgbm_table_distinct_rows(self.h, C.byref(h), C.byref(m), _p(inv, C.c_int64)), "rgbm_table_distinct_rows")
         d = Table._adopt(h, self.device_id)
         return (d, inv) if want_inverse else d
+
+    def distinct_view_info(self):
+        """The distinct-row view train() keeps for this table (rgbm_table_distinct_view_info): its state ("none", "built", "not worth it",
+        "cannot"), its rows, and the distinct passes run for this table object."""
+        st, rows, builds = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        _check(lib().rgbm_table_distinct_view_info(self.h, C.byref(st), C.byref(rows), C.byref(builds)), "rgbm_table_distinct_view_info")
+        return {"state": VIEW_STATES[st.value], "rows": int(rows.value), "builds": int(builds.value)}
 
     def repair_chain_gather(self, models, target_col, feat_cols, row_begin=0, n_rows=None):
         """The chained repair of THIS rank's rows, the outputs all-gathered over the calling thread's communicator on the device (C2):
