@@ -385,6 +385,17 @@ int rgbm_table_rule_fill(rgbm_table* t, int32_t y_col, int32_t x_col /* -1: cons
  * -1 everywhere. */
 int rgbm_nearest_values(int32_t device_id, const int32_t* a_cp, const int64_t* a_off, int64_t n_a, const int32_t* b_cp, const int64_t* b_off,
                         int64_t n_b, const double* cost /* [n_a][n_b] or NULL */, double threshold, int32_t* nearest_out /* [n_a] */);
+/* ---- LOF in code space (LOFOutlierErrorDetector: scikit-learn's LocalOutlierFactor(novelty=False) on one attribute; repair/lof_codes.py) ----
+ * The local outlier factor of every entry of a sorted dictionary: values [d] ascending and finite, counts [d] >= 1 rows per entry (two rows
+ * in all at least), k_ = max(1, min(k, rows - 1)) neighbours.  The neighbours of an entry are min(count - 1, k_) copies of itself, then the
+ * nearest entries outward by |v_c - v_j|, each whole until k_ is reached and the last one partially; two candidates at one distance of which
+ * only one fits are a TIE, resolved to the left and counted.  score = the factor (the negated negative_outlier_factor_), float64, sums over
+ * the window's entries in ascending order; bit c of flag_bits_out is set when -score < -threshold.  info_out = {entries with a tie, entries
+ * with |score - threshold| <= threshold * 2^-40}.  RGBM_ERR_ARG: d < 1, k outside 1 .. 64, a count < 1, fewer than two rows in all, values
+ * that are not ascending or not finite. */
+int rgbm_lof_1d(int32_t device_id, const double* values /* [d], ascending, finite */, const int64_t* counts /* [d], >= 1 */,
+                int32_t d, int32_t k /* 1..64 */, double threshold /* 1.5 */,
+                double* score_out /* [d] or NULL */, uint64_t* flag_bits_out /* [ceil(d/64)] */, int64_t* info_out /* [2] = {n_ties, n_near} */);
 /* ---- q-gram k-means in code space (RepairMisc.splitInputTable; reference RepairMiscApi.scala:52-153; repair/qgram_kmeans.py) ----
  * One Lloyd assignment step over the resident table.  cols [n_cols <= 1024]: the attributes, code_off[j]: where the dictionary of cols[j]
  * starts among the d_tot dictionary entries of all of them.  p: [d_tot][k] row-major float64 (-2 E C^T), h: [k] (|C_k|^2).  The score of

@@ -91,7 +91,7 @@ def lib():
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
                      "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
                      "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
-                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read"):
+                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d"):
             getattr(l, name).restype = C.c_int
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible"):
             if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view)
@@ -121,6 +121,8 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
 ]
+# exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
+EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
 
 COMM_ID_BYTES = 128
 
@@ -548,6 +550,23 @@ def nearest_values(a=None, b=None, cost=None, threshold=0.0, device_id=0):
                                      _p(b_cp, C.c_int32), _p(b_off, C.c_int64), C.c_int64(len(b_off) - 1), None, C.c_double(threshold),
                                      _p(out, C.c_int32)), "rgbm_nearest_values")
     return out
+
+
+def lof_1d(values, counts, k=20, threshold=1.5, want_scores=True, device_id=0):
+    """The local outlier factor of every entry of a sorted dictionary (include/rgbm.h rgbm_lof_1d; the statement is
+    repair.lof_codes.lof_codes): ``values`` float64 [d] ascending, ``counts`` rows per entry -> (scores float64 [d] or None,
+    flag words uint64 [ceil(d / 64)], n_ties, n_near)."""
+    v = _f64(values).reshape(-1)
+    m = np.ascontiguousarray(counts, np.int64).reshape(-1)
+    if len(v) != len(m):
+        raise ValueError("values and counts must have one length")
+    score = np.zeros(len(v), np.float64) if want_scores else None
+    bits = np.zeros((len(v) + 63) // 64, np.uint64)
+    info = np.zeros(2, np.int64)
+    _check(lib().rgbm_lof_1d(C.c_int32(device_id), _p(v, C.c_double), _p(m, C.c_int64), C.c_int32(len(v)), C.c_int32(int(k)),
+                             C.c_double(threshold), _p(score, C.c_double) if want_scores else None, _p(bits, C.c_uint64),
+                             _p(info, C.c_int64)), "rgbm_lof_1d")
+    return score, bits, int(info[0]), int(info[1])
 
 
 class DcPred(C.Structure):

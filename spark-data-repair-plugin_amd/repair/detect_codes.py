@@ -1,4 +1,5 @@
-"""The value detectors of `repair.errors` (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector) as predicates on a column's
+"""The value detectors of `repair.errors` (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector, and LOFOutlierErrorDetector through
+repair.lof_codes) as predicates on a column's
 DICTIONARY CODES -- what `Table.detect_cells` (rgbm_table_detect_cells, csrc/rgbm_prep.hip) takes.
 
 A column of the label-encoded table holds codes 0..D-1 into its dictionary (`pipeline.encode_frame`: the distinct non-NULL values,
@@ -16,6 +17,7 @@ import numpy as np
 import pandas as pd
 
 NO_RANGE = (0, -1)
+LOF_MAX_RANGE = 1e150      # the LOF kind: beyond it the square of a difference leaves float64 (1.3e154) or comes close
 
 
 def pack_bits(flags):
@@ -99,9 +101,17 @@ def kept_code_range(values, lo, hi):
     return int(np.searchsorted(values, lo, side="left")), int(np.searchsorted(values, hi, side="right")) - 1
 
 
-def build_descriptors(detectors, columns, dicts, dtypes, counts, targets, null_all=False):
+def build_descriptors(detectors, columns, dicts, dtypes, counts, targets, null_all=False, lof=None, n_rows=None):
     """Per-column descriptors of `Table.detect_cells` for the detectors  dict(kind='regex', attr, regex) /
-    dict(kind='domain', attr, values, autofill, min_count_thres) / dict(kind='outlier', attrs=[continuous target attributes]).
+    dict(kind='domain', attr, values, autofill, min_count_thres) / dict(kind='outlier', attrs=[continuous target attributes]) /
+    dict(kind='lof', attrs=[continuous target attributes], k=20).
+
+    kind 'lof' (LOFOutlierErrorDetector; repair.lof_codes): `lof` is the callable (values, counts, k) -> (scores, flags, n_ties, n_near)
+    that evaluates the filled column's multiset -- the engine's `lof_codes` where it has one, `repair.lof_codes.lof_codes` when None --
+    and `n_rows` the rows of the table (rows minus the counted ones = the NULL cells, which the detector fills with the median).  A
+    column whose answer is not determined (a neighbour tie, a score within rounding of the threshold), that holds fewer than two rows,
+    that scikit-learn searches by brute force (k >= rows // 2: its x^2 + y^2 - 2xy distances are not the exact differences) or whose
+    values span more than LOF_MAX_RANGE (scikit-learn's squared distances overflow) raises `pipeline.NotResidentEligible`.
 
     columns: the table's attribute names; dicts[j]: dictionary of column j; dtypes: {attribute: dtype of the frame's column};
     counts: callable(j) -> rows per code of column j on the un-NULLed table (read only where a detector needs it); targets: the
@@ -163,6 +173,43 @@ def build_descriptors(detectors, columns, dicts, dtypes, counts, targets, null_a
                 elif klo <= khi:
                     s["lo"] = klo if s["lo"] is None else max(s["lo"], klo)
                     s["hi"] = khi if s["hi"] is None else min(s["hi"], khi)
+        elif kind == "lof":
+            from repair.lof_codes import filled_multiset, lof_codes
+            from repair.pipeline import NotResidentEligible
+            if n_rows is None:
+                raise ValueError("the LOF detector needs the table's row count")
+            for attr in d["attrs"]:
+                if attr not in tset or attr not in pos:
+                    continue
+                j = pos[attr]
+                vals = np.asarray(dicts[j], np.float64)
+                cnt = np.asarray(counts(j), np.int64)
+                n_null = int(n_rows) - int(cnt.sum())
+                fvals, fcnt, med_at, code_at = filled_multiset(vals, cnt, n_null)
+                n, k = int(fcnt.sum()), int(d.get("k", 20))
+                if n < 2:
+                    raise NotResidentEligible("LOF detector on `%s`: %d row(s), scikit-learn needs two" % (attr, n))
+                if k >= n // 2:
+                    # scikit-learn's algorithm='auto' then searches by brute force, with distances from x^2 + y^2 - 2xy: values that are
+                    # large next to their spread lose their differences there, and its answer is not |v_c - v_j|'s
+                    raise NotResidentEligible("LOF detector on `%s`: %d rows with %d neighbours, scikit-learn searches such a column by "
+                                              "brute force (k >= n // 2) and its distances are not exact" % (attr, n, k))
+                if not float(fvals[-1] - fvals[0]) <= LOF_MAX_RANGE:
+                    raise NotResidentEligible("LOF detector on `%s`: the values span more than %g, scikit-learn's squared distances "
+                                              "overflow" % (attr, LOF_MAX_RANGE))
+                _, bad, n_ties, n_near = (lof or lof_codes)(fvals, fcnt, k)
+                if n_ties + n_near > 0:
+                    raise NotResidentEligible("LOF detector on `%s`: %d value(s) whose neighbours are tied or whose score is within rounding of the "
+                                              "threshold (%d + %d)" % (attr, n_ties + n_near, n_ties, n_near))
+                bad = np.asarray(bad, bool)
+                f = np.zeros(len(vals), bool)
+                live = code_at >= 0
+                f[live] = bad[code_at[live]]
+                s = slot(attr)
+                s["kinds"].append(kind)
+                s["flags"] = f if s["flags"] is None else (s["flags"] | f)
+                if n_null > 0 and bad[med_at]:                 # the NULL cells hold the median
+                    s["null"] = True
         else:
             raise ValueError("unknown detector kind %r" % (kind,))
     out = []

@@ -91,6 +91,13 @@ class HipEngine:
             return _native.nearest_values(cost=cost, threshold=threshold, device_id=self.device_id)
         return _native.nearest_values(a, b, threshold=threshold, device_id=self.device_id)
 
+    def lof_codes(self, values, counts, k=20):
+        """`repair.lof_codes.lof_codes` on the device (rgbm_lof_1d), bit for bit: (lof float64 [D], flagged bool [D], n_ties, n_near)."""
+        from repair.detect_codes import unpack_bits
+        from repair.lof_codes import THRESHOLD
+        score, bits, n_ties, n_near = _native.lof_1d(values, counts, k=k, threshold=THRESHOLD, device_id=self.device_id)
+        return score, unpack_bits(bits, len(score)), n_ties, n_near
+
     def kmeans_assign(self, table, cols, code_off, p, h, first):
         """One assignment step of the q-gram k-means on a resident table (rgbm_table_kmeans_assign) -> (counts, sizes, n_changed)."""
         return table.kmeans_assign(cols, code_off, p, h, first)

@@ -20,9 +20,10 @@ import pandas as pd
 
 from repair import session
 from repair.costs import UpdateCostFunction
+from repair.detect_codes import LOF_MAX_RANGE
 from repair.encode import is_integral_column, is_numeric_column
-from repair.errors import (ConstraintErrorDetector, DomainValues, ErrorDetector, ErrorModel, GaussianOutlierErrorDetector, NullErrorDetector,
-                           RegExErrorDetector, parse_constraint, load_constraints, parse_and_verify_constraints, _to_sql_string)
+from repair.errors import (ConstraintErrorDetector, DomainValues, ErrorDetector, ErrorModel, GaussianOutlierErrorDetector, LOFOutlierErrorDetector,
+                           NullErrorDetector, RegExErrorDetector, parse_constraint, load_constraints, parse_and_verify_constraints, _to_sql_string)
 from repair.train import build_model, compute_class_nrow_stdv, rebalance_training_data, train_option_keys
 from repair.train import _opt_gpu_device_id as _train_opt_gpu_device_id
 from repair.utils import argtype_check, elapsed_time, get_option_value, job_group, setup_logger, to_list_str
@@ -103,6 +104,9 @@ class RepairModel():
     # new in this engine: the value detectors (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector) as code predicates on
     # the HBM-resident table (repair.detect_codes, `Table.detect_cells`)
     _opt_value_detectors_resident = _option("error.value_detectors.resident", False, bool, None, None)
+    # new in this engine: LOFOutlierErrorDetector on the HBM-resident table, evaluated once per dictionary entry (repair.lof_codes,
+    # rgbm_lof_1d); a column whose scikit-learn answer is not determined sends the run to the value-space path
+    _opt_lof_resident = _option("error.lof.resident", False, bool, None, None)
     # new in this engine: every parsed denial constraint (single-tuple constants, several IQs, LT / GT) on the HBM-resident table
     # (repair.dc_codes, `Table.detect_dc` / `Table.detect_row_bits`); `X -> Y` constraints take `Table.detect_constraint` either way
     _opt_constraints_resident = _option("error.constraints.resident", False, bool, None, None)
@@ -121,7 +125,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident,
-        _opt_value_detectors_resident, _opt_constraints_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -721,12 +725,18 @@ class RepairModel():
         types) qualify too: on the encoded table they are predicates on the dictionary codes (repair.detect_codes), found together
         with the NULL cells by one `Table.detect_cells` call.  The plan then carries `value_detectors`.
 
+        With `error.lof.resident` set, LOFOutlierErrorDetector (exactly this type) qualifies too: its factor is a function of the
+        dictionary entry (repair.lof_codes; `engine.lof_codes`, rgbm_lof_1d on the device), lowered to the same code predicates.  Not
+        for a table of so few rows that scikit-learn searches it by brute force (n_neighbors >= rows // 2: inexact distances), nor for
+        a column with an infinite value or a span beyond `detect_codes.LOF_MAX_RANGE` (scikit-learn raises there).
+
         With `error.constraints.resident` set, every other constraint `repair.dc_codes.check_constraint` accepts qualifies as well
         (single-tuple constants, several IQs, LT / GT): the plan carries its parsed predicates next to the `X -> Y` tuples and
         `pipeline.repair_frame` lowers them against the dictionaries.  A constraint that does not lower sends the run to the value-space
         path, as before, with the reason logged."""
         from repair.pipeline import constraint_to_columns
         value_resident = bool(self._get_option_value(*self._opt_value_detectors_resident))
+        lof_resident = bool(self._get_option_value(*self._opt_lof_resident))
         constraints_resident = bool(self._get_option_value(*self._opt_constraints_resident))
         general: List[Any] = []      # the parsed predicates of the constraints that are not `X -> Y`
         vdets: List[Dict[str, Any]] = []
@@ -763,6 +773,9 @@ class RepairModel():
                                       min_count_thres=d.min_count_thres))
             elif value_resident and type(d) is GaussianOutlierErrorDetector:
                 vdets.append(dict(kind="outlier", attrs=None))
+            elif lof_resident and type(d) is LOFOutlierErrorDetector:
+                # (`parallel_mode_threshold` / `num_parallelism` change nothing on the value-space path of this engine either)
+                vdets.append(dict(kind="lof", attrs=None, k=int(d.error_detector_cls().n_neighbors)))
             else:
                 return None
         from repair.utils import column_nunique
@@ -787,10 +800,13 @@ class RepairModel():
         if others and any(a in others for con in cons
                           for a in (list(con[0]) + [con[1]] if isinstance(con, tuple) else [r for p in con for r in p.references])):
             return None
-        if others and any(d["kind"] != "outlier" and d["attr"] in others for d in vdets):
+        if others and any(d["kind"] not in ("outlier", "lof") and d["attr"] in others for d in vdets):
             return None
-        if any(d["kind"] == "outlier" for d in vdets):
-            # the columns the outlier detector reads: plain numpy numeric ones only (`pd.to_numeric(.., errors="coerce")` of anything else
+        if any(d["kind"] == "lof" and d["k"] >= len(input_df) // 2 for d in vdets):
+            # scikit-learn searches so small a table by brute force, with inexact distances (`detect_codes.build_descriptors`)
+            return None
+        if any(d["kind"] in ("outlier", "lof") for d in vdets):
+            # the columns the outlier and LOF detectors read: plain numpy numeric ones only (`pd.to_numeric(.., errors="coerce")` of anything else
             # and the masked comparison of a nullable column stay with the pandas detector), integers within float64's exact range (the
             # dictionaries are float64)
             read = [c for c in continous_columns if c in cands]
@@ -800,8 +816,14 @@ class RepairModel():
                 if pd.api.types.is_integer_dtype(input_df[c]) and len(input_df) and input_df[c].notna().any() \
                         and float(input_df[c].abs().max()) >= 2.0 ** 53:
                     return None
+                if any(d["kind"] == "lof" for d in vdets) and len(input_df) and input_df[c].notna().any():
+                    # scikit-learn refuses an infinite value, and its squared distances overflow on a wider span: its errors to report
+                    x = input_df[c].to_numpy(dtype=np.float64)
+                    with np.errstate(over="ignore", invalid="ignore"):
+                        if not float(np.nanmax(x) - np.nanmin(x)) <= LOF_MAX_RANGE:
+                            return None
             for d in vdets:
-                if d["kind"] == "outlier":
+                if d["kind"] in ("outlier", "lof"):
                     d["attrs"] = list(read)
         plan = self._resident_plan(input_df, cands, continous_columns, domain_stats, compute_repair_candidate_prob, maximal_likelihood_repair)
         if plan is None:
@@ -908,6 +930,8 @@ class RepairModel():
                     # is the value-space detector's to report
                     try:
                         return build_descriptors(*a, **kw)
+                    except NotResidentEligible:
+                        raise
                     except Exception as e:  # noqa: BLE001
                         raise NotResidentEligible("value detectors: %s" % e)
 

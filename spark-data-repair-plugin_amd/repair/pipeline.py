@@ -714,11 +714,12 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     get regressors and `repaired` is the predicted number, rounded for integer columns); `constraints` are `X1,..,Xm -> Y`
     dependencies given as the tuple ([x names], y name), or any other parsed constraint as its list of `repair.errors.Predicate`
     (`repair.dc_codes.lower_constraint` turns it into a program on the codes); `error_cells` is a frame with `row_id` and `attribute` columns
-    (RepairModel.setErrorCells).  Regex / value-domain / outlier detectors come as `value_detectors`; LOF-style detectors stay with
-    `repair.model.RepairModel` (the value-space API).
+    (RepairModel.setErrorCells).  Regex / value-domain / outlier / LOF detectors come as `value_detectors`; any other scikit-learn
+    backed detector stays with `repair.model.RepairModel` (the value-space API).
 
     value_detectors: dict(detectors=[dict(kind='regex', attr, regex) | dict(kind='domain', attr, values, autofill, min_count_thres) |
-    dict(kind='outlier', attrs)][, build=callable(detectors, columns, dicts, dtypes, counts, targets, null_all) -> descriptors]) -- the
+    dict(kind='outlier', attrs) | dict(kind='lof', attrs, k)][, build=callable(detectors, columns, dicts, dtypes, counts, targets, null_all[, lof,
+    n_rows: with a 'lof' kind]) -> descriptors]) -- the
     detectors by attribute name and what turns them into per-column code predicates (default `repair.detect_codes.build_descriptors`).
     The descriptors are built after the upload, so `counts(j)` (rows per code of column j: autofill, quartiles) comes from the table;
     one `Table.detect_cells` call then finds their cells and the NULL cells.  The details hold `value_detectors`: per descriptor the
@@ -846,8 +847,10 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         if build is None:
             from repair.detect_codes import build_descriptors as build
         dets = list(value_detectors["detectors"])
+        # the LOF kind evaluates the filled column: it needs the NULL count (rows minus the counted ones) and the engine's `lof_codes`
+        extra = dict(lof=getattr(engine, "lof_codes", None), n_rows=len(df)) if any(d["kind"] == "lof" for d in dets) else {}
         return lambda table: build(dets, cols, dicts, dtypes, lambda j: table.count_codes(j)[0], list(targets),
-                                   null_all=bool(detect_nulls_))
+                                   null_all=bool(detect_nulls_), **extra)
 
     def build_and_run(cells_, detect_nulls_, constraints_, analyse=True):
         table = engine.upload_dictionaries(indices, remaps)
