@@ -312,6 +312,18 @@ int rgbm_table_gather_rows(const rgbm_table* t, const int64_t* rows, int64_t n_r
 /* Rows per code of one column (+ NULL count): class weights (train.py:39-40,105), domain statistics. */
 int rgbm_table_count_codes(const rgbm_table* t, int32_t col, int64_t* counts_out /* [n_codes[col]] */,
                            int64_t* n_null_out /* may be NULL */);
+/* Column statistics of a resident table in ONE call (RepairMiscApi.computeAndGetStats in code space; the statement is
+ * repair.table_stats.column_stats).  stats_out [n_cols][6] = {nulls, distinct, min_code, max_code, len_sum, len_max};
+ * edges_out [n_cols][n_bins + 1] or NULL when n_bins == 0.  len_lut[j]: int32 [n_codes[cols[j]]] or NULL.
+ * A column may be listed more than once.  1 <= n_bins <= 254 or 0.
+ * A code outside [0, n_codes) is NULL, as for rgbm_table_count_codes.  distinct = codes held by at least one row; min_code / max_code
+ * = the lowest / highest of them (-1: none); len_sum = sum(rows of code * len_lut[code]), len_max = the largest len_lut entry (>= 0) of
+ * an occurring code (both 0 without a LUT).  With m = the column's non-NULL rows: edges[0] = min_code and edges[i] = the smallest
+ * code whose cumulative non-NULL row count is >= (i * m + n_bins - 1) / n_bins (integer division); all -1 when m = 0.  The per-code
+ * counts stay on the device.  RGBM_ERR_ARG / RGBM_ERR_PARAM: n_cols < 1 or > 65535, a column outside the table, n_bins outside
+ * 0, 1..254, edges_out == NULL with n_bins > 0; a refused call leaves the table as it was. */
+int rgbm_table_column_stats(const rgbm_table* t, const int32_t* cols, int32_t n_cols, const int32_t* const* len_lut,
+                            int32_t n_bins, int64_t* stats_out, int32_t* edges_out);
 /* Encoding on the device (replaces the pandas encoders of python/repair/model.py:701-729): per column, Arrow-style
  * dictionary indices (idx < 0 = NULL) are mapped through remap[col][idx] (the rank of the dictionary value in
  * sorted order, or -1) into the code table. */

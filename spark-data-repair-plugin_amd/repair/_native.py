@@ -91,7 +91,7 @@ def lib():
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
                      "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
                      "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
-                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d"):
+                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats"):
             getattr(l, name).restype = C.c_int
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible"):
             if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view)
@@ -120,6 +120,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
+    "rgbm_table_column_stats",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -807,6 +808,28 @@ class Table:
         nn = C.c_int64(0)
         _check(lib().rgbm_table_count_codes(self.h, C.c_int32(col), _p(out, C.c_int64), C.byref(nn)), "rgbm_table_count_codes")
         return out, int(nn.value)
+
+    def column_stats(self, cols, len_luts=None, n_bins=0):
+        """Column statistics of the listed columns in one call (include/rgbm.h rgbm_table_column_stats), exactly the integers of
+        ``repair.table_stats.column_stats``: a dict of int64 [len(cols)] arrays ``nulls``, ``distinct``, ``min_code``, ``max_code``,
+        ``len_sum``, ``len_max`` and ``edges`` (int32 [len(cols)][n_bins + 1], None when n_bins == 0).  ``len_luts``: per listed column an
+        int32 [n_codes] array (the length of every dictionary entry) or None; a column may be listed more than once."""
+        from repair.table_stats import FIELDS
+        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
+        luts = [None] * len(cc) if len_luts is None else [None if l is None else _i32(np.asarray(l, np.int32).reshape(-1)) for l in len_luts]
+        if len(luts) != len(cc):
+            raise ValueError("one length LUT (or None) per listed column expected")
+        for c, l in zip(cc, luts):
+            if l is not None and 0 <= c < self.c and len(l) != int(self.n_codes[c]):
+                raise ValueError("the length LUT of column %d must hold one entry per code (%d)" % (c, int(self.n_codes[c])))
+        ptrs = (C.POINTER(C.c_int32) * max(len(cc), 1))(*[_p(l, C.c_int32) for l in luts])
+        stats = np.zeros((len(cc), len(FIELDS)), np.int64)
+        edges = np.full((len(cc), n_bins + 1), -1, np.int32) if n_bins > 0 else None
+        _check(lib().rgbm_table_column_stats(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), ptrs if any(l is not None for l in luts) else None,
+                                             C.c_int32(n_bins), _p(stats, C.c_int64), _p(edges, C.c_int32)), "rgbm_table_column_stats")
+        out = {f: stats[:, i].copy() for i, f in enumerate(FIELDS)}
+        out["edges"] = edges
+        return out
 
     def fd_map(self, x, y):
         """The rule model of the functional dependency x -> y (include/rgbm.h rgbm_table_fd_map): int32 [n_codes[x]], the single y code

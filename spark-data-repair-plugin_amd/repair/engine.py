@@ -106,6 +106,10 @@ class HipEngine:
         """The labels of the last `kmeans_assign` on this table (rgbm_table_kmeans_read)."""
         return table.kmeans_read()
 
+    def column_stats(self, table, cols, len_luts=None, n_bins=0):
+        """`repair.table_stats.column_stats` on a resident table (rgbm_table_column_stats), the same integers: the per-code counts stay on the device."""
+        return table.column_stats(cols, len_luts=len_luts, n_bins=n_bins)
+
     def repair_chain_gather(self, table, models, targets, feats, row_begin, n_rows):
         """C2 on device buffers: the chain over this rank's rows, labels / probabilities all-gathered over the rank's communicator before
         they leave the device (include/rgbm.h rgbm_table_repair_chain_gather) -> (labels, probs of ALL ranks' rows in rank order, first row of this rank)."""

@@ -2,8 +2,10 @@
 
 `repair` (apply predicted updates, RepairMiscApi.repairAttrsFrom), `flatten` (RepairMiscApi.flattenTable), `injectNull`
 (RepairMiscApi.injectNullAt, the error injector the synthetic benchmark tables use), `splitInputTable` (k-means over q-gram
-features, on the resident code table when a device is present: repair/qgram_kmeans.py), `toHistogram` and
-`toErrorMap`; `describe` (Spark's ANALYZE statistics) and `generateDepGraph` (graphviz output) stay unimplemented.
+features, on the resident code table when a device is present: repair/qgram_kmeans.py), `toHistogram`,
+`toErrorMap`, `describe` (the column statistics of Spark's ANALYZE, from per-code row counts: repair/table_stats.py) and
+`generateDepGraph` (the Graphviz text of DepGraph.computeDepGraph from dense pair counts: repair/depgraph.py); the last two run on the
+resident code table when a device is present and on their numpy statements otherwise, with the same result.
 """
 from typing import Any, Dict, List
 
@@ -145,7 +147,18 @@ class RepairMisc():
         return df
 
     def describe(self) -> DataFrame:
-        raise NotImplementedError("describe (Spark's ANALYZE column statistics) is outside the rebuilt path")
+        """Column statistics of an input table (RepairMiscApi.computeAndGetStats): [attrName, distinctCnt, min, max, nullCnt, avgLen,
+        maxLen, hist], one row per column in frame order (the reference's order is a hash map's; callers sort).  Option `num_bins`
+        (default 8, at most 254): the bins of the equi-height histogram of a numeric column.  The counts are exact where Spark's
+        are HyperLogLog++ sketches, and the histogram edges are the exact ranks ceil(i * m / num_bins) where Spark's are approximate
+        percentiles."""
+        self._check_required_options(["table_name"])
+        try:
+            n_bins = int(self.opts.get("num_bins", "8"))
+        except ValueError:
+            raise ValueError("Option 'num_bins' must be an integer, but '%s' found" % self.opts["num_bins"]) from None
+        from repair import table_stats
+        return table_stats.describe_frame(self._input(), n_bins=n_bins, engine=self._resident_engine())
 
     def toHistogram(self) -> DataFrame:
         """The value counts of the listed attributes (RepairMiscApi.convertToHistogram, :276-301): one row [attribute, histogram] per
@@ -184,4 +197,18 @@ class RepairMisc():
         return pd.DataFrame({rid: df[rid].to_numpy(), "error_map": ["".join(m) for m in marks]})
 
     def generateDepGraph(self) -> None:
-        raise NotImplementedError("generateDepGraph is outside the rebuilt path")
+        """Writes the dependency graph of an input table as `<path>/<filename_prefix>.dot` (DepGraph.generateDepGraph) and, when Graphviz's
+        `dot` is installed, its SVG rendering next to it.  Options: `target_attr_list` (default: every column), `max_domain_size`
+        (100), `max_attr_value_num` (30), `max_attr_value_length` (70), `pairwise_attr_stat_threshold` (1.0), `edge_label` and
+        `overwrite` (non-empty = on), `filename_prefix` ("depgraph")."""
+        self._check_required_options(["path", "table_name"])
+        from repair import depgraph
+        df = self._input()
+        attrs = [a.strip() for a in self._target_attr_list.split(",") if a.strip()]
+        self._check_attrs(df, attrs)
+        text = depgraph.compute_dep_graph(
+            df, attrs, max_domain_size=int(self.opts.get("max_domain_size", "100")), max_attr_value_num=int(self.opts.get("max_attr_value_num", "30")),
+            max_attr_value_length=int(self.opts.get("max_attr_value_length", "70")),
+            pairwise_attr_stat_threshold=float(self.opts.get("pairwise_attr_stat_threshold", "1.0")),
+            edge_label=len(self.opts.get("edge_label", "")) > 0, engine=self._resident_engine())
+        depgraph.write_dep_graph(text, self.opts["path"], "svg", self.opts.get("filename_prefix", "depgraph"), len(self.opts.get("overwrite", "")) > 0)
