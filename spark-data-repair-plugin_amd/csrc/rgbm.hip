@@ -14,8 +14,10 @@
 // There is NO CPU fallback in this library: without a HIP device every compute entry point
 // returns RGBM_ERR_NO_DEVICE (the CPU oracle under oracle/ is test infrastructure and is never
 // linked or loaded from here).
+//
+// The device-memory pool, the error text and the page-locked upload live in rgbm_runtime.hip, the communicator in rgbm_comm.hip; this file
+// holds the trainer, the batched trainer, the predictor, model I/O and the chained repair.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -38,411 +40,11 @@
 #include "rgbm_level.h"
 #include "rgbm_small.h"
 
-#define RGBM_VERSION 220   // numerics spec v2.2: float32 (g, h) as LightGBM computes them, exact integer histogram sums on a fixed-point grid chosen per class tree and boosting iteration (rgbm_numerics.h)
 
-namespace {
-
-thread_local std::string g_err;
-}  // namespace
-std::string& rgh::last_error() { return g_err; }
-
-// ---- caching device-memory pool (rgbm_host.h)
-namespace {
-struct PoolBlock { void* p; size_t bytes; unsigned long long stamp; };
-struct DevPool {
-    std::mutex mu;
-    std::multimap<std::pair<int, size_t>, PoolBlock> free_blocks;     // (device, bytes) -> block
-    size_t cached = 0; unsigned long long clock = 0;
-    size_t cap() {
-        static const size_t c = [] { const char* e = getenv("RGBM_POOL_MB"); long long mb = e ? atoll(e) : 65536; return (size_t)std::max<long long>(mb, 0) << 20; }();
-        return c;
-    }
-    // drop the least recently freed blocks until at most `keep` bytes stay cached (mu held)
-    void trim_locked(size_t keep) {
-        while (cached > keep && !free_blocks.empty()) {
-            auto victim = free_blocks.begin();
-            for (auto it = free_blocks.begin(); it != free_blocks.end(); ++it) if (it->second.stamp < victim->second.stamp) victim = it;
-            int cur = 0; (void)hipGetDevice(&cur);
-            if (cur != victim->first.first) (void)hipSetDevice(victim->first.first);
-            (void)hipFree(victim->second.p);
-            if (cur != victim->first.first) (void)hipSetDevice(cur);
-            cached -= victim->second.bytes;
-            free_blocks.erase(victim);
-        }
-    }
-    ~DevPool() { /* process exit: the driver reclaims device memory; HIP may already be shut down here */ }
-};
-DevPool& pool() { static DevPool* p = new DevPool(); return *p; }
-}  // namespace
-
-// RGBM_GUARD=1 (debugging): every buffer sits between two 2 MB guard zones filled with 0xC3, and so is the slack between the bytes asked
-// for and the end of the pool block; pool_free checks that nobody wrote there and says so on stderr.  A kernel that READS out of
-// bounds sees the same 0xC3 bytes in every process instead of a neighbour's live data.
-namespace {
-constexpr size_t GUARD = 2u << 20;
-bool guard_on() { static const bool g = getenv("RGBM_GUARD") != nullptr; return g; }
-std::mutex g_guard_mu; std::map<void*, size_t> g_guard_bytes;
-__global__ void k_guard_check(const unsigned char* p, size_t n, unsigned long long* bad /* [0] count, [1] first offset */) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        if (p[i] != 0xC3) { atomicAdd(&bad[0], 1ull); atomicMin(&bad[1], (unsigned long long)i); }
-}
-// RGBM_TRACE (debugging): wrapping 64-bit sum of a buffer's words
-__global__ void k_trace_sum(const unsigned long long* p, size_t nwords, unsigned long long* out) {
-    unsigned long long a = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += (size_t)gridDim.x * blockDim.x) a += p[i] * (2 * (unsigned long long)i + 1);
-    atomicAdd(out, a);
-}
-void* pool_alloc_raw(size_t bytes, size_t* block_bytes, int* device);
-void pool_free_raw(void* p, size_t block_bytes, int device);
-}  // namespace
-
-void* rgh::pool_alloc(size_t bytes, size_t* block_bytes, int* device) {
-    if (!guard_on()) return pool_alloc_raw(bytes, block_bytes, device);
-    unsigned char* raw = static_cast<unsigned char*>(pool_alloc_raw(bytes + 2 * GUARD, block_bytes, device));
-    if (hipMemset(raw, 0xC3, GUARD) != hipSuccess || hipMemset(raw + GUARD + bytes, 0xC3, *block_bytes - GUARD - bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
-        throw std::runtime_error("RGBM_GUARD: hipMemset failed");
-    { std::lock_guard<std::mutex> lk(g_guard_mu); g_guard_bytes[raw + GUARD] = bytes; }
-    return raw + GUARD;
-}
-
-void rgh::pool_free(void* p, size_t block_bytes, int device) {
-    if (!p) return;
-    if (!guard_on()) { pool_free_raw(p, block_bytes, device); return; }
-    size_t bytes = 0;
-    { std::lock_guard<std::mutex> lk(g_guard_mu); auto it = g_guard_bytes.find(p); if (it != g_guard_bytes.end()) { bytes = it->second; g_guard_bytes.erase(it); } }
-    unsigned char* raw = static_cast<unsigned char*>(p) - GUARD;
-    static thread_local unsigned long long* d_bad = nullptr;
-    if (!d_bad) (void)hipMalloc(&d_bad, 16);
-    const size_t tail = block_bytes - GUARD - bytes;
-    const struct { const unsigned char* q; size_t n; const char* what; } zones[2] = {{raw, GUARD, "front guard"}, {raw + GUARD + bytes, tail, "slack + back guard"}};
-    for (const auto& z : zones) {
-        unsigned long long h[2] = {0ull, ~0ull};
-        (void)hipMemcpy(d_bad, h, 16, hipMemcpyHostToDevice);
-        hipLaunchKernelGGL(k_guard_check, dim3(1024), dim3(256), 0, nullptr, z.q, z.n, d_bad);
-        (void)hipMemcpy(h, d_bad, 16, hipMemcpyDeviceToHost);
-        if (h[0]) fprintf(stderr, "[rgbm guard] buffer of %zu bytes (block %zu): %llu byte(s) of the %s were overwritten, first at offset %lld from the buffer's %s\n",
-                          bytes, block_bytes, h[0], z.what, z.q == raw ? (long long)h[1] - (long long)GUARD : (long long)h[1], z.q == raw ? "start" : "end");
-    }
-    pool_free_raw(raw, block_bytes, device);
-}
-
-namespace {
-void* pool_alloc_raw(size_t bytes, size_t* block_bytes, int* device) {
-    int dev = 0; (void)hipGetDevice(&dev);
-    *device = dev;
-    DevPool& P = pool();
-    // round up so that nearly equal requests can share blocks: 256 B below 1 MB, 2 MB above
-    const size_t want = bytes < (1u << 20) ? ((bytes + 255) & ~(size_t)255) : ((bytes + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1));
-    if (P.cap() > 0) {
-        std::lock_guard<std::mutex> lk(P.mu);
-        auto it = P.free_blocks.lower_bound(std::make_pair(dev, want));
-        // a request never swallows a much larger block (up to 8x its size, 4x below 1 MB)
-        if (it != P.free_blocks.end() && it->first.first == dev && it->first.second <= want * (want >= (1u << 20) ? 8 : 4)) {
-            void* p = it->second.p; *block_bytes = it->second.bytes;
-            P.cached -= it->second.bytes;
-            P.free_blocks.erase(it);
-            return p;
-        }
-    }
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess && P.cap() > 0) {       // out of memory with blocks parked in the pool: give them back and retry once
-        (void)hipGetLastError();
-        { std::lock_guard<std::mutex> lk(P.mu); P.trim_locked(0); }
-        e = hipMalloc(&p, want);
-    }
-    if (e != hipSuccess) { (void)hipGetLastError(); char b[256]; snprintf(b, sizeof(b), "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e)); throw rgh::device_oom(b); }
-    *block_bytes = want;
-    return p;
-}
-
-void pool_free_raw(void* p, size_t block_bytes, int device) {
-    if (!p) return;
-    DevPool& P = pool();
-    if (P.cap() == 0 || block_bytes > P.cap()) {
-        int cur = 0; (void)hipGetDevice(&cur);
-        if (cur != device) (void)hipSetDevice(device);
-        (void)hipFree(p);
-        if (cur != device) (void)hipSetDevice(cur);
-        return;
-    }
-    std::lock_guard<std::mutex> lk(P.mu);
-    P.free_blocks.emplace(std::make_pair(device, block_bytes), PoolBlock{p, block_bytes, ++P.clock});
-    P.cached += block_bytes;
-    if (P.cached > P.cap()) P.trim_locked(P.cap());
-}
-
-}  // namespace
-
-void rgh::pool_trim(size_t keep_bytes) { DevPool& P = pool(); std::lock_guard<std::mutex> lk(P.mu); P.trim_locked(keep_bytes); }
 namespace {
 using rgh::fail; using rgh::DevBuf; using rgh::use_device; using rgh::StreamGuard; using rgh::guarded;
-
-// ---------------------------------------------------------------------------------------------
-// Row-sharded multi-GPU training (DESIGN.md "Multi-GPU"): every rank holds a row shard of the table and grows the
-// SAME trees; the only exchanges are integer all-reduces of (a) the code counts used for binning, (b) the built
-// children's histograms after each level pass and (c) the exact child row counts.  Sums are exact integers, so the
-// model is bit-identical to single-GPU training for any number of ranks and any row split.
-// Two transports: RCCL (one process per GPU, all-reduce enqueued on the training stream: no host round trip) and an
-// in-process thread group (one rank per host thread on one device) that exists so the sharding logic can be
-// verified on a single GPU.
-// ---------------------------------------------------------------------------------------------
-struct LocalGroup {
-    int nranks = 0, device = 0;
-    std::mutex mu; std::condition_variable cv;
-    int arrived = 0; long long generation = 0;
-    std::vector<void*> ptr;
-    void barrier() {
-        std::unique_lock<std::mutex> lk(mu);
-        const long long gen = generation;
-        if (++arrived == nranks) { arrived = 0; ++generation; cv.notify_all(); }
-        else cv.wait(lk, [&] { return generation != gen; });
-    }
-};
-
-struct Fusion;
-struct Comm {
-    int kind = 0;   // 0 none, 1 RCCL, 2 local thread group, 3 member of a fusion group (the rank's communicator lives in the group)
-    int rank = 0, nranks = 1;
-    ncclComm_t nccl = nullptr;
-    LocalGroup* lg = nullptr;
-    void* tmp = nullptr; size_t tmp_bytes = 0;
-    Fusion* fusion = nullptr; int member = 0;      // kind 3
-};
-thread_local Comm g_comm;
-
-enum { AR_I64 = 0, AR_U32 = 1, AR_I32 = 2 };
-
-// ---------------------------------------------------------------------------------------------
-// Fusion group (round 5): the row-sharded training calls of ONE rank that run at the same time -- one host thread and one HIP stream
-// each -- and exchange in LOCK STEP.  Every row-sharded training call makes the same sequence of collectives (code counts once, then per
-// boosting iteration one all-reduce per level and one of the deepest counts: the sequence is fixed by the parameters, not by the
-// data), so the i-th collective of every member is carried by ONE all-reduce of the rank's communicator over the members' buffers laid
-// side by side: a member records an event behind its producers and waits at a host barrier; the last one to arrive copies all parts
-// into a staging buffer on the group's stream, enqueues the collective and the copies back and records a `done` event; every member's
-// stream then waits for that event.  Nothing synchronises with the device: the host threads only meet at enqueue time.
-// What it buys: the row-sharded targets of a rank trained one after another on the thread that owns the
-// communicator -- the in-rank concurrency (22 % at N = 1) was gone exactly where every target is row-sharded, and a job paid 8
-// collectives per target-iteration.  Now they overlap like the target-sharded ones and a rank issues 8 collectives per iteration of
-// ALL its row-sharded targets.  The members' order inside the fused buffer is their index, so it is the same on every rank.
-// A member that fails breaks the group: the others raise at their next collective (and the RCCL communicator is aborted, as before).
-// ---------------------------------------------------------------------------------------------
-struct Fusion {
-    static constexpr int MAX_MEMBERS = 64;
-    Comm comm;                  // the rank's communicator (moved in by rgbm_fusion_create, moved back by rgbm_fusion_free)
-    int device = 0;
-    int n = 0;                  // members still taking part
-    int n_members = 0;          // members the group was created for (rgbm_fusion_join checks the index against it)
-    bool joined[MAX_MEMBERS] = {};
-    std::mutex mu; std::condition_variable cv;
-    int arrived = 0; long long gen = 0; bool broken = false; std::string why;
-    struct Part { void* buf = nullptr; size_t count = 0; int type = 0; hipStream_t s = nullptr; hipEvent_t ready = nullptr; bool in = false; } part[MAX_MEMBERS];
-    void* stage = nullptr; size_t stage_bytes = 0;
-    hipStream_t cs = nullptr; hipEvent_t done = nullptr;
-    long long collectives = 0, fused_parts = 0;    // statistics
-};
-
-void all_reduce_on(Comm& c, void* buf, size_t count, int type, hipStream_t s);
-
-// RGBM_COMM_TIMEOUT_S: seconds without progress after which a collective is given up (default 600; read once)
-double comm_timeout_s() {
-    static const double limit = [] { const char* e = getenv("RGBM_COMM_TIMEOUT_S"); double v = e ? atof(e) : 600.0; return v > 0.0 ? v : 600.0; }();
-    return limit;
-}
-
-// the collective of one step for every member that is parked in it (called with f->mu held, by the last member to arrive -- or by a member
-// that leaves while all the remaining ones are parked).  Members may be at different points of their sequences (one is counting codes for
-// its next target while another is in the middle of an iteration): the parts are grouped by element type, one all-reduce per type present,
-// in a fixed type order -- the same on every rank, because which member takes part in the k-th step only depends on the sequences.
-void fusion_run_step_locked(Fusion* f) {
-    try {
-        for (int type = 0; type < 3; ++type) {
-            const size_t esz = type == AR_I64 ? 8 : 4;
-            size_t total = 0; int nparts = 0;
-            for (int j = 0; j < Fusion::MAX_MEMBERS; ++j) if (f->part[j].in && f->part[j].type == type) { total += f->part[j].count; ++nparts; }
-            if (nparts == 0) continue;
-            if (total * esz > f->stage_bytes) {
-                HIPCHK(hipStreamSynchronize(f->cs));
-                if (f->stage) (void)hipFree(f->stage);
-                f->stage_bytes = std::max<size_t>(total * esz * 2, 1 << 20);
-                HIPCHK(hipMalloc(&f->stage, f->stage_bytes));
-            }
-            size_t off = 0;
-            for (int j = 0; j < Fusion::MAX_MEMBERS; ++j) {
-                Fusion::Part& q = f->part[j];
-                if (!q.in || q.type != type) continue;
-                HIPCHK(hipStreamWaitEvent(f->cs, q.ready, 0));
-                if (q.count) HIPCHK(hipMemcpyAsync(static_cast<char*>(f->stage) + off * esz, q.buf, q.count * esz, hipMemcpyDeviceToDevice, f->cs));
-                off += q.count;
-            }
-            all_reduce_on(f->comm, f->stage, total, type, f->cs);
-            off = 0;
-            for (int j = 0; j < Fusion::MAX_MEMBERS; ++j) {
-                Fusion::Part& q = f->part[j];
-                if (!q.in || q.type != type) continue;
-                if (q.count) HIPCHK(hipMemcpyAsync(q.buf, static_cast<char*>(f->stage) + off * esz, q.count * esz, hipMemcpyDeviceToDevice, f->cs));
-                off += q.count; f->fused_parts += 1;
-            }
-            f->collectives += 1;
-        }
-        for (int j = 0; j < Fusion::MAX_MEMBERS; ++j) f->part[j].in = false;
-        HIPCHK(hipEventRecord(f->done, f->cs));
-    } catch (const std::exception& e) { f->broken = true; f->why = e.what(); }
-    f->arrived = 0; ++f->gen; f->cv.notify_all();
-}
-
-// one fused collective; called by every member with its own buffer
-void fused_all_reduce(Fusion* f, int me, void* buf, size_t count, int type, hipStream_t s) {
-    Fusion::Part& mine = f->part[me];
-    if (!mine.ready) HIPCHK(hipEventCreateWithFlags(&mine.ready, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(mine.ready, s));
-    std::unique_lock<std::mutex> lk(f->mu);
-    if (f->broken) throw std::runtime_error("fusion group: a concurrent row-sharded training call of this rank failed (" + f->why + ")");
-    mine.buf = buf; mine.count = count; mine.type = type; mine.s = s; mine.in = true;
-    const long long gen = f->gen;
-    if (++f->arrived >= f->n) fusion_run_step_locked(f);
-    else {
-        // bounded: a member of this rank that never arrives and never leaves -- its thread died before its next collective -- must not
-        // park the others (and, through them, the peer ranks) for ever: after RGBM_COMM_TIMEOUT_S the group is broken and everybody raises
-        const double limit = comm_timeout_s();
-        if (!f->cv.wait_for(lk, std::chrono::duration<double>(limit), [&] { return f->gen != gen || f->broken; })) {
-            f->broken = true; f->why = "a member of this rank did not reach its next collective within " + std::to_string((int)limit) + " s";
-            if (f->comm.kind == 1 && f->comm.nccl) { (void)ncclCommAbort(f->comm.nccl); f->comm.nccl = nullptr; f->comm.kind = 0; }
-            f->cv.notify_all();
-        }
-    }
-    if (f->broken) throw std::runtime_error("fusion group: a concurrent row-sharded training call of this rank failed (" + f->why + ")");
-    HIPCHK(hipStreamWaitEvent(s, f->done, 0));
-}
-
-// a member is done (its training call returned or failed): the others go on among themselves
-void fusion_leave(bool failed, const char* why) {
-    Comm& c = g_comm;
-    if (c.kind != 3 || !c.fusion) return;
-    Fusion* f = c.fusion;
-    {
-        std::lock_guard<std::mutex> lk(f->mu);
-        f->part[c.member].in = false;
-        if (failed && !f->broken) { f->broken = true; f->why = why ? why : "unknown error"; if (f->comm.kind == 1 && f->comm.nccl) { (void)ncclCommAbort(f->comm.nccl); f->comm.nccl = nullptr; f->comm.kind = 0; } }
-        f->n -= 1;
-        if (f->broken) f->cv.notify_all();
-        else if (f->n > 0 && f->arrived >= f->n) fusion_run_step_locked(f);     // the remaining members are all parked in their next step: it is theirs alone
-    }
-    g_comm = Comm();
-}
-
-// Fail-safe for the RCCL transport.  A rank that dies (or throws) in the middle of a training call never enqueues its next
-// all-reduce, and its peers would sit in theirs for ever.  So (a) a rank that fails ABORTS its communicator before the error
-// leaves the library (comm_abort_on_failure), and (b) every rank waits for its training stream through a watchdog instead of
-// a blocking synchronise: it polls the stream, asks RCCL for asynchronous errors and gives up after RGBM_COMM_TIMEOUT_S seconds
-// (default 600) without progress -- then it aborts its own communicator (which takes the stuck collective kernel off the stream)
-// and raises.  After an abort the thread has no communicator: the caller falls back to target sharding (repair/dist.py).
-void comm_abort() {
-    Comm& c = g_comm;
-    if (c.kind == 1 && c.nccl) { (void)ncclCommAbort(c.nccl); c.nccl = nullptr; c.kind = 0; c.nranks = 1; c.rank = 0; }
-    if (c.kind == 3 && c.fusion) fusion_leave(true, "a member's stream failed or timed out inside a collective");
-}
-
-void stream_sync_watchdog(hipStream_t s) {
-    Comm& c = g_comm;
-    const bool fused_rccl = c.kind == 3 && c.fusion && c.fusion->comm.kind == 1;
-    if (c.kind != 1 && !fused_rccl) { HIPCHK(hipStreamSynchronize(s)); return; }
-    const double limit = comm_timeout_s();
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipSuccess) return;
-        if (q != hipErrorNotReady) { (void)hipGetLastError(); comm_abort(); throw std::runtime_error(std::string("training stream failed during a collective: ") + hipGetErrorString(q)); }
-        ncclResult_t ae = ncclSuccess; bool have_ae = false;
-        if (fused_rccl) {
-            // the group's state belongs to its mutex: another member may be leaving right now -- writing `why`, aborting the communicator
-            // and clearing the handle -- so the flag, the text and the asynchronous-error query are taken under the lock
-            bool broken; std::string w;
-            {
-                std::lock_guard<std::mutex> lk(c.fusion->mu);
-                broken = c.fusion->broken; if (broken) w = c.fusion->why;
-                if (!broken && c.fusion->comm.nccl) have_ae = ncclCommGetAsyncError(c.fusion->comm.nccl, &ae) == ncclSuccess;
-            }
-            if (broken) { comm_abort(); throw std::runtime_error("fusion group broken: " + w); }
-        } else if (c.nccl) have_ae = ncclCommGetAsyncError(c.nccl, &ae) == ncclSuccess;
-        if (have_ae && ae != ncclSuccess && ae != ncclInProgress) {
-            const std::string what = ncclGetErrorString(ae);
-            comm_abort();
-            throw std::runtime_error("RCCL reported an asynchronous error (a peer rank failed?): " + what);
-        }
-        const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (waited > limit) {
-            comm_abort();
-            throw std::runtime_error("row-sharded training: no progress for " + std::to_string((int)limit) + " s inside a collective (a peer rank is gone); communicator aborted");
-        }
-        std::this_thread::sleep_for(std::chrono::microseconds(waited < 0.05 ? 50 : 1000));
-    }
-}
-
-struct PtrList { const void* p[16]; };
-template <typename T>
-__global__ void k_sum_ranks(PtrList src, int n, T* __restrict__ out, size_t count) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    T acc = 0;
-    for (int r = 0; r < n; ++r) acc += reinterpret_cast<const T*>(src.p[r])[i];
-    out[i] = acc;
-}
-
-// in-place sum all-reduce of `count` elements on stream s
-void all_reduce(void* buf, size_t count, int type, hipStream_t s) {
-    Comm& c = g_comm;
-    if (c.kind == 3) { fused_all_reduce(c.fusion, c.member, buf, count, type, s); return; }     // (also with count == 0: every member takes part in every step)
-    all_reduce_on(c, buf, count, type, s);
-}
-void all_reduce_on(Comm& c, void* buf, size_t count, int type, hipStream_t s) {
-    if (c.kind == 0 || count == 0) return;
-    const size_t esz = type == AR_I64 ? 8 : 4;
-    if (c.kind == 1) {
-        const ncclDataType_t dt = type == AR_I64 ? ncclInt64 : (type == AR_U32 ? ncclUint32 : ncclInt32);
-        ncclResult_t r = ncclAllReduce(buf, buf, count, dt, ncclSum, c.nccl, s);
-        if (r != ncclSuccess) throw std::runtime_error(std::string("ncclAllReduce failed: ") + ncclGetErrorString(r));
-        return;
-    }
-    LocalGroup* g = c.lg;
-    if (c.tmp_bytes < count * esz) { if (c.tmp) (void)hipFree(c.tmp); HIPCHK(hipMalloc(&c.tmp, count * esz)); c.tmp_bytes = count * esz; }
-    HIPCHK(hipStreamSynchronize(s));
-    { std::lock_guard<std::mutex> lk(g->mu); g->ptr[c.rank] = buf; }
-    g->barrier();
-    PtrList pl; for (int r = 0; r < g->nranks; ++r) pl.p[r] = g->ptr[r];
-    const unsigned blocks = (unsigned)((count + 255) / 256);
-    if (type == AR_I64) hipLaunchKernelGGL(k_sum_ranks<long long>, dim3(blocks), dim3(256), 0, s, pl, g->nranks, (long long*)c.tmp, count);
-    else if (type == AR_U32) hipLaunchKernelGGL(k_sum_ranks<unsigned int>, dim3(blocks), dim3(256), 0, s, pl, g->nranks, (unsigned int*)c.tmp, count);
-    else hipLaunchKernelGGL(k_sum_ranks<int>, dim3(blocks), dim3(256), 0, s, pl, g->nranks, (int*)c.tmp, count);
-    HIPCHK(hipStreamSynchronize(s));
-    g->barrier();                                   // everyone has read every buffer
-    HIPCHK(hipMemcpyAsync(buf, c.tmp, count * esz, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    g->barrier();
-}
-
-// all-gather of equal-sized device blocks over the calling thread's own communicator (not from inside a fusion group): recv = [nranks][bytes].
-// RCCL: ncclAllGather on the library's communicator, enqueued on s; thread group: every rank copies every rank's block (device copies
-// between two barriers); no communicator: a copy.  What the C1 / C2 exchanges of a multi-GPU job ride on (model blobs, repaired cells).
-struct GatherStats { std::atomic<long long> bytes{0}, ns{0}, calls{0}; };
-GatherStats& gather_stats() { static GatherStats g; return g; }
-void all_gather_on(Comm& c, const void* send, void* recv, size_t bytes, hipStream_t s) {
-    if (c.kind == 3) throw std::invalid_argument("all-gather from inside a fusion group");
-    if (bytes == 0) return;
-    if (c.kind == 0 || c.nranks <= 1) { if (c.kind != 1) { HIPCHK(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, s)); return; } }
-    if (c.kind == 1) {
-        ncclResult_t r = ncclAllGather(send, recv, bytes, ncclUint8, c.nccl, s);
-        if (r != ncclSuccess) throw std::runtime_error(std::string("ncclAllGather failed: ") + ncclGetErrorString(r));
-        return;
-    }
-    LocalGroup* g = c.lg;
-    HIPCHK(hipStreamSynchronize(s));
-    { std::lock_guard<std::mutex> lk(g->mu); g->ptr[c.rank] = const_cast<void*>(send); }
-    g->barrier();
-    for (int r = 0; r < g->nranks; ++r) HIPCHK(hipMemcpyAsync(static_cast<char*>(recv) + (size_t)r * bytes, g->ptr[r], bytes, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    g->barrier();                                   // everyone has read every block
-}
+using rgh::AR_I64; using rgh::AR_U32; using rgh::AR_I32; using rgh::all_reduce; using rgh::all_gather_on; using rgh::stream_sync_watchdog; using rgh::comm_abort;
+using rgh::comm_kind; using rgh::comm_rank; using rgh::comm_nranks; using rgh::upload_pinned;
 
 struct Feat {
     int32_t n_codes = 0, V = 0, has_nan = 0; std::vector<int32_t> ub;
@@ -1110,7 +712,7 @@ struct LevelTrace {
     void sum(const char* name, const void* src, size_t bytes) {
         if (!on || used + 16 > buf.n) return;
         HIPCHK(hipMemsetAsync(buf.p + used, 0, 8, s));
-        hipLaunchKernelGGL(k_trace_sum, dim3(2048), dim3(256), 0, s, (const unsigned long long*)src, bytes / 8, (unsigned long long*)(buf.p + used));
+        rgh::trace_sum(src, bytes, (unsigned long long*)(buf.p + used), s);
         idx.push_back({name, cur_it, -1, used, 8}); used += 16;
     }
     void write(int target_col) {            // (after the stream has drained)
@@ -1355,7 +957,7 @@ struct LevelGrower {
         if (st.sw.lv_lds >= 65536 && st.sw.lv_lds <= LV_LDS_BYTES) lc.lds_bytes = st.sw.lv_lds;      // testing: a smaller LDS pool forces several built-slot windows per level
         lc.nchunk = st.h.nchunk; lc.K = st.K; lc.F = st.F; lc.totbins = st.h.tc.totbins;
         lc.num_leaves = st.NL; lc.max_depth = st.p.max_depth; lc.min_data_in_leaf = st.p.min_data_in_leaf; lc.N = st.N; lc.NS = (st.N + 255) & ~255ll; lc.NG = lc.NS;
-        lc.sib_local = (st.dp && g_comm.rank == 0) ? 1 : 0;
+        lc.sib_local = (st.dp && comm_rank() == 0) ? 1 : 0;
         lc.has_mult = st.tab.has_mult ? 1u : 0u;
         passes = plan_level_passes(st.sw, st.h.fmeta, st.h.cmeta, st.N, st.K, st.p.max_depth, st.tab.has_mult, lc.lds_bytes);
         lc.gx = passes.root_gx; lc.xcd_blocks = 1; lc.max_built = 1;
@@ -1577,7 +1179,7 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     // ---- 1. prologue: code frequencies of the training rows -> bins, tables, label statistics (fit_setup) -> bin records
     st.bins.count_codes(tab, target_col, feat_cols, F, st.h, s);
     if (st.dp) {   // the table is one rank's row shard: the counts are summed over the ranks
-        if (g_comm.kind == 0) throw std::invalid_argument("row-sharded training requested but this thread has no communicator (rgbm_comm_init)");
+        if (comm_kind() == 0) throw std::invalid_argument("row-sharded training requested but this thread has no communicator (rgbm_comm_init)");
         all_reduce(st.bins.cnt.p, st.bins.cnt.n, AR_U32, s);
     }
     st.bins.download_counts(st.h, s);
@@ -1629,12 +1231,12 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
             // [bag_off, bag_off + bag_local), bag_off = training rows of the ranks before it (one all-reduce of a per-rank count vector)
             unsigned int h_local = 0; st.counter.download(&h_local, 1, s); stream_sync_watchdog(s);
             bag_local = (long long)h_local;
-            std::vector<long long> rc((size_t)g_comm.nranks, 0); rc[(size_t)g_comm.rank] = bag_local;
+            std::vector<long long> rc((size_t)comm_nranks(), 0); rc[(size_t)comm_rank()] = bag_local;
             DevBuf<long long> d_rc(rc.size()); d_rc.upload(rc.data(), rc.size(), s);
             all_reduce(d_rc.p, rc.size(), AR_I64, s);
             d_rc.download(rc.data(), rc.size(), s); stream_sync_watchdog(s);
             long long tot = 0;
-            for (int r = 0; r < g_comm.nranks; ++r) { if (r < g_comm.rank) bag_off += rc[(size_t)r]; tot += rc[(size_t)r]; }
+            for (int r = 0; r < comm_nranks(); ++r) { if (r < comm_rank()) bag_off += rc[(size_t)r]; tot += rc[(size_t)r]; }
             if (tot != st.h.n_train) throw std::runtime_error("row-sharded bagging: the ranks' training-row counts do not add up");
             st.bagcnt_g.alloc(2);
         }
@@ -1678,7 +1280,7 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
     model_from_trees(st.h.model.get(), ht, st.NE, st.K, st.NL);
     if (stats) {
         float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev_begin.e, ev_end.e));
-        const int nranks = st.dp ? g_comm.nranks : 1;
+        const int nranks = st.dp ? comm_nranks() : 1;
         fill_train_stats(stats, ms, st.timers, ht, p, st.level_mode, st.use_bagging, nranks, st.N, st.h.n_train, F, lg ? lg->root_feats : F, st.K, lg ? lg->statrows : 0);
         if (view_stats && st.level_mode && st.h.n_train > 0) {
             // n_train and the device's counter weigh a row by its multiplicity.  Streamed rows: the root passes exactly (every training row of the
@@ -2220,62 +1822,6 @@ void rgh::model_shape(const rgbm_model* m, int32_t* objective, int32_t* num_clas
     *objective = m->objective; *num_class = m->num_class; *n_features = m->F;
 }
 
-// Host -> HBM copy of a caller-owned block.  A pageable block handed to hipMemcpy is staged by the driver through one small
-// bounce buffer (measured 4-7 GB/s for the 735 MB of the 10M x 16 tables); page-locking it in place (hipHostRegister) costs more
-// than it saves for a one-off copy (4.4 GB/s).  So the library stages it itself: two page-locked 32 MB buffers kept for the
-// life of the process, filled by a few host threads while the copy engine drains the other one.  Blocks that already are
-// pinned (rgbm_host_alloc, or registered by the caller) go straight to the copy engine.  RGBM_NO_PIN=1: plain hipMemcpy.
-namespace {
-struct StageRing {
-    std::mutex mu; void* buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; hipStream_t s = nullptr; int device = -1; bool ok = false;
-    static constexpr size_t CHUNK = 32u << 20;
-    bool ready(int dev) {
-        if (ok && device == dev) return true;
-        if (ok) return false;                                        // ring belongs to another device: plain copy for this one
-        if (hipHostMalloc(&buf[0], CHUNK, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&buf[1], CHUNK, hipHostMallocDefault) != hipSuccess ||
-            hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        device = dev; ok = true;
-        return true;
-    }
-};
-StageRing& stage_ring() { static StageRing* r = new StageRing(); return *r; }
-}  // namespace
-
-static void upload_pinned(void* dst, const void* src, size_t bytes) {
-    if (bytes == 0) return;
-    hipPointerAttribute_t attr; memset(&attr, 0, sizeof(attr));
-    const bool pinned = hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeHost;
-    if (!pinned) (void)hipGetLastError();
-    int dev = 0; (void)hipGetDevice(&dev);
-    StageRing& R = stage_ring();
-    if (pinned || bytes < (8u << 20) || getenv("RGBM_NO_PIN") != nullptr) { HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return; }
-    std::lock_guard<std::mutex> lk(R.mu);
-    if (!R.ready(dev)) { HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return; }
-    const int nthr = (int)std::min<size_t>(8, std::max<size_t>(1, std::thread::hardware_concurrency() / 2));
-    size_t off = 0; int i = 0;
-    while (off < bytes) {
-        const size_t n = std::min(StageRing::CHUNK, bytes - off);
-        const int b = i & 1;
-        if (i >= 2) HIPCHK(hipEventSynchronize(R.ev[b]));            // the copy engine is done with this buffer
-        std::vector<std::thread> th;
-        const size_t per = (n + nthr - 1) / nthr;
-        for (int t = 1; t < nthr; ++t) {
-            const size_t o = per * t; if (o >= n) break;
-            th.emplace_back([=, &R]() { memcpy((char*)R.buf[b] + o, (const char*)src + off + o, std::min(per, n - o)); });
-        }
-        memcpy(R.buf[b], (const char*)src + off, std::min(per, n));
-        for (auto& t : th) t.join();
-        HIPCHK(hipMemcpyAsync((char*)dst + off, R.buf[b], n, hipMemcpyHostToDevice, R.s));
-        HIPCHK(hipEventRecord(R.ev[b], R.s));
-        off += n; ++i;
-    }
-    HIPCHK(hipStreamSynchronize(R.s));
-}
-
 // page-locked staging of the chain's outputs (two blocks: model t's labels / probabilities leave the device and are copied into the
 // caller's arrays while model t + 1 is scored); kept for the life of the process, at most 256 MiB a block
 namespace {
@@ -2362,19 +1908,9 @@ std::shared_ptr<const rgbm_table> acquire_view(const rgbm_table& t, uint64_t key
 }
 }  // namespace
 
-// =============================================================================================
-// C-ABI
-// =============================================================================================
-extern "C" {
-
-
-RGBM_EXPORT int rgbm_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
-RGBM_EXPORT const char* rgbm_last_error(void) { return g_err.c_str(); }
-RGBM_EXPORT int rgbm_version(void) { return RGBM_VERSION; }
-RGBM_EXPORT int rgbm_release_cache(void) {
-    return guarded([&]() {
-        rgh::pool_trim(0);
-        // the page-locked blocks kept for the tree harvest of a batch and for the outputs of a repair chain (not while a call uses them)
+// rgbm_release_cache (rgbm_runtime.hip): the page-locked blocks kept for the tree harvest of a batch and for the outputs of a repair chain (not
+// while a call uses them)
+void rgh::release_host_staging() {
         {
             HarvestArena& a = harvest_arena();
             std::unique_lock<std::mutex> lk(a.mu, std::try_to_lock);
@@ -2385,9 +1921,12 @@ RGBM_EXPORT int rgbm_release_cache(void) {
             std::unique_lock<std::mutex> lk(c.mu, std::try_to_lock);
             if (lk.owns_lock()) { for (int i = 0; i < 2; ++i) if (c.p[i]) { (void)hipHostFree(c.p[i]); c.p[i] = nullptr; } c.cap = 0; c.device = -1; }
         }
-        return RGBM_OK;
-    });
 }
+
+// =============================================================================================
+// C-ABI
+// =============================================================================================
+extern "C" {
 
 RGBM_EXPORT int rgbm_table_create(const int32_t* codes, int64_t n, int32_t c, const int32_t* n_codes, int32_t device_id, rgbm_table** out) {
     if (!codes || !n_codes || !out || n <= 0 || c <= 0) return fail(RGBM_ERR_ARG, "rgbm_table_create: bad argument");
@@ -2401,18 +1940,6 @@ RGBM_EXPORT int rgbm_table_create(const int32_t* codes, int64_t n, int32_t c, co
         return RGBM_OK;
     });
 }
-
-RGBM_EXPORT int rgbm_host_alloc(size_t bytes, void** out) {
-    if (!out || bytes == 0) return fail(RGBM_ERR_ARG, "rgbm_host_alloc: bad argument");
-    return guarded([&]() {
-        void* p = nullptr;
-        HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-        *out = p;
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT void rgbm_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
 RGBM_EXPORT int rgbm_table_set_column_kind(rgbm_table* t, int32_t col, int32_t kind) {
     if (!t || col < 0 || col >= t->c || kind < 0 || kind > 1) return fail(RGBM_ERR_ARG, "rgbm_table_set_column_kind: bad argument");
@@ -2471,7 +1998,7 @@ RGBM_EXPORT int rgbm_table_train(const rgbm_table* t, int32_t target_col, const 
             *out = train_core(*t, target_col, feat_cols, f, y_value, class_weight, nullptr, nullptr, *p, stats);
         } catch (...) {
             // a rank that fails inside a row-sharded call must not leave its peers waiting in their next all-reduce
-            if ((p->reserved & RGBM_FLAG_ROW_SHARDED) && (g_comm.kind == 1 || g_comm.kind == 3)) comm_abort();
+            if ((p->reserved & RGBM_FLAG_ROW_SHARDED) && (comm_kind() == 1 || comm_kind() == 3)) comm_abort();
             throw;
         }
         return RGBM_OK;
@@ -2779,157 +2306,6 @@ RGBM_EXPORT int rgbm_model_load(const void* buf, size_t len, rgbm_model** out) {
     });
 }
 
-// ---- row-sharded multi-GPU training: communicator of the CALLING THREAD --------------------------------------
-RGBM_EXPORT int rgbm_comm_unique_id(void* id_out) {
-    if (!id_out) return fail(RGBM_ERR_ARG, "rgbm_comm_unique_id: bad argument");
-    return guarded([&]() {
-        static_assert(sizeof(ncclUniqueId) <= RGBM_COMM_ID_BYTES, "ncclUniqueId larger than RGBM_COMM_ID_BYTES");
-        ncclUniqueId id; memset(&id, 0, sizeof(id));
-        ncclResult_t r = ncclGetUniqueId(&id);
-        if (r != ncclSuccess) throw std::runtime_error(std::string("ncclGetUniqueId failed: ") + ncclGetErrorString(r));
-        memset(id_out, 0, RGBM_COMM_ID_BYTES); memcpy(id_out, &id, sizeof(id));
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT int rgbm_comm_init(const void* id, int32_t rank, int32_t nranks, int32_t device_id) {
-    if (!id || rank < 0 || nranks < 1 || rank >= nranks) return fail(RGBM_ERR_ARG, "rgbm_comm_init: bad argument");
-    return guarded([&]() {
-        if (g_comm.kind != 0) throw std::invalid_argument("rgbm_comm_init: this thread already has a communicator");
-        use_device(device_id);
-        ncclUniqueId uid; memcpy(&uid, id, sizeof(uid));
-        ncclComm_t c = nullptr;
-        ncclResult_t r = ncclCommInitRank(&c, nranks, uid, rank);
-        if (r != ncclSuccess) throw std::runtime_error(std::string("ncclCommInitRank failed: ") + ncclGetErrorString(r));
-        g_comm.kind = 1; g_comm.rank = rank; g_comm.nranks = nranks; g_comm.nccl = c;
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT int rgbm_local_group_create(int32_t nranks, int32_t device_id, void** group_out) {
-    if (!group_out || nranks < 1 || nranks > 16) return fail(RGBM_ERR_ARG, "rgbm_local_group_create: bad argument (1..16 ranks)");
-    return guarded([&]() {
-        use_device(device_id);
-        LocalGroup* g = new LocalGroup(); g->nranks = nranks; g->device = device_id; g->ptr.assign(nranks, nullptr);
-        *group_out = g;
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT void rgbm_local_group_free(void* group) { delete static_cast<LocalGroup*>(group); }
-
-RGBM_EXPORT int rgbm_comm_init_local(void* group, int32_t rank) {
-    LocalGroup* g = static_cast<LocalGroup*>(group);
-    if (!g || rank < 0 || rank >= g->nranks) return fail(RGBM_ERR_ARG, "rgbm_comm_init_local: bad argument");
-    return guarded([&]() {
-        if (g_comm.kind != 0) throw std::invalid_argument("rgbm_comm_init_local: this thread already has a communicator");
-        use_device(g->device);
-        g_comm.kind = 2; g_comm.rank = rank; g_comm.nranks = g->nranks; g_comm.lg = g;
-        return RGBM_OK;
-    });
-}
-
-// ---- fusion group: concurrent row-sharded training calls of one rank, one collective per step for all of them (see struct Fusion)
-RGBM_EXPORT int rgbm_fusion_create(int32_t n_members, void** out) {
-    if (!out || n_members < 1 || n_members > Fusion::MAX_MEMBERS) return fail(RGBM_ERR_ARG, "rgbm_fusion_create: bad argument (1..64 members)");
-    return guarded([&]() {
-        if (g_comm.kind != 1 && g_comm.kind != 2) throw std::invalid_argument("rgbm_fusion_create: the calling thread has no communicator (rgbm_comm_init)");
-        std::unique_ptr<Fusion> f(new Fusion());
-        HIPCHK(hipGetDevice(&f->device));
-        HIPCHK(hipStreamCreateWithFlags(&f->cs, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&f->done, hipEventDisableTiming));
-        f->n = n_members; f->n_members = n_members;
-        f->comm = g_comm; g_comm = Comm();         // the communicator lives in the group until rgbm_fusion_free hands it back
-        *out = f.release();
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT int rgbm_fusion_join(void* fusion, int32_t member) {
-    Fusion* f = static_cast<Fusion*>(fusion);
-    if (!f || member < 0 || member >= Fusion::MAX_MEMBERS) return fail(RGBM_ERR_ARG, "rgbm_fusion_join: bad argument");
-    return guarded([&]() {
-        if (g_comm.kind != 0) throw std::invalid_argument("rgbm_fusion_join: this thread already has a communicator");
-        {
-            std::lock_guard<std::mutex> lk(f->mu);
-            if (member >= f->n_members) throw std::invalid_argument("rgbm_fusion_join: member index beyond the members the group was created for");
-            if (f->joined[member]) throw std::invalid_argument("rgbm_fusion_join: this member index is taken");
-            f->joined[member] = true;
-        }
-        use_device(f->device);
-        g_comm.kind = 3; g_comm.rank = f->comm.rank; g_comm.nranks = f->comm.nranks; g_comm.fusion = f; g_comm.member = member;
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT int rgbm_fusion_leave(int32_t failed) {
-    fusion_leave(failed != 0, "a member reported a failure");
-    return RGBM_OK;
-}
-
-RGBM_EXPORT int rgbm_fusion_info(void* fusion, int64_t* info /* [4] = {collectives issued, member parts carried, members still in, broken} */) {
-    Fusion* f = static_cast<Fusion*>(fusion);
-    if (!f || !info) return fail(RGBM_ERR_ARG, "rgbm_fusion_info: bad argument");
-    std::lock_guard<std::mutex> lk(f->mu);
-    info[0] = f->collectives; info[1] = f->fused_parts; info[2] = f->n; info[3] = f->broken ? 1 : 0;
-    return RGBM_OK;
-}
-
-RGBM_EXPORT int rgbm_fusion_free(void* fusion) {
-    Fusion* f = static_cast<Fusion*>(fusion);
-    if (!f) return RGBM_OK;
-    return guarded([&]() {
-        (void)hipSetDevice(f->device);
-        if (f->cs) { (void)hipStreamSynchronize(f->cs); (void)hipStreamDestroy(f->cs); }
-        if (f->done) (void)hipEventDestroy(f->done);
-        for (auto& q : f->part) if (q.ready) (void)hipEventDestroy(q.ready);
-        if (f->stage) (void)hipFree(f->stage);
-        // the communicator goes back to the calling thread (unless that thread has one already, or the group broke and aborted it)
-        if (g_comm.kind == 0 && (f->comm.kind == 1 || f->comm.kind == 2)) g_comm = f->comm;
-        else { if (f->comm.kind == 1 && f->comm.nccl) (void)ncclCommDestroy(f->comm.nccl); if (f->comm.tmp) (void)hipFree(f->comm.tmp); }
-        delete f;
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT int rgbm_comm_finalize(void) {
-    if (g_comm.kind == 3) { fusion_leave(false, nullptr); return RGBM_OK; }      // a member thread: leave the group (the communicator is the group's)
-    if (g_comm.kind == 1 && g_comm.nccl) (void)ncclCommDestroy(g_comm.nccl);
-    if (g_comm.tmp) (void)hipFree(g_comm.tmp);
-    g_comm = Comm();
-    return RGBM_OK;
-}
-
-// ---- C1 / C2 of a multi-GPU job on the library's OWN communicator ("C1 / C2 on device buffers and one communicator"): the
-// serialised models (Spark broadcast, python/repair/model.py:1069) and the repaired cells (the union of the UDF outputs, model.py:1142) are
-// all-gathered by ncclAllGather over xGMI on the communicator the row-sharded trainer uses -- a rank holds ONE RCCL communicator; torch's process
-// group only carries control traffic (gloo).  Equal-sized blocks: the callers pad to the largest rank (sizes first, through the same path).
-static void gather_host_blocks(const void* send, size_t my_bytes, size_t block_bytes, void* recv) {
-    Comm& c = g_comm;
-    const int nr = std::max(1, c.nranks);
-    StreamGuard sg; hipStream_t s = sg.s;
-    const auto t0 = std::chrono::steady_clock::now();
-    DevBuf<unsigned char> d_send(std::max<size_t>(block_bytes, 1)), d_recv(std::max<size_t>(block_bytes, 1) * (size_t)nr);
-    d_send.zero(s);
-    if (my_bytes) HIPCHK(hipMemcpyAsync(d_send.p, send, my_bytes, hipMemcpyHostToDevice, s));
-    all_gather_on(c, d_send.p, d_recv.p, block_bytes, s);
-    if (block_bytes) HIPCHK(hipMemcpyAsync(recv, d_recv.p, block_bytes * (size_t)nr, hipMemcpyDeviceToHost, s));
-    stream_sync_watchdog(s);
-    GatherStats& G = gather_stats();
-    G.bytes += (long long)(block_bytes * (size_t)nr); G.calls += 1;
-    G.ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-}
-
-RGBM_EXPORT int rgbm_comm_all_gather_sizes(const int64_t* mine, int32_t n, int64_t* all /* [nranks][n] */) {
-    if (!mine || !all || n < 1) return fail(RGBM_ERR_ARG, "rgbm_comm_all_gather_sizes: bad argument");
-    return guarded([&]() { gather_host_blocks(mine, (size_t)n * 8, (size_t)n * 8, all); return RGBM_OK; });
-}
-
-RGBM_EXPORT int rgbm_comm_all_gather_bytes(const void* send, int64_t my_bytes, int64_t block_bytes, void* recv /* [nranks][block_bytes] */) {
-    if (my_bytes < 0 || block_bytes < my_bytes || !recv || (my_bytes > 0 && !send)) return fail(RGBM_ERR_ARG, "rgbm_comm_all_gather_bytes: bad argument");
-    return guarded([&]() { gather_host_blocks(send, (size_t)my_bytes, (size_t)block_bytes, recv); return RGBM_OK; });
-}
-
 // The chained repair of this rank's rows with its outputs LEFT ON THE DEVICE, all-gathered over the communicator there, and only then copied to
 // the host: out_label / out_prob = [nranks][T][max_rows] (a rank's block holds its n_rows rows of every model, padded to max_rows = the largest
 // rank's row count -- the caller exchanged the counts with rgbm_comm_all_gather_sizes).  Same labels / probabilities as rgbm_table_repair_chain.
@@ -2941,8 +2317,7 @@ RGBM_EXPORT int rgbm_table_repair_chain_gather(rgbm_table* t, const rgbm_model* 
     return guarded([&]() {
         use_device(t->device);
         rgh::ViewWrite view_wr(t);
-        Comm& c = g_comm;
-        const int nr = std::max(1, c.nranks);
+        const int nr = std::max(1, comm_nranks());
         StreamGuard sg; hipStream_t s = sg.s;
         const size_t blk = (size_t)T * (size_t)max_rows;
         DevBuf<int32_t> d_lab(blk), d_lab_all(blk * (size_t)nr); DevBuf<double> d_prob(blk), d_prob_all(blk * (size_t)nr);
@@ -2951,45 +2326,14 @@ RGBM_EXPORT int rgbm_table_repair_chain_gather(rgbm_table* t, const rgbm_model* 
             chain_device(const_cast<rgbm_model* const*>(models), T, target_col, feat_cols, feat_off, nullptr, nullptr, t->codes.p, t->n, row_begin, n_rows,
                          t->device, s, nullptr, nullptr, d_lab.p, d_prob.p, (long long)max_rows);
         const auto t0 = std::chrono::steady_clock::now();
-        all_gather_on(c, d_lab.p, d_lab_all.p, blk * sizeof(int32_t), s);
-        all_gather_on(c, d_prob.p, d_prob_all.p, blk * sizeof(double), s);
+        all_gather_on(d_lab.p, d_lab_all.p, blk * sizeof(int32_t), s);
+        all_gather_on(d_prob.p, d_prob_all.p, blk * sizeof(double), s);
         HIPCHK(hipMemcpyAsync(out_label, d_lab_all.p, blk * (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(out_prob, d_prob_all.p, blk * (size_t)nr * sizeof(double), hipMemcpyDeviceToHost, s));
         stream_sync_watchdog(s);
-        GatherStats& G = gather_stats();
+        rgh::GatherStats& G = rgh::gather_stats();
         G.bytes += (long long)(blk * (size_t)nr * 12); G.calls += 2;
         G.ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        return RGBM_OK;
-    });
-}
-
-RGBM_EXPORT int rgbm_comm_gather_stats(int64_t* out /* [3] = {bytes received by all-gathers of this process, nanoseconds spent in them, collectives} */) {
-    if (!out) return fail(RGBM_ERR_ARG, "rgbm_comm_gather_stats: bad argument");
-    GatherStats& G = gather_stats();
-    out[0] = G.bytes.load(); out[1] = G.ns.load(); out[2] = G.calls.load();
-    return RGBM_OK;
-}
-
-RGBM_EXPORT int rgbm_comm_info(int32_t* info) {
-    if (!info) return fail(RGBM_ERR_ARG, "rgbm_comm_info: bad argument");
-    info[0] = g_comm.kind; info[1] = g_comm.rank; info[2] = g_comm.nranks;     // (kind 3: member of a fusion group)
-    return RGBM_OK;
-}
-
-// ranks the calling thread's RCCL communicator really spans (ncclCommCount), 1 for no communicator: what a multi-GPU job prints so that a
-// silent fall-back to fewer ranks is visible in its result line
-RGBM_EXPORT int rgbm_comm_count(int32_t* n_out) {
-    if (!n_out) return fail(RGBM_ERR_ARG, "rgbm_comm_count: bad argument");
-    return guarded([&]() {
-        *n_out = 1;
-        const Comm& c = (g_comm.kind == 3 && g_comm.fusion) ? g_comm.fusion->comm : g_comm;
-        if (c.kind == 2) *n_out = c.nranks;
-        if (c.kind == 1 && c.nccl) {
-            int n = 0;
-            ncclResult_t r = ncclCommCount(c.nccl, &n);
-            if (r != ncclSuccess) throw std::runtime_error(std::string("ncclCommCount failed: ") + ncclGetErrorString(r));
-            *n_out = n;
-        }
         return RGBM_OK;
     });
 }

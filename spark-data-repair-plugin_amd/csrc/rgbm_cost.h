@@ -3,7 +3,7 @@
 //
 //   k_edit_distance       Levenshtein distance of every (a, b) pair of two string pools      (repair.costs.edit_distance)
 //   k_edit_distance_long  the same for pairs whose strings are BOTH longer than 64 code points
-//   k_weighted_pmf        k_top_k_pmf after the cost re-weighting + renormalisation        (_compute_weighted_probs)
+//   k_weighted_pmf        the stable top-k candidates of every cell, after the cost re-weighting + renormalisation where asked for   (_compute_weighted_probs)
 //
 // Strings are int32 Unicode code points with int64 offsets (Python's str indexes code points, so the distances are the
 // ones repair.costs computes).  Probabilities follow the Python expression order step by step; the library is built with
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(64) void k_edit_distance_long(const int32_t* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_top_k_pmf with the update costs (model.py `_compute_repair_pmf`, reference `_compute_weighted_probs` model.py:1145-1165).
+// the top-k candidate distributions, with or without the update costs (model.py `_compute_repair_pmf`, reference `_compute_weighted_probs` model.py:1145-1165).
 // One wave per cell; lane l owns the classes c = l (mod 64) and overwrites proba[cell][c] with the final probability, so no
 // lane reads what another wrote.  Per cell, in the order (and the roundings) of the Python loop:
 //   p_c *= 1.0 / (1.0 + weight * cost[row][c])    for cost_row[cell] = row >= 0 and cost[row][c] not NaN (NaN = None)
@@ -145,7 +145,8 @@ __global__ __launch_bounds__(256) void k_weighted_pmf(double* __restrict__ proba
     const int row = (cost && cost_row) ? cost_row[cell] : -1;
     const double* crow = row >= 0 ? cost + (long long)row * K : nullptr;
     double norm = 0.0;
-    for (int base = 0; base < K; base += 64) {
+    const int Kw = (crow || renormalise) ? K : 0;          // (uniform over the wave) with neither, the probabilities stay as they are: no pass over them
+    for (int base = 0; base < Kw; base += 64) {
         const int c = base + lane;
         double v = 0.0;
         if (c < K) {
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(256) void k_weighted_pmf(double* __restrict__ proba
                     const double den = 1.0 + weight * cc;
                     v = v * (1.0 / den);
                 }
+                p[c] = v;                                    // (only where a cost row exists: nothing else changes a value here)
             }
-            p[c] = v;
         }
         if (renormalise) {                                   // every lane adds the chunk's values in class order: the same sum everywhere
             const int cnt = K - base < 64 ? K - base : 64;

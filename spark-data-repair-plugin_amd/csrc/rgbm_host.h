@@ -2,6 +2,7 @@
 // thread-local error text, HIP error checks, device buffers, the HBM-resident table object.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
@@ -18,7 +19,7 @@
 
 namespace rgh {
 
-std::string& last_error();                       // thread-local (defined in rgbm.hip)
+std::string& last_error();                       // thread-local (defined in rgbm_runtime.hip)
 inline int fail(int code, const std::string& msg) { last_error() = msg; return code; }
 
 #define HIPCHK(expr)                                                                                   \
@@ -35,7 +36,7 @@ inline int fail(int code, const std::string& msg) { last_error() = msg; return c
 // tree (scores, gradients, node ids, ...) and hipMalloc/hipFree of 12 GB cost 0.3 s -- more than 15 boosting iterations.
 // Freed blocks are kept (best fit: the smallest cached block that is large enough) up to RGBM_POOL_MB (default 65536;
 // 0 = plain hipMalloc/hipFree); callers release buffers only after synchronising the stream that used them.
-void* pool_alloc(size_t bytes, size_t* block_bytes, int* device);     // defined in rgbm.hip; throws std::runtime_error
+void* pool_alloc(size_t bytes, size_t* block_bytes, int* device);     // defined in rgbm_runtime.hip; throws std::runtime_error
 void pool_free(void* p, size_t block_bytes, int device);
 void pool_trim(size_t keep_bytes);
 
@@ -94,6 +95,31 @@ inline void once_per_device(int device, OnceTag tag, void (*fn)()) {
     fn();
     done[device & 63][tag] = 1;
 }
+
+// ---- rgbm_runtime.hip
+// blocking host -> HBM copy of a caller-owned block on the current device, through the page-locked staging ring when it pays (RGBM_NO_PIN=1: never); throws
+void upload_pinned(void* dst, const void* src, size_t bytes);
+// RGBM_TRACE: enqueues on s the wrapping sum of the 64-bit words of src [bytes / 8] (device) into *d_out (device, zeroed by the caller)
+void trace_sum(const void* src, size_t bytes, unsigned long long* d_out, hipStream_t s);
+// defined in rgbm.hip for rgbm_release_cache: frees the page-locked blocks the batch harvest and the repair chain keep, unless a call is using them
+void release_host_staging();
+
+// ---- rgbm_comm.hip: the communicator of the CALLING THREAD, as far as the trainer and the chained repair (rgbm.hip) use it
+enum { AR_I64 = 0, AR_U32 = 1, AR_I32 = 2 };     // element type of all_reduce
+int comm_kind();                                 // 0 none, 1 RCCL, 2 in-process thread group, 3 member of a fusion group
+int comm_rank();                                 // this thread's rank; 0 without a communicator
+int comm_nranks();                               // ranks of the communicator; 1 without one
+// in-place sum of `count` elements over the ranks, enqueued on s (a fusion member: parks until all members of its group have arrived); no-op without a communicator; throws
+void all_reduce(void* buf, size_t count, int type, hipStream_t s);
+// recv [nranks][bytes] = every rank's send [bytes] (device), enqueued on s; a copy without a communicator; throws from inside a fusion group
+void all_gather_on(const void* send, void* recv, size_t bytes, hipStream_t s);
+// waits for s; with an RCCL communicator it polls, and on a stream error, an RCCL error or RGBM_COMM_TIMEOUT_S without progress it aborts the communicator and throws
+void stream_sync_watchdog(hipStream_t s);
+// a failing rank gives up its RCCL communicator (or leaves its fusion group as failed) so that no peer waits for its next collective; the thread has none afterwards
+void comm_abort();
+// bytes received by, nanoseconds spent in and number of the all-gathers of this process (rgbm_comm_gather_stats)
+struct GatherStats { std::atomic<long long> bytes{0}, ns{0}, calls{0}; };
+GatherStats& gather_stats();
 
 // the RGBM_ERR_* code an exception stands for
 inline int status_of(const std::exception& e) {

@@ -24,7 +24,7 @@
 // behind, exclusive scan of the per-block counts, emit pass over the ballots) and never uses arrival order.
 // Every later section uses the ONE copy of each mechanism that this first section holds -- compaction: flags_to_ballots, scan_emit (into the
 // table's cell list: emit_to_table, compact<MODE>), rows_to_cells;  keys: key_digit / row_key, key_spec, table_capacity, ht_claim, wave_add;
-// bitsets: append_bitset, bitset_stage / bitset_test;  scratch: enum Scr, with the slots every entry point holds together.
+// bitsets: append_bitset, bitset_stage / bitset_test;  scratch: enum Scr, with its rule; every entry point names its slots above its definition.
 #include "rgbm_host.h"
 #include "rgbm_cost.h"
 
@@ -510,45 +510,6 @@ __global__ void k_encode_dict(const int32_t* __restrict__ idx, long long n, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// candidate distributions (python/repair/model.py:1196-1212): per cell, classes by descending probability (ties keep
-// class order), those > threshold, at most top_k.  One wave per cell: every step each lane proposes its best class
-// that comes AFTER the previous pick in (prob desc, class asc) order, a wave arg-max picks the next one.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_top_k_pmf(const double* __restrict__ proba, long long m, int K, int top_k, double threshold,
-                                                   const int32_t* __restrict__ cur_code, int32_t* __restrict__ cls_out,
-                                                   double* __restrict__ prob_out, double* __restrict__ cur_prob_out) {
-    const long long cell = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (cell >= m) return;
-    const int lane = lane_id();
-    const double* p = proba + cell * K;
-    double last_p = INFINITY; int last_c = -1;
-    for (int j = 0; j < top_k; ++j) {
-        double bp = -1.0; int bc = 0x7FFFFFFF;
-        for (int c = lane; c < K; c += 64) {
-            const double v = p[c];
-            const bool after = v < last_p || (v == last_p && c > last_c);
-            if (after && v > threshold && (v > bp || (v == bp && c < bc))) { bp = v; bc = c; }
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const double op = __shfl_xor(bp, d); const int oc = __shfl_xor(bc, d);
-            if (op > bp || (op == bp && oc < bc)) { bp = op; bc = oc; }
-        }
-        const bool found = bc != 0x7FFFFFFF;
-        if (lane == 0) { cls_out[cell * top_k + j] = found ? bc : -1; prob_out[cell * top_k + j] = found ? bp : 0.0; }
-        if (!found) {                                   // nothing left above the threshold: pad the rest
-            for (int r = j + 1 + lane; r < top_k; r += 64) { cls_out[cell * top_k + r] = -1; prob_out[cell * top_k + r] = 0.0; }
-            break;
-        }
-        last_p = bp; last_c = bc;
-    }
-    if (cur_prob_out && lane == 0) {
-        const int cc = cur_code ? cur_code[cell] : -1;
-        cur_prob_out[cell] = (cc >= 0 && cc < K) ? p[cc] : 0.0;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 inline unsigned nblocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
@@ -558,21 +519,10 @@ hipStream_t table_stream(const rgbm_table& t) {
     return t.stream;
 }
 // The table's twelve scratch buffers by what they hold.  A buffer's content lives from its scr / scr_upload call to the entry point's last
-// synchronise (prep_mu is held all that time); inside one entry point no two uses may share a slot.  Slots held together, per entry:
-//   detect_nulls, repair_pmf[_weighted]   COLS | BALLOTS BCOUNT BOFF
-//   detect_cells                          COLS TABLE_A (descriptors) TABLE_B (bitsets) | BALLOTS BCOUNT BOFF
-//   detect_constraint                     TABLE_A (keys) TABLE_B (state) ROW_MASK | BALLOTS BCOUNT BOFF | COLS (the cell columns, rows_to_cells)
-//   detect_dc                             ROW_MASK | BALLOTS BCOUNT BOFF | COLS          (its hash table and operands are DevBufs)
-//   detect_row_bits                       TABLE_A (descriptors) TABLE_B (bitsets) BALLOTS BCOUNT BOFF | COLS
-//   rows_of_cells                         ROW_MASK IN_ROWS | BALLOTS BCOUNT BOFF
-//   null_cells                            COLS (is-target bytes) IN_ROWS IN_COLS
-//   write_cells, read_cells               IN_ROWS IN_COLS VALS;     gather_rows  IN_ROWS;     count_codes  VALS
-//   pair_counts                           TABLE_A (groups) TABLE_B (pairs) COLS (group columns)
-//   cell_domains                          TABLE_A (attributes) COLS (single_ok) IN_ROWS ROW_MASK (weak) IN_COLS (top) VALS (top_prob)
-//   fd_map                                TABLE_A (lo) TABLE_B (hi) VALS (map);     rule_fill  IN_COLS (lut) VALS (labels)
-//   kmeans_assign                         TABLE_A (P, h) TABLE_B (column descriptors) VALS (counts, sizes, n_changed)
-//   column_stats                          TABLE_A (column descriptors) TABLE_B (the six numbers per column) COLS (edges) IN_COLS (length LUTs) VALS (counts)
-// (distinct_rows works on a const table whose cell list and scratch must survive: DevBufs of its own throughout.)
+// synchronise (prep_mu is held all that time); inside one entry point no two uses may share a slot.  Every entry point names the slots it
+// holds together in the line above its definition ("scratch slots held together": a | separates the slots the entry takes itself from those
+// of the compaction or of rows_to_cells it calls).  rgbm_table_distinct_rows works on a const table whose cell list and scratch must survive:
+// DevBufs of its own throughout.
 enum Scr {
     SCR_BALLOTS = 0,      // compaction: the 64-row ballots of every (block, column)
     SCR_BCOUNT = 1,       // compaction: flags per (block, column)
@@ -769,10 +719,70 @@ void edit_distance_on_device(const int32_t* a_cp, const int64_t* a_off, int64_t 
     HIPCHK(hipStreamSynchronize(s));
 }
 
+// ---------------------------------------------------------------------------------------------
+// candidate distributions (python/repair/model.py:1196-1212): per cell, classes by descending probability (ties keep
+// class order), those > threshold, at most top_k -- k_weighted_pmf (rgbm_cost.h), which without a cost matrix and without renormalisation
+// leaves the probabilities as they are.  The body of rgbm_table_repair_pmf (weighted = false: no costs, the caller passes cost_row, cost
+// and top1_cost_out null, n_cost_rows 0, renormalise 0) and of rgbm_table_repair_pmf_weighted; the error texts carry the entry's name.
+// scratch slots held together: COLS | BALLOTS BCOUNT BOFF
+// ---------------------------------------------------------------------------------------------
+int repair_pmf(bool weighted, rgbm_table* t, const rgbm_model* m, int32_t target_col, const int32_t* feat_cols, int32_t f, int32_t top_k, double threshold,
+               const int32_t* cur_code, const int32_t* cost_row, const double* cost, int64_t n_cost_rows, double weight, int32_t renormalise, int64_t cap,
+               int64_t* n_cells_out, int64_t* rows_out, int32_t* class_out, double* prob_out, double* cur_prob_out, double* top1_cost_out) {
+    const char* entry = weighted ? "rgbm_table_repair_pmf_weighted" : "rgbm_table_repair_pmf";
+    if (!t || !m || !feat_cols || f <= 0 || target_col < 0 || target_col >= t->c || top_k <= 0 || !n_cells_out || cap < 0 || n_cost_rows < 0 ||
+        (cost_row && !cost))
+        return fail(RGBM_ERR_ARG, std::string(entry) + ": bad argument");
+    return guarded([&]() {
+        use_device(t->device);
+        check_cols(*t, feat_cols, f, entry);
+        int32_t obj = 0, K = 0, F = 0;
+        model_shape(m, &obj, &K, &F);
+        if (obj == 2)
+            throw std::invalid_argument(std::string(entry) + ": a regressor has no class distribution" + (weighted ? "" : " (model.py:1214-1221 handles continuous attributes)"));
+        if (F != f) throw std::invalid_argument(std::string(entry) + ": the model was trained on a different number of features");
+        if (cost && (unsigned long long)(n_cost_rows + 1) * (unsigned long long)K > (1ull << 28))
+            throw std::invalid_argument(std::string(entry) + ": the cost matrix holds more than 2^28 entries");
+        std::lock_guard<std::mutex> prep_lk(t->prep_mu); struct { hipStream_t s; } sg{table_stream(*t)};
+        const int32_t* d_tc = scr_upload<int32_t>(*t, SCR_COLS, &target_col, 1, sg.s);
+        const long long cells = compact<0>(*t, nullptr, d_tc, 1, false, sg.s);      // ascending rows whose target cell is NULL
+        *n_cells_out = cells;
+        if (cells == 0) return RGBM_OK;
+        if (cells > cap) throw std::invalid_argument(std::string(entry) + ": output capacity too small (n_cells_out holds the needed size)");
+        if (!rows_out || !class_out || !prob_out) throw std::invalid_argument(std::string(entry) + ": output arrays missing");
+        if (cost_row)
+            for (long long i = 0; i < cells; ++i)
+                if (cost_row[i] < -1 || cost_row[i] >= n_cost_rows) throw std::invalid_argument(std::string(entry) + ": cost_row out of range");
+        // the cells' rows as a small code block, scored in one go
+        DevBuf<int32_t> sub((size_t)cells * t->c);
+        hipLaunchKernelGGL(k_gather_rows, dim3(nblocks(cells, 256), (unsigned)t->c), dim3(256), 0, sg.s, t->codes.p, (long long)t->n, sub.p, cells, t->cell_rows.p);
+        DevBuf<int32_t> d_fc((size_t)f); d_fc.upload(feat_cols, (size_t)f, sg.s);
+        DevBuf<double> proba((size_t)cells * K);
+        predict_proba_device(m, t->device, sg.s, sub.p, cells, d_fc.p, proba.p);
+        DevBuf<int32_t> d_cls((size_t)cells * top_k); DevBuf<double> d_pr((size_t)cells * top_k);
+        DevBuf<int32_t> d_cur, d_row; DevBuf<double> d_cp, d_cost, d_tc1;
+        if (cur_prob_out) { d_cp.alloc((size_t)cells); if (cur_code) { d_cur.alloc((size_t)cells); d_cur.upload(cur_code, (size_t)cells, sg.s); } }
+        if (cost) { d_cost.alloc((size_t)(n_cost_rows + 1) * K); d_cost.upload(cost, (size_t)(n_cost_rows + 1) * K, sg.s); }
+        if (cost_row) { d_row.alloc((size_t)cells); d_row.upload(cost_row, (size_t)cells, sg.s); }
+        if (top1_cost_out) d_tc1.alloc((size_t)cells);
+        hipLaunchKernelGGL(k_weighted_pmf, dim3(nblocks(cells, 4)), dim3(256), 0, sg.s, proba.p, cells, (int)K, (int)top_k, threshold,
+                           d_cur.p, d_row.p, d_cost.p, (long long)n_cost_rows, weight, renormalise ? 1 : 0, d_cls.p, d_pr.p, d_cp.p, d_tc1.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rows_out, t->cell_rows.p, (size_t)cells * 8, hipMemcpyDeviceToHost, sg.s));
+        d_cls.download(class_out, (size_t)cells * top_k, sg.s);
+        d_pr.download(prob_out, (size_t)cells * top_k, sg.s);
+        if (cur_prob_out) d_cp.download(cur_prob_out, (size_t)cells, sg.s);
+        if (top1_cost_out) d_tc1.download(top1_cost_out, (size_t)cells, sg.s);
+        HIPCHK(hipStreamSynchronize(sg.s));
+        return RGBM_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
 
+// scratch slots held together: COLS | BALLOTS BCOUNT BOFF
 RGBM_EXPORT int rgbm_table_detect_nulls(rgbm_table* t, const int32_t* cols, int32_t n_cols, int64_t* n_cells_out) {
     if (!t || !n_cells_out || n_cols < 0 || (n_cols > 0 && !cols)) return fail(RGBM_ERR_ARG, "rgbm_table_detect_nulls: bad argument");
     return guarded([&]() {
@@ -786,6 +796,7 @@ RGBM_EXPORT int rgbm_table_detect_nulls(rgbm_table* t, const int32_t* cols, int3
     });
 }
 
+// scratch slots held together: COLS TABLE_A (descriptors) TABLE_B (bitsets) | BALLOTS BCOUNT BOFF
 RGBM_EXPORT int rgbm_table_detect_cells(rgbm_table* t, const int32_t* cols, int32_t n_cols, const uint8_t* null_is_error,
                                         const int32_t* keep_lo, const int32_t* keep_hi, const uint64_t* const* flag_bits, int64_t* n_cells_out) {
     if (!t || !n_cells_out || n_cols < 0 || (n_cols > 0 && (!cols || !null_is_error || !keep_lo || !keep_hi)))
@@ -814,6 +825,7 @@ RGBM_EXPORT int rgbm_table_detect_cells(rgbm_table* t, const int32_t* cols, int3
     });
 }
 
+// scratch slots held together: TABLE_A (keys) TABLE_B (state) ROW_MASK | BALLOTS BCOUNT BOFF | COLS (the cell columns, rows_to_cells)
 RGBM_EXPORT int rgbm_table_detect_constraint(rgbm_table* t, const int32_t* eq_cols, int32_t n_eq, int32_t iq_col,
                                              const int32_t* cell_cols, int32_t n_cell_cols, int64_t* n_rows_out, int64_t* n_cells_out) {
     if (!t || n_eq < 0 || n_eq > 12 || (n_eq > 0 && !eq_cols) || n_cell_cols < 0 || (n_cell_cols > 0 && !cell_cols) || !n_cells_out)
@@ -842,6 +854,7 @@ RGBM_EXPORT int rgbm_table_detect_constraint(rgbm_table* t, const int32_t* eq_co
     });
 }
 
+// scratch slots held together: ROW_MASK IN_ROWS | BALLOTS BCOUNT BOFF
 RGBM_EXPORT int rgbm_table_rows_of_cells(rgbm_table* t, const int64_t* rows, int64_t n_cells, int64_t* n_rows_out) {
     if (!t || !n_rows_out || n_cells < 0 || (n_cells > 0 && !rows)) return fail(RGBM_ERR_ARG, "rgbm_table_rows_of_cells: bad argument");
     return guarded([&]() {
@@ -873,6 +886,7 @@ RGBM_EXPORT int rgbm_table_cells_fetch(const rgbm_table* t, int64_t* rows_out, i
     });
 }
 
+// scratch slots held together: COLS (is-target bytes) IN_ROWS IN_COLS
 RGBM_EXPORT int rgbm_table_null_cells(rgbm_table* t, const int64_t* rows, const int32_t* cols, int64_t n_cells,
                                       const int32_t* target_cols, int32_t n_targets) {
     if (!t || n_cells < 0 || (n_cells > 0 && (!rows || !cols)) || n_targets < 0 || (n_targets > 0 && !target_cols))
@@ -896,6 +910,7 @@ RGBM_EXPORT int rgbm_table_null_cells(rgbm_table* t, const int64_t* rows, const 
     });
 }
 
+// scratch slots held together: IN_ROWS IN_COLS VALS
 RGBM_EXPORT int rgbm_table_write_cells(rgbm_table* t, const int64_t* rows, const int32_t* cols, const int32_t* codes, int64_t n_cells) {
     if (!t || n_cells < 0 || (n_cells > 0 && (!rows || !cols || !codes))) return fail(RGBM_ERR_ARG, "rgbm_table_write_cells: bad argument");
     return guarded([&]() {
@@ -915,6 +930,7 @@ RGBM_EXPORT int rgbm_table_write_cells(rgbm_table* t, const int64_t* rows, const
     });
 }
 
+// scratch slots held together: IN_ROWS IN_COLS VALS
 RGBM_EXPORT int rgbm_table_read_cells(const rgbm_table* t, const int64_t* rows, const int32_t* cols, int64_t n_cells, int32_t* codes_out) {
     if (!t || n_cells < 0 || (n_cells > 0 && (!rows || !cols || !codes_out))) return fail(RGBM_ERR_ARG, "rgbm_table_read_cells: bad argument");
     return guarded([&]() {
@@ -933,6 +949,7 @@ RGBM_EXPORT int rgbm_table_read_cells(const rgbm_table* t, const int64_t* rows, 
     });
 }
 
+// scratch slots held together: IN_ROWS
 RGBM_EXPORT int rgbm_table_gather_rows(const rgbm_table* t, const int64_t* rows, int64_t n_rows, rgbm_table** out) {
     if (!t || !out || n_rows <= 0 || !rows) return fail(RGBM_ERR_ARG, "rgbm_table_gather_rows: bad argument (at least one row)");
     return guarded([&]() {
@@ -952,6 +969,7 @@ RGBM_EXPORT int rgbm_table_gather_rows(const rgbm_table* t, const int64_t* rows,
     });
 }
 
+// scratch slots held together: VALS
 RGBM_EXPORT int rgbm_table_count_codes(const rgbm_table* t, int32_t col, int64_t* counts_out, int64_t* n_null_out) {
     if (!t || !counts_out || col < 0 || col >= t->c) return fail(RGBM_ERR_ARG, "rgbm_table_count_codes: bad argument");
     return guarded([&]() {
@@ -972,6 +990,7 @@ RGBM_EXPORT int rgbm_table_count_codes(const rgbm_table* t, int32_t col, int64_t
     });
 }
 
+// scratch slots held together: TABLE_A (column descriptors) TABLE_B (the six numbers per column) COLS (edges) IN_COLS (length LUTs) VALS (counts)
 RGBM_EXPORT int rgbm_table_column_stats(const rgbm_table* t, const int32_t* cols, int32_t n_cols, const int32_t* const* len_lut, int32_t n_bins,
                                         int64_t* stats_out, int32_t* edges_out) {
     if (!t || !cols || !stats_out || n_cols < 1) return fail(RGBM_ERR_ARG, "rgbm_table_column_stats: bad argument (at least one column)");
@@ -1048,91 +1067,16 @@ RGBM_EXPORT int rgbm_table_create_dict(const int32_t* idx_colmajor, int64_t n, i
 RGBM_EXPORT int rgbm_table_repair_pmf(rgbm_table* t, const rgbm_model* m, int32_t target_col, const int32_t* feat_cols, int32_t f, int32_t top_k,
                                       double threshold, const int32_t* cur_code, int64_t cap, int64_t* n_cells_out, int64_t* rows_out,
                                       int32_t* class_out, double* prob_out, double* cur_prob_out) {
-    if (!t || !m || !feat_cols || f <= 0 || target_col < 0 || target_col >= t->c || top_k <= 0 || !n_cells_out || cap < 0)
-        return fail(RGBM_ERR_ARG, "rgbm_table_repair_pmf: bad argument");
-    return guarded([&]() {
-        use_device(t->device);
-        check_cols(*t, feat_cols, f, "rgbm_table_repair_pmf");
-        int32_t obj = 0, K = 0, F = 0;
-        model_shape(m, &obj, &K, &F);
-        if (obj == 2) throw std::invalid_argument("rgbm_table_repair_pmf: a regressor has no class distribution (model.py:1214-1221 handles continuous attributes)");
-        if (F != f) throw std::invalid_argument("rgbm_table_repair_pmf: the model was trained on a different number of features");
-        std::lock_guard<std::mutex> prep_lk(t->prep_mu); struct { hipStream_t s; } sg{table_stream(*t)};
-        const int32_t* d_tc = scr_upload<int32_t>(*t, SCR_COLS, &target_col, 1, sg.s);
-        const long long cells = compact<0>(*t, nullptr, d_tc, 1, false, sg.s);      // ascending rows whose target cell is NULL
-        *n_cells_out = cells;
-        if (cells == 0) return RGBM_OK;
-        if (cells > cap) throw std::invalid_argument("rgbm_table_repair_pmf: output capacity too small (n_cells_out holds the needed size)");
-        if (!rows_out || !class_out || !prob_out) throw std::invalid_argument("rgbm_table_repair_pmf: output arrays missing");
-        // the cells' rows as a small code block, scored in one go
-        DevBuf<int32_t> sub((size_t)cells * t->c);
-        hipLaunchKernelGGL(k_gather_rows, dim3(nblocks(cells, 256), (unsigned)t->c), dim3(256), 0, sg.s, t->codes.p, (long long)t->n, sub.p, cells, t->cell_rows.p);
-        DevBuf<int32_t> d_fc((size_t)f); d_fc.upload(feat_cols, (size_t)f, sg.s);
-        DevBuf<double> proba((size_t)cells * K);
-        predict_proba_device(m, t->device, sg.s, sub.p, cells, d_fc.p, proba.p);
-        DevBuf<int32_t> d_cls((size_t)cells * top_k); DevBuf<double> d_pr((size_t)cells * top_k);
-        DevBuf<int32_t> d_cur; DevBuf<double> d_cp;
-        if (cur_prob_out) { d_cp.alloc((size_t)cells); if (cur_code) { d_cur.alloc((size_t)cells); d_cur.upload(cur_code, (size_t)cells, sg.s); } }
-        hipLaunchKernelGGL(k_top_k_pmf, dim3(nblocks(cells, 4)), dim3(256), 0, sg.s, proba.p, cells, (int)K, (int)top_k, threshold,
-                           d_cur.p, d_cls.p, d_pr.p, d_cp.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rows_out, t->cell_rows.p, (size_t)cells * 8, hipMemcpyDeviceToHost, sg.s));
-        d_cls.download(class_out, (size_t)cells * top_k, sg.s);
-        d_pr.download(prob_out, (size_t)cells * top_k, sg.s);
-        if (cur_prob_out) d_cp.download(cur_prob_out, (size_t)cells, sg.s);
-        HIPCHK(hipStreamSynchronize(sg.s));
-        return RGBM_OK;
-    });
+    return repair_pmf(false, t, m, target_col, feat_cols, f, top_k, threshold, cur_code, nullptr, nullptr, 0, 0.0, 0, cap, n_cells_out, rows_out, class_out,
+                      prob_out, cur_prob_out, nullptr);
 }
 
 RGBM_EXPORT int rgbm_table_repair_pmf_weighted(rgbm_table* t, const rgbm_model* m, int32_t target_col, const int32_t* feat_cols, int32_t f,
                                                int32_t top_k, double threshold, const int32_t* cur_code, const int32_t* cost_row, const double* cost,
                                                int64_t n_cost_rows, double weight, int32_t renormalise, int64_t cap, int64_t* n_cells_out,
                                                int64_t* rows_out, int32_t* class_out, double* prob_out, double* cur_prob_out, double* top1_cost_out) {
-    if (!t || !m || !feat_cols || f <= 0 || target_col < 0 || target_col >= t->c || top_k <= 0 || !n_cells_out || cap < 0 || n_cost_rows < 0 ||
-        (cost_row && !cost))
-        return fail(RGBM_ERR_ARG, "rgbm_table_repair_pmf_weighted: bad argument");
-    return guarded([&]() {
-        use_device(t->device);
-        check_cols(*t, feat_cols, f, "rgbm_table_repair_pmf_weighted");
-        int32_t obj = 0, K = 0, F = 0;
-        model_shape(m, &obj, &K, &F);
-        if (obj == 2) throw std::invalid_argument("rgbm_table_repair_pmf_weighted: a regressor has no class distribution");
-        if (F != f) throw std::invalid_argument("rgbm_table_repair_pmf_weighted: the model was trained on a different number of features");
-        if (cost && (unsigned long long)(n_cost_rows + 1) * (unsigned long long)K > (1ull << 28))
-            throw std::invalid_argument("rgbm_table_repair_pmf_weighted: the cost matrix holds more than 2^28 entries");
-        std::lock_guard<std::mutex> prep_lk(t->prep_mu); struct { hipStream_t s; } sg{table_stream(*t)};
-        const int32_t* d_tc = scr_upload<int32_t>(*t, SCR_COLS, &target_col, 1, sg.s);
-        const long long cells = compact<0>(*t, nullptr, d_tc, 1, false, sg.s);      // ascending rows whose target cell is NULL
-        *n_cells_out = cells;
-        if (cells == 0) return RGBM_OK;
-        if (cells > cap) throw std::invalid_argument("rgbm_table_repair_pmf_weighted: output capacity too small (n_cells_out holds the needed size)");
-        if (!rows_out || !class_out || !prob_out) throw std::invalid_argument("rgbm_table_repair_pmf_weighted: output arrays missing");
-        if (cost_row)
-            for (long long i = 0; i < cells; ++i)
-                if (cost_row[i] < -1 || cost_row[i] >= n_cost_rows) throw std::invalid_argument("rgbm_table_repair_pmf_weighted: cost_row out of range");
-        DevBuf<int32_t> sub((size_t)cells * t->c);
-        hipLaunchKernelGGL(k_gather_rows, dim3(nblocks(cells, 256), (unsigned)t->c), dim3(256), 0, sg.s, t->codes.p, (long long)t->n, sub.p, cells, t->cell_rows.p);
-        DevBuf<int32_t> d_fc((size_t)f); d_fc.upload(feat_cols, (size_t)f, sg.s);
-        DevBuf<double> proba((size_t)cells * K);
-        predict_proba_device(m, t->device, sg.s, sub.p, cells, d_fc.p, proba.p);
-        DevBuf<int32_t> d_cls((size_t)cells * top_k); DevBuf<double> d_pr((size_t)cells * top_k);
-        DevBuf<int32_t> d_cur, d_row; DevBuf<double> d_cp, d_cost, d_tc1;
-        if (cur_prob_out) { d_cp.alloc((size_t)cells); if (cur_code) { d_cur.alloc((size_t)cells); d_cur.upload(cur_code, (size_t)cells, sg.s); } }
-        if (cost) { d_cost.alloc((size_t)(n_cost_rows + 1) * K); d_cost.upload(cost, (size_t)(n_cost_rows + 1) * K, sg.s); }
-        if (cost_row) { d_row.alloc((size_t)cells); d_row.upload(cost_row, (size_t)cells, sg.s); }
-        if (top1_cost_out) d_tc1.alloc((size_t)cells);
-        hipLaunchKernelGGL(k_weighted_pmf, dim3(nblocks(cells, 4)), dim3(256), 0, sg.s, proba.p, cells, (int)K, (int)top_k, threshold,
-                           d_cur.p, d_row.p, d_cost.p, (long long)n_cost_rows, weight, renormalise ? 1 : 0, d_cls.p, d_pr.p, d_cp.p, d_tc1.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rows_out, t->cell_rows.p, (size_t)cells * 8, hipMemcpyDeviceToHost, sg.s));
-        d_cls.download(class_out, (size_t)cells * top_k, sg.s);
-        d_pr.download(prob_out, (size_t)cells * top_k, sg.s);
-        if (cur_prob_out) d_cp.download(cur_prob_out, (size_t)cells, sg.s);
-        if (top1_cost_out) d_tc1.download(top1_cost_out, (size_t)cells, sg.s);
-        HIPCHK(hipStreamSynchronize(sg.s));
-        return RGBM_OK;
-    });
+    return repair_pmf(true, t, m, target_col, feat_cols, f, top_k, threshold, cur_code, cost_row, cost, n_cost_rows, weight, renormalise, cap, n_cells_out,
+                      rows_out, class_out, prob_out, cur_prob_out, top1_cost_out);
 }
 
 RGBM_EXPORT int rgbm_edit_distance(int32_t device_id, const int32_t* a_cp, const int64_t* a_off, int64_t n_a, const int32_t* b_cp,
@@ -1305,6 +1249,7 @@ __global__ __launch_bounds__(256) void k_cell_domains(const int32_t* __restrict_
 
 extern "C" {
 
+// scratch slots held together: TABLE_A (groups) TABLE_B (pairs) COLS (group columns)
 RGBM_EXPORT int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, int32_t n_pairs, const int32_t* const* luts,
                                        const int32_t* n_bins, int64_t* counts_out) {
     if (!t || !pair_cols || n_pairs <= 0 || !n_bins || !counts_out) return fail(RGBM_ERR_ARG, "rgbm_table_pair_counts: bad argument");
@@ -1395,6 +1340,7 @@ RGBM_EXPORT int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, 
     });
 }
 
+// scratch slots held together: TABLE_A (attributes) COLS (single_ok) IN_ROWS ROW_MASK (weak) IN_COLS (top) VALS (top_prob)
 RGBM_EXPORT int rgbm_table_cell_domains(rgbm_table* t, int32_t target_col, const int64_t* rows, int64_t n_cells, const int32_t* pair_idx, int32_t k,
                                         const int64_t* min_cnt, const uint8_t* single_ok, double beta, int64_t row_count, uint8_t* weak_out,
                                         int32_t* top_out, double* top_prob_out, double* probs_out) {
@@ -1554,6 +1500,7 @@ __global__ __launch_bounds__(256) void k_row_nearest(const T* __restrict__ mat, 
 
 extern "C" {
 
+// scratch slots held together: TABLE_A (lo) TABLE_B (hi) VALS (map)
 RGBM_EXPORT int rgbm_table_fd_map(const rgbm_table* t, int32_t x_col, int32_t y_col, int32_t* map_out) {
     if (!t || !map_out || x_col < 0 || x_col >= t->c || y_col < 0 || y_col >= t->c || x_col == y_col)
         return fail(RGBM_ERR_ARG, "rgbm_table_fd_map: bad argument");
@@ -1588,6 +1535,7 @@ RGBM_EXPORT int rgbm_table_fd_map(const rgbm_table* t, int32_t x_col, int32_t y_
     });
 }
 
+// scratch slots held together: IN_COLS (lut) VALS (labels)
 RGBM_EXPORT int rgbm_table_rule_fill(rgbm_table* t, int32_t y_col, int32_t x_col, const int32_t* lut, int32_t n_lut, int64_t row_begin,
                                      int64_t n_rows, int32_t* out_label) {
     if (!t || y_col < 0 || y_col >= t->c || x_col >= t->c || x_col == y_col || !lut || n_lut < 1 || row_begin < 0 || n_rows < 0 ||
@@ -1971,6 +1919,7 @@ void kmeans_launch(unsigned grid, size_t lds, hipStream_t s, const int32_t* code
 
 extern "C" {
 
+// scratch slots held together: TABLE_A (P, h) TABLE_B (column descriptors) VALS (counts, sizes, n_changed)
 RGBM_EXPORT int rgbm_table_kmeans_assign(rgbm_table* t, const int32_t* cols, int32_t n_cols, const int64_t* code_off, int32_t k, const double* p,
                                          int64_t d_tot, const double* h, int32_t first, int64_t* counts_out, int64_t* sizes_out,
                                          int64_t* n_changed_out) {
@@ -2457,6 +2406,7 @@ void launch_dc_pairs(unsigned nb, size_t lds, hipStream_t s, const int32_t* lop,
 
 extern "C" {
 
+// scratch slots held together: ROW_MASK | BALLOTS BCOUNT BOFF | COLS          (its hash table and operands are DevBufs)
 RGBM_EXPORT int rgbm_table_detect_dc(rgbm_table* t, const rgbm_dc_pred* preds, int32_t n_preds, const int32_t* cell_cols, int32_t n_cell_cols,
                                      int64_t max_pairs, int64_t* n_rows_out, int64_t* n_cells_out) {
     if (!t || !preds || n_preds < 2 || n_preds > DC_MAX_PREDS || n_cell_cols < 0 || (n_cell_cols > 0 && !cell_cols) || !n_cells_out)
@@ -2552,6 +2502,7 @@ RGBM_EXPORT int rgbm_table_detect_dc(rgbm_table* t, const rgbm_dc_pred* preds, i
     });
 }
 
+// scratch slots held together: TABLE_A (descriptors) TABLE_B (bitsets) BALLOTS BCOUNT BOFF | COLS
 RGBM_EXPORT int rgbm_table_detect_row_bits(rgbm_table* t, const int32_t* cols, int32_t n_cols, const uint64_t* const* bits, const int32_t* cell_cols,
                                            int32_t n_cell_cols, int64_t* n_rows_out, int64_t* n_cells_out) {
     if (!t || n_cols < 1 || !cols || !bits || n_cell_cols < 0 || (n_cell_cols > 0 && !cell_cols) || !n_cells_out)

@@ -4,14 +4,30 @@ The oracle backend exposes the same train()/Model API as repair._native so the p
 (repair.gbm / repair.model) can be exercised on CPU-only machines.  It lives under tests/ because
 only tests may touch oracle/.
 """
+import glob
 import gzip
 import json
 import os
+import re
 
 import numpy as np
 import pandas as pd
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "spark-data-repair-plugin_amd", "csrc")
+
+
+def csrc_constant(name):
+    """`constexpr int NAME = <digits>;` of the library's sources (csrc/*.hip, csrc/*.h), wherever it is defined: the constant of the source, not
+    a copy of it.  Exactly one definition, or an AssertionError that names the files."""
+    hits = []
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
+        with open(path, encoding="utf-8") as f:
+            hits += [(os.path.basename(path), int(v)) for v in re.findall(r"constexpr int %s = (\d+);" % re.escape(name), f.read())]
+    assert len(hits) == 1, "%s: %d definitions in csrc (%s)" % (name, len(hits), ", ".join(h[0] for h in hits))
+    return hits[0][1]
 
 
 def load_golden(name):

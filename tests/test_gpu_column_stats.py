@@ -1,23 +1,19 @@
 """-m gpu: `rgbm_table_column_stats` (csrc/rgbm_prep.hip: k_colstat_count, k_colstat_reduce) against its numpy statement
 `repair.table_stats.column_stats` -- integers throughout, so equality, no tolerance -- and `RepairMisc.describe` / `generateDepGraph`
 through the HIP engine against their numpy paths."""
-import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import misc_restatement as R
+from tests.helpers import csrc_constant
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _const(name):
     """A constant of the source, not a copy of it."""
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    return int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
+    return csrc_constant(name)
 
 
 CC_LDS = _const("CC_LDS")                      # codes up to which the count pass keeps 32-bit counters in LDS

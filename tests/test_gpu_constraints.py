@@ -1,8 +1,6 @@
 """-m gpu: rgbm_table_detect_dc and rgbm_table_detect_row_bits (csrc/rgbm_prep.hip) against their numpy restatements
 (tests/dc_restatement.py) -- integers, so equality of rows and columns, order included -- a 20 001-row table the host detector refuses,
 and `RepairModel.run()` with `error.constraints.resident` through the HIP engine against the value-space path."""
-import os
-import re
 
 import numpy as np
 import pandas as pd
@@ -10,18 +8,17 @@ import pytest
 
 from repair import detect_codes as DC
 from tests import dc_restatement as R
+from tests.helpers import csrc_constant
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G, A, B, C_ = 0, 1, 2, 3                       # columns: the group attribute, two ranked attributes, a small one
 NA, NB, NC = 7, 65, 3
 
 
 def _tiles():
     """(t1 rows per workgroup, t2 rows per LDS tile) of the pair kernel: the constants of the source, not copies of them."""
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    return tuple(int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1)) for k in ("DC_T1", "DC_T2"))
+    return tuple(csrc_constant(k) for k in ("DC_T1", "DC_T2"))
 
 
 def _groups(n, shape, rng):
@@ -230,8 +227,7 @@ def test_detect_row_bits_equals_the_restatement(n):
 
 def _lds_bits():
     """The most bits of a bitset that is staged into LDS: the constant of the source, not a copy of it."""
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    return int(re.search(r"constexpr int DET_LDS_WORDS = (\d+);", src).group(1)) * 64
+    return csrc_constant("DET_LDS_WORDS") * 64
 
 
 def test_row_bits_bitset_either_side_of_the_lds_bound():

@@ -1,23 +1,19 @@
 """-m gpu: the device step of the q-gram k-means (csrc/rgbm_prep.hip: rgbm_table_kmeans_assign / rgbm_table_kmeans_read) against the
 numpy step of repair/qgram_kmeans.py -- labels, counts, sizes and n_changed are integers that follow from float64 additions in one fixed
 order, so equality, no tolerance -- and `RepairMisc.splitInputTable` through the HIP engine against the numpy path."""
-import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import kmeans_restatement as R
+from tests.helpers import csrc_constant
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _const(name):
     """A constant of the source, not a copy of it."""
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    return int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
+    return csrc_constant(name)
 
 
 WG_ROWS = _const("KM_B") * _const("KM_UNROLL")       # rows of one workgroup on a table of up to 512 workgroups

@@ -2,23 +2,20 @@
 rgbm_nearest_values) against their numpy restatements (tests/rule_restatements.py) -- integers, so equality -- and
 `RepairModel.run()` with `setRepairByRules(True)` and `model.rule.resident` through the HIP engine against the value-space path."""
 import os
-import re
 
 import numpy as np
 import pandas as pd
 import pytest
 
 from tests import rule_restatements as R
+from tests.helpers import csrc_constant
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _lds_codes():
     """The largest n_codes[x] whose (lo, hi) tables stay in LDS: the constant of the source, not a copy of it."""
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    return int(re.search(r"constexpr int FD_LDS_CODES = (\d+);", src).group(1))
+    return csrc_constant("FD_LDS_CODES")
 
 
 N_ROWS = 200_003            # 25 workgroups of 8192 rows; not a multiple of the 2048-row load tile

@@ -1,8 +1,6 @@
 """-m gpu: rgbm_table_detect_cells (csrc/rgbm_prep.hip) against its numpy restatement (tests/detector_restatements.py) -- integers, so
 equality of rows and columns, order included -- and one `RepairModel.run()` with the value detectors on the resident table through
 the HIP engine against the value-space path."""
-import os
-import re
 
 import numpy as np
 import pandas as pd
@@ -10,17 +8,16 @@ import pytest
 
 from repair import detect_codes as DC
 from tests import detector_restatements as R
+from tests.helpers import csrc_constant
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODES = [1, 63, 64, 65, 129]                 # codes per column: the edges of the 64-bit bitset words
 
 
 def _lds_codes():
     """The most codes whose bitset is staged into LDS: the constant of the source, not a copy of it."""
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    return int(re.search(r"constexpr int DET_LDS_WORDS = (\d+);", src).group(1)) * 64
+    return csrc_constant("DET_LDS_WORDS") * 64
 
 
 def _table(n, n_codes, seed):
