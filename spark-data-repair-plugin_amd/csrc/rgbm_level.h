@@ -1415,11 +1415,95 @@ __global__ __launch_bounds__(64) void k_level_replay(LvPlan* __restrict__ plan, 
 // k_level_final: the last routing step (depth max_depth-1 -> max_depth, no histogram), the exact
 // row counts of the deepest children and ScoreUpdater::AddScore in ONE streaming pass: every
 // training row ends in its final speculative node, whose score delta the replay has tabulated.
-// grid (gx, K), block 256, 4 rows per thread.
+// grid (gx, K), block 256, 4 rows per thread: rows i..i+3 with i % 4 == 0, so that their node ids
+// are one aligned dword (NS is a multiple of 256).
+// The scores are [K][N] with stride N itself, so a class tree's first score sits at 0 mod 16 bytes
+// or, for an odd class tree of an odd N, at 8 mod 16.  The four scores of a group are loaded and
+// stored non-temporally in one of two forms, chosen per workgroup (blockIdx.y = k: no divergence):
+//   16 + 16 bytes      sk + i, sk + i + 2                                  sk 16-byte aligned
+//   8 + 16 + 8 bytes   sk[i], the aligned pair at sk + i + 1, sk[i + 3]    sk at 8 mod 16
+// Only the last, incomplete group of a class tree (i + 3 >= N) takes the scalar path.  (Before the
+// second form every odd class tree of a table -- or distinct-row view -- of odd N took the scalar
+// path for ALL its rows: profiles/EXPERIMENTS.md, round 12.)  The score stride stays N: the array
+// is shared with the leaf-wise grower, the bagging / out-of-bag updates, the validation scores,
+// k_init_score and the trace sums, and a padded stride would touch all of them for no further gain.
 // ------------------------------------------------------------------------------------------------
 // (A variant that also wrote the NEXT iteration's gradients -- one read of the K x N scores instead of two -- was built twice in round 5 and
 // measured slower both times (profiles/r5b_*, profiles/EXPERIMENTS.md); it left the tree with numerics v2.2, whose grid is measured by
 // the gradient kernels.)
+
+// One row of the last routing step: the node the row ends in (n itself where the plan did not expand n), counted when the row is in the bag.
+// Rows with multiplicities carry theirs in byte 15 of their LAST record: when the split feature lives in that chunk (always, for a table of
+// <= 16 features) one 16-byte fetch gives both bytes instead of two gathers into the same record.
+__device__ __forceinline__ int lv_final_route(int n, long long row, const uint4* __restrict__ rec, const uint8_t* __restrict__ inbag, const uint32_t* route0,
+                                              const uint32_t* route1, int32_t* cnt, int child_first, int lane, const LevelConst& c) {
+    const uint32_t w0 = route0[n];
+    if (!(w0 & (1u << 24))) return n;
+    const int f = (int)(w0 & 0xFFu), theta1 = (int)((w0 >> 8) & 0xFFu), nanbin = (int)((w0 >> 16) & 0xFFu);
+    const uint8_t* rec8 = reinterpret_cast<const uint8_t*>(rec);
+    const long long last = (long long)(c.nchunk - 1) * c.N + row;
+    int bin, mult = 1;
+    if (c.has_mult && (f >> 4) == c.nchunk - 1) {
+        const uint4 r = rec[last];
+        bin = (int)rec_byte(r, f & 15); mult = (int)(r.w >> 24);
+    } else {
+        bin = (int)rec8[((long long)(f >> 4) * c.N + row) * 16 + (f & 15)];
+        if (c.has_mult) mult = (int)rec8[last * 16 + 15];
+    }
+    const bool left = (bin == nanbin) ? ((w0 >> 25) & 1u) != 0u : (bin < theta1);
+    const uint32_t w1 = route1[n];
+    n = left ? (int)(w1 & 0xFFu) : (int)((w1 >> 8) & 0xFFu);
+    if (!inbag || inbag[row]) atomicAdd(&cnt[(n - child_first) * LV_CNT_REP + (lane & (LV_CNT_REP - 1))], mult);
+    return n;
+}
+
+// the rows of one workgroup; MIS: the class tree's scores start at 8 mod 16 bytes (the 8 + 16 + 8 form)
+template <bool MIS>
+__device__ __forceinline__ void lv_final_rows(const uint4* __restrict__ rec, const uint8_t* __restrict__ node, const uint8_t* __restrict__ inbag, double* __restrict__ sk,
+                                              const double* nd, const uint32_t* route0, const uint32_t* route1, int32_t* cnt, int child_first, const LevelConst& c) {
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    const long long N = c.N;
+    const int tid = threadIdx.x, lane = tid & 63;
+    // node ids and scores are loaded together (independent loads), then routed and written back
+    for (long long i = ((long long)blockIdx.x * 256 + tid) * 4; i < N; i += (long long)gridDim.x * 1024) {
+        if (i + 3 < N) {
+            // (non-temporal: every score is read and written once per iteration -- 19 GB per step of the 10M x 16 job that would otherwise push the bin records the
+            // level passes of the other targets in flight re-read out of the L2)
+            const uint32_t n4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(node + i));
+            double sv[4];
+            if (MIS) {
+                sv[0] = __builtin_nontemporal_load(sk + i);
+                const v2d s12 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(sk + i + 1));
+                sv[3] = __builtin_nontemporal_load(sk + i + 3);
+                sv[1] = s12.x; sv[2] = s12.y;
+            } else {
+                const v2d s01 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(sk + i)), s23 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(sk + i + 2));
+                sv[0] = s01.x; sv[1] = s01.y; sv[2] = s23.x; sv[3] = s23.y;
+            }
+            if (n4 == 0xFFFFFFFFu) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n = (int)((n4 >> (8 * j)) & 0xFFu);
+                if (n == LV_INACTIVE) continue;
+                sv[j] += nd[lv_final_route(n, i + j, rec, inbag, route0, route1, cnt, child_first, lane, c)];
+            }
+            if (MIS) {
+                v2d s12; s12.x = sv[1]; s12.y = sv[2];
+                __builtin_nontemporal_store(sv[0], sk + i); __builtin_nontemporal_store(s12, reinterpret_cast<v2d*>(sk + i + 1)); __builtin_nontemporal_store(sv[3], sk + i + 3);
+            } else {
+                v2d s01, s23; s01.x = sv[0]; s01.y = sv[1]; s23.x = sv[2]; s23.y = sv[3];
+                __builtin_nontemporal_store(s01, reinterpret_cast<v2d*>(sk + i)); __builtin_nontemporal_store(s23, reinterpret_cast<v2d*>(sk + i + 2));
+            }
+            continue;
+        }
+        for (long long row = i; row < N; ++row) {     // the last, incomplete group of the class tree
+            const int n = node[row];
+            if (n == LV_INACTIVE) continue;
+            sk[row] += nd[lv_final_route(n, row, rec, inbag, route0, route1, cnt, child_first, lane, c)];
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_level_final(const uint4* __restrict__ rec, const uint8_t* __restrict__ node_all,
                                                      const uint8_t* __restrict__ inbag, const LvPlan* __restrict__ plan, const TreeOut out,
                                                      const double* __restrict__ node_delta, double* __restrict__ score, int32_t* __restrict__ count,
@@ -1433,61 +1517,15 @@ __global__ __launch_bounds__(256) void k_level_final(const uint4* __restrict__ r
     const LvPlan* pp = &plan[k];
     const bool route = !pp->done;                      // plan(max_depth) expanded at least one node
     const int n_exp = route ? pp->n_exp : 0, child_first = pp->child_first;
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     nd[tid] = node_delta[(long long)k * 256 + tid];
     route0[tid] = route ? pp->route0[tid] : 0u; route1[tid] = pp->route1[tid];
     for (int i = tid; i < 2 * n_exp * LV_CNT_REP; i += 256) cnt[i] = 0;
     __syncthreads();
-    const long long N = c.N;
     const uint8_t* node = node_all + (long long)k * c.NS;
-    const uint8_t* rec8 = reinterpret_cast<const uint8_t*>(rec);
-    double* sk = score + (long long)k * N;
-    // 4 rows per thread; node ids and scores are loaded together (independent loads), then routed and written back
-    const bool aligned16 = (((unsigned long long)sk) & 15ull) == 0ull;   // uniform
-    for (long long i = ((long long)blockIdx.x * 256 + tid) * 4; i < N; i += (long long)gridDim.x * 1024) {
-        if (i + 3 < N && aligned16) {
-            // (non-temporal: every score is read and written once per iteration -- 19 GB per step of the 10M x 16 job that would otherwise push the bin records the
-            // level passes of the other targets in flight re-read out of the L2)
-            typedef double v2d __attribute__((ext_vector_type(2)));
-            const uint32_t n4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(node + i));
-            v2d s01 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(sk + i)), s23 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(sk + i + 2));
-            if (n4 == 0xFFFFFFFFu) continue;
-            double sv[4] = {s01.x, s01.y, s23.x, s23.y};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int n = (int)((n4 >> (8 * j)) & 0xFFu);
-                if (n == LV_INACTIVE) continue;
-                const long long row = i + j;
-                const uint32_t w0 = route0[n];
-                if (w0 & (1u << 24)) {
-                    const int f = (int)(w0 & 0xFFu), theta1 = (int)((w0 >> 8) & 0xFFu), nanbin = (int)((w0 >> 16) & 0xFFu);
-                    const int bin = (int)rec8[((long long)(f >> 4) * N + row) * 16 + (f & 15)];
-                    const bool left = (bin == nanbin) ? ((w0 >> 25) & 1u) != 0u : (bin < theta1);
-                    const uint32_t w1 = route1[n];
-                    n = left ? (int)(w1 & 0xFFu) : (int)((w1 >> 8) & 0xFFu);
-                    if (!inbag || inbag[row]) atomicAdd(&cnt[(n - child_first) * LV_CNT_REP + (lane & (LV_CNT_REP - 1))], c.has_mult ? (int)rec8[((long long)(c.nchunk - 1) * N + row) * 16 + 15] : 1);
-                }
-                sv[j] += nd[n];
-            }
-            s01.x = sv[0]; s01.y = sv[1]; s23.x = sv[2]; s23.y = sv[3];
-            __builtin_nontemporal_store(s01, reinterpret_cast<v2d*>(sk + i)); __builtin_nontemporal_store(s23, reinterpret_cast<v2d*>(sk + i + 2));
-            continue;
-        }
-        for (long long row = i; row < N && row < i + 4; ++row) {
-            int n = node[row];
-            if (n == LV_INACTIVE) continue;
-            const uint32_t w0 = route0[n];
-            if (w0 & (1u << 24)) {
-                const int f = (int)(w0 & 0xFFu), theta1 = (int)((w0 >> 8) & 0xFFu), nanbin = (int)((w0 >> 16) & 0xFFu);
-                const int bin = (int)rec8[((long long)(f >> 4) * N + row) * 16 + (f & 15)];
-                const bool left = (bin == nanbin) ? ((w0 >> 25) & 1u) != 0u : (bin < theta1);
-                const uint32_t w1 = route1[n];
-                n = left ? (int)(w1 & 0xFFu) : (int)((w1 >> 8) & 0xFFu);
-                if (!inbag || inbag[row]) atomicAdd(&cnt[(n - child_first) * LV_CNT_REP + (lane & (LV_CNT_REP - 1))], c.has_mult ? (int)rec8[((long long)(c.nchunk - 1) * N + row) * 16 + 15] : 1);
-            }
-            sk[row] += nd[n];
-        }
-    }
+    double* sk = score + (long long)k * c.N;
+    if ((((unsigned long long)sk) & 15ull) == 0ull) lv_final_rows<false>(rec, node, inbag, sk, nd, route0, route1, cnt, child_first, c);   // uniform
+    else lv_final_rows<true>(rec, node, inbag, sk, nd, route0, route1, cnt, child_first, c);
     __syncthreads();
     for (int ci = tid; ci < 2 * n_exp; ci += 256) {
         int tot = 0;
