@@ -1,5 +1,5 @@
 """CPU restatement (numpy) of the relational steps either side of the repair models, in code space.
-TEST INFRASTRUCTURE ONLY -- the product path is csrc/rgbm_prep.hip; nothing under the package imports this.
+TEST INFRASTRUCTURE ONLY -- the product path is csrc/rgbm_prep.hip (top_k_pmf: csrc/rgbm_pmf.hip); nothing under the package imports this.
 
 A table is an int32 array ``codes[c][n]`` (column-major, -1 = NULL); a cell is (row position, column index).
 Each function cites the reference code it follows (read-only study copy under /root/reference):

@@ -1,5 +1,5 @@
 // rgbm_cost.h -- the update-cost side of the probability modes (python/repair/model.py `_compute_repair_pmf`, `_compute_score`;
-// reference model.py:1145-1277), included by rgbm_prep.hip:
+// reference model.py:1145-1277), included by rgbm_pmf.hip and by no other source (the kernels are file-local):
 //
 //   k_edit_distance       Levenshtein distance of every (a, b) pair of two string pools      (repair.costs.edit_distance)
 //   k_edit_distance_long  the same for pairs whose strings are BOTH longer than 64 code points

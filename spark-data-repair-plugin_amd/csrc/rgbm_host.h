@@ -146,7 +146,7 @@ void model_shape(const rgbm_model* m, int32_t* objective, int32_t* num_class, in
 struct distinct_cannot : std::invalid_argument { using std::invalid_argument::invalid_argument; };
 struct device_oom : std::runtime_error { using std::runtime_error::runtime_error; };
 
-// the body of rgbm_table_distinct_rows (rgbm_prep.hip), shared with the distinct-row view; throws.  inverse_host_out [n] may be null: then no
+// the body of rgbm_table_distinct_rows (rgbm_distinct.hip), shared with the distinct-row view; throws.  inverse_host_out [n] may be null: then no
 // inverse is computed and nothing but two counters leaves the device.  max_rows >= 0: a result of more rows is counted (rows) but not made (tab stays null)
 struct DistinctOut { std::unique_ptr<rgbm_table> tab; int64_t rows = 0; };
 DistinctOut distinct_rows_device(const rgbm_table& t, int64_t* inverse_host_out, int64_t max_rows);
@@ -175,9 +175,9 @@ struct rgbm_table {
     // rows with MULTIPLICITIES (rgbm_table_set_row_multiplicity): row i stands for mult[i] (1..255) identical rows of a larger table -- every count,
     // every gradient sum and every coarse magnitude of a training call weighs it so; the model is byte for byte the one the expanded table gives
     rgh::DevBuf<uint8_t> mult; bool has_mult = false; int64_t mult_total = 0;
-    // result of the last rgbm_table_detect_* call (rgbm_prep.hip): cells (row, column), device resident
+    // result of the last rgbm_table_detect_* call (rgbm_prep.hip, rgbm_dc.hip): cells (row, column), device resident
     rgh::DevBuf<long long> cell_rows; rgh::DevBuf<int32_t> cell_cols; int64_t n_cells = 0;
-    // stream + scratch of the relational steps (rgbm_prep.hip), kept with the table: a hipMalloc / hipFree / stream
+    // stream + scratch of the relational steps (rgbm_prep.h: table_stream, enum Scr), kept with the table: a hipMalloc / hipFree / stream
     // creation per call costs more than the kernels (one call at a time per table, as the header says)
     // Python threads share one table (the folds of a hyper-parameter search gather from the training table, ctypes drops the
     // GIL): every entry point that touches the stream / scratch / cell list holds prep_mu from the first use to its final synchronise.

@@ -617,7 +617,7 @@ class Table:
                                             C.byref(h)), "rgbm_table_create_dict")
         return cls._adopt(h, device_id)
 
-    # ---- relational steps around the models (csrc/rgbm_prep.hip)
+    # ---- relational steps around the models (csrc/rgbm_prep.hip and the rgbm_<step>.hip sources beside it)
     def _fetch_cells(self, n, want_cols):
         rows = np.zeros(n, np.int64)
         cols = np.zeros(n, np.int32) if want_cols else None

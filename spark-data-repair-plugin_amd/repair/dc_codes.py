@@ -1,5 +1,5 @@
 """Parsed denial constraints (`repair.errors.parse_constraint`) as programs on a table's DICTIONARY CODES -- what
-`Table.detect_constraint` / `Table.detect_dc` / `Table.detect_row_bits` (csrc/rgbm_prep.hip) take.
+`Table.detect_constraint` / `Table.detect_dc` / `Table.detect_row_bits` (csrc/rgbm_prep.hip the first, csrc/rgbm_dc.hip the other two) take.
 
 A column of the label-encoded table holds codes 0..D-1 into its dictionary (`pipeline.encode_frame`: the distinct non-NULL values,
 ascending; -1 = NULL).  `lower_constraint` gives one of three programs, each with exactly the rows `errors._violating_rows` gives on
@@ -27,7 +27,7 @@ from repair.detect_codes import dictionary_series, pack_bits
 from repair.errors import _constant_predicate_holds
 
 MAX_PREDS = 16          # rgbm_table_detect_dc
-MAX_EQ = 12             # KeySpec of csrc/rgbm_prep.hip
+MAX_EQ = 12             # KeySpec of csrc/rgbm_prep.h
 
 
 class NotLowerable(ValueError):

@@ -3,7 +3,7 @@
 `computeAttrStats`, 479-675 `computeDomainInErrorCells`), re-stated on code matrices: int32 codes, -1 = NULL.
 
 This module is the value-space implementation and DEFINES the result; the device entries (`Table.pair_counts`,
-`Table.cell_domains`, csrc/rgbm_prep.hip) must equal it -- counts exactly, probabilities bit for bit.  The entropy / selection
+`Table.cell_domains`, csrc/rgbm_domain.hip) must equal it -- counts exactly, probabilities bit for bit.  The entropy / selection
 code (`candidate_pairs`, `pairwise_stats`, `analyse`) is shared by both paths: it only sees integer counts.
 
 Stated deviations from the reference (DESIGN.md "Cell-domain analysis"):

@@ -1,6 +1,6 @@
 """`LOFOutlierErrorDetector` (scikit-learn's `LocalOutlierFactor(novelty=False)` on one continuous attribute whose NULLs are replaced
 by the median, repair/errors.py `ScikitLearnBackedErrorDetector._detect_impl`) as a function of a column's DICTIONARY CODES -- the
-statement `rgbm_lof_1d` (csrc/rgbm_prep.hip) computes bit for bit, and what `detect_codes.build_descriptors` turns into `flag_bits`.
+statement `rgbm_lof_1d` (csrc/rgbm_lof.hip) computes bit for bit, and what `detect_codes.build_descriptors` turns into `flag_bits`.
 
 A continuous column's dictionary is its distinct values in ascending order and `count_codes` gives the rows per code.  In one
 dimension the k nearest neighbours of a value are the other copies of itself plus a contiguous window of at most k neighbouring

@@ -2,7 +2,7 @@
 
 The reference walks  detect errors -> convertErrorCellsToNull -> clean/dirty split -> per-attribute models ->
 chained repair -> flatten + join with the error cells  through Spark SQL and pandas (python/repair/model.py:1293-1419).
-Here every step is a call on the engine's table object (csrc/rgbm_prep.hip for the relational steps,
+Here every step is a call on the engine's table object (csrc/rgbm_prep.hip and the rgbm_<step>.hip sources beside it for the relational steps,
 csrc/rgbm.hip for the models); the host only merges the (small) cell lists.  The engine is an argument so the same
 job logic runs on the CPU oracle engine in the tests.
 
@@ -330,7 +330,7 @@ def unseen_categories(table, dirty_tab, targets, ordered_cols=(), train_tables=N
 
 
 class TableBackend:
-    """`repair.domain` backend on a resident table: `Table.pair_counts` / `Table.cell_domains` (csrc/rgbm_prep.hip).  Dense tables
+    """`repair.domain` backend on a resident table: `Table.pair_counts` / `Table.cell_domains` (csrc/rgbm_domain.hip).  Dense tables
     beyond the library's cap (RGBM_ERR_PARAM) or more correlated attributes than the kernel takes leave the resident path."""
     MAX_CORR = 8
 

@@ -1,4 +1,4 @@
-"""Column statistics in code space: the numpy statement of `rgbm_table_column_stats` (csrc/rgbm_prep.hip) and what `RepairMisc.describe`
+"""Column statistics in code space: the numpy statement of `rgbm_table_column_stats` (csrc/rgbm_colstats.hip) and what `RepairMisc.describe`
 makes of its integers (RepairMiscApi.computeAndGetStats, RepairMiscApi.scala).
 
 A label-encoded column is a dictionary (its distinct values in ascending order) and one int32 code per row.  Every figure of Spark's

@@ -1,4 +1,4 @@
-"""-m gpu: `rgbm_table_column_stats` (csrc/rgbm_prep.hip: k_colstat_count, k_colstat_reduce) against its numpy statement
+"""-m gpu: `rgbm_table_column_stats` (csrc/rgbm_colstats.hip: k_colstat_count, k_colstat_reduce) against its numpy statement
 `repair.table_stats.column_stats` -- integers throughout, so equality, no tolerance -- and `RepairMisc.describe` / `generateDepGraph`
 through the HIP engine against their numpy paths."""
 

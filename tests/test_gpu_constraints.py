@@ -1,4 +1,4 @@
-"""-m gpu: rgbm_table_detect_dc and rgbm_table_detect_row_bits (csrc/rgbm_prep.hip) against their numpy restatements
+"""-m gpu: rgbm_table_detect_dc and rgbm_table_detect_row_bits (csrc/rgbm_dc.hip) against their numpy restatements
 (tests/dc_restatement.py) -- integers, so equality of rows and columns, order included -- a 20 001-row table the host detector refuses,
 and `RepairModel.run()` with `error.constraints.resident` through the HIP engine against the value-space path."""
 

@@ -1,4 +1,4 @@
-"""-m gpu: the device step of the q-gram k-means (csrc/rgbm_prep.hip: rgbm_table_kmeans_assign / rgbm_table_kmeans_read) against the
+"""-m gpu: the device step of the q-gram k-means (csrc/rgbm_kmeans.hip: rgbm_table_kmeans_assign / rgbm_table_kmeans_read) against the
 numpy step of repair/qgram_kmeans.py -- labels, counts, sizes and n_changed are integers that follow from float64 additions in one fixed
 order, so equality, no tolerance -- and `RepairMisc.splitInputTable` through the HIP engine against the numpy path."""
 

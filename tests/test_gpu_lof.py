@@ -1,4 +1,4 @@
-"""-m gpu: rgbm_lof_1d (csrc/rgbm_prep.hip: k_lof_window, k_lof_lrd, k_lof_score) against the numpy statement repair/lof_codes.py --
+"""-m gpu: rgbm_lof_1d (csrc/rgbm_lof.hip: k_lof_window, k_lof_lrd, k_lof_score) against the numpy statement repair/lof_codes.py --
 scores as uint64 views, flag words and both counters, so equality -- and one `RepairModel.run()` with LOFOutlierErrorDetector on the
 resident table through the HIP engine against the value-space path."""
 import numpy as np

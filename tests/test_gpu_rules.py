@@ -1,4 +1,4 @@
-"""-m gpu: the device entries of the rule-based repairs (csrc/rgbm_prep.hip: rgbm_table_fd_map, rgbm_table_rule_fill,
+"""-m gpu: the device entries of the rule-based repairs (csrc/rgbm_rules.hip: rgbm_table_fd_map, rgbm_table_rule_fill,
 rgbm_nearest_values) against their numpy restatements (tests/rule_restatements.py) -- integers, so equality -- and
 `RepairModel.run()` with `setRepairByRules(True)` and `model.rule.resident` through the HIP engine against the value-space path."""
 import os

@@ -1,4 +1,4 @@
-"""Column statistics of a resident table: ONE call of `Table.column_stats` (rgbm_table_column_stats, csrc/rgbm_prep.hip: the per-code
+"""Column statistics of a resident table: ONE call of `Table.column_stats` (rgbm_table_column_stats, csrc/rgbm_colstats.hip: the per-code
 counts stay on the device) against one call of `Table.count_codes` per column (rgbm_table_count_codes: the counts of every column come to
 the host, n_codes x 8 B each), which is what a caller had before the entry existed.  Wall clock around calls that end in a stream
 synchronise, result copies included; the two are timed alternately in the same process, best and median of `--reps` after a warm-up.

@@ -1,4 +1,4 @@
-"""`Table.detect_dc` (rgbm_table_detect_dc, csrc/rgbm_prep.hip) on synthetic tables in the three regimes of the pair kernel --
+"""`Table.detect_dc` (rgbm_table_detect_dc, csrc/rgbm_dc.hip) on synthetic tables in the three regimes of the pair kernel --
 
   * fd_like     n = 1M rows in groups of 3: millions of tiny groups, the cost is the grouping;
   * groups_1000 n = 1M rows in groups of ~1000: EQ + GT + LT, early exit at work;

@@ -22,7 +22,6 @@ device result is compared with the numpy restatement (tests/detector_restatement
 import argparse
 import json
 import os
-import re
 import sys
 import time
 
@@ -36,6 +35,7 @@ from repair import _native as N                                                 
 from repair import detect_codes as DC                                             # noqa: E402
 from repair.errors import GaussianOutlierErrorDetector, RegExErrorDetector       # noqa: E402
 from tests import detector_restatements as R                                     # noqa: E402
+from tests.helpers import csrc_constant                                          # noqa: E402
 from tests.synth import make_table                                                # noqa: E402
 
 COPY_CEILING = 6.29e12                       # B/s, DESIGN.md
@@ -75,8 +75,7 @@ def main():
     every = list(range(c))
     floor = n * c * 4 / COPY_CEILING
     res = dict(rows=n, cols=c, stream_floor_ms=floor * 1e3, lds_bound_codes=None)
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    lds_max = int(re.search(r"constexpr int DET_LDS_WORDS = (\d+);", src).group(1)) * 64
+    lds_max = csrc_constant("DET_LDS_WORDS") * 64
     res["lds_bound_codes"] = lds_max
 
     def narrowed(k):

@@ -1,4 +1,4 @@
-"""`Table.distinct_rows()` (rgbm_table_distinct_rows, csrc/rgbm_prep.hip) on the bench table shape (synthetic 10M rows x 16 columns, 1 % NULLs)
+"""`Table.distinct_rows()` (rgbm_table_distinct_rows, csrc/rgbm_distinct.hip) on the bench table shape (synthetic 10M rows x 16 columns, 1 % NULLs)
 against yardsticks measured in the same process --
 
   * the host statement `repair.pipeline.distinct_rows` (numpy.unique over mixed-radix keys) on the same code matrix;

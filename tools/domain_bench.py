@@ -1,5 +1,5 @@
 """Cell-domain analysis on the bench table shape (synthetic 10M rows x 16 columns, 1 % NULLs, 16 targets -> 120 column pairs):
-pair counting and cell domains on the device (csrc/rgbm_prep.hip) against two yardsticks measured in the same process --
+pair counting and cell domains on the device (csrc/rgbm_domain.hip) against two yardsticks measured in the same process --
 
   * the host path of repair/domain.py (sparse counting with numpy, the same cell-domain arithmetic), and
   * the stream floor: the bytes of the columns read ONCE (rows x columns x 4 B) over the 6.29 TB/s copy ceiling DESIGN.md uses.

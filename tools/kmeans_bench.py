@@ -1,4 +1,4 @@
-"""One Lloyd assignment step of the q-gram k-means (`Table.kmeans_assign`, rgbm_table_kmeans_assign, csrc/rgbm_prep.hip) on the bench
+"""One Lloyd assignment step of the q-gram k-means (`Table.kmeans_assign`, rgbm_table_kmeans_assign, csrc/rgbm_kmeans.hip) on the bench
 table shape (synthetic 10M rows x 16 columns, 1 % NULLs), all columns, k = 2, 8, 32, with random P and h of the table's dictionaries --
 
   * ms per call, best of `--reps` after a warm-up call, and the median: wall clock, the upload of P / h and the copy of counts / sizes
@@ -14,7 +14,6 @@ The device step is compared with the numpy step on the first `--check-rows` rows
 import argparse
 import json
 import os
-import re
 import sys
 import time
 
@@ -25,6 +24,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "spark-data-repair-plugin_amd")]
 
 from repair import _native as N                                                   # noqa: E402
 from repair import qgram_kmeans as Q                                              # noqa: E402
+from tests.helpers import csrc_constant                                           # noqa: E402
 from tests.synth import make_table                                                # noqa: E402
 
 COPY_CEILING = 6.29e12                       # B/s, DESIGN.md
@@ -72,8 +72,7 @@ def main():
     cols = np.arange(c, dtype=np.int32)
     off = np.concatenate([[0], np.cumsum(n_codes[:-1], dtype=np.int64)]).astype(np.int64)
     d_tot = int(n_codes.sum())
-    src = open(os.path.join(ROOT, "spark-data-repair-plugin_amd", "csrc", "rgbm_prep.hip")).read()
-    bound = {name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1)) for name in ("KM_LDS_P_DOUBLES", "KM_LDS_COUNTERS")}
+    bound = {name: csrc_constant(name) for name in ("KM_LDS_P_DOUBLES", "KM_LDS_COUNTERS")}
     floor = n * (4 * c + 8) / COPY_CEILING
     res = dict(rows=n, cols=c, d_tot=d_tot, stream_floor_ms=floor * 1e3, lds_bounds=bound, steps={})
     tab = N.Table(codes, n_codes)

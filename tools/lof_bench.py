@@ -1,5 +1,5 @@
 """LOFOutlierErrorDetector on one continuous column: the code-space evaluation on the device -- `Table.count_codes` on the resident
-column plus `HipEngine.lof_codes` (rgbm_lof_1d, csrc/rgbm_prep.hip), wall clock with the upload of the dictionary and the copy of the
+column plus `HipEngine.lof_codes` (rgbm_lof_1d, csrc/rgbm_lof.hip), wall clock with the upload of the dictionary and the copy of the
 scores and flag words included -- against scikit-learn's `LocalOutlierFactor(novelty=False).fit_predict` on the same column in value
 space, which is what the value-space detector (repair/errors.py) runs.  Two tie-free columns of normal doubles:
 

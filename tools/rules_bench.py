@@ -1,5 +1,5 @@
 """Rule-based repairs on the bench table shape (synthetic 10M rows x 16 columns, 1 % NULLs): the three device entries of
-csrc/rgbm_prep.hip (rgbm_table_fd_map, rgbm_table_rule_fill, rgbm_nearest_values) against yardsticks measured in the same process --
+csrc/rgbm_rules.hip (rgbm_table_fd_map, rgbm_table_rule_fill, rgbm_nearest_values) against yardsticks measured in the same process --
 
   * `fd_map`: pandas `RepairModel._build_rule_model` on the same two columns, and the stream floor: rows x 8 B (two int32 columns read
     once) over the 6.29 TB/s copy ceiling DESIGN.md uses;
