@@ -485,6 +485,16 @@ int rgbm_model_info(const rgbm_model* m, int32_t* info);
  * dynamic-stride scorer, 2 = walk over index-linked nodes (the other entries are 0).  A function of the model and of the environment
  * switches RGBM_QS_FIXED=0 / RGBM_PREDICTOR=walk alone: it needs no device, and the predictor launches from the same rule. */
 int rgbm_model_predict_form(const rgbm_model* m, int32_t* out);
+/* The launch plan of the level grower's passes for a table of n_rows rows and f features with nbins[j] bins (1..256) each, k class trees and
+ * max_depth (1..7); with_mult: the rows carry multiplicities.  A function of these and of the environment switches (RGBM_LV_BLOCKS, RGBM_MT_BLOCKS,
+ * RGBM_MT_TREES, RGBM_LV_LDS, ...) alone: it needs no device, and the trainer launches from the same rule.  out (doubles, whole numbers but for the times):
+ *   [0..5]  root pass: row blocks per class tree (gx), nodes of the largest set of workgroup partials (part_items), level-pass launches L, workgroups,
+ *           modelled fixed time of a workgroup (us), modelled row-loop time of a workgroup (us);
+ *   then per level-pass launch, in launch order, 12 values: level, chunk, first built slot, built slots, routing launch?, class trees per workgroup (T),
+ *           class tree groups (G), row blocks (gx), both-chunk form?, rotated?, modelled fixed time (us), modelled row-loop time of a workgroup (us).
+ * *n_out = values the plan has (6 + 12 L); RGBM_ERR_ARG when out_len is smaller.  A feature set that the training call would refuse (the
+ * histograms of one node exceed the LDS) fails here the same way. */
+int rgbm_level_pass_plan(const int32_t* nbins, int32_t f, int64_t n_rows, int32_t k, int32_t max_depth, int32_t with_mult, double* out, int32_t out_len, int32_t* n_out);
 /* LightGBM feature_importances_ (train.py:219): type 0 = split counts, 1 = total gain. */
 int rgbm_model_importance(const rgbm_model* m, int32_t type, double* out /* [n_features] */);
 

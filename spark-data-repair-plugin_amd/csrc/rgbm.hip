@@ -493,6 +493,25 @@ struct LevelPassPlan {
     size_t part_items = 0;                          // nodes of the largest set of workgroup partials (root or level)
 };
 
+// What a launch of one-workgroup-per-CU passes costs, as the grid rules below see it:
+//     rounds(workgroups) x (t_fix + rows per workgroup x (t_row + class trees per workgroup x t_pair)),   rounds(w) = ceil(w / 256 CUs).
+// t_fix is what a workgroup does before its first row and after its last one (plan and layout look-up, route-table fill, zeroing, flush of its partials) plus
+// its share of the launch; t_row the fetch of a row's record(s), once per workgroup; t_pair one (row, class tree) step of the row loop.  Calibration constants
+// per form, from the per-launch intercepts and slopes of profiles/r13_step0_intercepts_parent_vs_new.md (its `new` columns; tools/level_setup_intercept.py: the same fits at two row counts
+// with the row blocks pinned).  The model ranks grids of ONE launch form against each other; it is not a prediction of the step.
+struct PassCost { double t_fix_us, t_row_ns, t_pair_ns; };
+constexpr PassCost MT_COST_REP{14.0, 0.2, 0.75};      // k_level_mt, replicated layout
+constexpr PassCost MT_COST_ROT{14.0, 1.0, 0.5};      // k_level_mt, rotated
+constexpr PassCost ROOT_PASS_COST{8.0, 1.2, 0.0};        // k_level_root (one class tree per workgroup)
+inline const PassCost& mt_pass_cost(bool /*acc2*/, bool rot) { return rot ? MT_COST_ROT : MT_COST_REP; }       // (the both-chunk forms: the one-chunk constants of their layout)
+inline double pass_model_us(long long workgroups, double rows_per_block, int T, const PassCost& c) {
+    const long long rounds = (workgroups + 255) / 256;
+    return (double)rounds * (c.t_fix_us + rows_per_block * (c.t_row_ns + (double)T * c.t_pair_ns) * 1e-3);
+}
+
+// LDS bytes the level grower's passes size their histograms for (RGBM_LV_LDS, testing: a smaller pool forces several built-slot windows per level)
+inline int level_lds_bytes(const RunSwitches& sw) { return (sw.lv_lds >= 65536 && sw.lv_lds <= rg::LV_LDS_BYTES) ? sw.lv_lds : rg::LV_LDS_BYTES; }
+
 LevelPassPlan plan_level_passes(const RunSwitches& sw, const std::vector<rg::FeatMeta>& fmeta, const std::vector<rg::ChunkMeta>& cmeta,
                                 long long N, int K, int max_depth, bool wm /* rows carry multiplicities */, int lds_bytes) {
     using namespace rg;
@@ -503,20 +522,20 @@ LevelPassPlan plan_level_passes(const RunSwitches& sw, const std::vector<rg::Fea
     // ---- root pass: one 1024-thread workgroup per CU and (class tree, row block, chunk).  Contiguous row blocks, a multiple of 8 per
     // class tree with all class trees of a row block on one XCD (k_level_root), about four rounds of 256 workgroups when the class
     // trees alone nearly fill the chip (measured at K = 64, 10M rows: 8 / 16 / 40 blocks per class tree = 23.0 / 21.0 / 23.2 ms per
-    // iteration), else the fewest blocks that fill one round; <= 2^22 rows per workgroup.  RGBM_LV_BLOCKS overrides.
+    // iteration); <= 2^22 rows per workgroup.  RGBM_LV_BLOCKS overrides.
     {
         const long long cu_slots = 256, per = (long long)K * nchunk;
         const long long gmin = std::max<long long>(1, (N + (1ll << 22) - 1) >> 22);
-        auto eff_of = [&](long long g) { const long long tot = g * per, rounds = (tot + cu_slots - 1) / cu_slots; return (double)tot / (double)(rounds * cu_slots); };
+        // Among the admitted block counts the modelled time decides (pass_model_us: a workgroup costs t_fix besides its rows), ties to the fewer workgroups.
+        auto time_of = [&](long long g) { return pass_model_us(g * per, (double)N / (double)g, 1, ROOT_PASS_COST); };
         const long long gfloor = std::max<long long>(8, (gmin + 7) / 8 * 8), gcap = std::max<long long>(gfloor, std::min<long long>(512, (ntiles + 7) / 8 * 8));
         long long g2 = gfloor; double best2 = -1.0;
-        for (long long g = gfloor; g <= gcap; g += 8) {
-            if (per >= 16 && (g * per < 3 * cu_slots || g * per > 5 * cu_slots)) continue;
-            const double e = eff_of(g);
-            if (e > best2 + 1e-9) { best2 = e; g2 = g; }
-            if (e >= 0.99) break;
-        }
-        if (best2 < 0.0) for (long long g = gfloor; g <= gcap; g += 8) { const double e = eff_of(g); if (e > best2 + 1e-9) { best2 = e; g2 = g; } if (e >= 0.99) break; }
+        for (int pass = 0; pass < 2 && best2 < 0.0; ++pass)          // (second pass: no block count inside the three-to-five-round window)
+            for (long long g = gfloor; g <= gcap; g += 8) {
+                if (pass == 0 && per >= 16 && (g * per < 3 * cu_slots || g * per > 5 * cu_slots)) continue;
+                const double t = time_of(g);
+                if (best2 < 0.0 || t < best2 * (1.0 - 1e-9)) { best2 = t; g2 = g; }
+            }
         if (sw.lv_blocks >= 1) g2 = (sw.lv_blocks + 7) / 8 * 8;
         P.root_gx = (int)g2;
     }
@@ -530,7 +549,6 @@ LevelPassPlan plan_level_passes(const RunSwitches& sw, const std::vector<rg::Fea
     P.part_items = (size_t)K * P.root_gx;                   // root partials: one node per (class tree, row block)
     for (int level = 1; level < max_depth; ++level) {
         const int worst = 1 << (level - 1);
-        int G_first = 1;
         // tables of 17..32 features: ONE wave-specialised pass per level accumulates both 16-feature chunks (k_level_mt<2, ., ., MT_THREADS_ACC2, true, true>:
         // both records of a row in registers and in the ring) instead of one pass per chunk that streams every (node id, g, h) again
         bool acc2 = nchunk == 2 && sw.mt_acc2;
@@ -577,7 +595,6 @@ LevelPassPlan plan_level_passes(const RunSwitches& sw, const std::vector<rg::Fea
             // a rotated launch needs ONE copy: as many class trees per workgroup as the LDS holds
             if (rot && sw.mt_T < 1) T = (int)std::max<long long>(T, T_rot);
             const int G = (K + T - 1) / T;
-            if (ch == 0) G_first = G;
             for (int s0 = 0; s0 < worst; s0 += win)
                 P.mt[level].push_back(MtLaunch{ch, s0, win, (ch == 0 && s0 == 0) ? 1 : 0, T, G, 0, acc2 ? 1 : 0, rot ? 1 : 0});
         }
@@ -586,12 +603,14 @@ LevelPassPlan plan_level_passes(const RunSwitches& sw, const std::vector<rg::Fea
         // blocks leave a quarter of the chip idle, 32 make three full rounds) without cutting the table into slivers
         const long long nwt = (N + MT_WT_ROWS - 1) / MT_WT_ROWS;
         const long long gx_lo = std::max<long long>(8, (gmin + 7) / 8 * 8), gx_hi = std::max<long long>(gx_lo, std::min<long long>(512, (nwt / (4 * (LV_THREADS / 64)) + 7) / 8 * 8));
-        long long gx = gx_lo; double best = -1.0;
+        // ... chosen by the modelled time of the level's launches (pass_model_us): a workgroup costs t_fix before its first row, so 1496 workgroups of
+        // 18 k rows (G = 11: six rounds filled to 97 %, what filling whole rounds alone picks) lose to 440 of 62 k rows (two rounds filled to 86 %).
+        // Ties go to the fewer workgroups.
+        long long gx = gx_lo; double best = 0.0;
         for (long long g = gx_lo; g <= gx_hi; g += 8) {
-            const long long tot = g * G_first, rounds = (tot + 255) / 256;
-            const double eff = (double)tot / (double)(rounds * 256) - 0.01 * (double)rounds;   // fuller rounds first, then fewer of them
-            if (eff > best + 1e-9) { best = eff; gx = g; }
-            if (tot >= 256 && (double)tot / (double)(rounds * 256) >= 0.97) break;
+            double t = 0.0;
+            for (const auto& L : P.mt[level]) t += pass_model_us((long long)L.G * g, (double)N / (double)g, std::min(L.T, K), mt_pass_cost(L.acc2 != 0, L.rot != 0));
+            if (g == gx_lo || t < best * (1.0 - 1e-9)) { best = t; gx = g; }
         }
         if (sw.mt_blocks >= 1) gx = (sw.mt_blocks + 7) / 8 * 8;
         P.mt_gx[level] = (int)gx;
@@ -949,12 +968,19 @@ struct LevelGrower {
     const int score_gx = (int)std::max<long long>(1, std::min<long long>((st.N + 1023) / 1024, (2048 + st.K - 1) / st.K));
     LevelTrace trace;
     int32_t h_err = 0;
+    // layout tables of the root pass and of the level passes (the host copies live as long as the uploads may be in flight)
+    std::vector<rg::RootLayout> h_root_lay; std::vector<rg::MtLayout> h_mt_lay; std::vector<int> mt_lay_keys;
+    DevBuf<rg::RootLayout> root_lay; DevBuf<rg::MtLayout> mt_lay;
+    static int mt_lay_key(const MtLaunch& L) { return L.ch * 4 + (L.acc2 ? 2 : 0) + (L.rot ? 1 : 0); }
+    int mt_lay_index(const MtLaunch& L) const {
+        for (size_t i = 0; i < mt_lay_keys.size(); ++i) if (mt_lay_keys[i] == mt_lay_key(L)) return (int)i;
+        return -1;
+    }
 
     explicit LevelGrower(FitState& st_) : st(st_), s(st_.s), root_feats(st_.F), trace(true, st_.K, st_.s) {
         using namespace rg;
         memset(&lc, 0, sizeof(lc)); memset(&lcj, 0, sizeof(lcj));
-        lc.lds_bytes = LV_LDS_BYTES;
-        if (st.sw.lv_lds >= 65536 && st.sw.lv_lds <= LV_LDS_BYTES) lc.lds_bytes = st.sw.lv_lds;      // testing: a smaller LDS pool forces several built-slot windows per level
+        lc.lds_bytes = level_lds_bytes(st.sw);
         lc.nchunk = st.h.nchunk; lc.K = st.K; lc.F = st.F; lc.totbins = st.h.tc.totbins;
         lc.num_leaves = st.NL; lc.max_depth = st.p.max_depth; lc.min_data_in_leaf = st.p.min_data_in_leaf; lc.N = st.N; lc.NS = (st.N + 255) & ~255ll; lc.NG = lc.NS;
         lc.sib_local = (st.dp && comm_rank() == 0) ? 1 : 0;
@@ -985,12 +1011,30 @@ struct LevelGrower {
                 hipLaunchKernelGGL(k_pack_joint, dim3((unsigned)((st.N + 255) / 256)), dim3(256), 0, s, st.bins.rec.p, (long long)st.N, st.F, jf.p, rec_j.p, st.tab.has_mult ? st.h.nchunk - 1 : -1);
                 part_j.alloc((size_t)st.K * lc.gx * vtotbins); red_j.alloc((size_t)st.K * vtotbins + (size_t)st.K * 128 /* k_level_reduce parks the counts behind the bins */);
                 lcj = lc; lcj.nchunk = 1; lcj.F = VF; lcj.totbins = vtotbins; lcj.max_built = 1;
+                h_root_lay.resize(1); root_layout_fill(h_root_lay[0], jp.vfm.data(), VF, lc.lds_bytes);
                 use_reduce = true; root_feats = VF;
                 HIPCHK(hipStreamSynchronize(s));   // jp's vectors are locals
             }
         }
         if (st.tab.has_mult && st.h.nchunk == 2 && !joint_root)
             throw std::invalid_argument("a two-chunk table with row multiplicities needs the joint-bin root pass (its record carries the multiplicity); this feature set does not pack into 15 groups");
+        // layout tables (rgbm_level.h, "LAYOUT TABLES"): one per chunk of the root pass, one per (chunk, form) of the level passes
+        if (!joint_root) {
+            h_root_lay.resize(st.h.nchunk);
+            for (int ch = 0; ch < st.h.nchunk; ++ch) root_layout_fill(h_root_lay[ch], st.h.fmeta.data() + st.h.cmeta[ch].first_feat, st.h.cmeta[ch].nfeat, lc.lds_bytes);
+        }
+        root_lay.alloc(h_root_lay.size()); root_lay.upload(h_root_lay.data(), h_root_lay.size(), s);
+        lc.root_lay = root_lay.p; lcj.root_lay = root_lay.p;
+        for (int level = 1; level < st.p.max_depth; ++level) for (const auto& L : passes.mt[level]) if (mt_lay_index(L) < 0) {
+            const bool acc2 = L.acc2 != 0;
+            const ChunkMeta& cm = st.h.cmeta[L.ch];
+            const int nf_last = acc2 ? st.h.cmeta[1].nfeat : cm.nfeat;
+            const bool li_in_rec = nf_last <= 15 && !st.tab.has_mult;               // (as k_level_mt decides it)
+            mt_lay_keys.push_back(mt_lay_key(L)); h_mt_lay.emplace_back();
+            mt_layout_fill(h_mt_lay.back(), st.h.fmeta.data() + cm.first_feat, cm.nfeat, acc2 ? st.h.fmeta.data() + st.h.cmeta[1].first_feat : nullptr, acc2 ? st.h.cmeta[1].nfeat : 0,
+                           cm.wide_bins, L.rot != 0, mt_hist_bytes(lc.lds_bytes, acc2 ? MT_THREADS_ACC2 : LV_THREADS, acc2, acc2, !li_in_rec));
+        }
+        if (!h_mt_lay.empty()) { mt_lay.alloc(h_mt_lay.size()); mt_lay.upload(h_mt_lay.data(), h_mt_lay.size(), s); }
         if (st.sw.timing) {
             fprintf(stderr, "[rgbm] root: gx %d joint %d groups %d\n", lc.gx, joint_root ? 1 : 0, joint_root ? lcj.F : 0);
             for (int level = 1; level < st.p.max_depth; ++level) for (const auto& L : passes.mt[level])
@@ -1057,6 +1101,7 @@ struct LevelGrower {
             for (const MtLaunch& L : passes.mt[level]) {
                 LevelConst l1 = lp;
                 l1.mt_T = L.T; l1.mt_G = L.G; l1.mt_ch = L.ch; l1.mt_slot0 = L.slot0; l1.mt_nslots = L.nslots; l1.mt_route = L.route; l1.mt_sparse = st.sw.mt_sparse ? 1 : 0;
+                l1.mt_lay = mt_lay.p + mt_lay_index(L);
                 const bool acc2 = L.acc2 != 0;
                 const MtForm form{acc2 ? 2 : (st.h.nchunk <= 2 ? st.h.nchunk : 0), acc2 ? MT_THREADS_ACC2 : LV_THREADS, acc2, acc2, L.rot != 0};
                 st.timers.timed(false, [&]() {
@@ -2351,6 +2396,40 @@ RGBM_EXPORT int rgbm_model_predict_form(const rgbm_model* m, int32_t* out) {
     return guarded([&]() {
         const PredictForm pf = predict_form(m);
         out[0] = pf.form; out[1] = pf.mw; out[2] = pf.tw; out[3] = pf.tb; out[4] = (int32_t)pf.lds;
+        return RGBM_OK;
+    });
+}
+
+RGBM_EXPORT int rgbm_level_pass_plan(const int32_t* nbins, int32_t f, int64_t n_rows, int32_t k, int32_t max_depth, int32_t with_mult, double* out, int32_t out_len, int32_t* n_out) {
+    if (!nbins || !out || !n_out || f < 1 || f > 255 || n_rows < 1 || k < 1 || max_depth < 1 || max_depth > rg::LV_MAX_DEPTH) return fail(RGBM_ERR_ARG, "rgbm_level_pass_plan: bad argument");
+    return guarded([&]() {
+        using namespace rg;
+        const RunSwitches sw = read_switches();
+        std::vector<FeatMeta> fmeta(f); std::vector<ChunkMeta> cmeta((f + 15) / 16);
+        int totbins = 0;
+        for (int j = 0; j < f; ++j) {
+            if (nbins[j] < 1 || nbins[j] > 256) return fail(RGBM_ERR_ARG, "rgbm_level_pass_plan: a feature has 1..256 bins");
+            FeatMeta& m = fmeta[j]; memset(&m, 0, sizeof(m)); m.nbins = nbins[j]; m.V = nbins[j]; m.hoff = totbins; totbins += nbins[j];
+        }
+        for (size_t ch = 0; ch < cmeta.size(); ++ch) {
+            ChunkMeta& cm = cmeta[ch]; cm.first_feat = (int)ch * 16; cm.nfeat = std::min(16, f - (int)ch * 16); cm.fast_slots = 0; cm.wide_bins = 0;
+            for (int j = 0; j < cm.nfeat; ++j) { fmeta[ch * 16 + j].wide_off = cm.wide_bins; cm.wide_bins += fmeta[ch * 16 + j].nbins; }
+        }
+        const LevelPassPlan P = plan_level_passes(sw, fmeta, cmeta, n_rows, k, max_depth, with_mult != 0, level_lds_bytes(sw));
+        std::vector<double> v;
+        const long long root_wg = (long long)P.root_gx * k * (long long)cmeta.size();
+        v.insert(v.end(), {(double)P.root_gx, (double)P.part_items, 0.0, (double)root_wg, ROOT_PASS_COST.t_fix_us, (double)n_rows / P.root_gx * ROOT_PASS_COST.t_row_ns * 1e-3});
+        int nl = 0;
+        for (int level = 1; level < max_depth; ++level) for (const MtLaunch& L : P.mt[level]) {
+            const PassCost& c = mt_pass_cost(L.acc2 != 0, L.rot != 0);
+            v.insert(v.end(), {(double)level, (double)L.ch, (double)L.slot0, (double)L.nslots, (double)L.route, (double)L.T, (double)L.G, (double)L.gx, (double)L.acc2, (double)L.rot,
+                               c.t_fix_us, (double)n_rows / L.gx * (c.t_row_ns + std::min(L.T, (int)k) * c.t_pair_ns) * 1e-3});
+            ++nl;
+        }
+        v[2] = (double)nl;
+        *n_out = (int32_t)v.size();
+        if ((size_t)out_len < v.size()) return fail(RGBM_ERR_ARG, "rgbm_level_pass_plan: output too small");
+        std::copy(v.begin(), v.end(), out);
         return RGBM_OK;
     });
 }

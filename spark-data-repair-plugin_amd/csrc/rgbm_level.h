@@ -84,8 +84,12 @@ struct LvPlan {   // per class tree; rewritten by k_level_init / k_level_plan
     uint32_t route1[256];              // left | right<<8 | left built slot<<16 | right built slot<<24  (0xFF = none)
 };
 
+struct MtLayout;
+struct RootLayout;
 struct LevelConst {
-    int32_t gx;                  // row blocks per class tree of THIS launch (partials: [K][gx][max_built][totbins])
+    const MtLayout* mt_lay;      // k_level_mt launch: the layout table of its (chunk, form); k_level_root: root_lay[chunk]  (built once per fit, "LAYOUT TABLES" below)
+    const RootLayout* root_lay;
+    int32_t gx;                 // row blocks per class tree of THIS launch (partials: [K][gx][max_built][totbins])
     int32_t max_built;           // built-node stride of the partials of THIS launch
     int32_t nchunk, K, F, totbins, num_leaves, max_depth, min_data_in_leaf, lds_bytes;
     int32_t sib_local;           // k_level_split also writes the derived sibling count into the LOCAL count array (row-sharded: rank 0 only)
@@ -180,6 +184,64 @@ __host__ __device__ constexpr long long mt_hist_bytes(long long lds_bytes, int t
 }
 
 // ------------------------------------------------------------------------------------------------
+// LAYOUT TABLES.  Everything about the LDS histogram layout of a pass depends on the feature set, the launch form and ONE number the
+// workgroup finds out at run time -- how many built nodes it holds -- so the host works it out once per fit (LevelGrower's constructor) for
+// every possible number, and a workgroup looks it up: before, lane 0 of every workgroup searched the slot exponent with up to 24 mt_slots
+// loops while 15 waves waited at a barrier, every thread ran 16 (32) mt_shift loops, and the flush found the feature of a bin with 15 compares.
+//   MtLayout: one per (chunk, form) of the fit's level passes.  RootLayout: one per chunk of the root pass (its single layout).
+// ------------------------------------------------------------------------------------------------
+constexpr int MT_LAY_Q = LV_MAX_Q + 1;
+struct MtLayout {
+    uint32_t q_spn[MT_MAX_NODES + 4];  // [built nodes of the workgroup] slot exponent q | slots per node << 8  (the largest q whose histograms fit)
+    int32_t wide[32], hdelta[32];      // per accumulated feature (second chunk of a both-chunk pass: 16..31): first wide bin (none: INT_MAX) | histogram offset - first wide bin
+    int32_t fb[MT_LAY_Q][32];          // [q] first slot of the feature inside a node
+    int32_t sh[MT_LAY_Q][32];          // [q] replication shift of the feature
+    uint8_t bin_feat[32 * 256];        // wide bin of the launch -> accumulated feature
+};
+struct RootLayout { int32_t q, spn, pad0, pad1; int32_t sh[16], fbase[16]; };
+
+inline void mt_layout_fill(MtLayout& L, const FeatMeta* fm, int nfeat, const FeatMeta* fm1 /* both-chunk pass: the second chunk, else null */, int nfeat1, int wide_bins0,
+                           bool rot, long long avail /* mt_hist_bytes of the form */) {
+    memset(&L, 0, sizeof(L));
+    const bool acc2 = fm1 != nullptr;
+    auto spn_of = [&](int q) { return mt_slots(fm, nfeat, q, rot) + (acc2 ? mt_slots(fm1, nfeat1, q, rot) : 0) + mt_rot_dummy(rot); };
+    for (int tot = 0; tot < MT_MAX_NODES + 4; ++tot) {
+        int q = mt_max_q(rot);
+        while (q > 0 && (long long)tot * spn_of(q) * 16 > avail) --q;
+        L.q_spn[tot] = (uint32_t)q | (uint32_t)spn_of(q) << 8;
+    }
+    for (int q = 0; q < MT_LAY_Q; ++q) {
+        int o = 0;
+        for (int a = 0; a < (acc2 ? 2 : 1); ++a) {
+            const FeatMeta* fa = a == 0 ? fm : fm1;
+            const int na = a == 0 ? nfeat : nfeat1;
+            for (int j = 0; j < 16; ++j) {
+                int shj = 0, fbj = 0;
+                if (j < na) { shj = mt_shift(fa[j].nbins, q, rot); fbj = o; o += fa[j].nbins << shj; }
+                L.fb[q][a * 16 + j] = fbj; L.sh[q][a * 16 + j] = shj;
+            }
+        }
+    }
+    for (int q = 0; q < 32; ++q) L.wide[q] = 0x7FFFFFFF;
+    for (int a = 0; a < (acc2 ? 2 : 1); ++a) {
+        const FeatMeta* fa = a == 0 ? fm : fm1;
+        const int na = a == 0 ? nfeat : nfeat1;
+        for (int j = 0; j < na && j < 16; ++j) {
+            const int wide = (a == 0 ? 0 : wide_bins0) + fa[j].wide_off;
+            L.wide[a * 16 + j] = wide; L.hdelta[a * 16 + j] = fa[j].hoff - wide;
+            for (int b = 0; b < fa[j].nbins && wide + b < 32 * 256; ++b) L.bin_feat[wide + b] = (uint8_t)(a * 16 + j);
+        }
+    }
+}
+inline void root_layout_fill(RootLayout& L, const FeatMeta* fm, int nfeat, int lds_bytes) {
+    memset(&L, 0, sizeof(L));
+    int q = LV_MAX_Q;
+    while (q > 0 && (long long)lv_slots(fm, nfeat, q) * 16 + LV_ROOT_FIXED > lds_bytes) --q;
+    L.q = q;
+    for (int j = 0; j < 16 && j < nfeat; ++j) { L.sh[j] = lv_shift(fm[j].nbins, q); L.fbase[j] = L.spn; L.spn += fm[j].nbins << L.sh[j]; }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_level_init: per class tree, start of a boosting iteration
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_level_init(LvPlan* __restrict__ plan, SNode* __restrict__ nodes, int32_t* __restrict__ count,
@@ -232,20 +294,17 @@ __global__ __launch_bounds__(LV_THREADS, 1) void k_level_root(const uint4* __res
     const ChunkMeta cm = cmeta[ch];
     const FeatMeta* fm = fmeta + cm.first_feat;
     const int tid = threadIdx.x, lane = tid & 63, nfeat = cm.nfeat;
-    // layout: the largest uniform replication that fits
-    int s = LV_MAX_Q;
-    while (s > 0 && (long long)lv_slots(fm, nfeat, s) * 16 + LV_ROOT_FIXED > c.lds_bytes) --s;
-    int sh[16], fbase[16], spn = 0;
+    // layout: the largest uniform replication that fits (root_layout_fill: uniform loads of the fit's table)
+    const RootLayout* lay = c.root_lay + ch;
+    int sh[16], fbase[16];
+    const int spn = lay->spn;
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        if (j < nfeat) { sh[j] = lv_shift(fm[j].nbins, s); fbase[j] = spn; spn += fm[j].nbins << sh[j]; }
-        else { sh[j] = 0; fbase[j] = 0; }
-    }
+    for (int j = 0; j < 16; ++j) { sh[j] = lay->sh[j]; fbase[j] = lay->fbase[j]; }
     // gradient sums and hessian sums live in SEPARATE arrays of 8-byte slots: one wave instruction of 64-bit atomics then spreads over
     // all 64 LDS banks (interleaved (g, h) pairs put every g on 16 of the 32 bank pairs: SQ_LDS_BANK_CONFLICT was 70 % of the LDS cycles)
     unsigned long long* hist_g = reinterpret_cast<unsigned long long*>(smem);
     unsigned long long* hist_h = hist_g + spn;
-    for (int i = tid; i < 2 * spn; i += LV_THREADS) hist_g[i] = 0ull;
+    for (int i = tid; i < spn; i += LV_THREADS) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0u, 0u, 0u, 0u);      // (2 spn sums of 8 bytes)
     int cj[16], sh3[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) { sh3[j] = sh[j] + 3; cj[j] = (fbase[j] + (lane & ((1 << sh[j]) - 1))) * 8; }
@@ -311,9 +370,7 @@ __global__ __launch_bounds__(LV_THREADS, 1) void k_level_root(const uint4* __res
     // flush this workgroup's partial histogram (plain stores: no global atomics, no zeroing)
     HistBin* dst = part + (((long long)k * c.gx + bx) * c.max_built) * c.totbins;
     for (int j = 0; j < nfeat; ++j) {
-        const int shj = lv_shift(fm[j].nbins, s);
-        int fb = 0;
-        for (int q = 0; q < j; ++q) fb += fm[q].nbins << lv_shift(fm[q].nbins, s);
+        const int shj = lay->sh[j], fb = lay->fbase[j];
         for (int b = tid; b < fm[j].nbins; b += LV_THREADS) {
             long long tg = 0, th = 0;
             const unsigned long long* sg_ = hist_g + fb + (b << shj); const unsigned long long* sh_ = hist_h + fb + (b << shj);
@@ -387,8 +444,6 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
     constexpr bool route = ROUTE;
     const ChunkMeta cm = cmeta[ch];
     const ChunkMeta cm1 = cmeta[ACC2 ? 1 : ch];
-    const FeatMeta* fm = fmeta + cm.first_feat;
-    const FeatMeta* fm1 = fmeta + cm1.first_feat;
     const int nfeat = cm.nfeat, nfeat1 = ACC2 ? cm1.nfeat : 0;
     const int wb = cm.wide_bins + (ACC2 ? cm1.wide_bins : 0);
     // the histogram slot of a ring entry rides in byte 15 of its (last) record whenever that chunk holds at most 15 features: one LDS
@@ -424,7 +479,10 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
     if (tid == 0 && ((long long)off > mt_fixed_bytes(THREADS, ACC2, SPEC, !li_in_rec) || (long long)off + MT_HD + avail / 2 > (long long)LV_LDS_TOTAL)) atomicOr(err_flag, 2);     // (never: mt_fixed_bytes covers the carve-up above)
 
     // ---- the class trees of this workgroup and their built slots inside this launch's window
+    const MtLayout* __restrict__ lay = c.mt_lay;
     if (tid < 64) {   // wave 0: lane kk reads the plan of class tree k0 + kk; exclusive prefix sums place its built slots and table entries
+        // (the layout of every possible number of built nodes, requested before the plan so that nothing waits for it twice)
+        const uint32_t qs0 = lay->q_spn[lane], qs1 = lay->q_spn[64 + lane], qs2 = lay->q_spn[128 + (lane & 3)];
         MtTree t; t.base = 0; t.nlev = 0; t.nb = 0; t.live = 0; t.child_first = 0; t.k = k0 + lane; t.slot0 = 0; t.rt_off = 0;
         if (lane < nk) {
             const LvPlan* pp = &plan[k0 + lane];
@@ -473,12 +531,11 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
         tpk[pos] = make_uint2((uint32_t)t.base | (uint32_t)t.nlev << 8 | (uint32_t)(ntab > 0 ? ntab - 1 : 0) << 17 | (t.live && lane < nk ? 1u << 31 : 0u), (uint32_t)t.rt_off | (uint32_t)t.k << 16);
         if (lane < 2) tpk[64 + lane] = make_uint2(0u, 0u);
         if (SPARSE) xmask[lane] = 0ull;
+        // replication: the largest uniform shift whose histograms fit -- the entry of `tot` built nodes in the layout table
+        const int tot = ok ? total : 0;                     // (uniform; <= MT_MAX_NODES)
+        const uint32_t qs = (uint32_t)__shfl((int)(tot < 64 ? qs0 : (tot < 128 ? qs1 : qs2)), tot & 63);
         if (lane == 0) {
-            // replication: the largest uniform shift whose histograms fit
-            int s = mt_max_q(ROT);
-            const int tot = ok ? total : 0;
-            while (s > 0 && (long long)tot * (mt_slots(fm, nfeat, s, ROT) + (ACC2 ? mt_slots(fm1, nfeat1, s, ROT) : 0) + mt_rot_dummy(ROT)) * 16 > avail) --s;
-            const int spn0 = mt_slots(fm, nfeat, s, ROT) + (ACC2 ? mt_slots(fm1, nfeat1, s, ROT) : 0) + mt_rot_dummy(ROT);
+            const int s = (int)(qs & 0xFFu), spn0 = (int)(qs >> 8);
             if ((long long)tot * spn0 * 16 > avail) atomicOr(err_flag, 2);          // (the host's window sizing guarantees the plain layout fits)
             scal[0] = tot; scal[1] = s; scal[2] = spn0; scal[3] = ((ok && livem != 0ull) ? 1 : 0) | nkd_ << 8 | (nkd_ + nks_) << 16;
         }
@@ -489,11 +546,13 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
     const int total = __builtin_amdgcn_readfirstlane(scal[0]), s = __builtin_amdgcn_readfirstlane(scal[1]), spn = __builtin_amdgcn_readfirstlane(scal[2]);
     if (!route && total == 0) return;
     const int nkd = __builtin_amdgcn_readfirstlane((scal[3] >> 8) & 0xFF), nke = __builtin_amdgcn_readfirstlane((scal[3] >> 16) & 0xFF);       // live dense class trees: [0, nkd), sparse ones: [nkd, nke)
-    for (int kk = 0; kk < nk; ++kk) {
+    // the route tables, in parallel over the class trees: wave w fills the tables of the class trees w, w + WAVES, ... (a table has at most 2^L + 1 entries: one
+    // or two rounds of a wave), so the dependent global loads of all of them -- route0 / route1 of the plan, the grid -- are in flight together
+    for (int kk = __builtin_amdgcn_readfirstlane(wave); kk < nk; kk += WAVES) {
         const MtTree t = ti[kk];
         const LvPlan* pp = &plan[t.k];
         const int ntab_k = (route ? (t.live ? t.child_first : 0) : t.nlev) + 1;
-        for (int i = tid; i < ntab_k; i += THREADS) {
+        for (int i = lane; i < ntab_k; i += 64) {
             const int n = route ? i : t.base + i;
             uint2 e;
             if (route) {
@@ -535,37 +594,39 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
             rt[t.rt_off + i] = e;
         }
         const uint2 sc_k = make_uint2((uint32_t)__double2hiint(fxs[t.k].sg), (uint32_t)__double2hiint(fxs[t.k].sh));
-        for (int i = tid; i < t.nb; i += THREADS) { nd_tree[t.slot0 + i] = (uint8_t)kk; nd_sc[t.slot0 + i] = sc_k; }
+        for (int i = lane; i < t.nb; i += 64) { nd_tree[t.slot0 + i] = (uint8_t)kk; nd_sc[t.slot0 + i] = sc_k; }
     }
     for (int i = tid; i < total * MT_CNT_REP; i += THREADS) cnt[i] = 0;
     if (tid < 48) rsync[tid] = 0u;            // (before the barrier below)
     unsigned long long* hist_h = hist_g + MT_HD / 8;
-    for (int i = tid; i < total * spn; i += THREADS) { hist_g[i] = 0ull; hist_h[i] = 0ull; }
+    {   // zero the histograms, 16 bytes per store.  Both halves start on a 16-byte boundary; an odd number of sums rounds up into the next slot of the same half, which
+        // nothing has written yet (the gradient half ends before MT_HD, a multiple of 16, the hessian half before the end of the LDS)
+        uint4* zg = reinterpret_cast<uint4*>(hist_g); uint4* zh = reinterpret_cast<uint4*>(hist_h);
+        const int n16 = (total * spn + 1) >> 1;
+        for (int i = tid; i < n16; i += THREADS) { zg[i] = make_uint4(0u, 0u, 0u, 0u); zh[i] = make_uint4(0u, 0u, 0u, 0u); }
+    }
     // per accumulated feature: replication shift (scalar) and this lane's byte offset inside a node's slots (first slot + replica)
     // the shifts, 4 bits each, packed into one 64-bit SCALAR per chunk (16 separate scalars cost the row loop ~80 spill reloads per step)
     unsigned long long sh3p[NACC];
     int cj[NACC][16];
-    {
-        int o = 0;
+    {   // (row s of the fit's layout table: uniform loads)
+        const int32_t* __restrict__ fb_s = lay->fb[s]; const int32_t* __restrict__ sh_s = lay->sh[s];
 #pragma unroll
         for (int a = 0; a < NACC; ++a) {
-            const FeatMeta* fa = a == 0 ? fm : fm1;
-            const int na = a == 0 ? nfeat : nfeat1;
             unsigned long long pk = 0ull;
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                int shj = 0, fb = 0;
-                if (j < na) { shj = mt_shift(fa[j].nbins, s, ROT); fb = o; o += fa[j].nbins << shj; }
+                const int shj = sh_s[a * 16 + j], fb = fb_s[a * 16 + j];
                 pk |= (unsigned long long)(shj + 3) << (4 * j); cj[a][j] = (fb + (lane & ((1 << shj) - 1))) * 8;
-                if (tid == 0) {
-                    const int q = a * 16 + j;
-                    const int wide = (a == 0 ? 0 : cm.wide_bins) + (j < na ? fa[j].wide_off : 0);
-                    ftab[q] = j < na ? wide : 0x7FFFFFFF; ftab[32 + q] = fb; ftab[64 + q] = shj; ftab[96 + q] = j < na ? fa[j].hoff - wide : 0;
-                }
             }
             sh3p[a] = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pk) |
                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(pk >> 32)) << 32;
         }
+        // the flush table: first wide bin | first slot | replication shift | histogram offset of every accumulated feature
+        if (tid < 128) { const int q = tid & 31, r = tid >> 5; ftab[tid] = r == 0 ? lay->wide[q] : (r == 1 ? fb_s[q] : (r == 2 ? sh_s[q] : lay->hdelta[q])); }
+        // the flush needs the table again (bin -> feature): its address waits in two spare words behind the ring counters, not in two SGPRs that the row loop
+        // would spill (every SGPR spill of this kernel takes a VGPR lane, and the rotated forms sit at their VGPR count)
+        if (tid == 0) { const unsigned long long la = (unsigned long long)reinterpret_cast<uintptr_t>(lay->bin_feat); rsync[48] = (uint32_t)la; rsync[49] = (uint32_t)(la >> 32); }
     }
     constexpr int hdelta = MT_HD / 8;
     __syncthreads();
@@ -1005,13 +1066,12 @@ __global__ __launch_bounds__(THREADS, 1) void k_level_mt(const uint4* __restrict
     else while (r_cnt > 0) run_batch(r_cnt < 64 ? r_cnt : 64);
     __syncthreads();
     // ---- flush this workgroup's partial histograms (plain stores: no global atomics, no zeroing) and the built-row counts
-    constexpr int NQ = NACC * 16;
+    const uint8_t* __restrict__ bin_feat = reinterpret_cast<const uint8_t*>((uintptr_t)((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)rsync[48]) |
+                                                                                      (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)rsync[49]) << 32));
     for (int i = tid; i < total * wb; i += THREADS) {
         const int ln = i / wb, b = i - ln * wb;
         const MtTree t = ti[nd_tree[ln]];
-        int j = 0;                                                  // accumulated feature of wide bin b: the last one whose first wide bin is <= b
-#pragma unroll
-        for (int q = 1; q < NQ; ++q) j += (b >= ftab[q]) ? 1 : 0;
+        const int j = bin_feat[b];                            // accumulated feature of wide bin b (layout table)
         const int shb = ftab[64 + j], s0 = ftab[32 + j] + ((b - ftab[j]) << shb);
         long long tg = 0, th = 0;
         const unsigned long long* sg_ = hist_g + (size_t)ln * spn + s0; const unsigned long long* sh_ = hist_h + (size_t)ln * spn + s0;

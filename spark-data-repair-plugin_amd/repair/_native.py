@@ -93,8 +93,8 @@ def lib():
                      "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
                      "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats"):
             getattr(l, name).restype = C.c_int
-        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible"):
-            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view)
+        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan"):
+            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry)
                 getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -120,7 +120,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
-    "rgbm_table_column_stats",
+    "rgbm_table_column_stats", "rgbm_level_pass_plan",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -393,6 +393,23 @@ class RgbmFitSpec(C.Structure):
     _fields_ = [("table", C.c_void_p), ("target_col", C.c_int32), ("n_features", C.c_int32), ("feat_cols", C.POINTER(C.c_int32)),
                 ("y_value", C.POINTER(C.c_double)), ("class_weight", C.POINTER(C.c_double)), ("params", C.POINTER(RgbmParams)),
                 ("valid_table", C.c_void_p), ("valid_label_out", C.POINTER(C.c_int32)), ("valid_value_out", C.POINTER(C.c_double))]
+
+
+def level_pass_plan(nbins, rows, K, max_depth=7, with_mult=False):
+    """The launch plan of the level grower's passes for a table shape (rgbm_level_pass_plan; no device needed; honours the RGBM_* switches of the
+    environment): dict(root_gx, part_items, root_workgroups, root_t_fix_us, root_t_rows_us, launches=[dict(level, ch, slot0, nslots, route, T, G, gx,
+    acc2, rot, t_fix_us, t_rows_us)]) -- t_fix_us / t_rows_us: the modelled fixed and row-loop time of one workgroup the grid rule ranks by."""
+    nb = _i32(nbins)
+    out = np.zeros(6 + 12 * 4096, np.float64)      # (<= 6 levels x 16 chunks x 32 windows of built slots)
+    n = C.c_int32(0)
+    _check(lib().rgbm_level_pass_plan(_p(nb, C.c_int32), C.c_int32(len(nb)), C.c_int64(rows), C.c_int32(K), C.c_int32(max_depth), C.c_int32(1 if with_mult else 0),
+                                      _p(out, C.c_double), C.c_int32(len(out)), C.byref(n)), "rgbm_level_pass_plan")
+    keys = ("level", "ch", "slot0", "nslots", "route", "T", "G", "gx", "acc2", "rot")
+    launches = []
+    for i in range(int(out[2])):
+        v = out[6 + 12 * i: 18 + 12 * i]
+        launches.append(dict({k: int(x) for k, x in zip(keys, v)}, t_fix_us=float(v[10]), t_rows_us=float(v[11])))
+    return dict(root_gx=int(out[0]), part_items=int(out[1]), root_workgroups=int(out[3]), root_t_fix_us=float(out[4]), root_t_rows_us=float(out[5]), launches=launches)
 
 
 def distinct_view_eligible(rows, f, table_has_mult=False, min_rows=0, **params):
