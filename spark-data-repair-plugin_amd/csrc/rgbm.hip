@@ -210,6 +210,9 @@ struct RunSwitches {
                                    // histograms, the eight the replicated layout is sized for (profiles/r6r_*)
     int mt_rot_tmin = 2;           // RGBM_MT_ROT_TMIN: ... or when replication leaves the workgroup fewer class trees than this although one copy
                                    // holds twice as many (0 = off).  0 / 2 / 4: bench step 80.4-80.8 / 80.0-80.1 / 80.8-81.2 ms (profiles/EXPERIMENTS.md, r7m / r7n)
+    bool step_readback = false;    // RGBM_STEP_READBACK=1: k_level_step scans the child histograms out of the pool, not out of LDS (tests: the path of wide tables)
+    int step_threads = 0;          // RGBM_STEP_THREADS: workgroup size of k_level_step (0: LevelGrower's choice)
+    int step_max_gx = 0;           // RGBM_STEP_MAX_GX: most workgroup partials per class tree k_level_step sums itself (0: LevelGrower's choice)
     bool fx_separate = false;      // RGBM_FX_MEASURE=separate: the coarse gradient sums of numerics v2.2 from a pass of their own (k_fx_measure, the
                                    // live path for K > 112) instead of out of the gradient kernels; same sums, same models
     bool distinct = true;          // RGBM_DISTINCT=0: rgbm_table_train never trains on the table's distinct-row view (the row-for-row figures)
@@ -227,6 +230,9 @@ RunSwitches read_switches() {
     if (const char* e = getenv("RGBM_JOINT_ROOT")) w.joint_root = atoi(e) != 0;
     if (const char* e = getenv("RGBM_MT_ACC2")) w.mt_acc2 = atoi(e) != 0;
     if (const char* e = getenv("RGBM_MT_SPARSE")) w.mt_sparse = atoi(e) != 0;
+    if (const char* e = getenv("RGBM_STEP_READBACK")) w.step_readback = atoi(e) != 0;
+    if (const char* e = getenv("RGBM_STEP_THREADS")) w.step_threads = atoi(e);
+    if (const char* e = getenv("RGBM_STEP_MAX_GX")) w.step_max_gx = atoi(e);
     if (const char* e = getenv("RGBM_FX_MEASURE")) w.fx_separate = strcmp(e, "separate") == 0;
     if (const char* e = getenv("RGBM_MT_ROT")) w.mt_rot = atoi(e);
     if (const char* e = getenv("RGBM_MT_ROT_COPIES2")) w.mt_rot_copies2 = atoi(e);
@@ -761,7 +767,7 @@ void fill_train_stats(rgbm_train_stats* stats, float total_ms, const HistTimers&
     stats->trees = (int64_t)NE * K;
     const bool root_done = n_train >= (int64_t)p.min_data_in_leaf * 2;
     if (level_mode) {
-        // rows whose (g,h) were accumulated: counted on the device (k_level_split); root passes = trees with a searched root
+        // rows whose (g,h) were accumulated: counted on the device (k_level_step); root passes = trees with a searched root
         // (bag sizes vary: not tracked separately).  Row-sharded: the device counter sums GLOBAL child counts on every rank; report this rank's share
         const int64_t root_rows = (root_done && !use_bagging) ? (int64_t)NE * K * n_train : 0;
         const int64_t rows_acc = (int64_t)(statrows / (unsigned long long)nranks);
@@ -927,7 +933,7 @@ struct FitState {
     DevBuf<double> cw, yv, sw_rows; DevBuf<uint8_t> used;
     BagState bag; DevBuf<unsigned int> bagcnt_g;
     const unsigned int* n_in_ptr = nullptr;          // rows in the bag of the current iteration, over ALL ranks when row-sharded (the root count of every tree)
-    DevBuf<int32_t> it;                // device-side iteration counter (k_next_iteration)
+    DevBuf<int32_t> it;                // device-side iteration counter of the level grower (k_level_init)
     HistTimers timers;
 
     FitState(const rgbm_table& tab_, int32_t target_col, int32_t F_, const rgbm_params& p_, bool timed, hipStream_t s_)
@@ -963,7 +969,11 @@ struct LevelGrower {
     // joint bins for the root pass (rgbm_level.h, k_pack_joint): a second record whose bytes hold GROUPS of low-cardinality features
     bool joint_root = false; int vtotbins = 0;
     DevBuf<rg::FeatMeta> vfmeta; DevBuf<rg::ChunkMeta> vcmeta; DevBuf<uint4> rec_j; DevBuf<rg::HistBin> part_j, red_j; DevBuf<rg::JointFeat> jf; DevBuf<int16_t> binfeat;
-    DevBuf<uint8_t> node; DevBuf<rg::LvPlan> plan; DevBuf<rg::SNode> snodes; DevBuf<rg::Cand> lcand;
+    DevBuf<uint8_t> node; DevBuf<rg::LvPlan> plan; DevBuf<rg::SNode> snodes;
+    // k_level_step: lane map of its packed threshold scan, waves a child needs, whether the two child histograms live in LDS, workgroup size, and the most
+    // workgroup partials per class tree it sums itself (more: k_level_reduce runs in front).  Threads and threshold: profiles/EXPERIMENTS.md, round 14.
+    DevBuf<rg::ScanLane> scan_map; std::vector<rg::ScanLane> h_scan; int scan_waves = 0; bool step_hist_lds = true;
+    int step_threads = 512, step_max_gx = 256;
     DevBuf<rg::HistBin> part, lpool, part_red; DevBuf<int32_t> count, count_g, err, leafnode; DevBuf<double> ndelta; DevBuf<unsigned long long> d_statrows;
     const int score_gx = (int)std::max<long long>(1, std::min<long long>((st.N + 1023) / 1024, (2048 + st.K - 1) / st.K));
     LevelTrace trace;
@@ -991,9 +1001,14 @@ struct LevelGrower {
         // the padding rows [N, NS) of every class tree stay LV_INACTIVE for the whole fit (the gradient kernels reset rows < N only): the level pass
         // routes rows by their id alone, and an id past the end of a class tree's table takes the dummy entry
         HIPCHK(hipMemsetAsync(node.p, 0xFF, (size_t)st.K * lc.NS, s));
-        plan.alloc(st.K); snodes.alloc((size_t)st.K * 256); lcand.alloc((size_t)st.K * 256 * st.F);
+        plan.alloc(st.K); snodes.alloc((size_t)st.K * 256);
         part.alloc(passes.part_items * st.h.tc.totbins); lpool.alloc((size_t)st.K * n_hnodes * st.h.tc.totbins);
-        count.alloc((size_t)st.K * 256); use_reduce = st.dp || lc.gx > 4;
+        scan_waves = scan_lane_map(st.h.fmeta.data(), st.F, h_scan);
+        scan_map.alloc(h_scan.size()); scan_map.upload(h_scan.data(), h_scan.size(), s);
+        step_hist_lds = ls_hist_in_lds(st.h.tc.totbins, st.F) && !st.sw.step_readback;
+        if (st.sw.step_threads >= 128 && st.sw.step_threads <= LS_MAX_THREADS && st.sw.step_threads % 64 == 0) step_threads = st.sw.step_threads;
+        if (st.sw.step_max_gx >= 1) step_max_gx = st.sw.step_max_gx;
+        count.alloc((size_t)st.K * 256); use_reduce = st.dp || lc.gx > step_max_gx;
         if (st.dp) count_g.alloc((size_t)st.K * 256);
         const int max_built_all = 1 << std::max(0, st.p.max_depth - 2);
         part_red.alloc((size_t)st.K * max_built_all * st.h.tc.totbins + (size_t)st.K * 128 /* K*256 int64 counts */);
@@ -1054,10 +1069,11 @@ struct LevelGrower {
         trace.copy("snodes", level, snodes.p, (size_t)st.K * 256 * sizeof(rg::SNode));
         trace.copy("lpool", level, lpool.p, (size_t)st.K * n_hnodes * st.h.tc.totbins * 16);
     }
-    // partials of this rank -> compact buffer (-> integer all-reduce when row-sharded); the split kernel then sees ONE partial
+    // partials of this rank -> compact buffer (-> integer all-reduce when row-sharded); the step kernel then sees ONE partial.  On one rank the step
+    // kernel sums up to step_max_gx partials itself (the root: use_reduce, which the joint-bin root pass also sets).
     std::pair<const rg::HistBin*, rg::LevelConst> exchange(bool root, int nb, const rg::LevelConst& lp) {
         using namespace rg;
-        if (root && !use_reduce) return {part.p, lp};
+        if (root ? !use_reduce : (!st.dp && lp.gx <= step_max_gx)) return {part.p, lp};
         if (root && joint_root) {   // partials -> one joint histogram per class tree (k_level_reduce in the joint bin space) -> marginals of the real features
             hipLaunchKernelGGL(k_level_reduce, dim3((vtotbins + 63) / 64, 1, st.K), dim3(256), 0, s, part_j.p, red_j.p, plan.p, count.p, 1, 1, lcj);
             hipLaunchKernelGGL(k_level_marginal, dim3((st.h.tc.totbins + 255) / 256, st.K), dim3(256), 0, s, red_j.p, part_red.p, plan.p, count.p, jf.p, binfeat.p, vtotbins, lc);
@@ -1077,7 +1093,8 @@ struct LevelGrower {
         const TreeOut to = st.trees.out();
         trace.cur_it = it;
         trace.sum("gh", st.gh.p, (size_t)st.K * st.h.tc.NG * 8);
-        hipLaunchKernelGGL(k_level_init, dim3(st.K), dim3(64), 0, s, plan.p, snodes.p, count.p, st.n_in_ptr, (long long)st.h.n_train, st.fxq.p, st.h.tc.fx, st.fxs.p, lc);
+        hipLaunchKernelGGL(k_level_init, dim3(st.K), dim3(64), 0, s, plan.p, snodes.p, count.p, st.n_in_ptr, (long long)st.h.n_train, st.fxq.p, st.h.tc.fx, st.fxs.p, st.it.p, lc);
+        const size_t step_lds = ls_lds_bytes(st.h.tc.totbins, st.F, step_hist_lds);
         int32_t* cntg = st.dp ? count_g.p : count.p;      // child row counts seen by split / leaf-count (global when row-sharded)
         st.timers.timed(true, [&]() {
             if (joint_root)   // the root pass over the joint record: one pair of atomics per feature GROUP and row
@@ -1089,12 +1106,12 @@ struct LevelGrower {
         });
         {
             auto ex = exchange(true, 1, lc);
-            hipLaunchKernelGGL(k_level_split<true>, dim3((st.F + 3) / 4, 1, st.K), dim3(256), 0, s, ex.first, lpool.p, plan.p, snodes.p, cntg, count.p, st.bins.fmeta.p,
-                               st.used.p, lcand.p, d_statrows.p, st.it.p, n_hnodes, st.fxs.p, st.h.tc, ex.second);
+            hipLaunchKernelGGL(k_level_step<true>, dim3(1, st.K), dim3(step_threads), step_lds, s, ex.first, lpool.p, plan.p, snodes.p, cntg, count.p, st.bins.fmeta.p,
+                               st.used.p, scan_map.p, scan_waves, step_hist_lds ? 1 : 0, d_statrows.p, st.it.p, n_hnodes, st.fxs.p, st.h.tc, ex.second);
             trace_level(0);
         }
         for (int level = 1; level < st.p.max_depth; ++level) {
-            hipLaunchKernelGGL(k_level_plan, dim3(st.K), dim3(256), 0, s, plan.p, snodes.p, lcand.p, st.bins.fmeta.p, level, st.h.tc, lc);
+            hipLaunchKernelGGL(k_level_plan, dim3(st.K), dim3(64), 0, s, plan.p, snodes.p, st.bins.fmeta.p, level, st.h.tc, lc);
             // the k_level_mt launches of the level; lp describes the partials they write
             LevelConst lp = lc;
             lp.xcd_blocks = 0; lp.gx = passes.mt_gx[level]; lp.max_built = 1 << (level - 1);
@@ -1110,12 +1127,12 @@ struct LevelGrower {
                 });
             }
             auto ex = exchange(false, 1 << (level - 1), lp);
-            hipLaunchKernelGGL(k_level_split<false>, dim3((st.F + 1) / 2, 1 << (level - 1), st.K), dim3(256), 0, s, ex.first, lpool.p, plan.p, snodes.p,
-                               cntg, count.p, st.bins.fmeta.p, st.used.p, lcand.p, d_statrows.p, st.it.p, n_hnodes, st.fxs.p, st.h.tc, ex.second);
+            hipLaunchKernelGGL(k_level_step<false>, dim3(1 << (level - 1), st.K), dim3(step_threads), step_lds, s, ex.first, lpool.p, plan.p, snodes.p,
+                               cntg, count.p, st.bins.fmeta.p, st.used.p, scan_map.p, scan_waves, step_hist_lds ? 1 : 0, d_statrows.p, st.it.p, n_hnodes, st.fxs.p, st.h.tc, ex.second);
             trace_level(level);
         }
         // last level: plan -> replay (leaf values never depend on the deepest counts) -> route + count + score in one pass
-        hipLaunchKernelGGL(k_level_plan, dim3(st.K), dim3(256), 0, s, plan.p, snodes.p, lcand.p, st.bins.fmeta.p, st.p.max_depth, st.h.tc, lc);
+        hipLaunchKernelGGL(k_level_plan, dim3(st.K), dim3(64), 0, s, plan.p, snodes.p, st.bins.fmeta.p, st.p.max_depth, st.h.tc, lc);
         hipLaunchKernelGGL(k_level_replay, dim3(st.K), dim3(64), 0, s, plan.p, snodes.p, cntg, to, st.init.p, ndelta.p, leafnode.p, st.trees.any.p, err.p, st.it.p, st.h.tc);
         // AddScore: the pass that routes, counts and adds in one
         hipLaunchKernelGGL(k_level_final, dim3(score_gx, st.K), dim3(256), 0, s, st.bins.rec.p, node.p, st.bag.inbag.p, plan.p, to, ndelta.p, st.score.p, count.p, st.it.p, lc);
@@ -1123,7 +1140,6 @@ struct LevelGrower {
         hipLaunchKernelGGL(k_level_leafcount, dim3(st.K), dim3(LV_MAX_LEAVES), 0, s, plan.p, cntg, leafnode.p, to, st.it.p, st.h.tc);
         trace_level(st.p.max_depth);
         trace.sum("score", st.score.p, (size_t)st.K * st.N * 8); trace.sum("node", node.p, (size_t)st.K * lc.NS);
-        hipLaunchKernelGGL(k_next_iteration, dim3(1), dim3(1), 0, s, st.it.p);
     }
     // behind the last iteration: what report() needs on the host; report() runs after the stream has drained and raises what the device flagged
     void enqueue_report() { err.download(&h_err, 1, s); d_statrows.download(&statrows, 1, s); }
@@ -1289,7 +1305,7 @@ rgbm_model* train_core(const rgbm_table& tab, int32_t target_col, const int32_t*
         HIPCHK(hipStreamSynchronize(s));
         st.n_in_ptr = st.dp ? st.bagcnt_g.p : st.bag.bagcnt.p;
     }
-    st.it.alloc(1); st.it.zero(s);
+    st.it.alloc(1); HIPCHK(hipMemsetAsync(st.it.p, 0xFF, sizeof(int32_t), s));      // -1: k_level_init advances it at the start of every iteration
     st.alloc_fx_parts();
     // the distinct-row view: the statistics count the rows the kernels stream, so the view's own training rows are counted once
     unsigned int view_train_rows = 0;
@@ -1459,15 +1475,8 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
         // used when a child's features fit half of the workgroup's waves (both children are scanned at once) and the two compact
         // histograms fit next to the rest in LDS -- otherwise one wave per feature (split_find_body)
         {
-            std::vector<ScanLane> sm; int lanes_used = 0;
-            for (int f = 0; f < F; ++f) {
-                const int nl_f = std::max(1, (h.fmeta[f].V + 3) / 4);
-                if (lanes_used % 64 + nl_f > 64) while (lanes_used % 64) { sm.push_back(ScanLane{-1, 0, 1, 0}); ++lanes_used; }
-                const int first = lanes_used % 64;
-                for (int q = 0; q < nl_f; ++q) { sm.push_back(ScanLane{f, 4 * q, q == 0 ? 1 : 0, first + nl_f - 1}); ++lanes_used; }
-            }
-            while (lanes_used % 64) { sm.push_back(ScanLane{-1, 0, 1, 0}); ++lanes_used; }
-            const int Wn = lanes_used / 64;
+            std::vector<ScanLane> sm;
+            const int Wn = scan_lane_map(h.fmeta.data(), F, sm);
             const bool off_switch = getenv("RGBM_SMALL_PACKED") && atoi(getenv("RGBM_SMALL_PACKED")) == 0;
             if (!off_switch && 2 * Wn <= SM_WAVES && h.tc.totbins <= 2048 && sm_lds_bytes(h.lds_hist, NL, F, h.tc.totbins) <= 150 * 1024) { d.scan_waves = Wn; d.h_scan = std::move(sm); }
         }

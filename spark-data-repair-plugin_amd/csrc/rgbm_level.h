@@ -12,8 +12,9 @@
 //     parent (the other is parent - child: sums are exact integers, so which child is built never
 //     changes a bit of the result); rows of the built child are counted, the sibling's count is
 //     parent - built;
-//   * k_level_split scans both children of every expanded parent (same FindBestThreshold code as
-//     the leaf-wise path);
+//   * k_level_step sums the built child of an expanded parent, derives its sibling, scans both (the
+//     FindBestThreshold code of the batched small-table trainer, bit for bit the leaf-wise path's)
+//     and leaves each child's best split in its node;
 //   * k_level_plan decides which nodes of the new level to expand.  A node is expanded unless it
 //     PROVABLY cannot be split by best-first growth: with pm(X) = min gain on the path root..X,
 //     every known node Y with pm(Y) > pm(X) is split before X (induction on the best-first
@@ -34,6 +35,7 @@
 // set of rows can overflow.
 #pragma once
 #include "rgbm_kernels.h"
+#include "rgbm_small.h"      // the packed threshold scan (ScanLane, scan_child_packed) of k_level_step
 
 namespace rg {
 
@@ -92,7 +94,7 @@ struct LevelConst {
     int32_t gx;                 // row blocks per class tree of THIS launch (partials: [K][gx][max_built][totbins])
     int32_t max_built;           // built-node stride of the partials of THIS launch
     int32_t nchunk, K, F, totbins, num_leaves, max_depth, min_data_in_leaf, lds_bytes;
-    int32_t sib_local;           // k_level_split also writes the derived sibling count into the LOCAL count array (row-sharded: rank 0 only)
+    int32_t sib_local;           // k_level_step also writes the derived sibling count into the LOCAL count array (row-sharded: rank 0 only)
     int32_t xcd_blocks;          // root pass: 1-D grid of K * gx blocks, contiguous row blocks, all class trees of a row block on one XCD
     // k_level_mt launch: class trees per workgroup, tree groups, chunk whose features are accumulated, built-slot window, routing?
     int32_t mt_T, mt_G, mt_ch, mt_slot0, mt_nslots, mt_route;
@@ -246,8 +248,12 @@ inline void root_layout_fill(RootLayout& L, const FeatMeta* fm, int nfeat, int l
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_level_init(LvPlan* __restrict__ plan, SNode* __restrict__ nodes, int32_t* __restrict__ count,
                                                    const unsigned int* __restrict__ n_in_ptr, long long n_train,
-                                                   unsigned long long* __restrict__ Q, FxGrid fx, FxScale* __restrict__ fxs, LevelConst c) {
+                                                   unsigned long long* __restrict__ Q, FxGrid fx, FxScale* __restrict__ fxs,
+                                                   int32_t* __restrict__ itp /* device-side iteration counter */, LevelConst c) {
     const int k = blockIdx.x, lane = lane_id();
+    // the iteration counter lives on the device so that one boosting iteration is the same launch sequence every time.  It starts at -1 and advances here, in the
+    // first kernel of an iteration: no block of this kernel reads it, every later kernel of the iteration does.
+    if (k == 0 && lane == 0) itp[0] += 1;
     // numerics v2.2: this class tree's fixed-point grid of the iteration from the coarse sums of its gradients (k_fx_scale's work, here so that
     // the chain of small kernels of an iteration does not grow by a launch); the sums go back to zero for the next iteration
     if (lane == 0) {
@@ -1179,127 +1185,170 @@ __global__ __launch_bounds__(256) void k_counts_unpack(const long long* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_level_split: sum the workgroup partials of the built child, derive the sibling by subtraction,
-// scan both (FindBestThreshold).  grid (ROOT ? ceil(F/4) : ceil(F/2), ROOT ? 1 : max parents, K), block 256.
+// k_level_step: everything between the pass of a level and the plan of the next one, for ONE expanded parent of one class tree per
+// workgroup: sum the workgroup partials of the built child (every thread, over all bins), derive the sibling by subtraction, write
+// both to the pool, scan both (FindBestThreshold, packed: scan_child_packed of rgbm_small.h, the features of a child share waves and
+// the two children are scanned by different waves) and reduce the per-feature candidates to the best split of each child
+// (SplitInfo::operator>).  grid (ROOT ? 1 : max parents, K), block LevelGrower::step_threads.
+//
+// What it replaces: k_level_reduce (one launch, unless the host keeps it: below) + k_level_split (one wave per (feature, side), each
+// re-walking plan -> exp -> node -> hslot and summing its own partials) + the first third of k_level_plan (best candidate per node out of
+// a [K][256][F] candidate array in global memory).  The candidates now live in LDS only.
+//
+// Dynamic LDS: [2][totbins] HistBin (left child, right child; ROOT: the root) | [2][F] Cand.  When the two histograms do not fit
+// (ls_hist_in_lds) the scan reads them back from the pool behind the barrier that follows their stores (hist_lds = 0; RGBM_STEP_READBACK=1
+// forces that path).
+// The host keeps k_level_reduce in front (gx = 1 here) when row-sharded -- the compact buffer is what is all-reduced -- and when the pass had
+// more than LS_MAX_GX workgroups per class tree.
 // ------------------------------------------------------------------------------------------------
+constexpr int LS_MAX_THREADS = 1024;
+constexpr int LS_LDS_BUDGET = 64 * 1024;           // what a launch gets without an attribute
+__host__ __device__ inline size_t ls_lds_bytes(int totbins, int F, bool hist_lds) { return (hist_lds ? (size_t)2 * totbins * sizeof(HistBin) : 0) + (size_t)2 * F * sizeof(Cand); }
+inline bool ls_hist_in_lds(int totbins, int F) { return ls_lds_bytes(totbins, F, true) + 1024 <= (size_t)LS_LDS_BUDGET; }
+
 template <bool ROOT>
-__global__ __launch_bounds__(256) void k_level_split(const HistBin* __restrict__ part, HistBin* __restrict__ pool, LvPlan* __restrict__ plan,
-                                                     SNode* __restrict__ nodes, int32_t* __restrict__ count, int32_t* __restrict__ count_local,
-                                                     const FeatMeta* __restrict__ fmeta, const uint8_t* __restrict__ used_all /* [NE][K][F] */,
-                                                     Cand* __restrict__ cand /* [K][256][F] */, unsigned long long* __restrict__ stat_rows,
-                                                     const int32_t* __restrict__ itp /* device-side iteration counter */,
-                                                     int n_hnodes, const FxScale* __restrict__ fxs, TrainConst c_model, LevelConst lc) {
-    const int k = blockIdx.z, pi = blockIdx.y;
-    const TrainConst c = tree_const(c_model, fxs, k);          // sums -> doubles on this class tree's grid
-    const uint8_t* used = used_all + (long long)(*itp) * c.K * c.F;
-    // ROOT: one wave per feature (4 per block).  Otherwise one wave per (feature, child side): 2 features per block,
-    // so the two FindBestThreshold scans of a parent run side by side instead of back to back.
-    const int wv = threadIdx.x >> 6;
-    const int f = ROOT ? blockIdx.x * 4 + wv : blockIdx.x * 2 + (wv >> 1);
-    const int side = wv & 1;   // 0 = left child, 1 = right child
+__global__ __launch_bounds__(LS_MAX_THREADS) void k_level_step(const HistBin* __restrict__ part, HistBin* __restrict__ pool, const LvPlan* __restrict__ plan,
+                                                               SNode* __restrict__ nodes, int32_t* __restrict__ count, int32_t* __restrict__ count_local,
+                                                               const FeatMeta* __restrict__ fmeta, const uint8_t* __restrict__ used_all /* [NE][K][F] */,
+                                                               const ScanLane* __restrict__ scan_map /* [scan_waves][64] */, int scan_waves, int hist_lds,
+                                                               unsigned long long* __restrict__ stat_rows, const int32_t* __restrict__ itp /* device-side iteration counter */,
+                                                               int n_hnodes, const FxScale* __restrict__ fxs, TrainConst c_model, LevelConst lc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int k = blockIdx.y, pi = blockIdx.x;
     const LvPlan* pp = &plan[k];
+    // ---- header: the plan fields, the parent and the two child counts are independent loads (the children of expanded parent pi are
+    // child_first + 2 pi, + 1 by k_level_plan's numbering: nothing but the parent itself waits for exp[pi])
     if (pp->done) return;
     if (!ROOT && pi >= pp->n_exp) return;
-    if (f >= c.F) return;
-    const int lane = lane_id();
-    const FeatMeta fm = fmeta[f];
+    const int T = blockDim.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nwaves = T >> 6;
+    const int tb = lc.totbins, F = lc.F;
+    const int l = ROOT ? 0 : pp->child_first + 2 * pi, r = ROOT ? 0 : l + 1;
+    const bool bl = ROOT ? true : pp->built_is_left[pi] != 0;
+    const long long n_in = pp->n_in;
     SNode* nk = nodes + (long long)k * 256;
-    Cand* ck = cand + (long long)k * 256 * c.F;
-    HistBin* pk = pool + (long long)k * n_hnodes * c.totbins;
-    const bool is_used = used[(long long)k * c.F + f] != 0;
-    long long ag[4], ah[4];
-    const int bslot = ROOT ? 0 : pi;
-    // built child = sum of the gx workgroup partials
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { ag[j] = 0; ah[j] = 0; }
-    for (int x = 0; x < lc.gx; ++x) {
-        const HistBin* src = part + (((long long)k * lc.gx + x) * lc.max_built + bslot) * c.totbins + fm.hoff;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int b = lane * 4 + j; if (b < fm.nbins) { const HistBin v = src[b]; ag[j] += v.g; ah[j] += v.h; } }
+    int nl = ROOT ? 0 : count[(long long)k * 256 + l], nr = ROOT ? 0 : count[(long long)k * 256 + r];
+    const int hs_l = ROOT ? 0 : nk[l].hslot, hs_r = ROOT ? 0 : nk[r].hslot;
+    const int p = ROOT ? 0 : (int)pp->exp[pi];
+    long long P_Gq = 0, P_Hq = 0, P_lGq = 0, P_lHq = 0; int P_count = 0, P_hslot = 0;
+    if (!ROOT) { const SNode& P = nk[p]; P_Gq = P.Gq; P_Hq = P.Hq; P_lGq = P.best.left_gq; P_lHq = P.best.left_hq; P_count = P.count; P_hslot = P.hslot; }
+    const TrainConst c = tree_const(c_model, fxs, k);          // sums -> doubles on this class tree's grid
+    const uint8_t* used_k = used_all + ((long long)(*itp) * lc.K + k) * F;
+    HistBin* pk = pool + (long long)k * n_hnodes * tb;
+    HistBin* gL = pk + (long long)hs_l * tb; HistBin* gR = pk + (long long)hs_r * tb;       // the children's pool slots (ROOT: slot 0)
+    HistBin* hL = hist_lds ? reinterpret_cast<HistBin*>(smem) : gL;                          // what the scan reads
+    HistBin* hR = hist_lds ? reinterpret_cast<HistBin*>(smem) + tb : gR;
+    Cand* ck = reinterpret_cast<Cand*>(smem + (hist_lds ? (size_t)2 * tb * sizeof(HistBin) : 0));      // [2][F]
+    HistBin* hbuilt = bl ? hL : hR; HistBin* hsib = bl ? hR : hL;
+
+    // ---- built child = sum of the gx workgroup partials, over all bins with every thread.  Where the block has more threads than bins, PL
+    // threads share a bin (k_level_reduce's (bin, partial-lane) arrangement) and meet in the LDS histogram with integer atomics.
+    {
+        const int bslot = ROOT ? 0 : pi;
+        const HistBin* src = part + (((long long)k * lc.gx) * lc.max_built + bslot) * tb;
+        const long long xs = (long long)lc.max_built * tb;
+        const int nbl = tb >= T ? T : ((tb + 63) & ~63);
+        int PL = hist_lds ? T / nbl : 1;
+        if (PL > lc.gx) PL = lc.gx;
+        if (PL > 1) {
+            for (int b = tid; b < tb; b += T) { HistBin z; z.g = 0; z.h = 0; hbuilt[b] = z; }
+            __syncthreads();
+            const int b = tid % nbl, xl = tid / nbl;
+            if (b < tb && xl < PL) {
+                long long ag = 0, ah = 0;
+#pragma unroll 8
+                for (int x = xl; x < lc.gx; x += PL) { const HistBin v = src[x * xs + b]; ag += v.g; ah += v.h; }
+                atomicAdd(reinterpret_cast<unsigned long long*>(&hbuilt[b].g), (unsigned long long)ag);
+                atomicAdd(reinterpret_cast<unsigned long long*>(&hbuilt[b].h), (unsigned long long)ah);
+            }
+        } else {
+            for (int b = tid; b < tb; b += T) {
+                long long ag = 0, ah = 0;
+#pragma unroll 8
+                for (int x = 0; x < lc.gx; ++x) { const HistBin v = src[x * xs + b]; ag += v.g; ah += v.h; }
+                HistBin o; o.g = ag; o.h = ah; hbuilt[b] = o;
+            }
+        }
+        __syncthreads();
     }
+    // ---- the sibling: parent - built (exact integers); both children go to the pool
     if (ROOT) {
-        HistBin* h0 = pk + fm.hoff;
-        long long sg_ = 0, sh_ = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int b = lane * 4 + j; if (b < fm.nbins) { HistBin v; v.g = ag[j]; v.h = ah[j]; h0[b] = v; } sg_ += ag[j]; sh_ += ah[j]; }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { sg_ += __shfl_xor(sg_, o); sh_ += __shfl_xor(sh_, o); }
-        if (f == 0 && lane == 0) { nk[0].Gq = sg_; nk[0].Hq = sh_; nk[0].searched = 1; atomicAdd(stat_rows, (unsigned long long)pp->n_in); }
-        if (!is_used) { if (lane == 0) ck[f].gain = -INFINITY; return; }
-        scan_child(ag, ah, fm, sg_, sh_, pp->n_in, c, &ck[f]);
-        return;
-    }
-    const int p = pp->exp[pi];
-    const SNode P = nk[p];
-    const int l = P.left, r = P.right;
-    const bool bl = pp->built_is_left[pi] != 0;
-    const int me = side == 0 ? l : r;
-    const bool i_am_built = (side == 0) == bl;
-    const HistBin* hp = pk + (long long)P.hslot * c.totbins + fm.hoff;
-    HistBin* hm = pk + (long long)nk[me].hslot * c.totbins + fm.hoff;
-    if (!i_am_built) {   // the sibling: parent - built (exact integers)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int b = lane * 4 + j;
-            if (b < fm.nbins) { const HistBin par = hp[b]; ag[j] = par.g - ag[j]; ah[j] = par.h - ah[j]; } else { ag[j] = 0; ah[j] = 0; }
+        if (hist_lds) for (int b = tid; b < tb; b += T) gL[b] = hL[b];
+    } else {
+        const HistBin* hp = pk + (long long)P_hslot * tb;
+        HistBin* gbuilt = bl ? gL : gR; HistBin* gsib = bl ? gR : gL;
+        for (int b = tid; b < tb; b += T) {
+            const HistBin bu = hbuilt[b], par = hp[b];
+            HistBin sb; sb.g = par.g - bu.g; sb.h = par.h - bu.h;
+            hsib[b] = sb;
+            if (hist_lds) { gbuilt[b] = bu; gsib[b] = sb; }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int b = lane * 4 + j; if (b < fm.nbins) { HistBin v; v.g = ag[j]; v.h = ah[j]; hm[b] = v; } }
-    int nl = count[(long long)k * 256 + l], nr = count[(long long)k * 256 + r];
-    {
-        // only the built child was counted (k_level_mt); its sibling holds the rest of the parent's rows.  The derived
-        // count is published for the leaf counts; row-sharded training sums the LOCAL arrays, so exactly one rank also
-        // stores it there (lc.sib_local).
-        const int nb = bl ? nl : nr, ns = P.count - nb;
+    // ---- counts.  Only the built child was counted (k_level_mt); its sibling holds the rest of the parent's rows.  The derived count is
+    // published for the leaf counts; row-sharded training sums the LOCAL arrays, so exactly one rank also stores it there (lc.sib_local).
+    bool go = true;
+    if (!ROOT) {
+        const int nb = bl ? nl : nr, ns = P_count - nb;
         if (bl) nr = ns; else nl = ns;
-        if (f == 0 && lane == 0 && side == 0) {
+        // SerialTreeLearner::BeforeFindBestSplit: both children too small -> neither is searched
+        go = !(nr < c.min_data_in_leaf * 2 && nl < c.min_data_in_leaf * 2);
+        if (tid == 0) {
             const int sib = bl ? r : l;
             count[(long long)k * 256 + sib] = ns;
             if (lc.sib_local && count_local != count) count_local[(long long)k * 256 + sib] = ns;
+            nk[l].count = nl; nk[l].searched = go ? 1 : 0;
+            nk[r].count = nr; nk[r].searched = go ? 1 : 0;
+            atomicAdd(stat_rows, (unsigned long long)nb);
         }
     }
-    // SerialTreeLearner::BeforeFindBestSplit: both children too small -> neither is searched
-    const bool go = !(nr < c.min_data_in_leaf * 2 && nl < c.min_data_in_leaf * 2);
-    if (f == 0 && lane == 0) {
-        nk[me].count = side == 0 ? nl : nr; nk[me].searched = go ? 1 : 0;
-        if (side == 0) atomicAdd(stat_rows, (unsigned long long)(bl ? nl : nr));
+    __syncthreads();       // the histograms are complete (LDS, or the pool slots this workgroup has just written)
+    // ---- FindBestThreshold, packed: wave (child, slot) scans the features of lane-map row `slot` for `child`
+    const int nch = ROOT ? 1 : 2;
+    if (go) {
+        for (int ws = wv; ws < nch * scan_waves; ws += nwaves) {
+            const int child = ws / scan_waves, slot = ws - child * scan_waves;
+            const ScanLane sl = scan_map[slot * 64 + lane];
+            if (ROOT) {
+                // node totals = sum over all bins of any one feature (every row sits in exactly one bin)
+                const FeatMeta f0 = fmeta[0];
+                long long sg_ = 0, sh_ = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const int b = lane * 4 + j; if (b < f0.nbins) { const HistBin v = hL[f0.hoff + b]; sg_ += v.g; sh_ += v.h; } }
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) { sg_ += __shfl_xor(sg_, o); sh_ += __shfl_xor(sh_, o); }
+                if (ws == 0 && lane == 0) { nk[0].Gq = sg_; nk[0].Hq = sh_; nk[0].searched = 1; atomicAdd(stat_rows, (unsigned long long)n_in); }
+                scan_child_packed(hL, fmeta, sl, sg_, sh_, n_in, c, used_k, ck);
+            } else if (child == 0) scan_child_packed(hL, fmeta, sl, P_lGq, P_lHq, (long long)nl, c, used_k, ck);
+            else scan_child_packed(hR, fmeta, sl, P_Gq - P_lGq, P_Hq - P_lHq, (long long)nr, c, used_k, ck + F);
+        }
     }
-    if (!go) return;
-    if (!is_used) { if (lane == 0) ck[(long long)me * c.F + f].gain = -INFINITY; return; }
-    const long long lGq = P.best.left_gq, lHq = P.best.left_hq;
-    if (side == 0) scan_child(ag, ah, fm, lGq, lHq, (long long)nl, c, &ck[(long long)l * c.F + f]);
-    else scan_child(ag, ah, fm, P.Gq - lGq, P.Hq - lHq, (long long)nr, c, &ck[(long long)r * c.F + f]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_level_plan: one wave per class tree, before pass `level` (which routes depth level-1 -> level).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_level_plan(LvPlan* __restrict__ plan, SNode* __restrict__ nodes,
-                                                    const Cand* __restrict__ cand, const FeatMeta* __restrict__ fmeta,
-                                                    int level, TrainConst c, LevelConst lc) {
-    __shared__ double pm[256];
-    const int k = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6;
-    LvPlan* pp = &plan[k];
-    if (pp->done) return;
-    SNode* nk = nodes + (long long)k * 256;
-    const Cand* ck = cand + (long long)k * 256 * c.F;
-    const int first = pp->lvl_first, end = pp->lvl_end, nlev = end - first;   // nodes of depth level-1 (<= 64)
-    // 1. best split of every node of the level (SplitInfo::operator>: gain, then smaller feature); one wave per node, 4 at a time
-    for (int n = first + wave; n < end; n += 4) {
-        if (!nk[n].searched) { if (lane == 0) { nk[n].best.gain = -INFINITY; nk[n].best_feature = -1; } continue; }
-        const Cand* cf = ck + (long long)n * c.F;
+    __syncthreads();
+    // ---- best split of each child over its features (SplitInfo::operator>: gain, then smaller feature); one wave per child
+    if (wv < nch) {
+        const int n = ROOT ? 0 : (wv == 0 ? l : r);
+        const Cand* cf = ck + wv * F;
         double bg = -INFINITY; int bf = -1;
-        for (int f = lane; f < c.F; f += 64) { const double g = cf[f].gain; if (g > -INFINITY && leaf_better(g, f, 0, bg, bf, 0)) { bg = g; bf = f; } }
+        if (go) for (int f = lane; f < F; f += 64) { const double g = cf[f].gain; if (g > -INFINITY && leaf_better(g, f, 0, bg, bf, 0)) { bg = g; bf = f; } }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) { const double g2 = __shfl_xor(bg, o); const int f2 = __shfl_xor(bf, o); if (leaf_better(g2, f2, 0, bg, bf, 0)) { bg = g2; bf = f2; } }
         if (lane == 0) {
             if (bf >= 0) { nk[n].best = cf[bf]; nk[n].best_feature = bf; } else { nk[n].best.gain = -INFINITY; nk[n].best_feature = -1; }
         }
     }
-    __syncthreads();
-    if (wave != 0) return;   // the rest is one wave's work (the barriers below only count live waves)
-    // 2. path-min gains
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_level_plan: one wave per class tree, before pass `level` (which routes depth level-1 -> level).  The best split of every node of
+// the level is in the node already (k_level_step).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_level_plan(LvPlan* __restrict__ plan, SNode* __restrict__ nodes, const FeatMeta* __restrict__ fmeta,
+                                                   int level, TrainConst c, LevelConst lc) {
+    __shared__ double pm[256];
+    const int k = blockIdx.x, lane = lane_id();
+    LvPlan* pp = &plan[k];
+    if (pp->done) return;
+    SNode* nk = nodes + (long long)k * 256;
+    const int first = pp->lvl_first, end = pp->lvl_end, nlev = end - first;   // nodes of depth level-1 (<= 64)
+    // 1. path-min gains
     for (int n = lane; n < first; n += 64) pm[n] = nk[n].pmin;
     __syncthreads();
     if (lane < nlev) {
@@ -1312,7 +1361,7 @@ __global__ __launch_bounds__(256) void k_level_plan(LvPlan* __restrict__ plan, S
         pm[n] = v; nk[n].pmin = v;
     }
     __syncthreads();
-    // 3. expansion test: X is dead once num_leaves-1 known nodes are split before it
+    // 2. expansion test: X is dead once num_leaves-1 known nodes are split before it
     bool expand = false;
     if (lane < nlev) {
         const double v = pm[first + lane];
@@ -1376,7 +1425,7 @@ __global__ __launch_bounds__(64) void k_level_replay(LvPlan* __restrict__ plan, 
                                                      int32_t* __restrict__ leaf_node_out /* [K][LV_MAX_LEAVES] */,
                                                      int32_t* __restrict__ any_split, int32_t* __restrict__ err_flag, const int32_t* __restrict__ itp, TrainConst c) {
     const int it = *itp;
-    __shared__ int leaf_node[LV_MAX_LEAVES], leaf_parent[LV_MAX_LEAVES], leaf_isleft[LV_MAX_LEAVES];
+    __shared__ int leaf_parent[LV_MAX_LEAVES], leaf_isleft[LV_MAX_LEAVES];
     __shared__ int node_leaf[256];
     __shared__ double upd[LV_MAX_LEAVES];
     const int k = blockIdx.x, lane = lane_id();
@@ -1402,46 +1451,65 @@ __global__ __launch_bounds__(64) void k_level_replay(LvPlan* __restrict__ plan, 
             s_left[n] = (short)sn.left; s_right[n] = (short)sn.right; s_parent[n] = (short)sn.parent;
         }
     }
-    if (lane == 0) { leaf_node[0] = 0; leaf_parent[0] = -1; leaf_isleft[0] = 0; }
+    if (lane == 0) { leaf_parent[0] = -1; leaf_isleft[0] = 0; }
     __syncthreads();
     if (lane == 0) node_leaf[0] = 0;
     __syncthreads();
+    // Leaf l lives in the registers of lane l & 63, slot l >> 6: its speculative node, and that node's gain and feature.  A selection step is
+    // one wave reduction of the gain; the winner among equal gains (ArrayArgs::ArgMax order, leaf_better: smaller feature, then smaller leaf)
+    // takes a ballot, and only a real tie pays two more reductions.  Lane 0 alone keeps the tree's bookkeeping in LDS.
+    static_assert(LV_MAX_LEAVES <= 128, "two leaves per lane");
+    double lg[2] = {-INFINITY, -INFINITY}; int lf[2] = {-1, -1}, ln[2] = {0, 0};
+    if (lane == 0) { lg[0] = s_gain[0]; lf[0] = s_feat[0]; }
     int L = 1;
     const int max_leaves = c.num_leaves < LV_MAX_LEAVES ? c.num_leaves : LV_MAX_LEAVES;
     while (L < max_leaves) {
-        double bg = -INFINITY; int bf = -1, bl = 0x7FFFFFFF;
-        for (int l = lane; l < L; l += 64) {
-            const int sn = leaf_node[l];
-            const double g = s_gain[sn]; const int f = s_feat[sn];
-            if (bl == 0x7FFFFFFF || leaf_better(g, f, l, bg, bf, bl)) { bg = g; bf = f; bl = l; }
-        }
+        // the better of the lane's two leaves (a slot without a leaf holds -inf and never wins: the winner's gain is positive)
+        const bool up = leaf_better(lg[1], lf[1], lane + 64, lg[0], lf[0], lane);
+        const double g = up ? lg[1] : lg[0]; const int f = up ? lf[1] : lf[0], l = up ? lane + 64 : lane, n = up ? ln[1] : ln[0];
+        double m = g;
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const double g2 = __shfl_xor(bg, o); const int f2 = __shfl_xor(bf, o), l2 = __shfl_xor(bl, o);
-            if (l2 != 0x7FFFFFFF && (bl == 0x7FFFFFFF || leaf_better(g2, f2, l2, bg, bf, bl))) { bg = g2; bf = f2; bl = l2; }
+        for (int o = 32; o >= 1; o >>= 1) { const double m2 = __shfl_xor(m, o); m = m2 > m ? m2 : m; }
+        if (!(m > 0.0)) break;
+        unsigned long long tie = __ballot(g == m);
+        int wl = __ffsll((long long)tie) - 1;
+        if (tie & (tie - 1ull)) {      // several leaves with the best gain
+            const int fk = (g == m) ? (f < 0 ? 0x7FFFFFFF : f) : 0x7FFFFFFF;
+            int fmin = fk;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) { const int f2 = __shfl_xor(fmin, o); fmin = f2 < fmin ? f2 : fmin; }
+            int lmin = (g == m && fk == fmin) ? l : 0x7FFFFFFF;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) { const int l2 = __shfl_xor(lmin, o); lmin = l2 < lmin ? l2 : lmin; }
+            wl = lmin & 63;
         }
-        if (!(bg > 0.0)) break;
-        const int sn = leaf_node[bl];
+        const int wpk = __shfl(n | (l >> 6) << 8, wl);
+        const int sn = wpk & 0xFF, bl = wl + 64 * (wpk >> 8), bf = s_feat[sn];
         const int sl = s_left[sn], sr = s_right[sn];
         if (sl < 0) { if (lane == 0) { pp->error = 1; atomicOr(err_flag, 1); } break; }   // the expansion bound was violated (must never happen)
         const int node = L - 1, right_leaf = L;
-        __syncthreads();   // every lane has read leaf_node[] before lane 0 rewrites it
         if (lane == 0) {
             out.feat[nb + node] = bf; out.theta[nb + node] = s_theta[sn]; out.dleft[nb + node] = (int)s_dleft[sn]; out.gain[nb + node] = s_gain[sn];
             out.left[nb + node] = ~bl; out.right[nb + node] = ~right_leaf;
             const int pn = leaf_parent[bl];
             if (pn >= 0) { if (leaf_isleft[bl]) out.left[nb + pn] = node; else out.right[nb + pn] = node; }
             s_lv[bl] = s_lout[sn]; s_lv[right_leaf] = s_rout[sn];
-            leaf_node[bl] = sl; leaf_node[right_leaf] = sr;
             leaf_parent[bl] = node; leaf_isleft[bl] = 1; leaf_parent[right_leaf] = node; leaf_isleft[right_leaf] = 0;
             node_leaf[sl] = bl; node_leaf[sr] = right_leaf;
         }
+        const double gl_ = s_gain[sl], gr_ = s_gain[sr]; const int fl_ = s_feat[sl], fr_ = s_feat[sr];
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            if (lane + 64 * s2 == bl) { lg[s2] = gl_; lf[s2] = fl_; ln[s2] = sl; }
+            if (lane + 64 * s2 == right_leaf) { lg[s2] = gr_; lf[s2] = fr_; ln[s2] = sr; }
+        }
         ++L;
-        __syncthreads();
     }
     __syncthreads();
     if (lane == 0) out.L[tbase] = L;
-    for (int l = lane; l < L; l += 64) leaf_node_out[(long long)k * LV_MAX_LEAVES + l] = leaf_node[l];   // leaf counts follow after the final pass
+    // leaf counts follow after the final pass
+    if (lane < L) leaf_node_out[(long long)k * LV_MAX_LEAVES + lane] = ln[0];
+    if (lane + 64 < L) leaf_node_out[(long long)k * LV_MAX_LEAVES + lane + 64] = ln[1];
     double* nd = node_delta + (long long)k * 256;
     if (L <= 1) {
         if (lane == 0) lv[0] = (it == 0) ? init[k] : 0.0;
@@ -1605,8 +1673,5 @@ __global__ __launch_bounds__(LV_MAX_LEAVES) void k_level_leafcount(const LvPlan*
     const int n = leaf_node[(long long)k * LV_MAX_LEAVES + l];
     out.leaf_count[tbase * c.num_leaves + l] = (n == 0) ? (int)plan[k].n_in : count[(long long)k * 256 + n];
 }
-
-// the iteration counter lives on the device so that one boosting iteration is the same launch sequence every time (hipGraph)
-__global__ void k_next_iteration(int32_t* it) { if (threadIdx.x == 0 && blockIdx.x == 0) it[0] += 1; }
 
 }  // namespace rg

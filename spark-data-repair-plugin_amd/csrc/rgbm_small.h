@@ -25,6 +25,8 @@
 // State of a class tree: leaves, per-feature candidates and the control block in LDS; row-index lists (ping-pong, as k_partition) and
 // the per-leaf histogram pool in global memory (L2-resident at this size).
 #pragma once
+#include <algorithm>
+#include <vector>
 #include "rgbm_kernels.h"
 
 namespace rg {
@@ -45,6 +47,21 @@ constexpr int SM_MAX_FEATS = 255;
 // evaluated by the same expressions, in the same order, as scan_child; a feature's winner is picked by the same total order
 // (scan_better), so the Cand of every (child, feature) is the one scan_child writes -- bit for bit.
 struct ScanLane { int32_t feat /* -1: idle lane */, bin0 /* first of the lane's 4 bins inside the feature */, seg_first /* 1: first lane of its feature */, seg_last /* last lane of its feature */; };
+
+// lane map of the packed scan over the features fm[0 .. F): a lane owns 4 value bins of one feature, a feature does not straddle waves (one with
+// more than 61 value bins left of a wave moves to the next one; V <= 255 is at most 64 lanes).  Returns the waves a child needs; sm holds waves * 64 lanes.
+inline int scan_lane_map(const FeatMeta* fm, int F, std::vector<ScanLane>& sm) {
+    sm.clear();
+    int lanes_used = 0;
+    for (int f = 0; f < F; ++f) {
+        const int nl_f = std::max(1, (fm[f].V + 3) / 4);
+        if (lanes_used % 64 + nl_f > 64) while (lanes_used % 64) { sm.push_back(ScanLane{-1, 0, 1, 0}); ++lanes_used; }
+        const int first = lanes_used % 64;
+        for (int q = 0; q < nl_f; ++q) { sm.push_back(ScanLane{f, 4 * q, q == 0 ? 1 : 0, first + nl_f - 1}); ++lanes_used; }
+    }
+    while (lanes_used % 64) { sm.push_back(ScanLane{-1, 0, 1, 0}); ++lanes_used; }
+    return lanes_used / 64;
+}
 
 __device__ __forceinline__ long long seg_incl_scan(long long v, bool first) {
     const int lane = lane_id();
