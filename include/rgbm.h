@@ -225,6 +225,15 @@ typedef struct {
     double* valid_value_out;
 } rgbm_fit_spec;
 int rgbm_table_train_batch(const rgbm_fit_spec* fits, int32_t n_fits, rgbm_model** out_models /* [n_fits] */, int32_t* out_status /* [n_fits] */);
+/* What the calling thread's last rgbm_table_train_batch call did with each of its n fits (n must be that call's n_fits):
+ * out[4 * i ..] = {route, scan_waves, nchunk, lds_bytes} of fit i.  route 0 = the fit failed before a route was chosen, 1 = the fused
+ * kernels, 2 = the single-fit trainer because the fit is not eligible (rows above RGBM_SMALL_ROWS, more than 256 leaves, more than 255
+ * features, a row-sharded call or row multiplicities), 3 = the single-fit trainer because the batch held one eligible fit, 4 = the
+ * single-fit trainer because the fit's working set exceeds the LDS.  Of a route-1 fit: scan_waves = the waves per child of the packed
+ * threshold scan (0: one wave per feature), nchunk = its 16-feature chunks, lds_bytes = the dynamic LDS its class trees use (the launch
+ * is sized for the largest fit of the batch); 0 otherwise (route 4: lds_bytes = what was too much).  A function of the fits and of the
+ * environment switches RGBM_SMALL_ROWS / RGBM_SMALL_PACKED=0 / RGBM_SMALL_ALWAYS=1; tests assert it before they compare models. */
+int rgbm_table_train_batch_report(int32_t* out /* [n][4] */, int32_t n);
 /* Chained repair of rows [row_begin, row_begin+n_rows) of the resident table, in place in HBM.
  * out_label/out_prob [T][n_rows] are copied back to the host (either may be NULL). */
 int rgbm_table_repair_chain(rgbm_table* t, const rgbm_model* const* models, int32_t T,

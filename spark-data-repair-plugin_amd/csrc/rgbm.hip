@@ -1418,15 +1418,24 @@ struct HarvestArena {
 };
 HarvestArena& harvest_arena() { static HarvestArena* a = new HarvestArena(); return *a; }
 
+// What the last rgbm_table_train_batch call of this thread did with each fit (rgbm_table_train_batch_report): {route, scan_waves, nchunk,
+// lds_bytes}; the last three describe the fused kernels' launch of a route-1 fit (route 4: the LDS bytes that were too many) and are 0 otherwise.
+enum { ROUTE_NONE = 0, ROUTE_FUSED = 1, ROUTE_SINGLE_INELIGIBLE = 2, ROUTE_SINGLE_ALONE = 3, ROUTE_SINGLE_LDS = 4 };
+struct BatchReportRow { int32_t route, scan_waves, nchunk, lds_bytes; };
+std::vector<BatchReportRow>& batch_report() { static thread_local std::vector<BatchReportRow> r; return r; }
+
 void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** out, int32_t* status) {
     using namespace rg;
+    std::vector<BatchReportRow>& report = batch_report();
+    report.assign((size_t)n_fits, BatchReportRow{ROUTE_NONE, 0, 0, 0});
     long long small_rows = 65536;
     if (const char* e = getenv("RGBM_SMALL_ROWS")) small_rows = atoll(e);
     const int device = specs[0].table->device;
     std::vector<int> batch;                                           // fits that go through the fused kernels
     auto record_error = [&](int i, const std::exception& e) { status[i] = rgh::status_of(e); rgh::last_error() = e.what(); };
-    auto run_single = [&](int i) {
+    auto run_single = [&](int i, int route) {
         const rgbm_fit_spec& sp = specs[i];
+        report[i].route = route;
         try {
             out[i] = train_core(*sp.table, sp.target_col, sp.feat_cols, sp.n_features, sp.y_value, sp.class_weight, nullptr, nullptr, *sp.params, nullptr); status[i] = RGBM_OK;
             score_valid_with_model(sp, out[i]);
@@ -1438,10 +1447,10 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
         const rgbm_fit_spec& sp = specs[i];
         if (!sp.table || !sp.feat_cols || !sp.params) { status[i] = RGBM_ERR_ARG; rgh::last_error() = "rgbm_table_train_batch: bad fit spec"; continue; }
         if (sp.table->device != device) throw std::invalid_argument("rgbm_table_train_batch: all tables of a batch must live on one device");
-        if (small_fit_eligible(*sp.table, sp.n_features, *sp.params, small_rows)) batch.push_back(i); else run_single(i);
+        if (small_fit_eligible(*sp.table, sp.n_features, *sp.params, small_rows)) batch.push_back(i); else run_single(i, ROUTE_SINGLE_INELIGIBLE);
     }
     if (batch.empty()) return;
-    if (batch.size() == 1 && !getenv("RGBM_SMALL_ALWAYS")) { run_single(batch[0]); return; }    // one fit: the level grower's kernel chain is faster than one workgroup per class tree
+    if (batch.size() == 1 && !getenv("RGBM_SMALL_ALWAYS")) { run_single(batch[0], ROUTE_SINGLE_ALONE); return; }    // one fit: the level grower's kernel chain is faster than one workgroup per class tree
 
     StreamGuard sg_; hipStream_t s = sg_.s;
     const bool timing = getenv("RGBM_TIMING") != nullptr;
@@ -1481,7 +1490,7 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
             if (!off_switch && 2 * Wn <= SM_WAVES && h.tc.totbins <= 2048 && sm_lds_bytes(h.lds_hist, NL, F, h.tc.totbins) <= 150 * 1024) { d.scan_waves = Wn; d.h_scan = std::move(sm); }
         }
         const size_t lds = sm_lds_bytes(h.lds_hist, NL, F, d.scan_waves > 0 ? h.tc.totbins : 0);
-        if (lds > 160 * 1024 - 2048) { dev[i].reset(); run_single(i); continue; }          // (histogram working set of one chunk + leaves exceed the LDS)
+        if (lds > 160 * 1024 - 2048) { dev[i].reset(); run_single(i, ROUTE_SINGLE_LDS); report[i].lds_bytes = (int32_t)lds; continue; }          // (histogram working set of one chunk + leaves exceed the LDS)
         const int nchunk = h.nchunk; const long long n_train = h.n_train;
         d.bins.fill(h, N, s);
         d.bins.pack(tab, s);
@@ -1528,6 +1537,7 @@ void train_batch_small(const rgbm_fit_spec* specs, int32_t n_fits, rgbm_model** 
         }
         NE_max = std::max(NE_max, NE); lds_max = std::max(lds_max, lds); N_max = std::max(N_max, N); ntrain_max = std::max(ntrain_max, n_train);
         ok.push_back(i);
+        report[i] = BatchReportRow{ROUTE_FUSED, d.scan_waves, nchunk, (int32_t)lds};
         }
         catch (const std::exception& e) { (void)hipStreamSynchronize(s); record_error(i, e); dev[i].reset(); continue; }
     }
@@ -2084,6 +2094,14 @@ RGBM_EXPORT int rgbm_table_train_batch(const rgbm_fit_spec* fits, int32_t n_fits
         catch (...) { for (int32_t i = 0; i < n_fits; ++i) { delete out_models[i]; out_models[i] = nullptr; } throw; }
         return RGBM_OK;
     });
+}
+
+RGBM_EXPORT int rgbm_table_train_batch_report(int32_t* out, int32_t n) {
+    if (!out || n < 0) return fail(RGBM_ERR_ARG, "rgbm_table_train_batch_report: bad argument");
+    const std::vector<BatchReportRow>& r = batch_report();
+    if ((size_t)n != r.size()) return fail(RGBM_ERR_ARG, "rgbm_table_train_batch_report: n is not the number of fits of this thread's last rgbm_table_train_batch call");
+    for (int32_t i = 0; i < n; ++i) { out[4 * i] = r[i].route; out[4 * i + 1] = r[i].scan_waves; out[4 * i + 2] = r[i].nchunk; out[4 * i + 3] = r[i].lds_bytes; }
+    return RGBM_OK;
 }
 
 RGBM_EXPORT int rgbm_train(const int32_t* X, int64_t n, int32_t f, const int32_t* n_codes, const int32_t* y_code, int32_t n_y_codes,

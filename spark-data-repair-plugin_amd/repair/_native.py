@@ -81,8 +81,8 @@ def lib():
         l = C.CDLL(path)
         l.rgbm_last_error.restype = C.c_char_p
         for name in ("rgbm_device_count", "rgbm_version", "rgbm_release_cache", "rgbm_train", "rgbm_predict", "rgbm_repair_chain",
-                     "rgbm_table_create", "rgbm_table_train", "rgbm_table_train_batch", "rgbm_table_repair_chain", "rgbm_table_read_column",
-                     "rgbm_model_save", "rgbm_model_load", "rgbm_model_info", "rgbm_model_importance", "rgbm_model_predict_form",
+                     "rgbm_table_create", "rgbm_table_train", "rgbm_table_train_batch", "rgbm_table_train_batch_report", "rgbm_table_repair_chain",
+                     "rgbm_table_read_column", "rgbm_model_save", "rgbm_model_load", "rgbm_model_info", "rgbm_model_importance", "rgbm_model_predict_form",
                      "rgbm_comm_unique_id", "rgbm_comm_init", "rgbm_comm_finalize", "rgbm_comm_info", "rgbm_comm_count",
                      "rgbm_local_group_create", "rgbm_comm_init_local",
                      "rgbm_table_detect_nulls", "rgbm_table_detect_constraint", "rgbm_table_rows_of_cells", "rgbm_table_cells_fetch",
@@ -120,7 +120,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
-    "rgbm_table_column_stats", "rgbm_level_pass_plan",
+    "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -472,6 +472,18 @@ def train_batch(fits):
             why = last_msg if (failing and i == failing[-1]) else ("status %d" % int(status[i]) if status[i] != 0 else "no model returned")
             out.append(RepairGbmError("fit %d of the batch failed (%d): %s" % (i, int(status[i]), why)))
     return out
+
+
+BATCH_ROUTES = ("none", "fused", "single: not eligible", "single: one eligible fit", "single: LDS")
+
+
+def train_batch_report(n):
+    """What this thread's last ``train_batch`` call of ``n`` fits did with each fit (rgbm_table_train_batch_report): a list of
+    dict(route, scan_waves, nchunk, lds_bytes) -- route 0 failed before a route was chosen, 1 fused kernels, 2 single-fit trainer (not
+    eligible), 3 single-fit trainer (one eligible fit in the batch), 4 single-fit trainer (LDS); scan_waves 0 = one wave per feature."""
+    a = np.zeros((max(int(n), 1), 4), np.int32)
+    _check(lib().rgbm_table_train_batch_report(_p(a, C.c_int32), C.c_int32(n)), "rgbm_table_train_batch_report")
+    return [dict(route=int(r[0]), scan_waves=int(r[1]), nchunk=int(r[2]), lds_bytes=int(r[3])) for r in a[:int(n)]]
 
 
 def _chain_args(models, feat_cols, class_codes):

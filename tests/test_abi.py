@@ -70,6 +70,23 @@ def test_model_blob_roundtrip_and_validation():
         _native.Model.load(bytes(bad))
 
 
+def test_batch_report_refuses_a_count_that_is_not_the_last_batch():
+    """rgbm_table_train_batch_report needs no device; a thread that has made no batch call holds a report of zero fits."""
+    import threading
+    from repair import _native
+    seen = []
+
+    def fresh_thread():
+        seen.append(_native.train_batch_report(0))
+        try:
+            _native.train_batch_report(3)
+        except _native.RepairGbmError as e:
+            seen.append(str(e))
+    th = threading.Thread(target=fresh_thread)
+    th.start(); th.join()
+    assert seen[0] == [] and len(seen) == 2 and "last rgbm_table_train_batch call" in seen[1], seen
+
+
 def test_params_struct_layout_matches_oracle():
     from oracle import oracle as O
     from repair import _native
