@@ -318,6 +318,26 @@ int rgbm_table_read_cells(const rgbm_table* t, const int64_t* rows, const int32_
 int rgbm_table_write_cells(rgbm_table* t, const int64_t* rows, const int32_t* cols, const int32_t* codes, int64_t n_cells);
 /* New resident table made of the given rows (the dirty-row frame the chained repair runs on). */
 int rgbm_table_gather_rows(const rgbm_table* t, const int64_t* rows, int64_t n_rows, rgbm_table** out);
+/* New resident table: the rows of the parts one after the other; kinds and values inherited, like rgbm_table_gather_rows.
+ * RGBM_ERR_PARAM: parts that differ in their columns, dictionaries (code counts, kinds, values) or device. */
+int rgbm_table_concat(const rgbm_table* const* parts, int32_t n_parts, rgbm_table** out);
+/* SMOTEN in code space (the over-sampling of the reference's training-data rebalancing, train.py:242-293; the statement is
+ * repair/rebalance_codes.py `smoten_codes`): every column is nominal, the Value Difference Metric is fitted on the n_fit rows `fit_rows`
+ *   P_f[v][c] = rows with code v in feature f and class c / rows with code v
+ *   dist(a, b) = sum over the features, in `feat_cols` order, of (sum over the classes, ascending, of |P_f[a_f][c] - P_f[b_f][c]|) squared
+ * in double, without contraction: the distances are the statement's, bit for bit.  For every listed class (ascending codes of the target)
+ * the k nearest neighbours of each of its m fit rows among the other m - 1, ordered by (distance, position): positions count the class's
+ * rows in `fit_rows` order, rows at distance 0 are neighbours, the row itself is not.  nn_out [sum m][k], class by class, may be NULL.
+ * picks [pick_off[n_classes]]: for class i the rows pick_off[i] .. pick_off[i + 1] - 1 of `out` are grown from the class's rows picks[..]
+ * (the caller's random draws): the target holds the class, every feature the most common code among the k neighbours of the drawn row (ties:
+ * the smallest code), every other column NULL (-1).  `out` inherits kinds and values like rgbm_table_gather_rows.
+ * RGBM_ERR_PARAM: k outside 1 .. 16; more than 64 features, one listed twice or equal to the target; a class with m <= k; a pick outside
+ * its class; a fit row outside the table or with a NULL in the target or a feature; no row to make; P tables above 2^28 entries. */
+int rgbm_table_smoten(const rgbm_table* t, int32_t target_col, const int32_t* feat_cols, int32_t f,
+                      const int64_t* fit_rows, int64_t n_fit, int32_t k,
+                      const int32_t* classes, int32_t n_classes,          /* ascending */
+                      const int64_t* pick_off /* [n_classes + 1] */, const int64_t* picks,
+                      int64_t* nn_out /* [sum m][k], class by class, or NULL */, rgbm_table** out /* pick_off[n_classes] rows */);
 /* Rows per code of one column (+ NULL count): class weights (train.py:39-40,105), domain statistics. */
 int rgbm_table_count_codes(const rgbm_table* t, int32_t col, int64_t* counts_out /* [n_codes[col]] */,
                            int64_t* n_null_out /* may be NULL */);

@@ -91,7 +91,8 @@ def lib():
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
                      "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
                      "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
-                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats"):
+                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats",
+                     "rgbm_table_smoten", "rgbm_table_concat"):
             getattr(l, name).restype = C.c_int
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan"):
             if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry)
@@ -120,7 +121,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
-    "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report",
+    "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -782,6 +783,39 @@ class Table:
         h = C.c_void_p()
         _check(lib().rgbm_table_gather_rows(self.h, _p(r, C.c_int64), C.c_int64(len(r)), C.byref(h)), "rgbm_table_gather_rows")
         return Table._adopt(h, self.device_id)
+
+    @staticmethod
+    def concat(parts):
+        """The rows of the tables `parts` one after the other (same columns, dictionaries and device): kinds and values inherited."""
+        parts = list(parts)
+        hs = (C.c_void_p * len(parts))(*[p.h for p in parts])
+        h = C.c_void_p()
+        _check(lib().rgbm_table_concat(hs, C.c_int32(len(parts)), C.byref(h)), "rgbm_table_concat")
+        return Table._adopt(h, parts[0].device_id)
+
+    def smoten(self, target_col, feat_cols, fit_rows, classes, pick_off, picks, k=5, want_nn=False):
+        """SMOTEN in code space (include/rgbm.h rgbm_table_smoten; the statement is `repair.rebalance_codes.smoten_codes`): the metric is
+        fitted on `fit_rows`; for class classes[i] (ascending) the rows pick_off[i] .. pick_off[i + 1] - 1 of the new table are grown from
+        the class's rows `picks` (positions within the class's fit rows).  Returns the table of the synthetic rows, with `want_nn`
+        (table, [nn [m][k] per class]): the neighbour lists as positions within the class's rows."""
+        fc, fr = _i32(feat_cols), np.ascontiguousarray(fit_rows, np.int64)
+        cl, po, pk = _i32(classes), np.ascontiguousarray(pick_off, np.int64), np.ascontiguousarray(picks, np.int64)
+        if len(po) != len(cl) + 1 or (len(po) and len(pk) != int(po[-1])):
+            raise ValueError("pick_off holds one entry more than classes and ends at len(picks)")
+        nn = None
+        if want_nn:
+            y = self.read_cells(fr, np.full(len(fr), target_col, np.int32)) if len(fr) else np.zeros(0, np.int32)
+            m = [int((y == c).sum()) for c in cl]
+            nn = np.full((max(sum(m), 1), int(k)), -1, np.int64)
+        h = C.c_void_p()
+        _check(lib().rgbm_table_smoten(self.h, C.c_int32(target_col), _p(fc, C.c_int32), C.c_int32(len(fc)), _p(fr, C.c_int64), C.c_int64(len(fr)),
+                                       C.c_int32(k), _p(cl, C.c_int32), C.c_int32(len(cl)), _p(po, C.c_int64), _p(pk if len(pk) else np.zeros(1, np.int64), C.c_int64),
+                                       _p(nn, C.c_int64), C.byref(h)), "rgbm_table_smoten")
+        tab = Table._adopt(h, self.device_id)
+        if not want_nn:
+            return tab
+        off = np.concatenate([[0], np.cumsum(m)])
+        return tab, [nn[off[i]:off[i + 1]] for i in range(len(cl))]
 
     def repair_pmf(self, model, target_col, feat_cols, top_k=32, threshold=0.0, cur_codes=None, want_cur_prob=False):
         """Candidate distributions of the NULL cells of ``target_col`` (model.py:1196-1212).  Returns

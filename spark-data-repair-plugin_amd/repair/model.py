@@ -101,6 +101,8 @@ class RepairModel():
     # new in this engine: the rule-based repairs (`setRepairByRules`: FD rule models, constant models, nearest-value merges) on the
     # HBM-resident pipeline
     _opt_rule_resident = _option("model.rule.resident", False, bool, None, None)
+    # `setTrainingDataRebalancingEnabled(True)` on the HBM-resident path: SMOTEN in code space on the device (repair.rebalance_codes)
+    _opt_rebalance_resident = _option("model.rebalance.resident", False, bool, None, None)
     # new in this engine: the value detectors (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector) as code predicates on
     # the HBM-resident table (repair.detect_codes, `Table.detect_cells`)
     _opt_value_detectors_resident = _option("error.value_detectors.resident", False, bool, None, None)
@@ -124,7 +126,7 @@ class RepairModel():
     option_keys = set([o.key for o in (
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
-        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident,
+        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident, _opt_rebalance_resident,
         _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
@@ -616,7 +618,8 @@ class RepairModel():
         `prob_modes`: the caller shapes the probability modes itself (`_resident_result`), so they and a cost function qualify.
 
         It can when everything between error detection and the result frame is the per-attribute model loop itself:
-        no rule-based repairs, no functional-dependency rule models, no rebalancing, no cost function, plain repair output
+        no rule-based repairs, no functional-dependency rule models, no rebalancing (unless `model.rebalance.resident` is set: the plan
+        then carries `rebalance`), no cost function, plain repair output
         (cells or repaired data), no feature selection, and every discrete target has at least two classes.  The
         hyper-parameter search (`model.hp.max_evals` > 1) runs on the resident tables too (pipeline.search_on_table).
         Otherwise the value-space path (pandas + one estimator per attribute) below handles the run.
@@ -632,8 +635,15 @@ class RepairModel():
                 return None
         elif not prob_modes and (compute_repair_candidate_prob or maximal_likelihood_repair or self.cf is not None):
             return None
+        rebalance = None
         if self.training_data_rebalancing_enabled:
-            return None
+            if not bool(self._get_option_value(*self._opt_rebalance_resident)):
+                return None
+            from repair import dist
+            if dist.world()[1] > 1:
+                _logger.info("rebalancing stays on the value-space path: a multi-rank job does not rebalance its row shards")
+                return None
+            rebalance = dict(k=5, random_state=42)
         from repair.train import (_opt_learning_rate, _opt_max_bin, _opt_max_depth, _opt_max_evals, _opt_min_split_gain,
                                   _opt_n_estimators, _opt_reg_alpha, _opt_boosting_type, _opt_class_weight)
         g = lambda o: get_option_value(self.opts, *o)  # noqa: E731
@@ -660,7 +670,7 @@ class RepairModel():
         distinct = None
         if bool(self._get_option_value(*self._opt_train_distinct_rows)):
             distinct = dict(max_ratio=float(self._get_option_value(*self._opt_train_distinct_rows_max_ratio)))
-        return dict(engine=engine, params=params, search=int(g(_opt_max_evals)) > 1, rules=rules, distinct=distinct)
+        return dict(engine=engine, params=params, search=int(g(_opt_max_evals)) > 1, rules=rules, distinct=distinct, rebalance=rebalance)
 
     def _resident_rules(self, input_df: DataFrame, target_columns: List[str], continous_columns: List[str], domain_stats: Dict[str, int],
                         prob_modes: bool) -> Optional[Dict[str, Any]]:
@@ -968,7 +978,7 @@ class RepairModel():
                                    continuous_columns=[c for c in continous_columns if c in target_columns],
                                    train_rows=self._training_row_sampler(), want_details=True,
                                    search_opts=dict(self.opts) if plan.get("search") else None, rules=rules,
-                                   distinct_training_rows=None if prob else plan.get("distinct"), **cells)
+                                   distinct_training_rows=None if prob else plan.get("distinct"), rebalance=plan.get("rebalance"), **cells)
         info["times"]["pipeline_wall"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         self._last_resident_info = info

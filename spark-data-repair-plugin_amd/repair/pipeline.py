@@ -204,11 +204,11 @@ def distinct_rows(codes, n_codes, max_mult=255):
     return np.ascontiguousarray(codes[:, rows]), mult.astype(np.uint8), start[inverse].astype(np.int64)
 
 
-def distinct_training_tables(engine, table, targets, base_params, spec, train_tables, search_opts=None, continuous=()):
+def distinct_training_tables(engine, table, targets, base_params, spec, train_tables, search_opts=None, continuous=(), rebalanced=()):
     """The opt-in hook `repair_table(distinct_training_rows=dict(max_ratio=..))`: enters ONE distinct-row table of `table`
     (`Table.distinct_rows()`: rgbm_table_distinct_rows, multiplicities attached) into `train_tables` for every target in `targets` that
     qualifies.  A target keeps the whole table, with the reason logged and returned, when
-      - `train_rows` picked a sample for it (`train_tables` holds it already);
+      - `train_rows` picked a sample for it (`train_tables` holds it already), or it trains on a rebalanced table (`rebalanced`);
       - a hyper-parameter search runs (`search_opts`): it gathers folds, and gathers drop multiplicities;
       - the parameters are not what the multiplicity trainer honours (include/rgbm.h rgbm_table_set_row_multiplicity: the level grower,
         1 <= max_depth <= 7, no bagging, at most 32 features with a free byte in the last 16-feature record), or the target is
@@ -247,6 +247,8 @@ def distinct_training_tables(engine, table, targets, base_params, spec, train_ta
     for t in targets:
         if for_all is not None:
             info["skipped"][t] = for_all
+        elif t in rebalanced:
+            info["skipped"][t] = "trained on a rebalanced table (rebalance)"
         elif t in train_tables:
             info["skipped"][t] = "trained on a row sample (train_rows)"
         elif t in continuous:
@@ -275,6 +277,36 @@ def distinct_training_tables(engine, table, targets, base_params, spec, train_ta
     if info["used_for"]:
         _logger.info("[Repair Model Training Phase] target columns %s train on the %d distinct rows of %d" % (info["used_for"], info["distinct"], N))
     return dtab, info
+
+
+def rebalanced_training_table(table, t, rows=None, k=5, random_state=42, name=None, class_names=None):
+    """The training table of discrete target column t after `rebalance_training_data` (train.py:242-293), built on the device: the NULL
+    pattern of the needed columns is read, `repair.rebalance_codes.rebalance_plan` makes every draw on the host, `Table.smoten` grows the
+    synthetic rows, and `gather_rows` + `concat` + one final `gather_rows` put the frame [rows without NULLs, synthetic rows class by class,
+    rows with NULLs] into the plan's order.  `rows`: the training rows in the value-space frame's order (the sampler's; default: the rows whose
+    target is not NULL, ascending).  Returns (table, plan)."""
+    from repair.rebalance_codes import rebalance_plan
+    rows = np.flatnonzero(table.read_column(t) >= 0) if rows is None else np.asarray(rows, np.int64)
+    sub = table.gather_rows(rows)                      # the training rows in frame order: everything below counts positions in it
+    feats = [c for c in range(int(table.c)) if c != t]
+    has_null = np.zeros(len(rows), bool)
+    for f in feats:
+        has_null |= sub.read_column(f) < 0
+    plan = rebalance_plan(sub.read_column(t), has_null, target=str(t) if name is None else name, class_names=class_names, k=k,
+                          random_state=random_state)
+    parts = []
+    if len(plan["fit"]):
+        parts.append(sub.gather_rows(plan["fit"]))
+    if len(plan["classes"]):
+        parts.append(sub.smoten(t, feats, plan["fit"], plan["classes"], plan["pick_off"], plan["picks"], k=k))
+    if len(plan["with_null"]):
+        parts.append(sub.gather_rows(plan["with_null"]))
+    frame = type(table).concat(parts)
+    out = frame.gather_rows(plan["order"])
+    for p in parts + [frame, sub]:
+        if hasattr(p, "close"):
+            p.close()
+    return out, plan
 
 
 class NotResidentEligible(ValueError):
@@ -480,7 +512,7 @@ def cell_pmfs(engine, table, pmf_tab, targets, models, rows, cols, current, dirt
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
@@ -521,8 +553,13 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
                  included.  Every target that does not qualify, or whose fit the trainer refuses on the distinct table, trains on the whole
                  table; the result's `distinct_rows` says which and why.  With `want_stats` the stats of a target trained on the distinct
                  table describe that fit (its M rows), not a fit on the N rows.
+    rebalance  : None (off) or dict(k=5, random_state=42[, names, class_names: callables for the log]) -- `setTrainingDataRebalancingEnabled`:
+                 every discrete target that is trained trains on its rebalanced table (`rebalanced_training_table`: SMOTEN on the device, the
+                 draws on the host), made from its `train_rows` in the order given (the sampler's) or from all its non-NULL rows.  The class
+                 weights, the unseen-category check and the hyper-parameter search see that table.  `rebalanced` of the result holds per
+                 target dict(median, rows, synthetic, classes).
     Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
-    dirty_rows, models, times, stats[, domain][, rule_steps, merged][, value_detectors][, distinct_rows]): one entry per error cell,
+    dirty_rows, models, times, stats[, domain][, rule_steps, merged][, value_detectors][, distinct_rows][, rebalanced]): one entry per error cell,
     ordered by (column, row).
     """
     continuous = dict(continuous or {})
@@ -616,8 +653,26 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
             if r is not None:
                 picked[t] = r
         train_rows = picked
+    rebalanced = {}
+    if rebalance is not None:
+        if not hasattr(table, "smoten"):
+            raise NotResidentEligible("rebalancing: the engine's table has no smoten")
+        from repair import dist
+        if dist.world()[1] > 1:
+            raise NotResidentEligible("rebalancing: a multi-rank job does not rebalance its row shards")
+        spec = dict(rebalance)
+        names, class_names = spec.pop("names", None), spec.pop("class_names", None)
+        for t in [t for t in targets if t not in rule_steps and t not in continuous]:
+            train_tables[t], plan = rebalanced_training_table(table, t, rows=(train_rows or {}).get(t), name=names(t) if names else None,
+                                                              class_names=class_names(t) if class_names else None, **spec)
+            label_counts[t] = train_tables[t].count_codes(t)[0]
+            rebalanced[t] = dict(median=plan["median"], rows=int(train_tables[t].n), synthetic=int(len(plan["picks"])),
+                                 classes=[int(c) for c in plan["classes"]])
+        out["rebalanced"] = rebalanced
     if train_rows:
         for t, r in train_rows.items():
+            if t in rebalanced:
+                continue
             train_tables[t] = table.gather_rows(np.sort(np.asarray(r, np.int64)))
             label_counts[t] = train_tables[t].count_codes(t)[0]
     if check_unseen:
@@ -630,7 +685,8 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         # after the error cells are NULLed, the merges written back, the label counts taken from the whole table and the unseen-category
         # check made on it: the distinct table holds rows whose target cell is NULL too (the trainer skips them, as on the whole table)
         distinct_tab, out["distinct_rows"] = distinct_training_tables(engine, table, [t for t in targets if t not in rule_steps], base_params,
-                                                                      distinct_training_rows, train_tables, search_opts, continuous)
+                                                                      distinct_training_rows, train_tables, search_opts, continuous,
+                                                                      rebalanced=rebalanced)
     search = None
     if search_opts is not None:
         def search(t, tab):
@@ -706,7 +762,7 @@ def encode_frame(df, columns):
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
@@ -742,7 +798,10 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     and `rule_steps` (`rule_step_summary` with attribute names).
 
     distinct_training_rows: None or dict(max_ratio=float), as `repair_table` takes it; the details then hold `distinct_rows` with attribute
-    names: dict(rows, distinct, used_for=[attributes], skipped={attribute: reason})."""
+    names: dict(rows, distinct, used_for=[attributes], skipped={attribute: reason}).
+
+    rebalance: None or dict(k=5, random_state=42), as `repair_table` takes it.  A column whose dictionary is not in the order of its sorted
+    values (mixed types) raises NotResidentEligible; the details hold `rebalanced` {attribute: dict(median, rows, synthetic, classes)}."""
     import pandas as pd
     cols = [c for c in df.columns if c != row_id]
     targets = list(targets) if targets is not None else list(cols)
@@ -750,6 +809,10 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     if unknown:
         raise ValueError("Target attributes not found in the input: %s" % ",".join(unknown))
     indices, remaps, dicts = encode_frame(df, cols)
+    if rebalance is not None:
+        from repair.rebalance_codes import check_dictionary_order
+        for j, c in enumerate(cols):
+            check_dictionary_order(dicts[j], "`%s`" % c)
     pos = {c: i for i, c in enumerate(cols)}
     dtypes = {c: df[c].dtype for c in cols}
     cells, given_current = None, None
@@ -887,6 +950,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                                    only_noisy_targets=only_noisy_targets, domain_analysis=da_spec, rules=table_rules(),
                                    value_detectors=table_detectors(detect_nulls_) if analyse else None,
                                    distinct_training_rows=distinct_training_rows,
+                                   rebalance=dict(rebalance, names=lambda t: cols[t], class_names=lambda t: dicts[t]) if rebalance is not None else None,
                                    check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
                                    train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
 
@@ -947,6 +1011,8 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         if res.get("value_detectors"):
             details["value_detectors"] = [dict(attribute=cols[d["col"]], kinds=d["kinds"], codes_flagged=d["codes_flagged"], cells=d["cells"])
                                           for d in res["value_detectors"]]
+        if res.get("rebalanced") is not None:
+            details["rebalanced"] = {cols[t]: d for t, d in res["rebalanced"].items()}
         if res.get("distinct_rows") is not None:
             d = res["distinct_rows"]
             details["distinct_rows"] = dict(rows=d["rows"], distinct=d["distinct"], used_for=[cols[t] for t in d["used_for"]],
