@@ -450,6 +450,20 @@ int rgbm_table_kmeans_assign(rgbm_table* t, const int32_t* cols, int32_t n_cols,
                              int32_t k, const double* p /* [d_tot][k] */, int64_t d_tot, const double* h /* [k] */,
                              int32_t first /* 1: there is no previous assignment */,
                              int64_t* counts_out /* [k][d_tot] */, int64_t* sizes_out /* [k] */, int64_t* n_changed_out);
+/* One pass of a level of the bisecting k-means (clustering_alg = "bisecting"; repair/qgram_bisect.py) on the same resident labels.
+ * A label names a tree node; slot_of[label] is the slot s (0 .. m - 1) of the node this level splits, for the node itself and for its two
+ * children, or -1.  p: [d_tot][2m], h: [2m], columns 2s and 2s + 1 = the left and right child of slot s.  A row of slot s is scored against
+ * these two only:  s0 = h[2s] + p[code_off[0] + code_0][2s] + ...,  s1 the same at 2s + 1 (float64, in this order, NULL adds nothing); its
+ * label becomes child[2s + 1] iff s1 < s0, else child[2s].  A row whose label lies outside [0, n_nodes) or has slot_of == -1 keeps its label
+ * and is counted nowhere.  first != 0: there are no labels yet, every row is node 0.  counts_out[2s + side][e] / sizes_out[2s + side]: the
+ * rows of that child (holding dictionary entry e); n_changed_out: the scored rows whose label differs from before the pass.
+ * RGBM_ERR_PARAM, the previous labels untouched: m outside 1 .. 512, n_nodes outside 1 .. 2048, n_cols outside 1 .. 1024, a column outside
+ * the table, d_tot * 2m outside 1 .. 2^27, code_off as above, a slot_of entry outside -1 .. m - 1, a child entry outside 0 .. n_nodes - 1,
+ * first == 0 without labels. */
+int rgbm_table_kmeans_bisect(rgbm_table* t, const int32_t* cols, int32_t n_cols, const int64_t* code_off /* [n_cols] */, int64_t d_tot,
+                             const int32_t* slot_of /* [n_nodes] */, int32_t n_nodes, int32_t m, const int32_t* child /* [2m] */,
+                             const double* p /* [d_tot][2m] */, const double* h /* [2m] */, int32_t first,
+                             int64_t* counts_out /* [2m][d_tot] */, int64_t* sizes_out /* [2m] */, int64_t* n_changed_out);
 int rgbm_table_kmeans_read(const rgbm_table* t, int32_t* assign_out /* [n] */);
 int rgbm_table_shape(const rgbm_table* t, int64_t* n_out, int32_t* c_out, int32_t* n_codes_out /* [c] or NULL */);
 

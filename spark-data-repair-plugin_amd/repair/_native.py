@@ -94,8 +94,8 @@ def lib():
                      "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats",
                      "rgbm_table_smoten", "rgbm_table_concat"):
             getattr(l, name).restype = C.c_int
-        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan"):
-            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry)
+        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect"):
+            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass)
                 getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -120,7 +120,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
     "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
-    "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
+    "rgbm_table_kmeans_assign", "rgbm_table_kmeans_bisect", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
     "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
@@ -964,6 +964,25 @@ class Table:
         _check(lib().rgbm_table_kmeans_assign(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), _p(off, C.c_int64), C.c_int32(k), _p(pp, C.c_double),
                                               C.c_int64(d_tot), _p(hh, C.c_double), C.c_int32(1 if first else 0), _p(counts, C.c_int64),
                                               _p(sizes, C.c_int64), C.byref(nch)), "rgbm_table_kmeans_assign")
+        return counts, sizes, int(nch.value)
+
+    def kmeans_bisect(self, cols, code_off, slot_of, child, p, h, first):
+        """One pass of a level of the bisecting k-means in code space (include/rgbm.h rgbm_table_kmeans_bisect; the statement is
+        repair.qgram_bisect.bisect_step).  ``slot_of`` int32 [n_nodes] (-1 = the node is not being split), ``child`` int32 [2m], ``p`` float64
+        [d_tot][2m], ``h`` float64 [2m].  Returns (counts int64 [2m][d_tot], sizes int64 [2m], n_changed); the labels (node ids) stay on the
+        device (``kmeans_read``)."""
+        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
+        off = np.ascontiguousarray(code_off, np.int64).reshape(-1)
+        so, ch = _i32(np.asarray(slot_of, np.int32).reshape(-1)), _i32(np.asarray(child, np.int32).reshape(-1))
+        pp, hh = np.ascontiguousarray(p, np.float64), np.ascontiguousarray(h, np.float64).reshape(-1)
+        if pp.ndim != 2 or pp.shape[1] != len(hh) or len(hh) != len(ch) or len(ch) % 2 or len(off) != len(cc):
+            raise ValueError("kmeans_bisect: p must be [d_tot][2m], h and child [2m], one offset per column")
+        d_tot, k = pp.shape
+        counts, sizes, nch = np.zeros((k, d_tot), np.int64), np.zeros(k, np.int64), C.c_int64(0)
+        _check(lib().rgbm_table_kmeans_bisect(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), _p(off, C.c_int64), C.c_int64(d_tot), _p(so, C.c_int32),
+                                              C.c_int32(len(so)), C.c_int32(k // 2), _p(ch, C.c_int32), _p(pp, C.c_double), _p(hh, C.c_double),
+                                              C.c_int32(1 if first else 0), _p(counts, C.c_int64), _p(sizes, C.c_int64), C.byref(nch)),
+               "rgbm_table_kmeans_bisect")
         return counts, sizes, int(nch.value)
 
     def kmeans_read(self):

@@ -102,8 +102,16 @@ class HipEngine:
         """One assignment step of the q-gram k-means on a resident table (rgbm_table_kmeans_assign) -> (counts, sizes, n_changed)."""
         return table.kmeans_assign(cols, code_off, p, h, first)
 
+    def kmeans_bisect(self, table, cols, code_off, slot_of, child, p, h, first):
+        """One pass of a level of the bisecting k-means on a resident table (rgbm_table_kmeans_bisect) -> (counts, sizes, n_changed)."""
+        return table.kmeans_bisect(cols, code_off, slot_of, child, p, h, first)
+
+    def count_codes(self, table, col):
+        """Rows per code of one column of a resident table (rgbm_table_count_codes): the root node of the bisecting k-means."""
+        return table.count_codes(col)[0]
+
     def kmeans_read(self, table):
-        """The labels of the last `kmeans_assign` on this table (rgbm_table_kmeans_read)."""
+        """The labels of the last `kmeans_assign` / `kmeans_bisect` on this table (rgbm_table_kmeans_read)."""
         return table.kmeans_read()
 
     def column_stats(self, table, cols, len_luts=None, n_bins=0):

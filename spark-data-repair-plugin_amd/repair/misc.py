@@ -93,9 +93,12 @@ class RepairMisc():
     def splitInputTable(self) -> DataFrame:
         """Splits an input table into `k` groups of similar rows: k-means over the bag-of-q-gram features of the target attributes
         (RepairMiscApi.scala:74-153) -> [row_id, "k"] in frame order.  Options: `target_attr_list` (default: every column but the row
-        id), `q` (2), `clustering_alg` ("bisect-kmeans" or "kmeans++"), `seed` (0), `max_iter` (20), `tol` (1e-4).  Both algorithm names
-        run the ONE loop of repair.qgram_kmeans (k-means++ seeding, Lloyd iterations in code space); Spark's bisecting k-means and
-        k-means|| seeding are not restated, so the labels are not Spark's -- the reference's own test pins only the set of ids."""
+        id), `q` (2), `clustering_alg` ("bisect-kmeans", "kmeans++" or "bisecting"), `seed` (0), `max_iter` (20), `tol` (1e-4).  The
+        reference's two algorithm names run the ONE Lloyd loop of repair.qgram_kmeans (k-means++ seeding, iterations in code space), as
+        before.  "bisecting" is the bisecting k-means of repair.qgram_bisect, modelled on MLlib's BisectingKMeans.run: a tree grown level by
+        level, the largest divisible leaves split first, every row scored against the two children of its own node only, so `k` may be
+        2 .. 1024 with it; it may return fewer than `k` groups (ids 0 .. k'-1) and does not read `tol`.  The seeding is not Spark's
+        (`k-means||` is not restated), so the labels are not Spark's -- the reference's own test pins only the set of ids."""
         self._check_required_options(["table_name", "row_id", "k"])
         if not self.opts["k"].isdigit():
             raise ValueError("Option 'k' must be an integer, but '%s' found" % self.opts["k"])
@@ -103,8 +106,10 @@ class RepairMisc():
         if k < 2:
             raise ValueError("Option 'k' must be 2 or more, but '%s' found" % self.opts["k"])
         alg = self.opts.get("clustering_alg", "bisect-kmeans")
-        if alg not in ("bisect-kmeans", "kmeans++"):
+        if alg not in ("bisect-kmeans", "kmeans++", "bisecting"):
             raise ValueError("Unknown clustering algorithm found: %s" % alg)
+        if alg == "bisecting" and k > 1024:
+            raise ValueError("Option 'k' must be 1024 or less with clustering_alg 'bisecting', but '%s' found" % self.opts["k"])
         try:
             q = int(self.opts.get("q", "2"))          # (the reference: `Try(optionMap("q").toInt).getOrElse(2)`)
         except ValueError:
@@ -118,7 +123,8 @@ class RepairMisc():
             attrs = [c for c in df.columns if c != rid]
         from repair import qgram_kmeans
         return qgram_kmeans.split_rows(df, rid, attrs, k, q=q, seed=int(self.opts.get("seed", "0")), max_iter=int(self.opts.get("max_iter", "20")),
-                                       tol=float(self.opts.get("tol", "1e-4")), engine=self._resident_engine())
+                                       tol=float(self.opts.get("tol", "1e-4")), engine=self._resident_engine(),
+                                       alg="bisecting" if alg == "bisecting" else "kmeans")
 
     def injectNull(self) -> DataFrame:
         """Randomly injects NULL into the given attributes: `IF(rand() > ratio, col, NULL)` per cell

@@ -13,7 +13,8 @@ counts[k][d_tot] of the codes each cluster holds:  C_k = counts[k] . E / n_k.  T
 is `assign_step` here (numpy) and `rgbm_table_kmeans_assign` on the device, and both compute the same float64 additions in the same
 order, so their labels are equal, not close.
 
-numpy / scipy only; `split_rows` is the entry, `lloyd` the loop both paths run.
+numpy / scipy only; `split_rows` is the entry, `lloyd` the loop both paths run.  `split_rows(alg="bisecting")` runs the bisecting k-means
+of repair/qgram_bisect.py on the same encoding and the same E instead.
 """
 import logging
 from typing import Any, Callable, List, Optional, Sequence, Tuple
@@ -191,13 +192,20 @@ def cluster(enc: Encoded, k: int, q: int = 2, seed: int = 0, max_iter: int = 20,
 
 
 def split_rows(df: pd.DataFrame, row_id: str, attrs: Sequence[str], k: int, q: int = 2, seed: int = 0, max_iter: int = 20, tol: float = 1e-4,
-               engine: Any = None) -> pd.DataFrame:
-    """`splitInputTableInto`: the frame [row_id, "k"], one row per input row in frame order, k = the row's cluster as int."""
+               engine: Any = None, alg: str = "kmeans") -> pd.DataFrame:
+    """`splitInputTableInto`: the frame [row_id, "k"], one row per input row in frame order, k = the row's cluster as int.  alg "kmeans": the
+    Lloyd loop of this module; "bisecting": the tree of repair/qgram_bisect.py (k up to 1024, possibly fewer groups than k, `tol` not read)."""
+    if alg not in ("kmeans", "bisecting"):
+        raise ValueError("alg must be 'kmeans' or 'bisecting', but %r found" % (alg,))
     if k < 2:
         raise ValueError("k must be 2 or more, but %d found" % k)
     if q <= 0:
         raise ValueError("`q` must be positive, but %d got" % q)
     if len(df) == 0:
         return pd.DataFrame({row_id: df[row_id].to_numpy(), "k": np.zeros(0, np.int64)})
-    labels = cluster(encode(df, list(attrs)), k, q=q, seed=seed, max_iter=max_iter, tol=tol, engine=engine)
+    if alg == "bisecting":
+        from repair import qgram_bisect
+        labels = qgram_bisect.cluster(encode(df, list(attrs)), k, q=q, seed=seed, max_iter=max_iter, engine=engine)
+    else:
+        labels = cluster(encode(df, list(attrs)), k, q=q, seed=seed, max_iter=max_iter, tol=tol, engine=engine)
     return pd.DataFrame({row_id: df[row_id].to_numpy(), "k": labels.astype(np.int64)})

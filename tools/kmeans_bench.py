@@ -10,6 +10,16 @@ table shape (synthetic 10M rows x 16 columns, 1 % NULLs), all columns, k = 2, 8,
 The device step is compared with the numpy step on the first `--check-rows` rows (a table of its own) before any time is reported.
 
     python tools/kmeans_bench.py [--rows 10000000] [--cols 16] [--reps 5] [--out profiles/kmeans_bench.json]
+
+`--bisect`: one pass of a level of the bisecting k-means instead (`Table.kmeans_bisect`, rgbm_table_kmeans_bisect) at m = 1, 4, 32, 512 slots
+(`--ms`).  The labels are grown as the loop grows them: a complete binary tree in level order, level l splitting all 2^l nodes of the level
+above with random P and h, so at m slots every row belongs to one of the m nodes being split and is scored.  The timed call repeats the
+level's pass (the rows carry their children's ids, nothing changes), best of `--reps` after a warm-up call and the median, beside the same
+stream floor.  Every pass of the tower is compared with the numpy pass (repair.qgram_bisect.bisect_step) on the first `--check-rows` rows
+before any time is reported.  `counter_sweeps`: 1 = the counters of all slots in LDS, n = the pass swept in n windows of slots, 0 = global
+counters.  For the k-means step of another build on the same machine:  RGBM_LIB_PATH=<its library> ... --ks 2,8,64 --no-host.
+
+    python tools/kmeans_bench.py --bisect [--ms 1,4,32,512] [--out profiles/kmeans_bisect_bench.json]
 """
 import argparse
 import json
@@ -55,8 +65,53 @@ def copy_ms(nbytes, reps):
     return best * 1e3
 
 
+def level(m):
+    """Level m of a complete binary tree in level order: (slot_of [4m - 1], child [2m]); nodes m-1 .. 2m-2 split into 2m-1 .. 4m-2."""
+    child = np.arange(2 * m - 1, 4 * m - 1, dtype=np.int32)
+    slot_of = np.full(4 * m - 1, -1, np.int32)
+    slot_of[m - 1:2 * m - 1] = np.arange(m)
+    slot_of[child] = np.repeat(np.arange(m), 2)
+    return slot_of, child
+
+
+def bisect(a, codes, n_codes, cols, off, d_tot, res):
+    from repair import qgram_bisect as QB
+    n = codes.shape[1]
+    ms = sorted(int(x) for x in a.ms.split(","))
+    assert all(m >= 1 and m & (m - 1) == 0 for m in ms), "--ms: powers of two (the levels of a complete tree)"
+    bound = {name: csrc_constant(name) for name in ("KB_LDS_P_DOUBLES", "KB_LDS_COUNTERS", "KB_MAX_SWEEPS")}
+    res.update(lds_bounds=bound, passes={})
+    tab = N.Table(codes, n_codes)
+    cm = min(a.check_rows, n)
+    sub = np.ascontiguousarray(codes[:, :cm])
+    small, ref = N.Table(sub, n_codes), None
+    rng = np.random.default_rng(5)
+    m = 1
+    while m <= ms[-1]:
+        slot_of, child = level(m)
+        p, h = rng.normal(size=(d_tot, 2 * m)) * 3.0, rng.random(2 * m) * 2.0
+        cnt, sz, nch = small.kmeans_bisect(cols, off, slot_of, child, p, h, m == 1)
+        ref, c_r, s_r, n_r = QB.bisect_step(sub, n_codes, off, p, h, slot_of, child, ref)
+        assert np.array_equal(small.kmeans_read(), ref) and np.array_equal(cnt, c_r) and np.array_equal(sz, s_r) and nch == n_r == cm, m
+        cnt, sz, nch = tab.kmeans_bisect(cols, off, slot_of, child, p, h, m == 1)
+        assert nch == n and int(sz.sum()) == n, m
+        if m in ms:
+            best, med, out = timed(lambda: tab.kmeans_bisect(cols, off, slot_of, child, p, h, False), a.reps)
+            assert out[2] == 0 and np.array_equal(out[1], sz) and np.array_equal(out[0], cnt)
+            cp = copy_ms(2 * m * d_tot * 8, a.reps)
+            win = min(m, bound["KB_LDS_COUNTERS"] // (2 * d_tot))            # the library's rule: slots whose counters fit the LDS together
+            sweeps = -(-m // win) if win >= 1 else 0
+            res["passes"]["m=%d" % m] = dict(ms_best=best * 1e3, ms_median=med * 1e3, ratio_to_stream_floor=best / (res["stream_floor_ms"] * 1e-3),
+                                             p_in_lds=(d_tot + 1) * (2 * m | 1) <= bound["KB_LDS_P_DOUBLES"],
+                                             counter_sweeps=sweeps if sweeps <= bound["KB_MAX_SWEEPS"] else 0, counts_copy_ms=cp,
+                                             counts_copy_share=cp / (best * 1e3), smallest_child=int(sz.min()), largest_child=int(sz.max()))
+        m *= 2
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bisect", action="store_true")
+    ap.add_argument("--ms", default="1,4,32,512")
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--cols", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
@@ -72,9 +127,13 @@ def main():
     cols = np.arange(c, dtype=np.int32)
     off = np.concatenate([[0], np.cumsum(n_codes[:-1], dtype=np.int64)]).astype(np.int64)
     d_tot = int(n_codes.sum())
-    bound = {name: csrc_constant(name) for name in ("KM_LDS_P_DOUBLES", "KM_LDS_COUNTERS")}
     floor = n * (4 * c + 8) / COPY_CEILING
-    res = dict(rows=n, cols=c, d_tot=d_tot, stream_floor_ms=floor * 1e3, lds_bounds=bound, steps={})
+    res = dict(rows=n, cols=c, d_tot=d_tot, stream_floor_ms=floor * 1e3, library="RGBM_LIB_PATH" if os.environ.get("RGBM_LIB_PATH") else "this build")
+    if a.bisect:
+        bisect(a, codes, n_codes, cols, off, d_tot, res)
+        return report(res, a.out)
+    bound = {name: csrc_constant(name) for name in ("KM_LDS_P_DOUBLES", "KM_LDS_COUNTERS")}
+    res.update(lds_bounds=bound, steps={})
     tab = N.Table(codes, n_codes)
     m = min(a.check_rows, n)
     small = N.Table(np.ascontiguousarray(codes[:, :m]), n_codes)
@@ -97,10 +156,14 @@ def main():
             hb, _, _ = timed(lambda: Q.assign_step(sub, n_codes, off, p, h, None), 1)
             step.update(numpy_ms=hb * 1e3 * n / hm, numpy_rows_measured=hm, speedup_vs_numpy=hb * n / hm / best)
         res["steps"]["k=%d" % k] = step
+    report(res, a.out)
+
+
+def report(res, out):
     txt = json.dumps(res, indent=1)
     print(txt)
-    if a.out:
-        with open(a.out, "w") as f:
+    if out:
+        with open(out, "w") as f:
             f.write(txt + "\n")
 
 
