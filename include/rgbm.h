@@ -395,9 +395,19 @@ int rgbm_edit_distance(int32_t device_id, const int32_t* a_cp, const int64_t* a_
  * itself) NULL = the codes are the bins, else int32 [n_codes[col]] code -> bin.  A code / bin outside its range counts as NULL.
  * counts_out: the pairs' tables one after the other, pair (x, y) as int64 [(n_bins[x] + 1)][(n_bins[y] + 1)] row-major with NULL in the last
  * slot of each side.  More than 2^24 dense cells in a pair or 2^25 in a call: RGBM_ERR_PARAM (count sparsely on the host).
- * The tables, bins and LUTs stay with the table (device memory) for rgbm_table_cell_domains until the next call. */
+ * The tables, bins and LUTs stay with the table (device memory) for rgbm_table_cell_domains until the next call.
+ * RGBM_ERR_ARG: a NULL argument other than luts, n_pairs < 1.  RGBM_ERR_PARAM, the previous result untouched: a column outside the table, a pair
+ * (x, x), n_bins < 1 for a column of a pair, the two cell limits above. */
 int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, int32_t n_pairs, const int32_t* const* luts /* [c] or NULL */,
                            const int32_t* n_bins /* [c] */, int64_t* counts_out);
+/* The plan the last successful rgbm_table_pair_counts call on the table took (read-only, no device work; for tests that must know their
+ * route).  The pairs are packed, in the given order, into groups whose counters share a workgroup's LDS; a group is closed when its counters
+ * or its distinct columns would exceed a limit; a pair above the counter limit on its own is counted by a second kernel straight in HBM.
+ * pairs_out [n_pairs][3]: {group (-1 = the HBM kernel), slot of x, slot of y among the group's staged columns (-1, -1 with the HBM kernel)}.
+ * head_out [6]: {groups, counters of the largest group, workgroups per group (grid x), rows per workgroup -- all 0 when no pair took a
+ * group --, the limit of a group's counters, the limit of a group's distinct columns}.  n_pairs must be that call's (0 before any call), else
+ * RGBM_ERR_ARG.  t == NULL with n_pairs == 0 gives the two limits alone and needs no device. */
+int rgbm_table_pair_counts_report(const rgbm_table* t, int64_t* head_out /* [6] */, int32_t* pairs_out /* [n_pairs][3] */, int32_t n_pairs);
 /* Domains of the error cells of ONE discrete target with the naive-Bayes posterior of RepairApi.computeDomainInErrorCells (:479-675)
  * and the weak-label rule of errors.py:517-521, on the tables the last rgbm_table_pair_counts left on the device.  rows: the cells' row
  * positions; pair_idx [k <= 8]: the pairs (of that call) holding the target and its correlated attributes, in order; an element (value c of
@@ -405,7 +415,11 @@ int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, int32_t n_pa
  * value is NULL / no group) wipes the attributes before it (the SQL's IF(ISNOTNULL(domain), CONCAT(domain, d), d));
  * score_c = sum over the attributes, in order, of element / row_count (0 where single_ok[c] == 0), prob_c = score_c / (score_0 + score_1 + ...).
  * top_out: the value of the largest prob > beta (ties: smallest code), -1 = none; weak_out: the cell holds exactly that value now.
- * probs_out [n_cells][n_bins[target]] is optional. */
+ * probs_out [n_cells][n_bins[target]] is optional.  A row outside the table has an empty domain (top -1, probability 0, not weak); a
+ * current code outside the target's bins counts as NULL.
+ * RGBM_ERR_ARG: the target outside the table, n_cells < 0, k < 0, row_count < 1, a NULL array that is needed.  RGBM_ERR_PARAM: k > 8, no
+ * rgbm_table_pair_counts result on the table, a target that was counted through a LUT, a pair index outside that call's pairs, a pair
+ * that does not hold the target. */
 int rgbm_table_cell_domains(rgbm_table* t, int32_t target_col, const int64_t* rows, int64_t n_cells, const int32_t* pair_idx, int32_t k,
                             const int64_t* min_cnt /* [k] */, const uint8_t* single_ok /* [n_bins[target]] */, double beta, int64_t row_count,
                             uint8_t* weak_out, int32_t* top_out, double* top_prob_out, double* probs_out /* or NULL */);

@@ -172,6 +172,8 @@ RGBM_EXPORT int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, 
         }
         // groups: pairs in the given order; a group is closed when its histograms or its distinct columns would not fit
         std::vector<PcGroup> groups; std::vector<PcPair> pairs; std::vector<int32_t> gcols; std::vector<int> global_pairs;
+        std::vector<int32_t> plan((size_t)n_pairs * 3, -1);       // per pair {group (-1 = the HBM kernel), slot of x, slot of y}: the report
+        long long plan_head[4] = {0, 0, 0, 0};                    // {groups, cells of the largest group, grid x, rows per workgroup}
         PcGroup cur{0, 0, 0, 0, 0};
         auto slot_of = [&](int col) { for (int s = 0; s < cur.ncols; ++s) if (gcols[cur.col_begin + s] == col) return s; return -1; };
         for (int p = 0; p < n_pairs; ++p) {
@@ -186,6 +188,7 @@ RGBM_EXPORT int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, 
             if (slot_of(x) < 0) { gcols.push_back(x); ++cur.ncols; }
             if (slot_of(y) < 0) { gcols.push_back(y); ++cur.ncols; }
             pairs.push_back(PcPair{slot_of(x), slot_of(y), n_bins[y] + 1, cur.cells, (uint32_t)cells, off[p]});
+            plan[3 * (size_t)p] = (int32_t)groups.size(); plan[3 * (size_t)p + 1] = pairs.back().sx; plan[3 * (size_t)p + 2] = pairs.back().sy;
             cur.cells += (uint32_t)cells; ++cur.npairs;
         }
         if (cur.npairs > 0) groups.push_back(cur);
@@ -209,6 +212,7 @@ RGBM_EXPORT int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, 
             chunks = std::max<long long>(chunks, 1);
             long long rows_per_wg = (n + chunks - 1) / chunks;
             rows_per_wg = (rows_per_wg + PC_B - 1) / PC_B * PC_B;
+            plan_head[0] = (long long)groups.size(); plan_head[1] = max_cells; plan_head[2] = (n + rows_per_wg - 1) / rows_per_wg; plan_head[3] = rows_per_wg;
             if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_pair_counts, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(k_pair_counts, dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg), (unsigned)groups.size()), dim3(PC_B), lds, s,
                                t->codes.p, n, d_groups, d_gcols, d_pairs, t->pc_bins.p, t->pc_lut_off.p, t->pc_luts.p, rows_per_wg, tile_off,
@@ -232,8 +236,23 @@ RGBM_EXPORT int rgbm_table_pair_counts(rgbm_table* t, const int32_t* pair_cols, 
         t->pc_nbins.assign((size_t)c, 0);
         for (int j = 0; j < c; ++j) t->pc_nbins[j] = colinfo[2 * j + 1];
         t->pc_has_lut = has_lut;
+        t->pc_plan = plan; std::copy(plan_head, plan_head + 4, t->pc_plan_head);
         return RGBM_OK;
     });
+}
+
+// no device work: the plan the last successful rgbm_table_pair_counts call on the table took, and the two limits its planner works to
+RGBM_EXPORT int rgbm_table_pair_counts_report(const rgbm_table* t, int64_t* head_out, int32_t* pairs_out, int32_t n_pairs) {
+    if (!head_out || n_pairs < 0 || (n_pairs > 0 && (!t || !pairs_out))) return fail(RGBM_ERR_ARG, "rgbm_table_pair_counts_report: bad argument");
+    for (int i = 0; i < 4; ++i) head_out[i] = 0;
+    head_out[4] = PC_LDS_CELLS; head_out[5] = PC_MAXC;
+    if (!t) return RGBM_OK;
+    std::lock_guard<std::mutex> prep_lk(t->prep_mu);
+    if ((size_t)n_pairs * 3 != t->pc_plan.size())
+        return fail(RGBM_ERR_ARG, "rgbm_table_pair_counts_report: n_pairs is not the number of pairs of the table's last rgbm_table_pair_counts call");
+    for (int i = 0; i < 4; ++i) head_out[i] = t->pc_plan_head[i];
+    std::copy(t->pc_plan.begin(), t->pc_plan.end(), pairs_out);
+    return RGBM_OK;
 }
 
 // scratch slots held together: TABLE_A (attributes) COLS (single_ok) IN_ROWS ROW_MASK (weak) IN_COLS (top) VALS (top_prob)

@@ -189,6 +189,9 @@ struct rgbm_table {
     mutable rgh::DevBuf<unsigned long long> pc_counts; mutable rgh::DevBuf<int32_t> pc_luts; mutable rgh::DevBuf<long long> pc_lut_off;
     mutable rgh::DevBuf<int32_t> pc_bins;
     mutable std::vector<int32_t> pc_x, pc_y, pc_dx, pc_dy, pc_nbins; mutable std::vector<long long> pc_off; mutable std::vector<uint8_t> pc_has_lut;
+    // the plan of that call, as its planner made it (rgbm_table_pair_counts_report): per pair {group (-1 = the HBM kernel), slot of x, slot of y};
+    // {groups, cells of the largest group, grid x, rows per workgroup}
+    mutable std::vector<int32_t> pc_plan; mutable long long pc_plan_head[4] = {0, 0, 0, 0};
     // the cluster of every row after the last rgbm_table_kmeans_assign call (int32 [n]); it leaves the device through rgbm_table_kmeans_read
     mutable rgh::DevBuf<int32_t> km_assign; mutable bool km_valid = false;
     mutable rgbm_distinct_view view;

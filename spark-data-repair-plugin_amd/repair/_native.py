@@ -94,8 +94,9 @@ def lib():
                      "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats",
                      "rgbm_table_smoten", "rgbm_table_concat"):
             getattr(l, name).restype = C.c_int
-        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect"):
-            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass)
+        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect",
+                     "rgbm_table_pair_counts_report"):
+            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass / no count report)
                 getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -122,6 +123,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_bisect", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
     "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
+    "rgbm_table_pair_counts_report",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -485,6 +487,14 @@ def train_batch_report(n):
     a = np.zeros((max(int(n), 1), 4), np.int32)
     _check(lib().rgbm_table_train_batch_report(_p(a, C.c_int32), C.c_int32(n)), "rgbm_table_train_batch_report")
     return [dict(route=int(r[0]), scan_waves=int(r[1]), nchunk=int(r[2]), lds_bytes=int(r[3])) for r in a[:int(n)]]
+
+
+def pair_counts_limits():
+    """The two limits that close a group of ``Table.pair_counts`` (rgbm_table_pair_counts_report without a table; needs no device):
+    dict(lds_cells = 32-bit counters of a group, max_cols = distinct columns of a group)."""
+    head = np.zeros(6, np.int64)
+    _check(lib().rgbm_table_pair_counts_report(None, _p(head, C.c_int64), None, C.c_int32(0)), "rgbm_table_pair_counts_report")
+    return dict(lds_cells=int(head[4]), max_cols=int(head[5]))
 
 
 def _chain_args(models, feat_cols, class_codes):
@@ -929,10 +939,22 @@ class Table:
         out = np.zeros(int(sum(a * b for a, b in shapes)), np.int64)
         _check(lib().rgbm_table_pair_counts(self.h, _p(pc, C.c_int32), C.c_int32(len(pc)), ptrs if keep else None, _p(nb, C.c_int32),
                                             _p(out, C.c_int64)), "rgbm_table_pair_counts")
+        self._pc_last = (len(pc), nb)                     # what the table now holds: the pairs and the bins per column of this call
         res, at = [], 0
         for a, b in shapes:
             res.append(out[at:at + a * b].reshape(a, b)); at += a * b
         return res
+
+    def pair_counts_report(self):
+        """The plan the last ``pair_counts`` call on this table took (include/rgbm.h rgbm_table_pair_counts_report): dict(pairs = one
+        dict(group, slot_x, slot_y) per pair, group -1 = the HBM kernel; groups, max_group_cells, grid_x, rows_per_wg; lds_cells, max_cols =
+        the two limits that close a group)."""
+        n_pairs = getattr(self, "_pc_last", (0, None))[0]
+        head, rows = np.zeros(6, np.int64), np.zeros((max(n_pairs, 1), 3), np.int32)
+        _check(lib().rgbm_table_pair_counts_report(self.h, _p(head, C.c_int64), _p(rows, C.c_int32), C.c_int32(n_pairs)),
+               "rgbm_table_pair_counts_report")
+        return dict(pairs=[dict(group=int(r[0]), slot_x=int(r[1]), slot_y=int(r[2])) for r in rows[:n_pairs]], groups=int(head[0]),
+                    max_group_cells=int(head[1]), grid_x=int(head[2]), rows_per_wg=int(head[3]), lds_cells=int(head[4]), max_cols=int(head[5]))
 
     def cell_domains(self, target_col, rows, pair_idx, min_cnt, single_ok, beta, row_count, want_probs=False):
         """Domains / weak labels of the error cells (``rows``) of one discrete target on the tables of the last ``pair_counts`` call
@@ -942,6 +964,9 @@ class Table:
         ok = np.ascontiguousarray(single_ok, np.uint8).reshape(-1)
         if len(pi) != len(mc):
             raise ValueError("one min_cnt per pair")
+        last = getattr(self, "_pc_last", None)            # (without one the library refuses the call before it reads single_ok)
+        if last is not None and 0 <= int(target_col) < self.c and len(ok) != int(last[1][int(target_col)]):
+            raise ValueError("single_ok must hold one entry per bin of the target (%d), not %d" % (int(last[1][int(target_col)]), len(ok)))
         m = len(r)
         weak, top, tp = np.zeros(m, np.uint8), np.full(m, -1, np.int32), np.zeros(m, np.float64)
         probs = np.zeros((m, len(ok)), np.float64) if want_probs else None

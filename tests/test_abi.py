@@ -87,6 +87,20 @@ def test_batch_report_refuses_a_count_that_is_not_the_last_batch():
     assert seen[0] == [] and len(seen) == 2 and "last rgbm_table_train_batch call" in seen[1], seen
 
 
+def test_pair_counts_report_gives_its_limits_without_a_table():
+    """rgbm_table_pair_counts_report needs no device for the two limits of a group; pairs without a table are a bad argument."""
+    from repair import _native
+    from tests.helpers import csrc_constant
+    lim = _native.pair_counts_limits()
+    assert lim["max_cols"] == csrc_constant("PC_MAXC") and lim["lds_cells"] > 0
+    # the counters and the uint16 row tile of a group share 160 KiB of LDS less 2 KiB
+    assert lim["lds_cells"] * 4 + lim["max_cols"] * csrc_constant("PC_B") * 2 == 160 * 1024 - 2048
+    head, rows = np.zeros(6, np.int64), np.zeros(3, np.int32)
+    rc = _native.lib().rgbm_table_pair_counts_report(None, head.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                     rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.c_int32(1))
+    assert rc == -1 and b"rgbm_table_pair_counts_report" in _native.lib().rgbm_last_error()
+
+
 def test_params_struct_layout_matches_oracle():
     from oracle import oracle as O
     from repair import _native

@@ -1,5 +1,6 @@
 """-m gpu: the device entries of the cell-domain analysis (csrc/rgbm_domain.hip: rgbm_table_pair_counts, rgbm_table_cell_domains)
-against repair.domain -- counts exactly, flags / top values / probabilities bit for bit -- and `run()` with
+against repair.domain -- counts exactly, flags / top values / probabilities bit for bit; their kernel edges are walked against a plain
+restatement in tests/test_gpu_domain_edges.py -- and `run()` with
 `error.domain_analysis.enabled` on the hospital fixture: the resident path ends with the cells of the value-space path."""
 import numpy as np
 import pandas as pd
