@@ -440,6 +440,30 @@ int rgbm_table_rule_fill(rgbm_table* t, int32_t y_col, int32_t x_col /* -1: cons
  * -1 everywhere. */
 int rgbm_nearest_values(int32_t device_id, const int32_t* a_cp, const int64_t* a_off, int64_t n_a, const int32_t* b_cp, const int64_t* b_off,
                         int64_t n_b, const double* cost /* [n_a][n_b] or NULL */, double threshold, int32_t* nearest_out /* [n_a] */);
+/* ---- regex-structure repair (RegexStructureRepair.scala, RepairApi.repairByRegularExpression :677-704; the statement is
+ * repair/regex_structure.py) ----
+ * The structure of a detector's regex as a program of 1 .. 32 segments, matched with the meaning of `findFirstMatchIn` on the derived regex
+ * (leftmost start, every segment greedy, first successful backtracking path) against every string of a pool (layout as in
+ * rgbm_edit_distance).  A capture takes min .. max (max -1: unbounded; both at most 65535) code points of its class; a constant takes 1 .. its
+ * length code points other than U+000A, U+000D, U+0085, U+2028, U+2029 (min = 1 and max = const_len say so).  anchors: bit 0 `^` (the match
+ * starts at position 0), bit 1 `$` (it ends at the string's end).  A string that matches is rewritten as its captures and the constants'
+ * texts in segment order: state 1, the repaired strings back to back in out_cp with out_off[i + 1] - out_off[i] code points (0 for the
+ * other states).  A string of up to 63 code points is matched by one lane (its positions are one 64-bit word), one of up to
+ * RGBM_RX_WAVE_MAX_CP by one wave; a longer one gets state 2 and is the caller's (the statement) to evaluate.
+ * RGBM_ERR_ARG: a NULL array that is needed, n_segs outside 1 .. 32, anchors outside 0 .. 3, a kind other than 0 / 1, capture bounds outside
+ * 0 <= min <= max <= 65535, a constant outside const_cp or with bounds other than 1 .. const_len, constants that overlap (their lengths sum
+ * to more than n_const_cp), off[0] != 0, offsets that decrease.  n == 0 is legal. */
+#define RGBM_RX_WAVE_MAX_CP 4095 /* positions 0 .. 4095 of the longest string: 64 per lane of one wave */
+typedef struct { int32_t kind /* 0 capture, 1 constant */, min, max /* -1 unbounded; constant: 1, length */;
+                 uint32_t cls[4] /* capture: bit c = ASCII code point c is in the class */;
+                 int32_t const_off, const_len /* constant: its text in const_cp */; } rgbm_rx_seg;
+int rgbm_regex_structure(int32_t device_id, const rgbm_rx_seg* segs, int32_t n_segs /* 1..32 */, int32_t anchors,
+                         const int32_t* const_cp, int32_t n_const_cp,
+                         const int32_t* cp, const int64_t* off, int64_t n,
+                         uint8_t* state_out /* [n]: 0 no match, 1 repaired, 2 longer than the device handles */,
+                         int64_t* out_off /* [n + 1] */,
+                         int32_t* out_cp /* capacity off[n] + n * n_const_cp */,
+                         int64_t* info_out /* [4] = {strings on the one-word route, on the wave route, state 2, repaired} */);
 /* ---- LOF in code space (LOFOutlierErrorDetector: scikit-learn's LocalOutlierFactor(novelty=False) on one attribute; repair/lof_codes.py) ----
  * The local outlier factor of every entry of a sorted dictionary: values [d] ascending and finite, counts [d] >= 1 rows per entry (two rows
  * in all at least), k_ = max(1, min(k, rows - 1)) neighbours.  The neighbours of an entry are min(count - 1, k_) copies of itself, then the

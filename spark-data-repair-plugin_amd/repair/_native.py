@@ -92,7 +92,7 @@ def lib():
                      "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
                      "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
                      "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats",
-                     "rgbm_table_smoten", "rgbm_table_concat"):
+                     "rgbm_table_smoten", "rgbm_table_concat", "rgbm_regex_structure"):
             getattr(l, name).restype = C.c_int
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect",
                      "rgbm_table_pair_counts_report"):
@@ -123,7 +123,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_bisect", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
     "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
-    "rgbm_table_pair_counts_report",
+    "rgbm_table_pair_counts_report", "rgbm_regex_structure",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -608,6 +608,51 @@ def lof_1d(values, counts, k=20, threshold=1.5, want_scores=True, device_id=0):
                              C.c_double(threshold), _p(score, C.c_double) if want_scores else None, _p(bits, C.c_uint64),
                              _p(info, C.c_int64)), "rgbm_lof_1d")
     return score, bits, int(info[0]), int(info[1])
+
+
+class RxSeg(C.Structure):
+    """``rgbm_rx_seg`` of include/rgbm.h."""
+    _fields_ = [("kind", C.c_int32), ("min", C.c_int32), ("max", C.c_int32), ("cls", C.c_uint32 * 4), ("const_off", C.c_int32),
+                ("const_len", C.c_int32)]
+
+
+RX_WORD_MAX_CP = 63           # the longest string one lane matches
+RX_WAVE_MAX_CP = 4095         # RGBM_RX_WAVE_MAX_CP: the longest string the device matches
+
+
+def regex_structure_raw(segs, anchors, const_cp, cp, off, device_id=0):
+    """rgbm_regex_structure as it is (include/rgbm.h): ``segs`` rows of (kind, min, max, (4 class words), const_off, const_len), a pool of
+    int32 code points and int64 offsets -> (state uint8 [n], out_off int64 [n + 1], out_cp int32 [out_off[n]], info int64 [4])."""
+    arr = (RxSeg * max(len(segs), 1))()
+    for i, (kind, mn, mx, cls, c_off, c_len) in enumerate(segs):
+        arr[i] = RxSeg(int(kind), int(mn), int(mx), (C.c_uint32 * 4)(*[int(w) for w in cls]), int(c_off), int(c_len))
+    const_cp = np.ascontiguousarray(const_cp, np.int32).reshape(-1)
+    cp = np.ascontiguousarray(cp, np.int32).reshape(-1)
+    off = np.ascontiguousarray(off, np.int64).reshape(-1)
+    n = len(off) - 1
+    state = np.zeros(max(n, 0), np.uint8)
+    out_off = np.zeros(max(n, 0) + 1, np.int64)
+    out = np.zeros(max(int(off[-1]) + n * len(const_cp), 1) if n > 0 else 1, np.int32)
+    info = np.zeros(4, np.int64)
+    _check(lib().rgbm_regex_structure(C.c_int32(device_id), arr, C.c_int32(len(segs)), C.c_int32(int(anchors)), _p(const_cp, C.c_int32),
+                                      C.c_int32(len(const_cp)), _p(cp, C.c_int32), _p(off, C.c_int64), C.c_int64(n), _p(state, C.c_uint8),
+                                      _p(out_off, C.c_int64), _p(out, C.c_int32), _p(info, C.c_int64)), "rgbm_regex_structure")
+    return state, out_off, out[:int(out_off[-1])], info
+
+
+def regex_structure(program, strings, device_id=0, want_info=False):
+    """Regex-structure repair of a list of strings on the device (include/rgbm.h rgbm_regex_structure; the statement is
+    repair.regex_structure.repair_values): a list of the repaired string or None.  A string beyond the device's cap (state 2) is evaluated
+    with the statement.  ``want_info``: also the int64 [4] route report."""
+    from repair.regex_structure import program_arrays, repair_value
+    strings = list(strings)
+    a = program_arrays(program)
+    cp, off = pack_code_points(strings)
+    state, out_off, out, info = regex_structure_raw(a["segs"], a["anchors"], a["const_cp"], cp, off, device_id)
+    text = out.astype("<u4").tobytes().decode("utf-32-le", "surrogatepass")
+    res = [text[out_off[i]:out_off[i + 1]] if state[i] == 1 else (repair_value(program, strings[i]) if state[i] == 2 else None)
+           for i in range(len(strings))]
+    return (res, info) if want_info else res
 
 
 class DcPred(C.Structure):

@@ -91,6 +91,11 @@ class HipEngine:
             return _native.nearest_values(cost=cost, threshold=threshold, device_id=self.device_id)
         return _native.nearest_values(a, b, threshold=threshold, device_id=self.device_id)
 
+    def regex_structure(self, program, strings):
+        """`repair.regex_structure.repair_values` on the device (rgbm_regex_structure), code point for code point: per string the
+        repaired string or None."""
+        return _native.regex_structure(program, strings, device_id=self.device_id)
+
     def lof_codes(self, values, counts, k=20):
         """`repair.lof_codes.lof_codes` on the device (rgbm_lof_1d), bit for bit: (lof float64 [D], flagged bool [D], n_ties, n_near)."""
         from repair.detect_codes import unpack_bits

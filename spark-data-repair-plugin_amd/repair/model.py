@@ -101,6 +101,9 @@ class RepairModel():
     # new in this engine: the rule-based repairs (`setRepairByRules`: FD rule models, constant models, nearest-value merges) on the
     # HBM-resident pipeline
     _opt_rule_resident = _option("model.rule.resident", False, bool, None, None)
+    # regex-structure repair (`model.rule.repair_by_regex.disabled=""`) on the HBM-resident pipeline as well (needs `model.rule.resident` too):
+    # the cells' strings through `engine.regex_structure` (rgbm_regex_structure), the repaired values into the encoding
+    _opt_rule_regex_resident = _option("model.rule.regex.resident", False, bool, None, None)
     # `setTrainingDataRebalancingEnabled(True)` on the HBM-resident path: SMOTEN in code space on the device (repair.rebalance_codes)
     _opt_rebalance_resident = _option("model.rebalance.resident", False, bool, None, None)
     # new in this engine: the value detectors (RegExErrorDetector, DomainValues, GaussianOutlierErrorDetector) as code predicates on
@@ -126,7 +129,7 @@ class RepairModel():
     option_keys = set([o.key for o in (
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
-        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident, _opt_rebalance_resident,
+        _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident, _opt_rule_regex_resident, _opt_rebalance_resident,
         _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
@@ -599,6 +602,48 @@ class RepairModel():
         repaired = error_cells_df[done].assign(repaired=rep[done])
         return error_cells_df[~done], repaired
 
+    def _regex_programs(self) -> List[Tuple[str, Any]]:
+        """(attribute, program) of every RegExErrorDetector, in list order, whose pattern gives a structure to repair with
+        (`repair.regex_structure.parse`); a pattern that does not is logged with the reason and repairs nothing, as in
+        `RepairApi.repairByRegularExpression` (RepairApi.scala:698-703).  (The reference's DomainValues is no RegExErrorDetector.)"""
+        from repair.regex_structure import NotRepairable, parse
+        out: List[Tuple[str, Any]] = []
+        for d in self.error_detectors:
+            if isinstance(d, RegExErrorDetector) and not isinstance(d, DomainValues):
+                try:
+                    out.append((d.attr, parse(d.regex)))
+                except NotRepairable as e:
+                    _logger.warning("Repairing using regex '%s' (attr='%s') failed because: %s" % (d.regex, d.attr, e))
+        if len({a for a, _ in out}) < len(out):
+            _logger.info("[Repairing Phase] several regexs on one attribute: the first that repairs a cell wins (the reference's union "
+                         "would list the cell once per regex)")
+        return out
+
+    def _repair_by_regexs(self, input_df: DataFrame, error_cells_df: DataFrame) -> Tuple[DataFrame, DataFrame]:
+        """Reference model.py:629-651 with `RegexStructureRepair` stated in `repair.regex_structure`: per RegExErrorDetector, in list
+        order, the remaining error cells of its attribute whose current value (as a string, `_sql_strs`) fits the structure of the
+        regex are rewritten from it; every distinct string is evaluated once.  They leave the error cells."""
+        from repair.regex_structure import repair_cells
+        programs = self._regex_programs()
+        attrs = error_cells_df["attribute"].to_numpy(dtype=object)
+        cur = error_cells_df["current_value"].to_numpy(dtype=object)
+        rep = np.empty(len(error_cells_df), object)
+        done = np.zeros(len(error_cells_df), bool)
+        if programs:
+            _logger.info("[Repairing Phase] Repairing data using the regexs of: %s" % to_list_str([a for a, _ in programs]))
+        for attr, program in programs:
+            idx = np.flatnonzero((attrs == attr) & ~done)
+            if not len(idx) or attr not in input_df.columns:
+                continue
+            integral = is_numeric_column(input_df[attr]) and is_integral_column(input_df[attr])
+            values, skipped = repair_cells(program, _sql_strs(cur[idx], integral))
+            if skipped:
+                _logger.info("[Repairing Phase] %d cells of `%s` hold a line terminator: left to the models" % (skipped, attr))
+            for i, v in zip(idx, values):
+                if v is not None:
+                    rep[i], done[i] = v, True
+        return error_cells_df[~done], error_cells_df[done].assign(repaired=rep[done])
+
     # ------------------------------------------------------------------ resident (device) path
     def _resident_engine(self) -> Any:
         """The engine of the HBM-resident path, or None: no HIP device, the estimator backend was swapped (CPU tests), or
@@ -675,7 +720,8 @@ class RepairModel():
     def _resident_rules(self, input_df: DataFrame, target_columns: List[str], continous_columns: List[str], domain_stats: Dict[str, int],
                         prob_modes: bool) -> Optional[Dict[str, Any]]:
         """The rule-based repairs of this run as the `rules` of `repair.pipeline.repair_frame` take them, or None (with the reason in the
-        log) where the resident pipeline does not restate them: the probability modes, regex-structure repair, an FD model for a
+        log) where the resident pipeline does not restate them: the probability modes, regex-structure repair without
+        `model.rule.regex.resident` (or together with nearest-value merges, or on a column that does not hold strings), an FD model for a
         continuous attribute or from a continuous target (its chain value is the raw prediction, not a dictionary entry), a cycle
         among the FD sources."""
         from repair.costs import Levenshtein
@@ -685,8 +731,21 @@ class RepairModel():
 
         if prob_modes:
             return no("the probability modes are combined with rules")
+        regex = None
         if self._repair_by_regex_enabled:
-            return no("regex-structure repair is enabled")
+            if not bool(self._get_option_value(*self._opt_rule_regex_resident)):
+                return no("regex-structure repair is enabled")
+            if self._repair_by_nearest_values_enabled:
+                # the merges read their domains from the table BEFORE the regex repairs are written (model.py `_run`); the resident table
+                # is built with them
+                return no("regex-structure repair together with nearest-value merges")
+            regex = []
+            for attr, program in self._regex_programs():
+                if attr not in input_df.columns or attr not in target_columns:
+                    continue
+                if is_numeric_column(input_df[attr]) or pd.api.types.infer_dtype(input_df[attr], skipna=True) != "string":
+                    return no("regex-structure repair of `%s`, which is not a column of strings" % attr)
+                regex.append(dict(attr=attr, program=program, current_str=lambda a, values: _sql_strs(values, False)))
         fd: Dict[str, str] = {}
         deps = self._get_functional_deps(target_columns) if self._repair_by_functional_deps_enabled else None
         for y in target_columns:
@@ -721,7 +780,7 @@ class RepairModel():
             nearest = dict(targets=[c for c in target_columns if c in cf.targets] if cf.targets else list(target_columns),
                            threshold=float(self._get_option_value(*self._opt_merge_threshold)),
                            cost=None if type(cf) is Levenshtein else cf.compute, current_str=current_str, domain_str=domain_str)
-        return dict(fd=fd, nearest=nearest)
+        return dict(fd=fd, nearest=nearest, regex=regex or None)
 
     def _device_detection_plan(self, input_df: DataFrame, continous_columns: List[str], compute_repair_candidate_prob: bool,
                                maximal_likelihood_repair: bool) -> Optional[Dict[str, Any]]:
@@ -960,9 +1019,12 @@ class RepairModel():
                     raise NotResidentEligible("%d NULL target cells of dirty rows are not error cells" % (nulls_in_dirty - null_error_cells))
             cells = dict(error_cells=error_cells_df[[rid, "attribute"]], detect_nulls=False)
             nearest = rules is not None and rules.get("nearest") is not None
-            if prob or nearest:
-                # the cost functions see the error cells' current values as `error_cells_df` holds them
+            regex = rules is not None and rules.get("regex") is not None
+            if prob or nearest or regex:
+                # the cost functions and the regex structures see the error cells' current values as `error_cells_df` holds them
                 current = self._current_values_by_position(input_df, error_cells_df)
+            if regex:
+                rules = dict(rules, regex=[dict(r, current=current) for r in rules["regex"]])
             if nearest:
                 rules = dict(rules, nearest=dict(rules["nearest"], current=current))
             _logger.info("[Repair Model Training Phase] Building %d models on the HBM-resident table to %s %s" % (
@@ -984,7 +1046,9 @@ class RepairModel():
         self._last_resident_info = info
         self._last_detection_on_device = detect
         try:
-            return self._resident_result(input_df, frame, info.get("merged_cells"), error_cells_df, continous_columns, compute_repair_prob,
+            by_rule = [f for f in (info.get("regex_cells"), info.get("merged_cells")) if f is not None and len(f)]
+            return self._resident_result(input_df, frame, pd.concat(by_rule, ignore_index=True) if by_rule else None, error_cells_df,
+                                         continous_columns, compute_repair_prob,
                                          compute_repair_score, repair_data, maximal_likelihood_repair, prob)
         finally:
             info["times"]["host_shape"] = time.perf_counter() - t0
@@ -1151,8 +1215,9 @@ class RepairModel():
         repaired_by_rules_df = None
         if self.repair_by_rules:
             repaired_by_rules_df = error_cells_df.iloc[0:0].assign(repaired=pd.Series([], dtype=object))
-            if self._repair_by_regex_enabled and any(isinstance(d, RegExErrorDetector) for d in self.error_detectors):
-                _logger.warning("regex-structure repair (RegexStructureRepair.scala) is outside the accelerated path and not available")
+            if self._repair_by_regex_enabled:
+                error_cells_df, by_regex = self._repair_by_regexs(input_df, error_cells_df)
+                repaired_by_rules_df = pd.concat([repaired_by_rules_df, by_regex], ignore_index=True)
             if self._repair_by_nearest_values_enabled:
                 error_cells_df, by_nv = self._repair_by_nearest_values(repair_base_df, error_cells_df, target_columns)
                 repaired_by_rules_df = pd.concat([repaired_by_rules_df, by_nv], ignore_index=True)

@@ -315,6 +315,13 @@ class NotResidentEligible(ValueError):
     (model.py:1008-1017, 779-783); `RepairModel._run` catches this and takes the value-space path, which has that short-cut."""
 
 
+def _detector_report(value_detectors):
+    if not value_detectors:
+        return None
+    return [dict(col=int(d["col"]), kinds=list(d.get("kinds", ())), codes_flagged=int(d.get("codes_flagged", 0)),
+                 cells=int(d.get("cells", 0))) for d in value_detectors]
+
+
 class DeadClasses(NotResidentEligible):
     """Detection ran on the device and found error cells that hold the ONLY occurrences of some values of a target attribute: the
     dictionaries were built before the cells were known, so those values would stay behind as classes without rows.  Carries the
@@ -512,7 +519,7 @@ def cell_pmfs(engine, table, pmf_tab, targets, models, rows, cols, current, dirt
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None, rebalance=None):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None, regex_cols=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
@@ -548,6 +555,9 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
                  then each FD target once its source is no longer pending.
     value_detectors: per-column code predicates of the regex / value-domain / outlier detectors (`detect_error_cells`), or a callable
                  (table) -> such a list, called on the table before any cell is NULLed (autofill and quartiles need its rows per code).
+    regex_cols : columns with a regex-structure repair (`repair_frame`: rules['regex']).  When the cells are detected here and one lies in such
+                 a column, nothing is NULLed: DeadClasses hands the (pruned) cells to the caller, who evaluates them and comes back with the
+                 remaining ones as `error_cells`.
     distinct_training_rows: None (off) or dict(max_ratio=float) -- train the targets that qualify on the DISTINCT rows of the NULLed table with
                  their multiplicities (`distinct_training_tables`: one `Table.distinct_rows()` call on the device); same models, bytes
                  included.  Every target that does not qualify, or whose fit the trainer refuses on the distinct table, trains on the whole
@@ -581,6 +591,13 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         rows, cols = rows[~da["weak"]], cols[~da["weak"]]
     t_detect = time.perf_counter() - t0
     t0 = time.perf_counter()
+    if regex_cols and error_cells is None and len(rows) and np.isin(cols, list(regex_cols)).any():
+        # regex-structure repair rewrites cells from their STRINGS, and a repaired string may be new to its column: the caller evaluates
+        # the cells, patches the encoding and comes back with the remaining cells as given (the route of DeadClasses)
+        e = DeadClasses("%d detected cells lie in attributes with a regex-structure repair" % int(np.isin(cols, list(regex_cols)).sum()), rows, cols)
+        e.domain_info = domain_info
+        e.value_detectors = _detector_report(value_detectors)
+        raise e
     current = table.read_cells(rows, cols)
     table.null_cells(rows, cols, targets)                       # convertErrorCellsToNull (RepairApi.scala:171-211)
     detected = (rows, cols)                                     # every detected cell: what a DeadClasses second pass starts from
@@ -598,8 +615,7 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     if domain_info is not None:
         out["domain"] = domain_info
     if value_detectors:
-        out["value_detectors"] = [dict(col=int(d["col"]), kinds=list(d.get("kinds", ())), codes_flagged=int(d.get("codes_flagged", 0)),
-                                       cells=int(d.get("cells", 0))) for d in value_detectors]
+        out["value_detectors"] = _detector_report(value_detectors)
     if len(rows) == 0:
         out.update(repaired=np.zeros(0, np.int32), repaired_value=np.zeros(0, np.float64), prob=np.zeros(0, np.float64),
                    times=dict(detect=t_detect, prepare=time.perf_counter() - t0))
@@ -796,6 +812,13 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     strings: the error cells' current values where the caller holds them already])).  The frame then lacks the merged cells; the details
     hold them as `merged_cells` (row_id, attribute, current_value, repaired: strings), their number per attribute as `nearest_values`,
     and `rule_steps` (`rule_step_summary` with attribute names).
+    rules['regex']: None or [dict(attr, program (`repair.regex_structure.parse`), current_str=callable(attribute, raw values) -> strings[,
+    current=callable(attribute, row positions) -> the cells' current values where the caller holds them])] in detector order -- regex-structure
+    repair (`_repair_by_regexs`).  Once the error cells are known (given, or detected on the device and handed back: the route of
+    DeadClasses), the DISTINCT current-value strings of each attribute's cells go through `engine.regex_structure`; a repaired cell gets
+    its new value in the dictionary indices (a string the column did not hold becomes a dictionary entry, the codes stay the ascending
+    ranks), the others are NULLed as given cells, and the table is built once.  The frame lacks the repaired cells; the details hold them
+    as `regex_cells` (a frame like `merged_cells`) and their number per attribute as `regex_repairs`.
 
     distinct_training_rows: None or dict(max_ratio=float), as `repair_table` takes it; the details then hold `distinct_rows` with attribute
     names: dict(rows, distinct, used_for=[attributes], skipped={attribute: reason}).
@@ -844,14 +867,59 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                 remaps[j] = new
         return gc.astype(np.int64) * len(df) + gr, gv
 
+    regex_rules = list((rules or {}).get("regex") or [])
+    regex_done = dict(rows=np.zeros(0, np.int64), cols=np.zeros(0, np.int32), current=np.zeros(0, object), repaired=np.zeros(0, object))
+
+    def known_cells(kr, kc):
+        """The error cells are known: regex-structure repair of those it applies to, `null_known_cells` of all of them (the reference
+        NULLs every error cell and then writes the rule repairs, model.py `_repair_attrs`), the repaired values written into the
+        encoding.  Returns (the remaining cells, what all of them held)."""
+        from repair.regex_structure import repair_cells
+        done = np.zeros(len(kr), bool)
+        cur_s, rep_s = np.empty(len(kr), object), np.empty(len(kr), object)
+        tset = {pos[t] for t in targets}
+        for r in regex_rules:
+            j = pos.get(r["attr"])
+            sel = np.flatnonzero((kc == j) & ~done) if j is not None and j in tset else np.zeros(0, np.int64)
+            if not len(sel):
+                continue
+            if r.get("current") is not None:
+                raw = list(r["current"](cols[j], kr[sel]))
+            else:
+                idx = indices[j, kr[sel]]
+                raw = [dicts[j][remaps[j][i]] if i >= 0 else None for i in idx]
+            strs = r["current_str"](cols[j], raw)
+            values, skipped = repair_cells(r["program"], strs, engine.regex_structure)
+            if skipped:
+                _logger.info("[Repairing Phase] %d cells of `%s` hold a line terminator: left to the models" % (skipped, cols[j]))
+            for i, sv, v in zip(sel, strs, values):
+                if v is not None:
+                    done[i], cur_s[i], rep_s[i] = True, sv, v
+        held = null_known_cells(kr, kc)
+        for j in np.unique(kc[done]):
+            at = np.flatnonzero(done & (kc == j))
+            for v in dict.fromkeys(rep_s[at]):
+                k = int(np.searchsorted(dicts[j], v))
+                if k < len(dicts[j]) and dicts[j][k] == v:
+                    entry = int(np.flatnonzero(remaps[j] == k)[0])
+                else:                                                   # a new dictionary entry; the codes stay the ascending ranks
+                    remaps[j] = np.append(np.where(remaps[j] >= k, remaps[j] + 1, remaps[j]), np.int32(k)).astype(np.int32)
+                    entry = len(remaps[j]) - 1
+                    grown = np.empty(len(dicts[j]) + 1, object)
+                    grown[:k], grown[k], grown[k + 1:] = dicts[j][:k], v, dicts[j][k:]
+                    dicts[j] = grown
+                indices[j, kr[at[rep_s[at] == v]]] = entry
+        for key, part in (("rows", kr[done]), ("cols", kc[done]), ("current", cur_s[done]), ("repaired", rep_s[done])):
+            regex_done[key] = np.concatenate([regex_done[key], part])
+        return (kr[~done], kc[~done]), held
+
     if error_cells is not None:
         if row_id not in error_cells.columns or "attribute" not in error_cells.columns:
             raise ValueError("Error cells should have `%s` and `attribute` in columns" % row_id)
         rpos = pd.Series(np.arange(len(df)), index=df[row_id].to_numpy()).reindex(error_cells[row_id].to_numpy()).to_numpy(np.float64)
         cpos = np.array([pos.get(a, -1) for a in error_cells["attribute"]], np.int64)
         ok = ~np.isnan(rpos) & (cpos >= 0)                      # cells of unknown rows / attributes drop out (join semantics)
-        cells = (rpos[ok].astype(np.int64), cpos[ok].astype(np.int32))
-        given_current = null_known_cells(cells[0], cells[1])
+        cells, given_current = known_cells(rpos[ok].astype(np.int64), cpos[ok].astype(np.int32))
     if error_cells is not None and not detect_nulls and not constraints and rules is None:
         # every error cell is known and NULLed: the class counts the models will see are final.  Say so BEFORE anything is uploaded
         # (a constraint / regex / user-given cell may hold the only occurrence of a class; an all-NULL numeric column has no value)
@@ -949,6 +1017,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                                    pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
                                    only_noisy_targets=only_noisy_targets, domain_analysis=da_spec, rules=table_rules(),
                                    value_detectors=table_detectors(detect_nulls_) if analyse else None,
+                                   regex_cols=[pos[r["attr"]] for r in regex_rules if r["attr"] in pos] if cells_ is None else None,
                                    distinct_training_rows=distinct_training_rows,
                                    rebalance=dict(rebalance, names=lambda t: cols[t], class_names=lambda t: dicts[t]) if rebalance is not None else None,
                                    check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
@@ -961,9 +1030,8 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         # known now: NULL them on the host side of the encoding, drop the dead values, upload the (cached) encoding again and go on
         # with the cells as GIVEN -- no second detection, no pandas detectors, no value-space fallback.
         _logger.info("%s: re-encoding the target dictionaries without them" % e)
-        cells = (e.rows, e.cols)
         first = given_current
-        given_current = null_known_cells(cells[0], cells[1])
+        cells, given_current = known_cells(e.rows, e.cols)
         if first is not None:
             # cells of a user-given error_cells frame were NULLed before the first attempt: the second pass sees None there, the first
             # one knows what they held
@@ -1033,6 +1101,11 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             details["merged_cells"] = pd.DataFrame({row_id: df[row_id].to_numpy()[mrows], "attribute": np.asarray(cols, object)[mcols],
                                                     "current_value": np.asarray(mcur, object), "repaired": np.asarray(mrep, object)})
             details["nearest_values"] = {cols[j]: int((mcols == j).sum()) for j in np.unique(mcols)}
+            if regex_rules:
+                details["regex_cells"] = pd.DataFrame({row_id: df[row_id].to_numpy()[regex_done["rows"]],
+                                                       "attribute": np.asarray(cols, object)[regex_done["cols"]],
+                                                       "current_value": regex_done["current"], "repaired": regex_done["repaired"]})
+                details["regex_repairs"] = {cols[j]: int((regex_done["cols"] == j).sum()) for j in np.unique(regex_done["cols"])}
         return frame, details
     return frame
 
