@@ -15,6 +15,7 @@ import time
 import numpy as np
 
 from repair.engine import run_job
+from repair.frame_encoding import FrameEncoding
 from repair.utils import setup_logger
 
 _logger = setup_logger()
@@ -326,11 +327,14 @@ class DeadClasses(NotResidentEligible):
     """Detection ran on the device and found error cells that hold the ONLY occurrences of some values of a target attribute: the
     dictionaries were built before the cells were known, so those values would stay behind as classes without rows.  Carries the
     detected cells (row positions, column indices): `repair_frame` NULLs them in the dictionary indices, drops the dead values,
-    uploads again and goes on WITHOUT detecting a second time (and without leaving the resident path)."""
+    uploads again and goes on WITHOUT detecting a second time (and without leaving the resident path).  What the first pass found out and
+    the second does not compute again rides along: `domain_info` (the cell-domain summary; the cells carried are the pruned ones) and
+    `value_detectors` (the detector report)."""
 
-    def __init__(self, msg, rows, cols):
+    def __init__(self, msg, rows, cols, domain_info=None, value_detectors=None):
         super().__init__(msg)
         self.rows, self.cols = np.asarray(rows, np.int64), np.asarray(cols, np.int32)
+        self.domain_info, self.value_detectors = domain_info, value_detectors
 
 
 class UnseenCategories(NotResidentEligible):
@@ -516,114 +520,74 @@ def cell_pmfs(engine, table, pmf_tab, targets, models, rows, cols, current, dirt
     return out
 
 
-def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
-                 want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
-                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None, rebalance=None, regex_cols=None):
-    """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).
+def _detect_and_prune(table, targets, constraints, detect_nulls, error_cells, only_noisy_targets, domain_analysis, value_detectors, regex_cols):
+    """Phase 1 of `repair_table`: the error cells, before anything is NULLed.  Returns (rows, cols, the targets to repair, domain summary or
+    None, the value detectors' descriptors, seconds).
 
-    continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
-                 double in the reference, RepairBase.scala:41-44): repaired by an L2 regressor on the values behind their codes
-                 (train.py:97-100), integral ones rounded (model.py:1130-1132); `repaired_value` carries the prediction.
-    only_noisy_targets: train models for the target attributes that hold at least one error cell only (the reference's
-                 `target_columns` are the noisy columns, errors.py:472-477) and insist that every label of such a target still has a
-                 training row once the cells are NULLed -- `RepairModel.run()` with detection on the device: the cells are not known
-                 when the dictionaries are built, so a value that only error cells held would stay behind as a class without rows
-                 (num_class enters the softmax hessian factor); NotResidentEligible then sends the run to the value-space path.
-    search_opts: reference option dict (model.hp.*, model.cv.n_splits): run the hyper-parameter search of every target on the
-                 resident tables before its final fit (`search_on_table`); None = the fixed parameters.
-    train_rows : {target: row positions} or a callable (target, positions of its non-NULL rows) -> positions -- train that
-                 target's model on these rows only (model.max_training_row_num sampling, model.py:755-766); default: every row
-                 whose target cell is not NULL.
-    pmf_costs  : (want_pmf) the probability modes of RepairModel.run(): a callable (target, ascending row positions of its error cells)
-                 -> dict(cost [R + 1][K] float64 or None, cost_row [cells] int32 (-1 = no cost), cur_code [cells] int32 (the current
-                 value's class, -1 = none), weight, renormalise) or None, handed to `Table.repair_pmf_weighted`; adds `top1_cost` and
-                 `pmf_value`.  With it the pmf table is chained as the value-space `_repair` chains it (model.py): in target order, a
-                 continuous target's prediction fills its NULL cells before the later targets are scored (`pmf_value` holds it),
-                 discrete targets stay NULL.
+    only_noisy_targets: train models for the target attributes that hold at least one error cell only (the reference's `target_columns` are
+                 the noisy columns, errors.py:472-477); `_target_plan` then insists that every label of such a target keeps a training row.
     domain_analysis: the checked `error.*` options and the view's inputs (`analyse_cell_domains`): the reference's cell-domain analysis
                  runs on the detected cells of the noisy targets before anything is NULLed, and the weak-labelled cells (the current
                  value is the most probable one) leave the error cells (errors.py:507-530).  None = every detected cell is repaired.
-    rules      : the rule-based repairs of `RepairModel.setRepairByRules` (model.py `_repair_by_nearest_values`, `_build_repair_models`,
-                 `_resolve_prediction_order`), None = none of them:  dict(fd={target: source column} -- the target is answered by the
-                 functional dependency source -> target (`Table.fd_map` on the whole NULLed table) unless it is left with fewer than two
-                 classes;  such a discrete target gets a constant step (its one live class, or NULL) instead of NotResidentEligible;
-                 nearest=None or dict(targets=[columns], threshold, current=callable(target, rows, codes) -> the cells' current-value
-                 strings (None / '' = no merge), domain=callable(target, live codes) -> their strings, cost=None (Levenshtein, on the
-                 device) or callable(current string, domain string) -> float or None) -- `nearest_value_merges`).  Merged cells leave the
-                 error cells (`merged` holds them), rule targets are not trained, and the chain runs the non-FD targets in target order,
-                 then each FD target once its source is no longer pending.
     value_detectors: per-column code predicates of the regex / value-domain / outlier detectors (`detect_error_cells`), or a callable
                  (table) -> such a list, called on the table before any cell is NULLed (autofill and quartiles need its rows per code).
     regex_cols : columns with a regex-structure repair (`repair_frame`: rules['regex']).  When the cells are detected here and one lies in such
                  a column, nothing is NULLed: DeadClasses hands the (pruned) cells to the caller, who evaluates them and comes back with the
-                 remaining ones as `error_cells`.
-    distinct_training_rows: None (off) or dict(max_ratio=float) -- train the targets that qualify on the DISTINCT rows of the NULLed table with
-                 their multiplicities (`distinct_training_tables`: one `Table.distinct_rows()` call on the device); same models, bytes
-                 included.  Every target that does not qualify, or whose fit the trainer refuses on the distinct table, trains on the whole
-                 table; the result's `distinct_rows` says which and why.  With `want_stats` the stats of a target trained on the distinct
-                 table describe that fit (its M rows), not a fit on the N rows.
-    rebalance  : None (off) or dict(k=5, random_state=42[, names, class_names: callables for the log]) -- `setTrainingDataRebalancingEnabled`:
-                 every discrete target that is trained trains on its rebalanced table (`rebalanced_training_table`: SMOTEN on the device, the
-                 draws on the host), made from its `train_rows` in the order given (the sampler's) or from all its non-NULL rows.  The class
-                 weights, the unseen-category check and the hyper-parameter search see that table.  `rebalanced` of the result holds per
-                 target dict(median, rows, synthetic, classes).
-    Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
-    dirty_rows, models, times, stats[, domain][, rule_steps, merged][, value_detectors][, distinct_rows][, rebalanced]): one entry per error cell,
-    ordered by (column, row).
-    """
-    continuous = dict(continuous or {})
+                 remaining ones as `error_cells`."""
     t0 = time.perf_counter()
-    targets = [int(t) for t in targets]
-    n_codes = np.asarray(table.n_codes, np.int32)
     if callable(value_detectors):
         value_detectors = value_detectors(table)
-    rows, cols = detect_error_cells(table, targets, constraints, detect_nulls, error_cells, value_detectors=value_detectors)
-    noisy = set(int(c) for c in np.unique(cols))
-    if only_noisy_targets:
-        targets = [t for t in targets if t in noisy]
-    domain_info = None
-    if domain_analysis is not None and len(rows):
-        da = analyse_cell_domains(table, [t for t in targets if t in noisy], rows, cols, domain_analysis)
-        domain_info = dict(pairwise=da["pairwise"], noisy_cells=int(len(rows)), weak_cells=int(da["weak"].sum()))
+    found_rows, found_cols = detect_error_cells(table, targets, constraints, detect_nulls, error_cells, value_detectors=value_detectors)
+    noisy = set(int(c) for c in np.unique(found_cols))
+    kept = [t for t in targets if t in noisy] if only_noisy_targets else targets
+    rows, cols, domain_info = found_rows, found_cols, None
+    if domain_analysis is not None and len(found_rows):
+        da = analyse_cell_domains(table, [t for t in kept if t in noisy], found_rows, found_cols, domain_analysis)
+        domain_info = dict(pairwise=da["pairwise"], noisy_cells=int(len(found_rows)), weak_cells=int(da["weak"].sum()))
         _logger.info("[Error Detection Phase] %d noisy cells fixed and %d error cells remaining..." % (domain_info["weak_cells"],
-                                                                                                   len(rows) - domain_info["weak_cells"]))
-        rows, cols = rows[~da["weak"]], cols[~da["weak"]]
-    t_detect = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    if regex_cols and error_cells is None and len(rows) and np.isin(cols, list(regex_cols)).any():
-        # regex-structure repair rewrites cells from their STRINGS, and a repaired string may be new to its column: the caller evaluates
-        # the cells, patches the encoding and comes back with the remaining cells as given (the route of DeadClasses)
-        e = DeadClasses("%d detected cells lie in attributes with a regex-structure repair" % int(np.isin(cols, list(regex_cols)).sum()), rows, cols)
-        e.domain_info = domain_info
-        e.value_detectors = _detector_report(value_detectors)
-        raise e
+                                                                                                   len(found_rows) - domain_info["weak_cells"]))
+        rows, cols = found_rows[~da["weak"]], found_cols[~da["weak"]]
+    seconds = time.perf_counter() - t0
+    if regex_cols and error_cells is None and len(rows):
+        in_regex = np.isin(cols, list(regex_cols))
+        if in_regex.any():
+            # regex-structure repair rewrites cells from their STRINGS, and a repaired string may be new to its column: the caller evaluates
+            # the cells, patches the encoding and comes back with the remaining cells as given (the route of DeadClasses)
+            raise DeadClasses("%d detected cells lie in attributes with a regex-structure repair" % int(in_regex.sum()), rows, cols,
+                              domain_info=domain_info, value_detectors=_detector_report(value_detectors))
+    return rows, cols, kept, domain_info, value_detectors, seconds
+
+
+def _null_and_merge(engine, table, targets, rows, cols, nearest):
+    """Phase 2: convertErrorCellsToNull (RepairApi.scala:171-211), then the nearest-value merges (`nearest`: rules['nearest'] of
+    `repair_table`, or None) written back -- model.py `_repair_attrs(repaired_by_rules_df, ..)`.  Returns (rows, cols, current of the
+    cells that stay error cells, the merged cells as dict(rows, cols, current, repaired) or None, the dirty rows: model.py:549-553)."""
     current = table.read_cells(rows, cols)
-    table.null_cells(rows, cols, targets)                       # convertErrorCellsToNull (RepairApi.scala:171-211)
-    detected = (rows, cols)                                     # every detected cell: what a DeadClasses second pass starts from
-    merged = None
-    if rules is not None and rules.get("nearest") is not None and len(rows):
-        near = nearest_value_merges(engine, table, targets, rows, cols, current, rules["nearest"])
-        done = near >= 0
-        merged = dict(rows=rows[done], cols=cols[done], current=current[done], repaired=near[done])
-        table.write_cells(merged["rows"], merged["cols"], merged["repaired"])     # model.py `_repair_attrs(repaired_by_rules_df, ..)`
-        rows, cols, current = rows[~done], cols[~done], current[~done]
-    dirty_rows = table.rows_of_cells(rows)                      # model.py:549-553
-    out = dict(rows=rows, cols=cols, current=current, dirty_rows=dirty_rows, models={}, stats=[])
-    if rules is not None:
-        out.update(rule_steps=[], merged=merged)
-    if domain_info is not None:
-        out["domain"] = domain_info
-    if value_detectors:
-        out["value_detectors"] = _detector_report(value_detectors)
-    if len(rows) == 0:
-        out.update(repaired=np.zeros(0, np.int32), repaired_value=np.zeros(0, np.float64), prob=np.zeros(0, np.float64),
-                   times=dict(detect=t_detect, prepare=time.perf_counter() - t0))
-        return out
-    dirty_tab = table.gather_rows(dirty_rows)
-    pmf_tab = table.gather_rows(dirty_rows) if want_pmf else None      # stays un-repaired: pmf mode does not chain (SURVEY 3.3(c))
-    label_counts = {}
-    rule_steps = {}
+    table.null_cells(rows, cols, targets)
+    if nearest is None or not len(rows):
+        return rows, cols, current, None, table.rows_of_cells(rows)
+    near = nearest_value_merges(engine, table, targets, rows, cols, current, nearest)
+    done = near >= 0
+    merged = dict(rows=rows[done], cols=cols[done], current=current[done], repaired=near[done])
+    table.write_cells(merged["rows"], merged["cols"], merged["repaired"])
+    return rows[~done], cols[~done], current[~done], merged, table.rows_of_cells(rows[~done])
+
+
+def _target_plan(table, targets, continuous, rules, only_noisy_targets, second_pass):
+    """Phase 3: what answers each target on the NULLed table.  Returns (label counts {model target: rows per class}, rule steps {target:
+    dict(x, lut, kind='fd' | 'constant')}, the chain: the targets in prediction order).
+
+    rules      : None, or dict(fd={target: source column}): the target is answered by the functional dependency source -> target
+                 (`Table.fd_map` on the whole NULLed table) unless it is left with fewer than two classes; such a discrete target gets a
+                 constant step (its one live class, or NULL) instead of NotResidentEligible.  Rule targets are not trained, and the chain runs
+                 the other targets in target order, then each FD target once its source is no longer pending (`_resolve_prediction_order`).
+    only_noisy_targets: every label of a discrete model target must still have a training row -- `RepairModel.run()` with detection on the
+                 device: the cells are not known when the dictionaries are built, so a value that only error cells held would stay behind
+                 as a class without rows (num_class enters the softmax hessian factor); DeadClasses then carries `second_pass`: every detected
+                 cell (the pruned ones), the domain summary and the detector report, so that the second pass does not analyse again.
+    A continuous target needs one non-NULL row, a discrete one two classes (the reference's `PoorModel`, model.py:1008-1017, is the
+    constant step of `rules`); NotResidentEligible otherwise."""
+    label_counts, rule_steps = {}, {}
     fd = dict(rules.get("fd") or {}) if rules is not None else {}
     for t in targets:
         cnt, _ = table.count_codes(t)
@@ -636,10 +600,7 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
             rule_steps[t] = dict(x=int(fd[t]), lut=np.asarray(table.fd_map(int(fd[t]), t), np.int32), kind="fd")
             continue
         elif only_noisy_targets and len(live) < len(cnt):
-            e = DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, len(cnt) - len(live), len(cnt)), *detected)
-            e.domain_info = domain_info          # the cells it carries are the pruned ones: the second pass does not analyse again
-            e.value_detectors = out.get("value_detectors")
-            raise e
+            raise DeadClasses("target column %d: %d of its %d values are held by error cells only" % (t, len(cnt) - len(live), len(cnt)), **second_pass)
         elif len(live) < 2 and rules is not None:
             # PoorModel (model.py:1008-1017): the one live class, or NULL when the column has no value left
             rule_steps[t] = dict(x=-1, lut=np.array([live[0] if len(live) else -1], np.int32), kind="constant")
@@ -648,28 +609,44 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
             raise NotResidentEligible("target column %d has fewer than two classes among its non-NULL rows; the reference short-cuts such "
                              "attributes with a constant model (model.py:1008-1017) -- drop it from `targets`" % t)
         label_counts[t] = cnt
-    if rule_steps:
-        # `_resolve_prediction_order`: the other targets in target order, then each FD target once its source is no longer pending
-        pending = [t for t in targets if rule_steps.get(t, {}).get("kind") == "fd"]
-        targets = [t for t in targets if t not in pending]
-        while pending:
-            ready = [t for t in pending if rule_steps[t]["x"] not in pending]
-            if not ready:
-                raise NotResidentEligible("the functional dependencies of target columns %s form a cycle" % pending)
-            targets += ready
-            pending = [t for t in pending if t not in ready]
-    t_prep = time.perf_counter() - t0
-    y_values = {t: np.asarray(continuous[t][0], np.float64) for t in targets if t in continuous}
-    integral = {t for t in targets if t in continuous and continuous[t][1]}
-    train_tables = {}
+    pending = [t for t in targets if rule_steps.get(t, {}).get("kind") == "fd"]
+    chain = [t for t in targets if t not in pending]
+    while pending:
+        ready = [t for t in pending if rule_steps[t]["x"] not in pending]
+        if not ready:
+            raise NotResidentEligible("the functional dependencies of target columns %s form a cycle" % pending)
+        chain += ready
+        pending = [t for t in pending if t not in ready]
+    return label_counts, rule_steps, chain
+
+
+def _training_tables(engine, table, dirty_tab, model_targets, continuous, label_counts, base_params, train_rows, rebalance, check_unseen,
+                     distinct_training_rows, search_opts):
+    """Phase 4: the table each of `model_targets` trains on where that is not the whole NULLed table.  Returns ({target: table}, the label
+    counts with those of such tables, `rebalanced` {target: dict(median, rows, synthetic, classes)} or None, the distinct-row table or
+    None (the caller closes it), its report or None).
+
+    train_rows : {target: row positions} or a callable (target, positions of its non-NULL rows) -> positions -- train that
+                 target's model on these rows only (model.max_training_row_num sampling, model.py:755-766); default: every row
+                 whose target cell is not NULL.
+    rebalance  : None (off) or dict(k=5, random_state=42[, names, class_names: callables for the log]) -- `setTrainingDataRebalancingEnabled`:
+                 every discrete target that is trained trains on its rebalanced table (`rebalanced_training_table`: SMOTEN on the device, the
+                 draws on the host), made from its `train_rows` in the order given (the sampler's) or from all its non-NULL rows.  The class
+                 weights, the unseen-category check and the hyper-parameter search see that table.
+    check_unseen: False, True or the ordered columns: raise UnseenCategories when a dirty row holds a category no training row of the
+                 target has (`unseen_categories`).
+    distinct_training_rows: None (off) or dict(max_ratio=float) -- train the targets that qualify on the DISTINCT rows of the NULLed table with
+                 their multiplicities (`distinct_training_tables`: one `Table.distinct_rows()` call on the device); same models, bytes
+                 included.  Taken after the error cells are NULLed, the merges written back, the label counts taken from the whole table and
+                 the unseen-category check made on it: the distinct table holds rows whose target cell is NULL too (the trainer skips them,
+                 as on the whole table)."""
+    train_tables, counts = {}, dict(label_counts)
     if callable(train_rows):
-        picked = {}
-        for t in [t for t in targets if t not in rule_steps]:
-            r = train_rows(t, np.flatnonzero(table.read_column(t) >= 0))
-            if r is not None:
-                picked[t] = r
-        train_rows = picked
-    rebalanced = {}
+        picked = {t: train_rows(t, np.flatnonzero(table.read_column(t) >= 0)) for t in model_targets}
+        sampled = {t: r for t, r in picked.items() if r is not None}
+    else:
+        sampled = dict(train_rows or {})
+    rebalanced = None
     if rebalance is not None:
         if not hasattr(table, "smoten"):
             raise NotResidentEligible("rebalancing: the engine's table has no smoten")
@@ -678,31 +655,38 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
             raise NotResidentEligible("rebalancing: a multi-rank job does not rebalance its row shards")
         spec = dict(rebalance)
         names, class_names = spec.pop("names", None), spec.pop("class_names", None)
-        for t in [t for t in targets if t not in rule_steps and t not in continuous]:
-            train_tables[t], plan = rebalanced_training_table(table, t, rows=(train_rows or {}).get(t), name=names(t) if names else None,
+        rebalanced = {}
+        for t in [t for t in model_targets if t not in continuous]:
+            train_tables[t], plan = rebalanced_training_table(table, t, rows=sampled.get(t), name=names(t) if names else None,
                                                               class_names=class_names(t) if class_names else None, **spec)
-            label_counts[t] = train_tables[t].count_codes(t)[0]
+            counts[t] = train_tables[t].count_codes(t)[0]
             rebalanced[t] = dict(median=plan["median"], rows=int(train_tables[t].n), synthetic=int(len(plan["picks"])),
                                  classes=[int(c) for c in plan["classes"]])
-        out["rebalanced"] = rebalanced
-    if train_rows:
-        for t, r in train_rows.items():
-            if t in rebalanced:
-                continue
+    for t, r in sampled.items():
+        if t not in (rebalanced or {}):
             train_tables[t] = table.gather_rows(np.sort(np.asarray(r, np.int64)))
-            label_counts[t] = train_tables[t].count_codes(t)[0]
+            counts[t] = train_tables[t].count_codes(t)[0]
     if check_unseen:
-        gone = unseen_categories(table, dirty_tab, [t for t in targets if t not in rule_steps], train_tables=train_tables, ordered_cols=set(continuous) | set(check_unseen if not isinstance(check_unseen, bool) else ()))
+        ordered = set(continuous) | set(check_unseen if not isinstance(check_unseen, bool) else ())
+        gone = unseen_categories(table, dirty_tab, model_targets, train_tables=train_tables, ordered_cols=ordered)
         if gone:
             raise UnseenCategories("%d (target, feature) pairs hold categories no training row has, e.g. target column %d / feature column %d"
                                    % (len(gone), gone[0][0], gone[0][1]))
-    distinct_tab = None
+    distinct_tab, distinct_info = None, None
     if distinct_training_rows is not None:
-        # after the error cells are NULLed, the merges written back, the label counts taken from the whole table and the unseen-category
-        # check made on it: the distinct table holds rows whose target cell is NULL too (the trainer skips them, as on the whole table)
-        distinct_tab, out["distinct_rows"] = distinct_training_tables(engine, table, [t for t in targets if t not in rule_steps], base_params,
-                                                                      distinct_training_rows, train_tables, search_opts, continuous,
-                                                                      rebalanced=rebalanced)
+        distinct_tab, distinct_info = distinct_training_tables(engine, table, model_targets, base_params, distinct_training_rows, train_tables,
+                                                               search_opts, continuous, rebalanced=rebalanced or {})
+    return train_tables, counts, rebalanced, distinct_tab, distinct_info
+
+
+def _train_and_repair(engine, table, dirty_tab, chain, label_counts, base_params, want_stats, y_values, integral, train_tables, search_opts,
+                      rule_steps, distinct_tab, distinct_info):
+    """Phase 5: `run_job`.  A fit the trainer refuses on the distinct table trains on the whole one (`fallback_tables`) and moves to
+    `skipped` of `distinct_info` with the trainer's message; the distinct table is closed either way.
+
+    search_opts: reference option dict (model.hp.*, model.cv.n_splits): run the hyper-parameter search of every target on the
+                 resident tables before its final fit (`search_on_table`); None = the fixed parameters."""
+    n_codes = np.asarray(table.n_codes, np.int32)
     search = None
     if search_opts is not None:
         def search(t, tab):
@@ -712,36 +696,103 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         from repair.train import search_fits_in_flight
         search.fits_in_flight = search_fits_in_flight(search_opts)
     try:
-        res = run_job(engine, table, dirty_tab, n_codes, targets, label_counts, base_params, want_stats=want_stats,
+        res = run_job(engine, table, dirty_tab, n_codes, chain, label_counts, base_params, want_stats=want_stats,
                       y_values=y_values, integral=integral, train_tables=train_tables, param_search=search, rule_steps=rule_steps,
-                      fallback_tables={t: table for t in out["distinct_rows"]["used_for"]} if distinct_tab is not None else None)
+                      fallback_tables={t: table for t in distinct_info["used_for"]} if distinct_tab is not None else None)
     finally:
         if distinct_tab is not None and hasattr(distinct_tab, "close"):
             distinct_tab.close()
     for t, why in (res.get("fell_back") or {}).items():          # the trainer refused the distinct table for this fit: it trained on the whole one
-        d = out["distinct_rows"]
-        d["used_for"] = [u for u in d["used_for"] if u != t]
-        d["skipped"][t] = "the trainer refused the distinct table: %s" % why
+        distinct_info["used_for"] = [u for u in distinct_info["used_for"] if u != t]
+        distinct_info["skipped"][t] = "the trainer refused the distinct table: %s" % why
         _logger.info("[Repair Model Training Phase] target column %d trained on the whole table after all: %s" % (t, why))
-    # flatten + join with the error cells (RepairMiscApi.scala:41-49, model.py:1398-1401)
-    t0 = time.perf_counter()
+    return res
+
+
+def _shape(engine, table, dirty_tab, pmf_tab, res, chain, rows, cols, current, dirty_rows, rule_steps, want_rule_steps, continuous, y_values,
+           integral, want_pmf, top_k, threshold, pmf_costs):
+    """Phase 6: flatten + join with the error cells (RepairMiscApi.scala:41-49, model.py:1398-1401).  Returns the per-cell entries of the
+    result: repaired, repaired_value, prob, models, stats[, rule_steps][, the entries of `cell_pmfs`].
+
+    pmf_costs  : (want_pmf) the probability modes of RepairModel.run(): a callable (target, ascending row positions of its error cells)
+                 -> dict(cost [R + 1][K] float64 or None, cost_row [cells] int32 (-1 = no cost), cur_code [cells] int32 (the current
+                 value's class, -1 = none), weight, renormalise) or None, handed to `Table.repair_pmf_weighted`; adds `top1_cost` and
+                 `pmf_value`.  With it the pmf table is chained as the value-space `_repair` chains it (model.py): in target order, a
+                 continuous target's prediction fills its NULL cells before the later targets are scored (`pmf_value` holds it),
+                 discrete targets stay NULL."""
     tpos = np.full(table.c, -1, np.int64)
-    tpos[targets] = np.arange(len(targets))
+    tpos[chain] = np.arange(len(chain))
     pos = np.searchsorted(dirty_rows, rows)
     repaired = res["labels"][tpos[cols], pos].astype(np.int32)
     prob = res["probs"][tpos[cols], pos] if res["probs"] is not None else None
     repaired_value = res["values"][tpos[cols], pos] if res.get("values") is not None else np.full(len(rows), np.nan)
-    out.update(repaired=repaired, repaired_value=repaired_value, prob=prob, models=res["models"], stats=res["stats"])
-    if rules is not None:
+    out = dict(repaired=repaired, repaired_value=repaired_value, prob=prob, models=res["models"], stats=res["stats"])
+    if want_rule_steps:
         out["rule_steps"] = [rule_step_summary(table, t, rule_steps[t], rows[cols == t], dirty_rows, dirty_tab, repaired[cols == t])
-                             for t in targets if t in rule_steps]
+                             for t in chain if t in rule_steps]
     if want_pmf:
-        out.update(cell_pmfs(engine, table, pmf_tab, targets, res["models"], rows, cols, current, dirty_rows, continuous, y_values, integral,
+        out.update(cell_pmfs(engine, table, pmf_tab, chain, res["models"], rows, cols, current, dirty_rows, continuous, y_values, integral,
                              top_k, threshold, pmf_costs))
-    t_shape = time.perf_counter() - t0
-    times = dict(res["times"])
-    times.update(detect=t_detect, prepare=t_prep, shape=t_shape)
-    out["times"] = times
+    return out
+
+
+def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
+                 want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
+                 check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
+                 value_detectors=None, distinct_training_rows=None, rebalance=None, regex_cols=None):
+    """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).  The phases, and where each
+    parameter is described: `_detect_and_prune` (constraints, detect_nulls and error_cells as `detect_error_cells` takes them,
+    only_noisy_targets, domain_analysis, value_detectors, regex_cols), `_null_and_merge` (rules['nearest']: `nearest_value_merges`),
+    `_target_plan` (rules['fd'], only_noisy_targets), `_training_tables` (train_rows, rebalance, check_unseen, distinct_training_rows),
+    `_train_and_repair` (search_opts), `_shape` (want_pmf, top_k, threshold, pmf_costs).
+
+    continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
+                 double in the reference, RepairBase.scala:41-44): repaired by an L2 regressor on the values behind their codes
+                 (train.py:97-100), integral ones rounded (model.py:1130-1132); `repaired_value` carries the prediction.
+    rules      : the rule-based repairs of `RepairModel.setRepairByRules`, None = none of them: dict(fd={target: source column},
+                 nearest=None or the dict of `nearest_value_merges`).  Merged cells leave the error cells (`merged` holds them).
+    want_stats : with `distinct_training_rows`, the stats of a target trained on the distinct table describe that fit (its M rows).
+    Returns dict(rows, cols, current, repaired, repaired_value, prob[, pmf_class, pmf_prob, current_prob[, top1_cost, pmf_value]],
+    dirty_rows, models, times, stats[, domain][, rule_steps, merged][, value_detectors][, distinct_rows][, rebalanced]): one entry per error cell,
+    ordered by (column, row).
+    """
+    continuous = dict(continuous or {})
+    det_rows, det_cols, run_targets, domain_info, detectors, t_detect = _detect_and_prune(
+        table, [int(t) for t in targets], constraints, detect_nulls, error_cells, only_noisy_targets, domain_analysis, value_detectors, regex_cols)
+    t_null = time.perf_counter()
+    rows, cols, current, merged, dirty_rows = _null_and_merge(engine, table, run_targets, det_rows, det_cols,
+                                                              rules.get("nearest") if rules is not None else None)
+    out = dict(rows=rows, cols=cols, current=current, dirty_rows=dirty_rows, models={}, stats=[])
+    if rules is not None:
+        out.update(rule_steps=[], merged=merged)
+    if domain_info is not None:
+        out["domain"] = domain_info
+    if detectors:
+        out["value_detectors"] = _detector_report(detectors)
+    if len(rows) == 0:
+        out.update(repaired=np.zeros(0, np.int32), repaired_value=np.zeros(0, np.float64), prob=np.zeros(0, np.float64),
+                   times=dict(detect=t_detect, prepare=time.perf_counter() - t_null))
+        return out
+    dirty_tab = table.gather_rows(dirty_rows)
+    pmf_tab = table.gather_rows(dirty_rows) if want_pmf else None      # stays un-repaired: pmf mode does not chain (SURVEY 3.3(c))
+    label_counts, rule_steps, chain = _target_plan(table, run_targets, continuous, rules, only_noisy_targets,
+                                                   dict(rows=det_rows, cols=det_cols, domain_info=domain_info, value_detectors=out.get("value_detectors")))
+    t_prep = time.perf_counter() - t_null
+    y_values = {t: np.asarray(continuous[t][0], np.float64) for t in chain if t in continuous}
+    integral = {t for t in chain if t in continuous and continuous[t][1]}
+    train_tables, train_counts, rebalanced, distinct_tab, distinct_info = _training_tables(
+        engine, table, dirty_tab, [t for t in chain if t not in rule_steps], continuous, label_counts, base_params, train_rows, rebalance,
+        check_unseen, distinct_training_rows, search_opts)
+    if rebalanced is not None:
+        out["rebalanced"] = rebalanced
+    if distinct_info is not None:
+        out["distinct_rows"] = distinct_info
+    res = _train_and_repair(engine, table, dirty_tab, chain, train_counts, base_params, want_stats, y_values, integral, train_tables,
+                            search_opts, rule_steps, distinct_tab, distinct_info)
+    t_shape = time.perf_counter()
+    out.update(_shape(engine, table, dirty_tab, pmf_tab, res, chain, rows, cols, current, dirty_rows, rule_steps, rules is not None,
+                      continuous, y_values, integral, want_pmf, top_k, threshold, pmf_costs))
+    out["times"] = dict(res["times"], detect=t_detect, prepare=t_prep, shape=time.perf_counter() - t_shape)
     return out
 
 
@@ -749,30 +800,207 @@ def encode_frame(df, columns):
     """Dictionary encoding of the listed columns: (indices [C][n] int32 with -1 = NULL, remaps, dictionaries).
 
     `remaps[c][i]` is the code of dictionary entry i: its rank among the column's distinct values in ascending order
-    (strings by code point, numbers numerically) -- the contract of repair.encode, so codes mean the same on both paths.
-    The per-row work (value -> dictionary index in order of first appearance) is one hash pass per column (`pandas.factorize`:
-    42 ms per 10^6 string cells, against 67-105 ms for an Arrow `dictionary_encode` of the same column); the index -> code gather
-    runs on the device (`Table.from_dictionaries`)."""
+    (strings by code point, numbers numerically) -- the contract of repair.encode, so codes mean the same on both paths;
+    `repair.frame_encoding.FrameEncoding` states it and holds the three while `repair_frame` edits them."""
+    enc = FrameEncoding.of_frame(df, columns)
+    return enc.indices, enc.remaps, enc.dicts
+
+
+def _cell_positions(enc, df, row_id, error_cells):
+    """An error-cell frame (`row_id`, `attribute`) -> (row positions, column positions); cells of unknown rows / attributes drop out
+    (join semantics)."""
     import pandas as pd
-    idx, remaps, dicts = [], [], []
-    for c in columns:
-        s = df[c]
-        numeric = pd.api.types.is_numeric_dtype(s) and not pd.api.types.is_bool_dtype(s)
-        if numeric:
-            codes, uniq = pd.factorize(s.to_numpy(dtype="float64", na_value=np.nan), use_na_sentinel=True)
-        else:
-            # one hash pass per column and run: inside RepairModel.run() the NULL detector / domain statistics have factorised the column
-            # already (repair.utils.column_code_cache); categorical / Arrow-backed columns factorise through their own dictionary or buffer
-            from repair.utils import column_factorize
-            codes, uniq = column_factorize(df, c)
-        vals = np.asarray(uniq, dtype=np.float64 if numeric else object)
-        order = np.argsort(vals, kind="stable")
-        remap = np.empty(len(vals), np.int32)
-        remap[order] = np.arange(len(vals), dtype=np.int32)
-        idx.append(codes.astype(np.int32, copy=False))
-        remaps.append(remap)
-        dicts.append(vals[order])
-    return (np.stack(idx) if idx else np.zeros((0, len(df)), np.int32)), remaps, dicts
+    if row_id not in error_cells.columns or "attribute" not in error_cells.columns:
+        raise ValueError("Error cells should have `%s` and `attribute` in columns" % row_id)
+    rpos = pd.Series(np.arange(len(df)), index=df[row_id].to_numpy()).reindex(error_cells[row_id].to_numpy()).to_numpy(np.float64)
+    cpos = np.array([enc.pos.get(a, -1) for a in error_cells["attribute"]], np.int64)
+    ok = ~np.isnan(rpos) & (cpos >= 0)
+    return rpos[ok].astype(np.int64), cpos[ok].astype(np.int32)
+
+
+def _known_cells(engine, enc, target_cols, kr, kc, regex_rules):
+    """The error cells (kr, kc) are known before the table is (re)built: regex-structure repair of those it applies to (the DISTINCT
+    current-value strings of each rule's cells go through `engine.regex_structure`; the first rule that repairs a cell wins), every cell of
+    a target column NULLed in the encoding and the classes only they held dropped (the reference NULLs every error cell and then writes the
+    rule repairs, model.py `_repair_attrs`), the repaired values written back.  Returns (the repaired cells: dict(rows, cols, current,
+    repaired: strings), the remaining cells (rows, cols))."""
+    from repair.regex_structure import repair_cells
+    done = np.zeros(len(kr), bool)
+    cur_s, rep_s = np.empty(len(kr), object), np.empty(len(kr), object)
+    for r in regex_rules:
+        j = enc.pos.get(r["attr"])
+        sel = np.flatnonzero((kc == j) & ~done) if j is not None and j in target_cols else np.zeros(0, np.int64)
+        if not len(sel):
+            continue
+        raw = list(r["current"](enc.columns[j], kr[sel])) if r.get("current") is not None else list(enc.values(kr[sel], j))
+        strs = r["current_str"](enc.columns[j], raw)
+        values, skipped = repair_cells(r["program"], strs, engine.regex_structure)
+        if skipped:
+            _logger.info("[Repairing Phase] %d cells of `%s` hold a line terminator: left to the models" % (skipped, enc.columns[j]))
+        for i, sv, v in zip(sel, strs, values):
+            if v is not None:
+                done[i], cur_s[i], rep_s[i] = True, sv, v
+    in_targets = np.isin(kc, target_cols)
+    enc.null_cells(kr[in_targets], kc[in_targets], prune=target_cols)
+    for j in np.unique(kc[done]):
+        at = np.flatnonzero(done & (kc == j))
+        enc.write(j, kr[at], rep_s[at])
+    return dict(rows=kr[done], cols=kc[done], current=cur_s[done], repaired=rep_s[done]), (kr[~done], kc[~done])
+
+
+def _nearest_current(enc, nv, t, rows, codes):
+    """The current-value strings of cells of column t for the nearest-value rule `nv`: the caller's where it holds them already."""
+    if nv.get("current") is not None:
+        return nv["current"](enc.columns[t], rows)
+    return nv["current_str"](enc.columns[t], list(enc.current_values(rows, np.full(len(rows), t, np.int32), codes)))
+
+
+def _column_space(engine, enc, df, targets, constraints, detect_nulls, analyse, keep_weak, continuous_columns=(), train_rows=None,
+                  check_unseen=False, pmf_costs=None, domain_analysis=None, rules=None, value_detectors=None, rebalance=None):
+    """The arguments of `repair_frame` that speak of attributes by NAME as `repair_table` takes them, by column position and code, against the
+    dictionaries the table was just built from: constraints, continuous, train_rows, check_unseen, pmf_costs, domain_analysis, rules,
+    value_detectors (`analyse`: not on a second pass, which detects nothing) and rebalance.  Returns them as keywords."""
+    import pandas as pd
+    cols, pos, dicts = enc.columns, enc.pos, enc.dicts
+    dtypes = {c: df[c].dtype for c in cols}
+    da_spec = None
+    if domain_analysis is not None and analyse:
+        ccols = domain_analysis.get("continuous_columns")
+        if ccols is None:
+            ccols = [c for j, c in enumerate(cols) if dicts[j].dtype != object]
+        da_spec = dict(options=domain_analysis.get("options") or {}, discrete_thres=domain_analysis["discrete_thres"],
+                       domain_stats=[len(d) for d in dicts], keep_weak=keep_weak,
+                       continuous={pos[c]: np.asarray(dicts[pos[c]], np.float64) for c in ccols if c in pos and dicts[pos[c]].dtype != object})
+    cons = []
+    for con in constraints:
+        if isinstance(con, tuple):
+            cons.append(([pos[x] for x in con[0]], pos[con[1]]))
+        else:                                  # a parsed constraint: lowered against the dictionaries the table is built from
+            from repair.dc_codes import NotLowerable, lower_constraint
+            try:
+                cons.append(lower_constraint(con, cols, dicts, dtypes))
+            except NotLowerable as e:
+                raise NotResidentEligible("denial constraint %s: %s" % (con, e))
+    cont = {pos[c]: (np.asarray(dicts[pos[c]], np.float64), pd.api.types.is_integer_dtype(df[c])) for c in continuous_columns
+            if c in pos and c in targets}
+    table_rules = None
+    if rules is not None:
+        table_rules = dict(fd={pos[y]: pos[x] for y, x in dict(rules.get("fd") or {}).items()}, nearest=None)
+        nv = rules.get("nearest")
+        if nv is not None:
+            table_rules["nearest"] = dict(targets=[pos[a] for a in nv["targets"] if a in pos], threshold=nv["threshold"], cost=nv.get("cost"),
+                                          current=lambda t, rows, codes: _nearest_current(enc, nv, t, rows, codes),
+                                          domain=lambda t, live: nv["domain_str"](cols[t], list(dicts[t][live])))
+    detectors = None
+    if analyse and value_detectors and value_detectors.get("detectors"):
+        build = value_detectors.get("build")
+        if build is None:
+            from repair.detect_codes import build_descriptors as build
+        dets = list(value_detectors["detectors"])
+        # the LOF kind evaluates the filled column: it needs the NULL count (rows minus the counted ones) and the engine's `lof_codes`
+        extra = dict(lof=getattr(engine, "lof_codes", None), n_rows=len(df)) if any(d["kind"] == "lof" for d in dets) else {}
+
+        def detectors(table):
+            return build(dets, cols, dicts, dtypes, lambda j: table.count_codes(j)[0], list(targets), null_all=bool(detect_nulls), **extra)
+    numeric = [pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])]
+    return dict(constraints=cons, detect_nulls=detect_nulls, continuous=cont, domain_analysis=da_spec, rules=table_rules, value_detectors=detectors,
+                pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
+                rebalance=dict(rebalance, names=lambda t: cols[t], class_names=lambda t: dicts[t]) if rebalance is not None else None,
+                check_unseen=(numeric or True) if check_unseen else False,
+                train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
+
+
+def _upload(engine, enc):
+    """The table of the encoding, with the column kinds and values the trainer bins by."""
+    table = engine.upload_dictionaries(enc.indices, enc.remaps)
+    for j, d in enumerate(enc.dicts):              # numeric columns: bin bounds at the midpoints of the values, like LightGBM on raw numbers
+        if d.dtype != object and len(d) > 0:
+            table.set_column_values(j, d)
+        elif d.dtype == object:
+            table.set_column_kind(j, True)         # categories a model's training rows do not show are missing for that model
+    return table
+
+
+def _upload_and_run(engine, enc, df, targets, cells, regex_rules, by_name, through, analyse=True):
+    """One pass: upload the encoding, `repair_table` on it.  `cells`: the known error cells or None; `by_name` / `through`: the keywords of
+    `_column_space` / those `repair_table` takes as they are.  Returns (the continuous targets {column: (values, is_integral)}, result)."""
+    table = _upload(engine, enc)
+    kw = _column_space(engine, enc, df, targets, analyse=analyse, **by_name)
+    regex_cols = [enc.pos[r["attr"]] for r in regex_rules if r["attr"] in enc.pos] if cells is None else None
+    return kw["continuous"], repair_table(engine, table, [enc.pos[t] for t in targets], error_cells=cells, regex_cols=regex_cols, **through, **kw)
+
+
+def _result_frame(enc, df, row_id, res, cont, want_pmf, with_costs):
+    """(row_id, attribute, current_value, repaired[, prob][, pmf, current_prob[, top1_cost, pmf_value]]) of the repaired cells."""
+    import pandas as pd
+    rows, ccols = res["rows"], res["cols"]
+    repaired = enc.decode(res["repaired"], ccols)
+    for j, (_, is_int) in cont.items():                       # continuous attributes: the regressor's value, not a dictionary entry
+        sel = ccols == j
+        v = res["repaired_value"][sel]
+        repaired[sel] = [int(x) for x in v] if is_int else [float(x) for x in v]
+    frame = pd.DataFrame({row_id: df[row_id].to_numpy()[rows], "attribute": np.asarray(enc.columns, object)[ccols],
+                          "current_value": enc.current_values(rows, ccols, res["current"]), "repaired": repaired})
+    if res.get("prob") is not None:
+        frame["prob"] = res["prob"]
+    if want_pmf and len(rows):
+        pc, pp = res["pmf_class"], res["pmf_prob"]
+        frame["pmf"] = [[{"class": enc.dicts[ccols[i]][k], "prob": float(p)} for k, p in zip(pc[i], pp[i]) if k >= 0] for i in range(len(rows))]
+        frame["current_prob"] = res["current_prob"]
+        if with_costs:
+            frame["top1_cost"] = res["top1_cost"]
+            pval = np.empty(len(rows), object)
+            pval[:] = None
+            for j, (_, is_int) in cont.items():
+                sel = np.flatnonzero(ccols == j)
+                v = res["pmf_value"][sel]
+                pval[sel] = [None if np.isnan(x) else (int(x) if is_int else float(x)) for x in v]
+            frame["pmf_value"] = pval
+    return frame
+
+
+def _cell_frame(enc, df, row_id, rows, cols, current, repaired):
+    import pandas as pd
+    return pd.DataFrame({row_id: df[row_id].to_numpy()[rows], "attribute": np.asarray(enc.columns, object)[cols],
+                         "current_value": np.asarray(current, object), "repaired": np.asarray(repaired, object)})
+
+
+def _details(enc, df, row_id, res, rules, regex_done):
+    """`repair_table`'s report with attribute names for column positions; `regex_done`: the cells of `_known_cells`, or None."""
+    cols = enc.columns
+    details = dict(times=res.get("times", {}), stats=res.get("stats", []), models=res.get("models", {}), columns=cols)
+    if res.get("domain") is not None:
+        d = res["domain"]
+        details.update(pairwise_attr_stats={cols[t]: [(cols[y], h) for y, h in lst] for t, lst in d["pairwise"].items()},
+                       noisy_cells=d["noisy_cells"], weak_cells=d["weak_cells"])
+    if res.get("value_detectors"):
+        details["value_detectors"] = [dict(attribute=cols[d["col"]], kinds=d["kinds"], codes_flagged=d["codes_flagged"], cells=d["cells"])
+                                      for d in res["value_detectors"]]
+    if res.get("rebalanced") is not None:
+        details["rebalanced"] = {cols[t]: d for t, d in res["rebalanced"].items()}
+    if res.get("distinct_rows") is not None:
+        d = res["distinct_rows"]
+        details["distinct_rows"] = dict(rows=d["rows"], distinct=d["distinct"], used_for=[cols[t] for t in d["used_for"]],
+                                        skipped={cols[t]: why for t, why in d["skipped"].items()})
+    if rules is not None:
+        details["rule_steps"] = [dict(st, target=cols[st["target"]], x=cols[st["x"]] if st["x"] >= 0 else None) for st in res.get("rule_steps", [])]
+        mg = res.get("merged")
+        mcur, mrep, mrows, mcols = [], [], np.zeros(0, np.int64), np.zeros(0, np.int32)
+        if mg is not None and len(mg["rows"]):
+            nv = rules["nearest"]
+            mrows, mcols = mg["rows"], mg["cols"]
+            raw_rep = enc.decode(mg["repaired"], mcols)
+            mcur, mrep = np.empty(len(mrows), object), np.empty(len(mrows), object)
+            for j in np.unique(mcols):
+                sel = np.flatnonzero(mcols == j)
+                mcur[sel] = _nearest_current(enc, nv, j, mrows[sel], mg["current"][sel])
+                mrep[sel] = nv["domain_str"](cols[j], list(raw_rep[sel]))
+        details["merged_cells"] = _cell_frame(enc, df, row_id, mrows, mcols, mcur, mrep)
+        details["nearest_values"] = {cols[j]: int((mcols == j).sum()) for j in np.unique(mcols)}
+        if regex_done is not None:
+            details["regex_cells"] = _cell_frame(enc, df, row_id, regex_done["rows"], regex_done["cols"], regex_done["current"], regex_done["repaired"])
+            details["regex_repairs"] = {cols[j]: int((regex_done["cols"] == j).sum()) for j in np.unique(regex_done["cols"])}
+    return details
 
 
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
@@ -825,289 +1053,57 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
 
     rebalance: None or dict(k=5, random_state=42), as `repair_table` takes it.  A column whose dictionary is not in the order of its sorted
     values (mixed types) raises NotResidentEligible; the details hold `rebalanced` {attribute: dict(median, rows, synthetic, classes)}."""
-    import pandas as pd
     cols = [c for c in df.columns if c != row_id]
     targets = list(targets) if targets is not None else list(cols)
     unknown = [t for t in targets if t not in cols]
     if unknown:
         raise ValueError("Target attributes not found in the input: %s" % ",".join(unknown))
-    indices, remaps, dicts = encode_frame(df, cols)
+    enc = FrameEncoding.of_frame(df, cols)
     if rebalance is not None:
         from repair.rebalance_codes import check_dictionary_order
         for j, c in enumerate(cols):
-            check_dictionary_order(dicts[j], "`%s`" % c)
-    pos = {c: i for i, c in enumerate(cols)}
-    dtypes = {c: df[c].dtype for c in cols}
-    cells, given_current = None, None
-
-    def null_known_cells(kr, kc):
-        """The cells (row positions kr, column indices kc) are known before the table is (re)built: NULL them in the dictionary
-        indices and drop the values that ONLY they held from the dictionaries of the target attributes -- the reference counts a
-        target's classes over the frame with the error cells removed (model.py:1005, count(distinct y)), and num_class enters the
-        softmax hessian factor K / (K - 1): a dead class would change every tree.  Returns (keys, values): what the cells held."""
-        tset = {pos[t] for t in targets}
-        sel = np.isin(kc, list(tset))
-        gr, gc = kr[sel], kc[sel]
-        gv = np.empty(len(gr), object)                          # the values the cells hold now: `current_value` of the result
-        for j in np.unique(gc):
-            m = gc == j
-            idx = indices[j, gr[m]]
-            v = np.empty(int(m.sum()), object)
-            v[idx >= 0] = dicts[j][remaps[j][idx[idx >= 0]]]
-            v[idx < 0] = None
-            gv[m] = v
-        indices[gc, gr] = -1
-        for j in sorted(tset):
-            live = np.bincount(indices[j][indices[j] >= 0], minlength=len(remaps[j])) > 0
-            if not live.all():
-                live_codes = np.sort(remaps[j][live])                     # surviving old codes, ascending
-                new = np.zeros(len(remaps[j]), np.int32)
-                new[live] = np.searchsorted(live_codes, remaps[j][live]).astype(np.int32)
-                dicts[j] = dicts[j][live_codes]
-                remaps[j] = new
-        return gc.astype(np.int64) * len(df) + gr, gv
-
+            check_dictionary_order(enc.dicts[j], "`%s`" % c)
+    target_cols = sorted(enc.pos[t] for t in targets)
     regex_rules = list((rules or {}).get("regex") or [])
-    regex_done = dict(rows=np.zeros(0, np.int64), cols=np.zeros(0, np.int32), current=np.zeros(0, object), repaired=np.zeros(0, object))
-
-    def known_cells(kr, kc):
-        """The error cells are known: regex-structure repair of those it applies to, `null_known_cells` of all of them (the reference
-        NULLs every error cell and then writes the rule repairs, model.py `_repair_attrs`), the repaired values written into the
-        encoding.  Returns (the remaining cells, what all of them held)."""
-        from repair.regex_structure import repair_cells
-        done = np.zeros(len(kr), bool)
-        cur_s, rep_s = np.empty(len(kr), object), np.empty(len(kr), object)
-        tset = {pos[t] for t in targets}
-        for r in regex_rules:
-            j = pos.get(r["attr"])
-            sel = np.flatnonzero((kc == j) & ~done) if j is not None and j in tset else np.zeros(0, np.int64)
-            if not len(sel):
-                continue
-            if r.get("current") is not None:
-                raw = list(r["current"](cols[j], kr[sel]))
-            else:
-                idx = indices[j, kr[sel]]
-                raw = [dicts[j][remaps[j][i]] if i >= 0 else None for i in idx]
-            strs = r["current_str"](cols[j], raw)
-            values, skipped = repair_cells(r["program"], strs, engine.regex_structure)
-            if skipped:
-                _logger.info("[Repairing Phase] %d cells of `%s` hold a line terminator: left to the models" % (skipped, cols[j]))
-            for i, sv, v in zip(sel, strs, values):
-                if v is not None:
-                    done[i], cur_s[i], rep_s[i] = True, sv, v
-        held = null_known_cells(kr, kc)
-        for j in np.unique(kc[done]):
-            at = np.flatnonzero(done & (kc == j))
-            for v in dict.fromkeys(rep_s[at]):
-                k = int(np.searchsorted(dicts[j], v))
-                if k < len(dicts[j]) and dicts[j][k] == v:
-                    entry = int(np.flatnonzero(remaps[j] == k)[0])
-                else:                                                   # a new dictionary entry; the codes stay the ascending ranks
-                    remaps[j] = np.append(np.where(remaps[j] >= k, remaps[j] + 1, remaps[j]), np.int32(k)).astype(np.int32)
-                    entry = len(remaps[j]) - 1
-                    grown = np.empty(len(dicts[j]) + 1, object)
-                    grown[:k], grown[k], grown[k + 1:] = dicts[j][:k], v, dicts[j][k:]
-                    dicts[j] = grown
-                indices[j, kr[at[rep_s[at] == v]]] = entry
-        for key, part in (("rows", kr[done]), ("cols", kc[done]), ("current", cur_s[done]), ("repaired", rep_s[done])):
-            regex_done[key] = np.concatenate([regex_done[key], part])
-        return (kr[~done], kc[~done]), held
-
+    by_name = dict(continuous_columns=continuous_columns, train_rows=train_rows, check_unseen=check_unseen, pmf_costs=pmf_costs,
+                   domain_analysis=domain_analysis, rules=rules, value_detectors=value_detectors, rebalance=rebalance,
+                   keep_weak=error_cells is not None)
+    through = dict(base_params=dict(base_params or {}), want_pmf=want_pmf, top_k=top_k, threshold=threshold, search_opts=search_opts,
+                   only_noisy_targets=only_noisy_targets, distinct_training_rows=distinct_training_rows)
+    cells = None
+    regex_done = [dict(rows=np.zeros(0, np.int64), cols=np.zeros(0, np.int32), current=np.zeros(0, object), repaired=np.zeros(0, object))]
     if error_cells is not None:
-        if row_id not in error_cells.columns or "attribute" not in error_cells.columns:
-            raise ValueError("Error cells should have `%s` and `attribute` in columns" % row_id)
-        rpos = pd.Series(np.arange(len(df)), index=df[row_id].to_numpy()).reindex(error_cells[row_id].to_numpy()).to_numpy(np.float64)
-        cpos = np.array([pos.get(a, -1) for a in error_cells["attribute"]], np.int64)
-        ok = ~np.isnan(rpos) & (cpos >= 0)                      # cells of unknown rows / attributes drop out (join semantics)
-        cells, given_current = known_cells(rpos[ok].astype(np.int64), cpos[ok].astype(np.int32))
+        done, cells = _known_cells(engine, enc, target_cols, *_cell_positions(enc, df, row_id, error_cells), regex_rules)
+        regex_done.append(done)
     if error_cells is not None and not detect_nulls and not constraints and rules is None:
         # every error cell is known and NULLed: the class counts the models will see are final.  Say so BEFORE anything is uploaded
         # (a constraint / regex / user-given cell may hold the only occurrence of a class; an all-NULL numeric column has no value)
         for t in targets:
-            j = pos[t]
-            live = len(np.unique(indices[j][indices[j] >= 0]))
+            live = enc.live_classes(enc.pos[t])
             if live < (1 if t in continuous_columns else 2):
                 raise NotResidentEligible("target `%s` is left with %d distinct value(s) once the error cells are removed" % (t, live))
-
-    def decode(codes, col_idx):
-        out = np.empty(len(codes), object)
-        for j in np.unique(col_idx):
-            sel = col_idx == j
-            d = dicts[j]
-            c = codes[sel]
-            v = np.empty(len(c), object)
-            ok = c >= 0
-            v[ok] = d[c[ok]]
-            v[~ok] = None
-            out[sel] = v
-        return out
-
-    def current_values(rows_, ccols_, codes_):
-        """What the cells held: their codes decoded, or -- for cells NULLed on the host before the upload -- what `null_known_cells` kept."""
-        current = decode(codes_, ccols_)
-        if given_current is not None and len(rows_):
-            key = ccols_.astype(np.int64) * len(df) + rows_
-            order = np.argsort(given_current[0], kind="stable")
-            at = np.searchsorted(given_current[0][order], key)
-            at = np.clip(at, 0, max(len(order) - 1, 0))
-            hit = given_current[0][order][at] == key if len(order) else np.zeros(len(key), bool)
-            current[hit] = given_current[1][order][at[hit]]
-        return current
-
-    def cur_strings(t, rows_, codes_):
-        """The current-value strings of cells of column t for the nearest-value rule: the caller's where it holds them already."""
-        nv = rules["nearest"]
-        if nv.get("current") is not None:
-            return nv["current"](cols[t], rows_)
-        return nv["current_str"](cols[t], list(current_values(rows_, np.full(len(rows_), t, np.int32), codes_)))
-
-    def table_rules():
-        if rules is None:
-            return None
-        spec = dict(fd={pos[y]: pos[x] for y, x in dict(rules.get("fd") or {}).items()}, nearest=None)
-        nv = rules.get("nearest")
-        if nv is not None:
-            spec["nearest"] = dict(targets=[pos[a] for a in nv["targets"] if a in pos], threshold=nv["threshold"], cost=nv.get("cost"),
-                                   current=cur_strings, domain=lambda t, live: nv["domain_str"](cols[t], list(dicts[t][live])))
-        return spec
-
-    def table_detectors(detect_nulls_):
-        if not value_detectors or not value_detectors.get("detectors"):
-            return None
-        build = value_detectors.get("build")
-        if build is None:
-            from repair.detect_codes import build_descriptors as build
-        dets = list(value_detectors["detectors"])
-        # the LOF kind evaluates the filled column: it needs the NULL count (rows minus the counted ones) and the engine's `lof_codes`
-        extra = dict(lof=getattr(engine, "lof_codes", None), n_rows=len(df)) if any(d["kind"] == "lof" for d in dets) else {}
-        return lambda table: build(dets, cols, dicts, dtypes, lambda j: table.count_codes(j)[0], list(targets),
-                                   null_all=bool(detect_nulls_), **extra)
-
-    def build_and_run(cells_, detect_nulls_, constraints_, analyse=True):
-        table = engine.upload_dictionaries(indices, remaps)
-        da_spec = None
-        if domain_analysis is not None and analyse:
-            ccols_ = domain_analysis.get("continuous_columns")
-            if ccols_ is None:
-                ccols_ = [c for j, c in enumerate(cols) if dicts[j].dtype != object]
-            da_spec = dict(options=domain_analysis.get("options") or {}, discrete_thres=domain_analysis["discrete_thres"],
-                           domain_stats=[len(d) for d in dicts], keep_weak=error_cells is not None,
-                           continuous={pos[c]: np.asarray(dicts[pos[c]], np.float64) for c in ccols_ if c in pos and dicts[pos[c]].dtype != object})
-        for j, c in enumerate(cols):               # numeric columns: bin bounds at the midpoints of the values, like LightGBM on raw numbers
-            if dicts[j].dtype != object and len(dicts[j]) > 0:
-                table.set_column_values(j, dicts[j])
-            elif dicts[j].dtype == object:
-                table.set_column_kind(j, True)     # categories a model's training rows do not show are missing for that model
-        cons = []
-        for con in constraints_:
-            if isinstance(con, tuple):
-                cons.append(([pos[x] for x in con[0]], pos[con[1]]))
-            else:                                  # a parsed constraint: lowered against the dictionaries the table is built from
-                from repair.dc_codes import NotLowerable, lower_constraint
-                try:
-                    cons.append(lower_constraint(con, cols, dicts, dtypes))
-                except NotLowerable as e:
-                    raise NotResidentEligible("denial constraint %s: %s" % (con, e))
-        cont_ = {}
-        for c in continuous_columns:
-            if c in pos and c in targets:
-                cont_[pos[c]] = (np.asarray(dicts[pos[c]], np.float64), pd.api.types.is_integer_dtype(df[c]))
-        return cont_, repair_table(engine, table, [pos[t] for t in targets], dict(base_params or {}), constraints=cons, detect_nulls=detect_nulls_,
-                                   error_cells=cells_, want_pmf=want_pmf, top_k=top_k, threshold=threshold, continuous=cont_, search_opts=search_opts,
-                                   pmf_costs=(lambda t, r: pmf_costs(cols[t], dicts[t], r)) if pmf_costs is not None else None,
-                                   only_noisy_targets=only_noisy_targets, domain_analysis=da_spec, rules=table_rules(),
-                                   value_detectors=table_detectors(detect_nulls_) if analyse else None,
-                                   regex_cols=[pos[r["attr"]] for r in regex_rules if r["attr"] in pos] if cells_ is None else None,
-                                   distinct_training_rows=distinct_training_rows,
-                                   rebalance=dict(rebalance, names=lambda t: cols[t], class_names=lambda t: dicts[t]) if rebalance is not None else None,
-                                   check_unseen=([pos[c] for c in cols if pd.api.types.is_numeric_dtype(df[c]) and not pd.api.types.is_bool_dtype(df[c])] or True) if check_unseen else False,
-                                   train_rows=(lambda t, r: train_rows(cols[t], r)) if callable(train_rows) else train_rows)
-
     try:
-        cont, res = build_and_run(cells, detect_nulls, constraints)
+        cont, res = _upload_and_run(engine, enc, df, targets, cells, regex_rules, dict(by_name, constraints=constraints, detect_nulls=detect_nulls),
+                                    through)
     except DeadClasses as e:
         # Detection ran on the device; some values of a target were held by error cells only (a typo occurs once).  The cells are
         # known now: NULL them on the host side of the encoding, drop the dead values, upload the (cached) encoding again and go on
-        # with the cells as GIVEN -- no second detection, no pandas detectors, no value-space fallback (ADVICE r3).
+        # with the cells as GIVEN -- no second detection, no pandas detectors, no value-space fallback (ADVICE r3).  Cells of a user-given
+        # error_cells frame were NULLed before the first attempt: what they held is what the encoding recorded then (ADVICE r4).
         _logger.info("%s: re-encoding the target dictionaries without them" % e)
-        first = given_current
-        cells, given_current = known_cells(e.rows, e.cols)
-        if first is not None:
-            # cells of a user-given error_cells frame were NULLed before the first attempt: the second pass sees None there, the first
-            # one knows what they held (ADVICE r4)
-            fresh = ~np.isin(given_current[0], first[0])
-            given_current = (np.concatenate([first[0], given_current[0][fresh]]), np.concatenate([first[1], given_current[1][fresh]]))
-        cont, res = build_and_run(cells, False, (), analyse=False)
-        if getattr(e, "domain_info", None) is not None:
+        done, second = _known_cells(engine, enc, target_cols, e.rows, e.cols, regex_rules)
+        regex_done.append(done)
+        cont, res = _upload_and_run(engine, enc, df, targets, second, regex_rules, dict(by_name, constraints=(), detect_nulls=False), through,
+                                    analyse=False)
+        if e.domain_info is not None:
             res["domain"] = e.domain_info
-        if getattr(e, "value_detectors", None):
+        if e.value_detectors:
             res["value_detectors"] = e.value_detectors
-    rows, ccols = res["rows"], res["cols"]
-    repaired = decode(res["repaired"], ccols)
-    for j, (_, is_int) in cont.items():                       # continuous attributes: the regressor's value, not a dictionary entry
-        sel = ccols == j
-        v = res["repaired_value"][sel]
-        repaired[sel] = [int(x) for x in v] if is_int else [float(x) for x in v]
-    current = current_values(rows, ccols, res["current"])
-    frame = pd.DataFrame({row_id: df[row_id].to_numpy()[rows], "attribute": np.asarray(cols, object)[ccols],
-                          "current_value": current, "repaired": repaired})
-    if res.get("prob") is not None:
-        frame["prob"] = res["prob"]
-    if want_pmf and len(rows):
-        pc, pp = res["pmf_class"], res["pmf_prob"]
-        pmf = []
-        for i in range(len(rows)):
-            d = dicts[ccols[i]]
-            pmf.append([{"class": d[k], "prob": float(p)} for k, p in zip(pc[i], pp[i]) if k >= 0])
-        frame["pmf"] = pmf
-        frame["current_prob"] = res["current_prob"]
-        if pmf_costs is not None:
-            frame["top1_cost"] = res["top1_cost"]
-            pval = np.empty(len(rows), object)
-            pval[:] = None
-            for j, (_, is_int) in cont.items():
-                sel = np.flatnonzero(ccols == j)
-                v = res["pmf_value"][sel]
-                pval[sel] = [None if np.isnan(x) else (int(x) if is_int else float(x)) for x in v]
-            frame["pmf_value"] = pval
-    if want_details:
-        details = dict(times=res.get("times", {}), stats=res.get("stats", []), models=res.get("models", {}), columns=cols)
-        if res.get("domain") is not None:
-            d = res["domain"]
-            details.update(pairwise_attr_stats={cols[t]: [(cols[y], h) for y, h in lst] for t, lst in d["pairwise"].items()},
-                           noisy_cells=d["noisy_cells"], weak_cells=d["weak_cells"])
-        if res.get("value_detectors"):
-            details["value_detectors"] = [dict(attribute=cols[d["col"]], kinds=d["kinds"], codes_flagged=d["codes_flagged"], cells=d["cells"])
-                                          for d in res["value_detectors"]]
-        if res.get("rebalanced") is not None:
-            details["rebalanced"] = {cols[t]: d for t, d in res["rebalanced"].items()}
-        if res.get("distinct_rows") is not None:
-            d = res["distinct_rows"]
-            details["distinct_rows"] = dict(rows=d["rows"], distinct=d["distinct"], used_for=[cols[t] for t in d["used_for"]],
-                                            skipped={cols[t]: why for t, why in d["skipped"].items()})
-        if rules is not None:
-            details["rule_steps"] = [dict(st, target=cols[st["target"]], x=cols[st["x"]] if st["x"] >= 0 else None) for st in res.get("rule_steps", [])]
-            mg = res.get("merged")
-            mcur, mrep, mrows, mcols = [], [], np.zeros(0, np.int64), np.zeros(0, np.int32)
-            if mg is not None and len(mg["rows"]):
-                nv = rules["nearest"]
-                mrows, mcols = mg["rows"], mg["cols"]
-                raw_rep = decode(mg["repaired"], mcols)
-                mcur, mrep = np.empty(len(mrows), object), np.empty(len(mrows), object)
-                for j in np.unique(mcols):
-                    sel = np.flatnonzero(mcols == j)
-                    mcur[sel] = cur_strings(j, mrows[sel], mg["current"][sel])
-                    mrep[sel] = nv["domain_str"](cols[j], list(raw_rep[sel]))
-            details["merged_cells"] = pd.DataFrame({row_id: df[row_id].to_numpy()[mrows], "attribute": np.asarray(cols, object)[mcols],
-                                                    "current_value": np.asarray(mcur, object), "repaired": np.asarray(mrep, object)})
-            details["nearest_values"] = {cols[j]: int((mcols == j).sum()) for j in np.unique(mcols)}
-            if regex_rules:
-                details["regex_cells"] = pd.DataFrame({row_id: df[row_id].to_numpy()[regex_done["rows"]],
-                                                       "attribute": np.asarray(cols, object)[regex_done["cols"]],
-                                                       "current_value": regex_done["current"], "repaired": regex_done["repaired"]})
-                details["regex_repairs"] = {cols[j]: int((regex_done["cols"] == j).sum()) for j in np.unique(regex_done["cols"])}
-        return frame, details
-    return frame
+    frame = _result_frame(enc, df, row_id, res, cont, want_pmf, pmf_costs is not None)
+    if not want_details:
+        return frame
+    regex_cells = {k: np.concatenate([d[k] for d in regex_done]) for k in regex_done[0]}
+    return frame, _details(enc, df, row_id, res, rules, regex_cells if regex_rules else None)
 
 
 def constraint_to_columns(preds, columns):
