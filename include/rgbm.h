@@ -296,6 +296,19 @@ typedef struct rgbm_dc_pred {
 } rgbm_dc_pred;
 int rgbm_table_detect_dc(rgbm_table* t, const rgbm_dc_pred* preds, int32_t n_preds, const int32_t* cell_cols, int32_t n_cell_cols,
                          int64_t max_pairs, int64_t* n_rows_out /* may be NULL */, int64_t* n_cells_out);
+/* rgbm_table_detect_dc for ORDER constraints, by sort and scan instead of pairs: the same predicate struct, the same semantics (row i
+ * as t1, any row j, i included, as t2) and the same result as rgbm_table_detect_dc gives with an unlimited max_pairs -- the ascending
+ * violating rows x cell_cols -- in O(n log n) whatever the groups are; no pair is evaluated, so there is no max_pairs.
+ * Accepted: 1 <= n_preds <= 16 predicates of which zero to 12 distinct EQ attributes (the 2^63 key-span rule as above), no IQ, and exactly
+ * one or two LT / GT predicates, within one attribute or across two, with or without rank arrays; n < 2^31 rows.  The argument errors
+ * are RGBM_ERR_ARG as rgbm_table_detect_dc gives them -- among them more than 12 distinct EQ attributes, more than 16 predicates, EQ / IQ
+ * across two attributes or with rank arrays, a column out of range -- but a single LT / GT predicate is a constraint here.  Well-formed
+ * arguments outside the accepted set (an IQ, no or three and more LT / GT, a key span of 2^63 or more, 2^31 rows or more) are
+ * RGBM_ERR_PARAM.  After either refusal the table's previous result is as it was.
+ * One order predicate: L < the group's maximum of R.  Two: the group's rows sorted by R1, the suffix maximum of R2 in that order, and
+ * per row a binary search for the first R1 above its L1. */
+int rgbm_table_detect_dc_scan(rgbm_table* t, const rgbm_dc_pred* preds, int32_t n_preds, const int32_t* cell_cols, int32_t n_cell_cols,
+                              int64_t* n_rows_out /* may be NULL */, int64_t* n_cells_out);
 /* ConstraintErrorDetector for single-tuple constraints (constant predicates, e.g. t1&EQ(t1.Sex,"Female")&EQ(t1.Relationship,"Husband")):
  * bits[k] holds n_codes[cols[k]] + 1 bits (bit v = bit v % 64 of word v / 64), bit v = "the predicates on cols[k] hold for code v",
  * the last bit for NULL (a code outside [0, n_codes) is NULL).  A row violates iff its bit is set in every listed column; one

@@ -90,7 +90,7 @@ def lib():
                      "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
                      "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
                      "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
-                     "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits",
+                     "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_dc_scan", "rgbm_table_detect_row_bits",
                      "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats",
                      "rgbm_table_smoten", "rgbm_table_concat", "rgbm_regex_structure"):
             getattr(l, name).restype = C.c_int
@@ -123,7 +123,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_bisect", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
     "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
-    "rgbm_table_pair_counts_report", "rgbm_regex_structure",
+    "rgbm_table_pair_counts_report", "rgbm_regex_structure", "rgbm_table_detect_dc_scan",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -754,11 +754,8 @@ class Table:
                                                   _p(cc, C.c_int32), C.c_int32(len(cc)), C.byref(nr), C.byref(nc)), "rgbm_table_detect_constraint")
         return self._fetch_cells(int(nc.value), len(cc) > 0)
 
-    def detect_dc(self, preds, cell_cols=(), max_pairs=0):
-        """Rows violating a two-tuple denial constraint (rgbm_table_detect_dc; repair.dc_codes lowers a parsed constraint to this).
-        ``preds``: 2 to 16 tuples (op, left_col, right_col, left_rank, right_rank) with op in 'EQ' / 'IQ' / 'LT' / 'GT' and the ranks int32
-        [n_codes[col]] arrays (an entry < 0 = the value has no number) or None.  ``max_pairs`` <= 0: the library default; a table
-        whose EQ groups hold more pairs raises RepairGbmError with code -2.  Returns as ``detect_constraint`` does."""
+    def _dc_preds(self, preds, who):
+        """``preds`` of `detect_dc` as an ``rgbm_dc_pred`` array, and the rank arrays it points into (keep them until the call returns)."""
         ops = dict(EQ=0, IQ=1, LT=2, GT=3)
         arr = (DcPred * max(len(preds), 1))()
         keep = []
@@ -769,13 +766,32 @@ class Table:
                     continue
                 r = _i32(np.asarray(r, np.int32).reshape(-1))
                 if 0 <= int(col) < self.c and len(r) != int(self.n_codes[int(col)]):
-                    raise ValueError("detect_dc: the rank array of column %d holds %d entries, its dictionary %d" % (col, len(r), int(self.n_codes[int(col)])))
+                    raise ValueError("%s: the rank array of column %d holds %d entries, its dictionary %d" % (who, col, len(r), int(self.n_codes[int(col)])))
                 keep.append(r)
                 setattr(arr[k], name, r.ctypes.data_as(C.POINTER(C.c_int32)))
+        return arr, keep
+
+    def detect_dc(self, preds, cell_cols=(), max_pairs=0):
+        """Rows violating a two-tuple denial constraint (rgbm_table_detect_dc; repair.dc_codes lowers a parsed constraint to this).
+        ``preds``: 2 to 16 tuples (op, left_col, right_col, left_rank, right_rank) with op in 'EQ' / 'IQ' / 'LT' / 'GT' and the ranks int32
+        [n_codes[col]] arrays (an entry < 0 = the value has no number) or None.  ``max_pairs`` <= 0: the library default; a table
+        whose EQ groups hold more pairs raises RepairGbmError with code -2.  Returns as ``detect_constraint`` does."""
+        arr, keep = self._dc_preds(preds, "detect_dc")
         cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
         nr, nc = C.c_int64(0), C.c_int64(0)
         _check(lib().rgbm_table_detect_dc(self.h, arr, C.c_int32(len(preds)), _p(cc, C.c_int32), C.c_int32(len(cc)), C.c_int64(int(max_pairs)),
                                           C.byref(nr), C.byref(nc)), "rgbm_table_detect_dc")
+        return self._fetch_cells(int(nc.value), len(cc) > 0)
+
+    def detect_dc_scan(self, preds, cell_cols=()):
+        """`detect_dc` for an ORDER constraint, by sort and scan instead of pairs (rgbm_table_detect_dc_scan): ``preds`` as there, EQ
+        predicates plus one or two LT / GT and no IQ (`repair.dc_codes.scan_eligible`; anything else raises RepairGbmError with code -2).
+        No pair is evaluated, so there is no ``max_pairs``: the result is that of `detect_dc` without a limit."""
+        arr, keep = self._dc_preds(preds, "detect_dc_scan")
+        cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
+        nr, nc = C.c_int64(0), C.c_int64(0)
+        _check(lib().rgbm_table_detect_dc_scan(self.h, arr, C.c_int32(len(preds)), _p(cc, C.c_int32), C.c_int32(len(cc)),
+                                               C.byref(nr), C.byref(nc)), "rgbm_table_detect_dc_scan")
         return self._fetch_cells(int(nc.value), len(cc) > 0)
 
     def detect_row_bits(self, cols, bits, cell_cols=()):

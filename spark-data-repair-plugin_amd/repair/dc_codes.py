@@ -1,5 +1,6 @@
 """Parsed denial constraints (`repair.errors.parse_constraint`) as programs on a table's DICTIONARY CODES -- what
 `Table.detect_constraint` / `Table.detect_dc` / `Table.detect_row_bits` (csrc/rgbm_prep.hip the first, csrc/rgbm_dc.hip the other two) take.
+`scan_eligible` says which `dc` programs `Table.detect_dc_scan` (csrc/rgbm_dc.hip too) takes as well: the order constraints.
 
 A column of the label-encoded table holds codes 0..D-1 into its dictionary (`pipeline.encode_frame`: the distinct non-NULL values,
 ascending; -1 = NULL).  `lower_constraint` gives one of three programs, each with exactly the rows `errors._violating_rows` gives on
@@ -126,6 +127,20 @@ def check_constraint(preds, columns, n_values):
         if span >= 1 << 63:
             raise NotLowerable("the EQ attributes span more than 2^63 value combinations")
     return "dc"
+
+
+def scan_eligible(preds):
+    """Whether the lowered predicates of a `kind="dc"` program -- [(op, left column, right column, left rank, right rank)] -- are an ORDER
+    constraint, which `Table.detect_dc_scan` (rgbm_table_detect_dc_scan) answers by sort and scan instead of pairs: at most MAX_PREDS
+    predicates, at most MAX_EQ distinct EQ attributes, no IQ, and exactly one or two LT / GT (within one attribute or across two, ranked
+    or not).  Any IQ and three or more order predicates take the pairs of `Table.detect_dc`."""
+    preds = list(preds)
+    ops = [p[0] for p in preds]
+    if not 1 <= len(preds) <= MAX_PREDS or any(op not in ("EQ", "LT", "GT") for op in ops):
+        return False
+    if len({p[1] for p in preds if p[0] == "EQ"}) > MAX_EQ or any(p[0] == "EQ" and p[1] != p[2] for p in preds):
+        return False
+    return 1 <= sum(op in ("LT", "GT") for op in ops) <= 2
 
 
 def lower_constraint(preds, columns, dicts, dtypes):

@@ -115,6 +115,11 @@ class RepairModel():
     # new in this engine: every parsed denial constraint (single-tuple constants, several IQs, LT / GT) on the HBM-resident table
     # (repair.dc_codes, `Table.detect_dc` / `Table.detect_row_bits`); `X -> Y` constraints take `Table.detect_constraint` either way
     _opt_constraints_resident = _option("error.constraints.resident", False, bool, None, None)
+    # ... and, with that option set, the ORDER constraints among them -- EQ predicates plus one or two LT / GT, no IQ
+    # (`repair.dc_codes.scan_eligible`) -- by sort and scan (`Table.detect_dc_scan`) instead of pairs: O(n log n) whatever the groups are, so
+    # a constraint without an EQ predicate is answered at any table size instead of refused above `max_pairs`.  Off by default.  Measured,
+    # the scan route is the slower one only on small tables (20 000 rows in groups of 50: 0.170 ms against 0.156 ms for pairs)
+    _opt_constraints_order_scan = _option("error.constraints.order_scan", False, bool, None, None)
     # new in this engine: on the HBM-resident pipeline, train every attribute's model on the DISTINCT rows of the table with their
     # multiplicities (found on the device, `Table.distinct_rows`): the same models, bytes included, at the cost of the distinct rows.  It
     # only matters for an attribute that `model.max_training_row_num` does not sample (a sampled attribute trains on its sample); the
@@ -130,7 +135,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident, _opt_rule_regex_resident, _opt_rebalance_resident,
-        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_constraints_order_scan, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -802,7 +807,8 @@ class RepairModel():
         With `error.constraints.resident` set, every other constraint `repair.dc_codes.check_constraint` accepts qualifies as well
         (single-tuple constants, several IQs, LT / GT): the plan carries its parsed predicates next to the `X -> Y` tuples and
         `pipeline.repair_frame` lowers them against the dictionaries.  A constraint that does not lower sends the run to the value-space
-        path, as before, with the reason logged."""
+        path, as before, with the reason logged.  With `error.constraints.order_scan` set as well the plan carries `order_scan=True`:
+        `pipeline.repair_frame` then sends the order constraints among them to `Table.detect_dc_scan`."""
         from repair.pipeline import constraint_to_columns
         value_resident = bool(self._get_option_value(*self._opt_value_detectors_resident))
         lof_resident = bool(self._get_option_value(*self._opt_lof_resident))
@@ -898,6 +904,8 @@ class RepairModel():
         if plan is None:
             return None
         plan.update(candidates=cands, constraints=cons, detect_nulls=has_null, value_detectors=vdets or None)
+        if constraints_resident and bool(self._get_option_value(*self._opt_constraints_order_scan)):
+            plan.update(order_scan=True)
         eopts = ErrorModel(row_id=self._row_id, targets=self.targets, discrete_thres=self.discrete_thres, error_detectors=self.error_detectors,
                            error_cells=None, opts=self.opts)._checked_options()
         if eopts[ErrorModel._opt_domain_analysis_enabled.key]:
@@ -1006,7 +1014,7 @@ class RepairModel():
 
                 vdets = dict(detectors=plan["value_detectors"], build=build)
             cells = dict(constraints=plan["constraints"], detect_nulls=plan["detect_nulls"], only_noisy_targets=True,
-                         domain_analysis=plan.get("domain_analysis"), value_detectors=vdets)
+                         domain_analysis=plan.get("domain_analysis"), value_detectors=vdets, order_scan=bool(plan.get("order_scan")))
             _logger.info("[Error Detection + Repair Model Training Phase] on the HBM-resident table, candidate attributes %s" % to_list_str(target_columns))
         else:
             if repair_data and not prob:

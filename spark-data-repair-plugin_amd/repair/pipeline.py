@@ -38,7 +38,8 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
                   violating row contributes the constraint's attributes that are targets (`attrs`, line 211).  Next to them the
                   programs of `repair.dc_codes.lower_constraint`: dict(kind="dc", preds, refs[, max_pairs]) -> `Table.detect_dc`,
                   dict(kind="row_bits", cols, bits, refs) -> `Table.detect_row_bits`; a `max_pairs` refusal of the device
-                  (RGBM_ERR_PARAM) raises NotResidentEligible
+                  (RGBM_ERR_PARAM) raises NotResidentEligible.  dict(kind="dc_scan", preds, refs): a `dc` program that
+                  `route_order_constraints` sent to `Table.detect_dc_scan`; its refusals (RGBM_ERR_PARAM) raise the same
     error_cells : (rows, cols) given by the caller (RepairModel.setErrorCells); non-target attributes are dropped
     value_detectors : per-column descriptors of the regex / value-domain / outlier detectors as code predicates
                   (`repair.detect_codes.build_descriptors`); one `Table.detect_cells` call answers them, and the NULL detector
@@ -76,6 +77,8 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
             try:
                 if con["kind"] == "dc":
                     parts.append(table.detect_dc(con["preds"], cell_cols=attrs, max_pairs=int(con.get("max_pairs", 0))))
+                elif con["kind"] == "dc_scan":         # an order constraint by sort and scan (`route_order_constraints`)
+                    parts.append(table.detect_dc_scan(con["preds"], cell_cols=attrs))
                 else:
                     parts.append(table.detect_row_bits(con["cols"], con["bits"], cell_cols=attrs))
             except Exception as e:  # noqa: BLE001
@@ -921,13 +924,39 @@ def _upload(engine, enc):
     return table
 
 
-def _upload_and_run(engine, enc, df, targets, cells, regex_rules, by_name, through, analyse=True):
+def route_order_constraints(constraints, table):
+    """The lowered constraints with every `kind="dc"` program that is an order constraint (`repair.dc_codes.scan_eligible`) marked
+    `kind="dc_scan"`: `detect_error_cells` sends those to `Table.detect_dc_scan`.  A table without that method keeps the pairs route."""
+    from repair.dc_codes import scan_eligible
+    if not hasattr(table, "detect_dc_scan"):
+        return list(constraints)
+    return [dict(con, kind="dc_scan") if isinstance(con, dict) and con["kind"] == "dc" and scan_eligible(con["preds"]) else con
+            for con in constraints]
+
+
+def constraint_routes(constraints):
+    """Per lowered constraint the entry that answers it: 'fd' (`Table.detect_constraint`), 'dc' (pairs), 'dc_scan' or 'row_bits'."""
+    return [con["kind"] if isinstance(con, dict) else "fd" for con in constraints]
+
+
+def _upload_and_run(engine, enc, df, targets, cells, regex_rules, by_name, through, analyse=True, order_scan=False):
     """One pass: upload the encoding, `repair_table` on it.  `cells`: the known error cells or None; `by_name` / `through`: the keywords of
-    `_column_space` / those `repair_table` takes as they are.  Returns (the continuous targets {column: (values, is_integral)}, result)."""
+    `_column_space` / those `repair_table` takes as they are; `order_scan`: `route_order_constraints` on the lowered constraints.
+    Returns (the continuous targets {column: (values, is_integral)}, result); the result (or the DeadClasses raised) holds
+    `constraint_routes`."""
     table = _upload(engine, enc)
     kw = _column_space(engine, enc, df, targets, analyse=analyse, **by_name)
+    if order_scan:
+        kw["constraints"] = route_order_constraints(kw["constraints"], table)
+    routes = constraint_routes(kw["constraints"])
     regex_cols = [enc.pos[r["attr"]] for r in regex_rules if r["attr"] in enc.pos] if cells is None else None
-    return kw["continuous"], repair_table(engine, table, [enc.pos[t] for t in targets], error_cells=cells, regex_cols=regex_cols, **through, **kw)
+    try:
+        res = repair_table(engine, table, [enc.pos[t] for t in targets], error_cells=cells, regex_cols=regex_cols, **through, **kw)
+    except DeadClasses as e:
+        e.constraint_routes = routes
+        raise
+    res["constraint_routes"] = routes
+    return kw["continuous"], res
 
 
 def _result_frame(enc, df, row_id, res, cont, want_pmf, with_costs):
@@ -969,6 +998,8 @@ def _details(enc, df, row_id, res, rules, regex_done):
     """`repair_table`'s report with attribute names for column positions; `regex_done`: the cells of `_known_cells`, or None."""
     cols = enc.columns
     details = dict(times=res.get("times", {}), stats=res.get("stats", []), models=res.get("models", {}), columns=cols)
+    if any(r != "fd" for r in res.get("constraint_routes") or ()):      # (runs with `X -> Y` constraints alone report what they always did)
+        details["constraint_routes"] = list(res["constraint_routes"])
     if res.get("domain") is not None:
         d = res["domain"]
         details.update(pairwise_attr_stats={cols[t]: [(cols[y], h) for y, h in lst] for t, lst in d["pairwise"].items()},
@@ -1006,14 +1037,16 @@ def _details(enc, df, row_id, res, rules, regex_done):
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None, rebalance=None):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None, order_scan=False):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
     Columns are discrete (one class per distinct value) unless named in `continuous_columns` (numeric columns; those targets
     get regressors and `repaired` is the predicted number, rounded for integer columns); `constraints` are `X1,..,Xm -> Y`
     dependencies given as the tuple ([x names], y name), or any other parsed constraint as its list of `repair.errors.Predicate`
-    (`repair.dc_codes.lower_constraint` turns it into a program on the codes); `error_cells` is a frame with `row_id` and `attribute` columns
+    (`repair.dc_codes.lower_constraint` turns it into a program on the codes; `order_scan`: the order constraints among those programs
+    -- `repair.dc_codes.scan_eligible` -- go to `Table.detect_dc_scan` where the engine's table has it; whenever one of the constraints is such
+    a program the details name each constraint's entry as `constraint_routes`: 'fd', 'dc', 'dc_scan' or 'row_bits', in the order given); `error_cells` is a frame with `row_id` and `attribute` columns
     (RepairModel.setErrorCells).  Regex / value-domain / outlier / LOF detectors come as `value_detectors`; any other scikit-learn
     backed detector stays with `repair.model.RepairModel` (the value-space API).
 
@@ -1084,7 +1117,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                 raise NotResidentEligible("target `%s` is left with %d distinct value(s) once the error cells are removed" % (t, live))
     try:
         cont, res = _upload_and_run(engine, enc, df, targets, cells, regex_rules, dict(by_name, constraints=constraints, detect_nulls=detect_nulls),
-                                    through)
+                                    through, order_scan=order_scan)
     except DeadClasses as e:
         # Detection ran on the device; some values of a target were held by error cells only (a typo occurs once).  The cells are
         # known now: NULL them on the host side of the encoding, drop the dead values, upload the (cached) encoding again and go on
@@ -1099,6 +1132,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
             res["domain"] = e.domain_info
         if e.value_detectors:
             res["value_detectors"] = e.value_detectors
+        res["constraint_routes"] = e.constraint_routes
     frame = _result_frame(enc, df, row_id, res, cont, want_pmf, pmf_costs is not None)
     if not want_details:
         return frame
