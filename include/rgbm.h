@@ -319,6 +319,25 @@ int rgbm_table_detect_row_bits(rgbm_table* t, const int32_t* cols, int32_t n_col
  * python/repair/model.py:549-553 (left-semi join on the row id). */
 int rgbm_table_rows_of_cells(rgbm_table* t, const int64_t* rows, int64_t n_cells, int64_t* n_rows_out);
 int rgbm_table_cells_fetch(const rgbm_table* t, int64_t* rows_out /* [n] or NULL */, int32_t* cols_out /* [n] or NULL */);
+/* The CELL SET of a table: the union of detector results, kept on the device between the detect calls.  A bit matrix
+ * of n_cols x ceil(n / 64) 64-bit words (rounded up to whole 4096-row compaction blocks), device memory of the table's own from the pool.
+ * None of these entries writes a code.
+ * open:  a zeroed set over `cols`: 1 <= n_cols <= columns, distinct and in range (RGBM_ERR_ARG otherwise).  A second open replaces the set.
+ * add:   ORs the table's cell list, as the last rgbm_table_detect_* call left it, into the set.  A cell whose column is not in the set (or that
+ *        lies outside the table) is skipped: join semantics, as in rgbm_table_null_cells.  A row list without columns (the n_cell_cols == 0
+ *        result of a constraint call) is RGBM_ERR_PARAM; an empty result adds nothing.  The cell list stays as it was.
+ * emit:  compacts the set into the table's cell list -- ordered by position in `cols`, then ascending row, every cell once -- and gathers
+ *        the codes those cells hold NOW (a code outside [0, n_codes) as it lies, as rgbm_table_read_cells gives it) into a device buffer of
+ *        the table.  counts_out[j] = cells of cols[j].  rgbm_table_cells_fetch copies rows / columns out as for every other result,
+ *        rgbm_table_cells_fetch_codes the codes.  The set stays open: emit twice gives the same result, add after emit and emit again is allowed.
+ * fetch_codes: RGBM_ERR_PARAM when the cell list is no longer that of the last emit (a detect / rows_of_cells call came after it).
+ * close: frees the set (rgbm_table_free does too); the last emit's cell list and codes stay fetchable.
+ * add / emit without an open set are RGBM_ERR_PARAM.  After every refusal the previous cell list and the set are as they were. */
+int rgbm_table_cellset_open(rgbm_table* t, const int32_t* cols, int32_t n_cols);
+int rgbm_table_cellset_add(rgbm_table* t);
+int rgbm_table_cellset_emit(rgbm_table* t, int64_t* n_cells_out, int64_t* counts_out /* [n_cols] or NULL */);
+int rgbm_table_cells_fetch_codes(const rgbm_table* t, int32_t* codes_out /* [n_cells] */);
+int rgbm_table_cellset_close(rgbm_table* t);
 /* convertErrorCellsToNull (src/main/scala/.../python/RepairApi.scala:171-211): NULL the listed cells whose
  * column is one of target_cols; cells outside the table are ignored (join semantics). */
 int rgbm_table_null_cells(rgbm_table* t, const int64_t* rows, const int32_t* cols, int64_t n_cells,

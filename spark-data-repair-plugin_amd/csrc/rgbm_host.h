@@ -177,6 +177,12 @@ struct rgbm_table {
     rgh::DevBuf<uint8_t> mult; bool has_mult = false; int64_t mult_total = 0;
     // result of the last rgbm_table_detect_* call (rgbm_prep.hip, rgbm_dc.hip): cells (row, column), device resident
     rgh::DevBuf<long long> cell_rows; rgh::DevBuf<int32_t> cell_cols; int64_t n_cells = 0;
+    uint64_t cell_version = 0;                     // bumped by whatever replaces the cell list (emit_to_table, rows_to_cells, no_cells)
+    // the CELL SET (rgbm_cellset.hip): a bit matrix of cs_n_cols x 64 * ceil(n / 4096) words in the compaction's ballot layout, its columns
+    // (cs_d_cols [cs_n_cols]; cs_d_pos [c]: column -> position, -1 = not in the set) and the codes of the last emit, which are the codes of
+    // the cell list while cell_version is still that emit's
+    rgh::DevBuf<unsigned long long> cs_bits; rgh::DevBuf<int32_t> cs_d_cols, cs_d_pos, cs_codes;
+    int32_t cs_n_cols = 0; bool cs_open = false, cs_emitted = false; uint64_t cs_emit_version = 0;
     // stream + scratch of the relational steps (rgbm_prep.h: table_stream, enum Scr), kept with the table: a hipMalloc / hipFree / stream
     // creation per call costs more than the kernels (one call at a time per table, as the header says)
     // Python threads share one table (the folds of a hyper-parameter search gather from the training table, ctypes drops the

@@ -1,7 +1,7 @@
 // rgbm_prep.hip -- the relational steps either side of the repair models, on the HBM-resident code table
 // (SURVEY.md 8(f) rows 2-4).  Everything here is HBM-bound integer work over int32 codes [c][n].  This source holds the compaction, the cell and
 // row primitives and the NULL, value and X -> Y detectors, and it defines the host functions that rgbm_prep.h declares.  The other steps have a
-// source each: rgbm_colstats.hip, rgbm_pmf.hip, rgbm_domain.hip, rgbm_rules.hip, rgbm_lof.hip, rgbm_kmeans.hip, rgbm_distinct.hip, rgbm_dc.hip.
+// source each: rgbm_colstats.hip, rgbm_pmf.hip, rgbm_domain.hip, rgbm_rules.hip, rgbm_lof.hip, rgbm_kmeans.hip, rgbm_distinct.hip, rgbm_dc.hip, rgbm_cellset.hip.
 //
 //   detect_nulls          NullErrorDetector                      (reference: ErrorDetectorApi.scala:128-157)
 //   detect_constraint     ConstraintErrorDetector for  X1..Xm -> Y  style denial constraints
@@ -319,7 +319,7 @@ long long emit_to_table(rgbm_table& t, const Ballots& b, const int32_t* d_cols, 
         *rows = t.cell_rows.p; *cols = t.cell_cols.p;
     });
     HIPCHK(hipStreamSynchronize(s));
-    t.n_cells = total;
+    t.n_cells = total; ++t.cell_version;
     return total;
 }
 template <int MODE>
@@ -346,13 +346,13 @@ void rows_to_cells(rgbm_table& t, long long m, const int32_t* cell_cols, int n_c
         HIPCHK(hipStreamSynchronize(s));
         t.cell_rows.swap(rows_r);
         t.cell_cols.swap(cols_r);
-        t.n_cells = m * n_cell_cols;
+        t.n_cells = m * n_cell_cols; ++t.cell_version;
     }
     *n_cells_out = t.n_cells;
 }
 
 int no_cells(rgbm_table& t, bool row_list, int64_t* n_rows_out, int64_t* n_cells_out) {
-    t.n_cells = 0; *n_cells_out = 0;
+    t.n_cells = 0; ++t.cell_version; *n_cells_out = 0;
     if (row_list) t.cell_cols.release();
     if (n_rows_out) *n_rows_out = 0;
     return RGBM_OK;

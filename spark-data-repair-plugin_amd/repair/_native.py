@@ -95,8 +95,9 @@ def lib():
                      "rgbm_table_smoten", "rgbm_table_concat", "rgbm_regex_structure"):
             getattr(l, name).restype = C.c_int
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect",
-                     "rgbm_table_pair_counts_report"):
-            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass / no count report)
+                     "rgbm_table_pair_counts_report", "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit",
+                     "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close"):
+            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass / no count report / no cell set)
                 getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
         l.rgbm_table_free.restype = None
@@ -124,6 +125,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_bisect", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
     "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
     "rgbm_table_pair_counts_report", "rgbm_regex_structure", "rgbm_table_detect_dc_scan",
+    "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit", "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -703,21 +705,23 @@ class Table:
         return cls._adopt(h, device_id)
 
     # ---- relational steps around the models (csrc/rgbm_prep.hip and the rgbm_<step>.hip sources beside it)
-    def _fetch_cells(self, n, want_cols):
+    def _fetch_cells(self, n, want_cols, fetch=True):
+        if not fetch:            # the result stays in the table's cell list (for `cellset_add`); the count is all that leaves the device
+            return n
         rows = np.zeros(n, np.int64)
         cols = np.zeros(n, np.int32) if want_cols else None
         if n:
             _check(lib().rgbm_table_cells_fetch(self.h, _p(rows, C.c_int64), _p(cols, C.c_int32)), "rgbm_table_cells_fetch")
         return (rows, cols) if want_cols else rows
 
-    def detect_nulls(self, cols):
+    def detect_nulls(self, cols, fetch=True):
         """NULL cells of ``cols`` as (rows, cols), ordered by position in ``cols`` then row (ErrorDetectorApi.scala:128-157)."""
         cc = _i32(np.asarray(cols, np.int32).reshape(-1))
         n = C.c_int64(0)
         _check(lib().rgbm_table_detect_nulls(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), C.byref(n)), "rgbm_table_detect_nulls")
-        return self._fetch_cells(int(n.value), True)
+        return self._fetch_cells(int(n.value), True, fetch)
 
-    def detect_cells(self, cols, null_is_error, keep_lo, keep_hi, flag_bits=None):
+    def detect_cells(self, cols, null_is_error, keep_lo, keep_hi, flag_bits=None, fetch=True):
         """Cells of ``cols`` flagged by per-column CODE predicates (rgbm_table_detect_cells; repair.detect_codes builds them from the
         regex / value-domain / outlier detectors) as (rows, cols), ordered by position in ``cols`` then row.  Per column j: NULL cells
         when ``null_is_error[j]``; codes outside [keep_lo[j], keep_hi[j]] unless keep_lo[j] > keep_hi[j]; codes whose bit is set in
@@ -742,9 +746,9 @@ class Table:
         n = C.c_int64(0)
         _check(lib().rgbm_table_detect_cells(self.h, _p(cc, C.c_int32), C.c_int32(k), _p(ne, C.c_uint8), _p(lo, C.c_int32), _p(hi, C.c_int32),
                                              ptrs, C.byref(n)), "rgbm_table_detect_cells")
-        return self._fetch_cells(int(n.value), True)
+        return self._fetch_cells(int(n.value), True, fetch)
 
-    def detect_constraint(self, eq_cols, iq_col, cell_cols=()):
+    def detect_constraint(self, eq_cols, iq_col, cell_cols=(), fetch=True):
         """Rows violating  EQ(eq_cols...) & IQ(iq_col)  (ErrorDetectorApi.scala:189-244).  Returns the ascending violating rows
         when ``cell_cols`` is empty, else the cells (rows, cols) = violating rows x cell_cols, column-major."""
         eq = _i32(np.asarray(eq_cols, np.int32).reshape(-1))
@@ -752,7 +756,7 @@ class Table:
         nr, nc = C.c_int64(0), C.c_int64(0)
         _check(lib().rgbm_table_detect_constraint(self.h, _p(eq, C.c_int32), C.c_int32(len(eq)), C.c_int32(iq_col),
                                                   _p(cc, C.c_int32), C.c_int32(len(cc)), C.byref(nr), C.byref(nc)), "rgbm_table_detect_constraint")
-        return self._fetch_cells(int(nc.value), len(cc) > 0)
+        return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
     def _dc_preds(self, preds, who):
         """``preds`` of `detect_dc` as an ``rgbm_dc_pred`` array, and the rank arrays it points into (keep them until the call returns)."""
@@ -771,7 +775,7 @@ class Table:
                 setattr(arr[k], name, r.ctypes.data_as(C.POINTER(C.c_int32)))
         return arr, keep
 
-    def detect_dc(self, preds, cell_cols=(), max_pairs=0):
+    def detect_dc(self, preds, cell_cols=(), max_pairs=0, fetch=True):
         """Rows violating a two-tuple denial constraint (rgbm_table_detect_dc; repair.dc_codes lowers a parsed constraint to this).
         ``preds``: 2 to 16 tuples (op, left_col, right_col, left_rank, right_rank) with op in 'EQ' / 'IQ' / 'LT' / 'GT' and the ranks int32
         [n_codes[col]] arrays (an entry < 0 = the value has no number) or None.  ``max_pairs`` <= 0: the library default; a table
@@ -781,9 +785,9 @@ class Table:
         nr, nc = C.c_int64(0), C.c_int64(0)
         _check(lib().rgbm_table_detect_dc(self.h, arr, C.c_int32(len(preds)), _p(cc, C.c_int32), C.c_int32(len(cc)), C.c_int64(int(max_pairs)),
                                           C.byref(nr), C.byref(nc)), "rgbm_table_detect_dc")
-        return self._fetch_cells(int(nc.value), len(cc) > 0)
+        return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
-    def detect_dc_scan(self, preds, cell_cols=()):
+    def detect_dc_scan(self, preds, cell_cols=(), fetch=True):
         """`detect_dc` for an ORDER constraint, by sort and scan instead of pairs (rgbm_table_detect_dc_scan): ``preds`` as there, EQ
         predicates plus one or two LT / GT and no IQ (`repair.dc_codes.scan_eligible`; anything else raises RepairGbmError with code -2).
         No pair is evaluated, so there is no ``max_pairs``: the result is that of `detect_dc` without a limit."""
@@ -792,9 +796,9 @@ class Table:
         nr, nc = C.c_int64(0), C.c_int64(0)
         _check(lib().rgbm_table_detect_dc_scan(self.h, arr, C.c_int32(len(preds)), _p(cc, C.c_int32), C.c_int32(len(cc)),
                                                C.byref(nr), C.byref(nc)), "rgbm_table_detect_dc_scan")
-        return self._fetch_cells(int(nc.value), len(cc) > 0)
+        return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
-    def detect_row_bits(self, cols, bits, cell_cols=()):
+    def detect_row_bits(self, cols, bits, cell_cols=(), fetch=True):
         """Rows whose code has its bit set in EVERY listed column (rgbm_table_detect_row_bits: single-tuple constraints).  ``bits[k]``:
         uint64 [ceil((n_codes[cols[k]] + 1) / 64)], bit v = the predicates on the column hold for code v, the last bit for NULL."""
         cols_ = _i32(np.asarray(cols, np.int32).reshape(-1))
@@ -813,7 +817,7 @@ class Table:
         nr, nc = C.c_int64(0), C.c_int64(0)
         _check(lib().rgbm_table_detect_row_bits(self.h, _p(cols_, C.c_int32), C.c_int32(k), ptrs, _p(cc, C.c_int32), C.c_int32(len(cc)),
                                                 C.byref(nr), C.byref(nc)), "rgbm_table_detect_row_bits")
-        return self._fetch_cells(int(nc.value), len(cc) > 0)
+        return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
     def rows_of_cells(self, rows):
         """Ascending positions of the rows that hold at least one of the given cells (the dirty rows, model.py:549-553)."""
@@ -821,6 +825,40 @@ class Table:
         n = C.c_int64(0)
         _check(lib().rgbm_table_rows_of_cells(self.h, _p(r, C.c_int64), C.c_int64(len(r)), C.byref(n)), "rgbm_table_rows_of_cells")
         return self._fetch_cells(int(n.value), False)
+
+    # ---- the cell set (csrc/rgbm_cellset.hip): the union of detector results, kept on the device.  Every `detect_*` method takes
+    # ``fetch=False``: the result then stays in the table's cell list for `cellset_add` and the method returns its cell count.
+    def cellset_open(self, cols):
+        """A zeroed cell set over the distinct columns ``cols`` (rgbm_table_cellset_open); a second open replaces it."""
+        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
+        _check(lib().rgbm_table_cellset_open(self.h, _p(cc, C.c_int32), C.c_int32(len(cc))), "rgbm_table_cellset_open")
+        self._cellset_cols = len(cc)
+
+    def cellset_add(self):
+        """ORs the cell list the last ``detect_*`` call left into the set; cells of columns outside the set are skipped."""
+        _check(lib().rgbm_table_cellset_add(self.h), "rgbm_table_cellset_add")
+
+    def cellset_emit(self, fetch=True):
+        """The set as (rows, cols, codes, counts): ordered by position in the set's columns, then ascending row; ``codes`` are the codes the
+        cells hold now, ``counts[j]`` the cells of the set's j-th column.  The set stays open.  ``fetch=False``: the cells stay in the
+        table's cell list and ``counts`` alone is returned."""
+        k = getattr(self, "_cellset_cols", 0)
+        n, counts = C.c_int64(0), np.zeros(max(k, 1), np.int64)
+        _check(lib().rgbm_table_cellset_emit(self.h, C.byref(n), _p(counts, C.c_int64)), "rgbm_table_cellset_emit")
+        if not fetch:
+            return counts[:k]
+        rows, cols = self._fetch_cells(int(n.value), True)
+        return rows, cols, self.cells_fetch_codes(int(n.value)), counts[:k]
+
+    def cells_fetch_codes(self, n):
+        """The codes of the last `cellset_emit` (rgbm_table_cells_fetch_codes; refused once another result replaced its cell list)."""
+        codes = np.zeros(n, np.int32)
+        _check(lib().rgbm_table_cells_fetch_codes(self.h, _p(codes, C.c_int32)), "rgbm_table_cells_fetch_codes")
+        return codes
+
+    def cellset_close(self):
+        _check(lib().rgbm_table_cellset_close(self.h), "rgbm_table_cellset_close")
+        self._cellset_cols = 0
 
     def null_cells(self, rows, cols, target_cols):
         """convertErrorCellsToNull (RepairApi.scala:171-211), in place in HBM."""

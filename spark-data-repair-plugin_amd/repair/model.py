@@ -120,6 +120,10 @@ class RepairModel():
     # a constraint without an EQ predicate is answered at any table size instead of refused above `max_pairs`.  Off by default.  Measured,
     # the scan route is the slower one only on small tables (20 000 rows in groups of 50: 0.170 ms against 0.156 ms for pairs)
     _opt_constraints_order_scan = _option("error.constraints.order_scan", False, bool, None, None)
+    # new in this engine: `run(detect_errors_only=True)` on the HBM-resident table (`_device_detect_only_plan`, `pipeline.detect_frame`): the
+    # detectors admitted by the options above run on the device, their cells are merged there (the table's cell set) and leave
+    # it once, with the codes they hold.  None of the model conditions of the resident repair run applies.  Off by default.
+    _opt_detect_only_resident = _option("error.detect_only.resident", False, bool, None, None)
     # new in this engine: on the HBM-resident pipeline, train every attribute's model on the DISTINCT rows of the table with their
     # multiplicities (found on the device, `Table.distinct_rows`): the same models, bytes included, at the cost of the distinct rows.  It
     # only matters for an attribute that `model.max_training_row_num` does not sample (a sampled attribute trains on its sample); the
@@ -135,7 +139,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident, _opt_rule_regex_resident, _opt_rebalance_resident,
-        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_constraints_order_scan, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_constraints_order_scan, _opt_detect_only_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -787,6 +791,99 @@ class RepairModel():
                            cost=None if type(cf) is Levenshtein else cf.compute, current_str=current_str, domain_str=domain_str)
         return dict(fd=fd, nearest=nearest, regex=regex or None)
 
+    def _detector_conditions(self, input_df: DataFrame, continous_columns: List[str], detectors: List[ErrorDetector],
+                             why: Optional[List[str]] = None) -> Optional[Dict[str, Any]]:
+        """The DETECTOR conditions of a device-side detection, stated once for `_device_detection_plan` and `_device_detect_only_plan`:
+        no `setErrorCells`, no detector with `targets` of its own, the detector types admitted under their options (docstring of
+        `_device_detection_plan`), and every constraint that is not `X -> Y` passing `repair.dc_codes.check_constraint`.  Returns
+        dict(cols, constraints, value_detectors (the outlier / LOF kinds still without their `attrs`), detect_nulls, domain_stats) or None;
+        `why`, where given, then receives the reason."""
+        def no(reason: str) -> None:
+            if why is not None:
+                why.append(reason)
+            return None
+
+        from repair.pipeline import constraint_to_columns
+        value_resident = bool(self._get_option_value(*self._opt_value_detectors_resident))
+        lof_resident = bool(self._get_option_value(*self._opt_lof_resident))
+        constraints_resident = bool(self._get_option_value(*self._opt_constraints_resident))
+        general: List[Any] = []      # the parsed predicates of the constraints that are not `X -> Y`
+        vdets: List[Dict[str, Any]] = []
+        if self.error_cells is not None:
+            return no("the error cells are given (`setErrorCells`)")
+        cols = [c for c in input_df.columns if c != self._row_id]
+        cons: List[Any] = []          # ([x names], y name) of `X -> Y` constraints; the parsed predicates of any other one
+        has_null = False
+        for d in detectors:
+            if getattr(d, "targets", None):
+                return no("%s has targets of its own" % d)
+            if type(d) is NullErrorDetector:
+                has_null = True
+            elif type(d) is ConstraintErrorDetector:
+                stmts = load_constraints(d.constraint_path, d.constraints)
+                try:
+                    plist = parse_and_verify_constraints(stmts, list(input_df.columns)) if stmts else []
+                except Exception:  # noqa: BLE001 - the pandas detector reports malformed constraints
+                    return no("%s does not parse" % d)
+                for preds in plist:
+                    cc = constraint_to_columns(preds, cols)
+                    if cc is not None:
+                        cons.append(([cols[i] for i in cc[0]], cols[cc[1]]))
+                    elif constraints_resident:
+                        general.append(preds)
+                        cons.append(preds)
+                    else:
+                        return no("constraint %s is not `X -> Y` and `%s` is not set" % (preds, self._opt_constraints_resident.key))
+            elif value_resident and type(d) is RegExErrorDetector:
+                vdets.append(dict(kind="regex", attr=d.attr, regex=d.regex))
+            elif value_resident and type(d) is DomainValues:
+                if d.attr not in continous_columns:          # `DomainValues._detect_impl`: nothing on a continuous attribute
+                    vdets.append(dict(kind="domain", attr=d.attr, values=list(d.values), autofill=bool(d.autofill),
+                                      min_count_thres=d.min_count_thres))
+            elif value_resident and type(d) is GaussianOutlierErrorDetector:
+                vdets.append(dict(kind="outlier", attrs=None))
+            elif lof_resident and type(d) is LOFOutlierErrorDetector:
+                # (`parallel_mode_threshold` / `num_parallelism` change nothing on the value-space path of this engine either)
+                vdets.append(dict(kind="lof", attrs=None, k=int(d.error_detector_cls().n_neighbors)))
+            else:
+                return no("%s is not a detector the resident table restates under the options set" % d)
+        from repair.utils import column_nunique
+        domain_stats = {c: column_nunique(input_df, c) for c in cols}
+        for preds in general:
+            from repair.dc_codes import NotLowerable, check_constraint
+            try:
+                check_constraint(preds, cols, domain_stats)
+            except NotLowerable as e:
+                _logger.info("[Error Detection Phase] constraint %s stays with the value-space detector: %s" % (preds, e))
+                return no("constraint %s does not lower: %s" % (preds, e))
+        return dict(cols=cols, constraints=cons, value_detectors=vdets, detect_nulls=has_null, domain_stats=domain_stats)
+
+    def _outlier_columns_ok(self, input_df: DataFrame, vdets: List[Dict[str, Any]], read: List[str]) -> bool:
+        """The column checks of the outlier and LOF detectors on the continuous attributes `read` that detection looks at; fills their `attrs`."""
+        if any(d["kind"] == "lof" and d["k"] >= len(input_df) // 2 for d in vdets):
+            # scikit-learn searches so small a table by brute force, with inexact distances (`detect_codes.build_descriptors`)
+            return False
+        if any(d["kind"] in ("outlier", "lof") for d in vdets):
+            # the columns the outlier and LOF detectors read: plain numpy numeric ones only (`pd.to_numeric(.., errors="coerce")` of anything else
+            # and the masked comparison of a nullable column stay with the pandas detector), integers within float64's exact range (the
+            # dictionaries are float64)
+            for c in read:
+                if not isinstance(input_df[c].dtype, np.dtype) or not is_numeric_column(input_df[c]):
+                    return False
+                if pd.api.types.is_integer_dtype(input_df[c]) and len(input_df) and input_df[c].notna().any() \
+                        and float(input_df[c].abs().max()) >= 2.0 ** 53:
+                    return False
+                if any(d["kind"] == "lof" for d in vdets) and len(input_df) and input_df[c].notna().any():
+                    # scikit-learn refuses an infinite value, and its squared distances overflow on a wider span: its errors to report
+                    x = input_df[c].to_numpy(dtype=np.float64)
+                    with np.errstate(over="ignore", invalid="ignore"):
+                        if not float(np.nanmax(x) - np.nanmin(x)) <= LOF_MAX_RANGE:
+                            return False
+            for d in vdets:
+                if d["kind"] in ("outlier", "lof"):
+                    d["attrs"] = list(read)
+        return True
+
     def _device_detection_plan(self, input_df: DataFrame, continous_columns: List[str], compute_repair_candidate_prob: bool,
                                maximal_likelihood_repair: bool) -> Optional[Dict[str, Any]]:
         """Can error DETECTION run on the resident table as well (reference python/repair/errors.py:545-582)?  Yes when the error
@@ -809,59 +906,12 @@ class RepairModel():
         `pipeline.repair_frame` lowers them against the dictionaries.  A constraint that does not lower sends the run to the value-space
         path, as before, with the reason logged.  With `error.constraints.order_scan` set as well the plan carries `order_scan=True`:
         `pipeline.repair_frame` then sends the order constraints among them to `Table.detect_dc_scan`."""
-        from repair.pipeline import constraint_to_columns
-        value_resident = bool(self._get_option_value(*self._opt_value_detectors_resident))
-        lof_resident = bool(self._get_option_value(*self._opt_lof_resident))
-        constraints_resident = bool(self._get_option_value(*self._opt_constraints_resident))
-        general: List[Any] = []      # the parsed predicates of the constraints that are not `X -> Y`
-        vdets: List[Dict[str, Any]] = []
-        if self.error_cells is not None or not self.error_detectors:
+        if not self.error_detectors:
             return None
-        cols = [c for c in input_df.columns if c != self._row_id]
-        cons: List[Any] = []          # ([x names], y name) of `X -> Y` constraints; the parsed predicates of any other one
-        has_null = False
-        for d in self.error_detectors:
-            if getattr(d, "targets", None):
-                return None
-            if type(d) is NullErrorDetector:
-                has_null = True
-            elif type(d) is ConstraintErrorDetector:
-                stmts = load_constraints(d.constraint_path, d.constraints)
-                try:
-                    plist = parse_and_verify_constraints(stmts, list(input_df.columns)) if stmts else []
-                except Exception:  # noqa: BLE001 - the pandas detector reports malformed constraints
-                    return None
-                for preds in plist:
-                    cc = constraint_to_columns(preds, cols)
-                    if cc is not None:
-                        cons.append(([cols[i] for i in cc[0]], cols[cc[1]]))
-                    elif constraints_resident:
-                        general.append(preds)
-                        cons.append(preds)
-                    else:
-                        return None
-            elif value_resident and type(d) is RegExErrorDetector:
-                vdets.append(dict(kind="regex", attr=d.attr, regex=d.regex))
-            elif value_resident and type(d) is DomainValues:
-                if d.attr not in continous_columns:          # `DomainValues._detect_impl`: nothing on a continuous attribute
-                    vdets.append(dict(kind="domain", attr=d.attr, values=list(d.values), autofill=bool(d.autofill),
-                                      min_count_thres=d.min_count_thres))
-            elif value_resident and type(d) is GaussianOutlierErrorDetector:
-                vdets.append(dict(kind="outlier", attrs=None))
-            elif lof_resident and type(d) is LOFOutlierErrorDetector:
-                # (`parallel_mode_threshold` / `num_parallelism` change nothing on the value-space path of this engine either)
-                vdets.append(dict(kind="lof", attrs=None, k=int(d.error_detector_cls().n_neighbors)))
-            else:
-                return None
-        from repair.utils import column_nunique
-        domain_stats = {c: column_nunique(input_df, c) for c in cols}
-        for preds in general:
-            from repair.dc_codes import NotLowerable, check_constraint
-            try:
-                check_constraint(preds, cols, domain_stats)
-            except NotLowerable as e:
-                _logger.info("[Error Detection Phase] constraint %s stays with the value-space detector: %s" % (preds, e))
-                return None
+        dets = self._detector_conditions(input_df, continous_columns, self.error_detectors)
+        if dets is None:
+            return None
+        cols, cons, vdets, has_null, domain_stats = dets["cols"], dets["constraints"], dets["value_detectors"], dets["detect_nulls"], dets["domain_stats"]
         discretized = [c for c in cols if c in continous_columns or 1 < domain_stats[c] <= self.discrete_thres]
         cands = [c for c in (self.targets if self.targets else cols) if c in discretized]
         if not cands:
@@ -877,34 +927,13 @@ class RepairModel():
             return None
         if others and any(d["kind"] not in ("outlier", "lof") and d["attr"] in others for d in vdets):
             return None
-        if any(d["kind"] == "lof" and d["k"] >= len(input_df) // 2 for d in vdets):
-            # scikit-learn searches so small a table by brute force, with inexact distances (`detect_codes.build_descriptors`)
+        if not self._outlier_columns_ok(input_df, vdets, [c for c in continous_columns if c in cands]):
             return None
-        if any(d["kind"] in ("outlier", "lof") for d in vdets):
-            # the columns the outlier and LOF detectors read: plain numpy numeric ones only (`pd.to_numeric(.., errors="coerce")` of anything else
-            # and the masked comparison of a nullable column stay with the pandas detector), integers within float64's exact range (the
-            # dictionaries are float64)
-            read = [c for c in continous_columns if c in cands]
-            for c in read:
-                if not isinstance(input_df[c].dtype, np.dtype) or not is_numeric_column(input_df[c]):
-                    return None
-                if pd.api.types.is_integer_dtype(input_df[c]) and len(input_df) and input_df[c].notna().any() \
-                        and float(input_df[c].abs().max()) >= 2.0 ** 53:
-                    return None
-                if any(d["kind"] == "lof" for d in vdets) and len(input_df) and input_df[c].notna().any():
-                    # scikit-learn refuses an infinite value, and its squared distances overflow on a wider span: its errors to report
-                    x = input_df[c].to_numpy(dtype=np.float64)
-                    with np.errstate(over="ignore", invalid="ignore"):
-                        if not float(np.nanmax(x) - np.nanmin(x)) <= LOF_MAX_RANGE:
-                            return None
-            for d in vdets:
-                if d["kind"] in ("outlier", "lof"):
-                    d["attrs"] = list(read)
         plan = self._resident_plan(input_df, cands, continous_columns, domain_stats, compute_repair_candidate_prob, maximal_likelihood_repair)
         if plan is None:
             return None
         plan.update(candidates=cands, constraints=cons, detect_nulls=has_null, value_detectors=vdets or None)
-        if constraints_resident and bool(self._get_option_value(*self._opt_constraints_order_scan)):
+        if bool(self._get_option_value(*self._opt_constraints_resident)) and bool(self._get_option_value(*self._opt_constraints_order_scan)):
             plan.update(order_scan=True)
         eopts = ErrorModel(row_id=self._row_id, targets=self.targets, discrete_thres=self.discrete_thres, error_detectors=self.error_detectors,
                            error_cells=None, opts=self.opts)._checked_options()
@@ -912,6 +941,73 @@ class RepairModel():
             # the reference's cell-domain analysis on the same resident table (repair.pipeline.analyse_cell_domains)
             plan.update(domain_analysis=dict(options=eopts, discrete_thres=self.discrete_thres, continuous_columns=list(continous_columns)))
         return plan
+
+    def _device_detect_only_plan(self, input_df: DataFrame, continous_columns: List[str]) -> Optional[Dict[str, Any]]:
+        """Can `run(detect_errors_only=True)` run on the resident table (option `error.detect_only.resident`)?  The DETECTOR conditions
+        of `_device_detection_plan` (`_detector_conditions`, `_outlier_columns_ok`) and an engine; none of `_resident_plan`'s model
+        conditions, and no "error cells outside the candidates" check: detection looks at ALL target attributes
+        (`ErrorModel._target_attrs`) and every cell is returned, repairable or not.  An empty detector list means the reference's defaults
+        (`ErrorModel._default_detectors`), which qualify when `error.value_detectors.resident` is set."""
+        emodel = ErrorModel(row_id=self._row_id, targets=self.targets, discrete_thres=self.discrete_thres, error_detectors=self.error_detectors,
+                            error_cells=None, opts=self.opts)
+        def no(reason: str) -> None:
+            _logger.info("[Error Detection Phase] device-side detection not taken: %s" % reason)
+            return None
+
+        why: List[str] = []
+        dets = self._detector_conditions(input_df, continous_columns, self.error_detectors or emodel._default_detectors(input_df), why)
+        if dets is None:
+            return no(why[0])
+        tattrs = emodel._target_attrs(list(input_df.columns))
+        if not tattrs or len(input_df) == 0:
+            return no("no target attribute, or no row")
+        if not self._outlier_columns_ok(input_df, dets["value_detectors"], [c for c in continous_columns if c in tattrs]):
+            return no("a continuous attribute that the outlier detectors of the resident table do not read as pandas does")
+        engine = self._resident_engine()
+        if engine is None:
+            return no("no engine for the resident table")
+        plan = dict(engine=engine, targets=tattrs, constraints=dets["constraints"], detect_nulls=dets["detect_nulls"],
+                    value_detectors=dets["value_detectors"] or None,
+                    order_scan=bool(self._get_option_value(*self._opt_constraints_resident))
+                    and bool(self._get_option_value(*self._opt_constraints_order_scan)))
+        eopts = emodel._checked_options()
+        if eopts[ErrorModel._opt_domain_analysis_enabled.key]:
+            plan.update(domain_analysis=dict(options=eopts, discrete_thres=self.discrete_thres, continuous_columns=list(continous_columns)))
+        return plan
+
+    def _detect_only_attempt(self, plan: Dict[str, Any], input_df: DataFrame, continous_columns: List[str]) -> Optional[DataFrame]:
+        """`pipeline.detect_frame` with the plan, or None (with the reason in the log) when the run turns out not to qualify."""
+        import time
+        from repair.pipeline import NotResidentEligible, detect_frame
+        vdets = None
+        if plan.get("value_detectors"):
+            from repair.detect_codes import build_descriptors
+
+            def build(*a: Any, **kw: Any) -> Any:
+                # whatever stops the restatement is the value-space detector's to report (as in `_resident_run`)
+                try:
+                    return build_descriptors(*a, **kw)
+                except NotResidentEligible:
+                    raise
+                except Exception as e:  # noqa: BLE001
+                    raise NotResidentEligible("value detectors: %s" % e)
+
+            vdets = dict(detectors=plan["value_detectors"], build=build)
+        _logger.info("[Error Detection Phase] on the HBM-resident table, target attributes %s" % to_list_str(plan["targets"]))
+        t0 = time.perf_counter()
+        try:
+            frame, info = detect_frame(plan["engine"], input_df, self._row_id, targets=plan["targets"], constraints=plan["constraints"],
+                                       detect_nulls=plan["detect_nulls"], value_detectors=vdets, domain_analysis=plan.get("domain_analysis"),
+                                       order_scan=plan["order_scan"], continuous_columns=list(continous_columns), want_details=True)
+        except NotResidentEligible as e:
+            self._last_resident_info = None
+            self._last_detection_on_device = False
+            _logger.info("device-side detection not taken: %s" % e)
+            return None
+        info["times"]["pipeline_wall"] = time.perf_counter() - t0
+        self._last_resident_info = info
+        self._last_detection_on_device = True
+        return frame
 
     def _cost_spec(self, engine: Any, attr: str, classes: Any, cur: List[Any], ml: bool) -> Dict[str, Any]:
         """The update costs of one target's cells as `repair.pipeline.repair_table(pmf_costs=...)` takes them, from the values
@@ -1192,6 +1288,12 @@ class RepairModel():
         # 0. Everything on the HBM-resident table, detection included, when the detectors and the run allow it
         dplan = None if detect_errors_only else self._device_detection_plan(input_df, continous_columns, compute_repair_candidate_prob,
                                                                             maximal_likelihood_repair)
+        if detect_errors_only and bool(self._get_option_value(*self._opt_detect_only_resident)):
+            oplan = self._device_detect_only_plan(input_df, continous_columns)
+            if oplan is not None:
+                out = self._detect_only_attempt(oplan, input_df, continous_columns)
+                if out is not None:
+                    return out
         if dplan is not None:
             out = self._resident_attempt("device-side detection", dplan, input_df, dplan["candidates"], continous_columns, None, *flags)
             if out is not None:

@@ -31,8 +31,14 @@ def _merge_cells(n, parts):
     return key % n, (key // n).astype(np.int32)
 
 
-def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_cells=None, value_detectors=None):
-    """Error cells of the target attributes.
+def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_cells=None, value_detectors=None, on_device=False):
+    """Error cells of the target attributes: (rows, cols), ordered by (column, row), every cell once.
+
+    on_device   : returns (rows, cols, codes), `codes` being what the cells hold now.  On a table with `cellset_open` the detectors'
+                  results never leave the device one by one: a cell set over the targets is opened, every part below is detected with
+                  ``fetch=False`` and followed by `Table.cellset_add`, and ONE `Table.cellset_emit` brings the union and its codes to the host
+                  (csrc/rgbm_cellset.hip).  Given `error_cells` are host arrays: they join last, by the host merge, and the codes
+                  are then read with `Table.read_cells`.  A table without the methods detects as with on_device=False and reads the codes.
 
     constraints : [(eq_cols, iq_col)] -- denial constraints  EQ(X1)..EQ(Xm) & IQ(Y)  (ErrorDetectorApi.scala:189-244); a
                   violating row contributes the constraint's attributes that are targets (`attrs`, line 211).  Next to them the
@@ -47,53 +53,86 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
     """
     tg = [int(t) for t in targets]
     parts = []
+    dev = bool(on_device) and bool(tg) and hasattr(table, "cellset_open")
+    given = None
     if error_cells is not None:
         r, c = np.asarray(error_cells[0], np.int64), np.asarray(error_cells[1], np.int32)
         keep = np.isin(c, tg) & (r >= 0) & (r < table.n)
-        parts.append((r[keep], c[keep]))
-    if value_detectors:
-        descs = {int(d["col"]): d for d in value_detectors if int(d["col"]) in tg}
-        call = []
-        for t in tg:                                   # position in the list = column order, as `_merge_cells` orders the result
-            d = descs.get(t)
-            null = bool(detect_nulls or (d is not None and d["null_is_error"]))
-            lo, hi, bits = (d["keep_lo"], d["keep_hi"], d["flag_bits"]) if d is not None else (0, -1, None)
-            if null or lo <= hi or bits is not None:
-                call.append((t, null, lo, hi, bits))
-        if call:
-            r, c = table.detect_cells([x[0] for x in call], [x[1] for x in call], [x[2] for x in call], [x[3] for x in call],
-                                      [x[4] for x in call])
-            parts.append((r, c))
-            found = np.bincount(c, minlength=table.c) if len(c) else np.zeros(table.c, np.int64)
-            for d in descs.values():
-                d["cells"] = int(found[int(d["col"])])
-    elif detect_nulls and tg:
-        parts.append(table.detect_nulls(tg))
-    for con in constraints:
-        if isinstance(con, dict):
-            attrs = [int(a) for a in con["refs"] if a in tg]
-            if not attrs:
-                continue
-            try:
-                if con["kind"] == "dc":
-                    parts.append(table.detect_dc(con["preds"], cell_cols=attrs, max_pairs=int(con.get("max_pairs", 0))))
-                elif con["kind"] == "dc_scan":         # an order constraint by sort and scan (`route_order_constraints`)
-                    parts.append(table.detect_dc_scan(con["preds"], cell_cols=attrs))
+        given = (r[keep], c[keep])
+        if not dev:
+            parts.append(given)
+
+    def part(method, *a, **kw):
+        """One detector call: its cells into `parts`, or (on the device) into the cell set; returns them or their count."""
+        if dev:
+            n = method(*a, fetch=False, **kw)
+            table.cellset_add()
+            return n
+        parts.append(method(*a, **kw))
+        return parts[-1]
+
+    set_cols = sorted(set(tg))                         # the set emits by position in this list: column order, as `_merge_cells` orders
+    if dev:
+        table.cellset_open(set_cols)
+    try:
+        if value_detectors:
+            descs = {int(d["col"]): d for d in value_detectors if int(d["col"]) in tg}
+            call = []
+            for t in tg:                                   # position in the list = column order, as `_merge_cells` orders the result
+                d = descs.get(t)
+                null = bool(detect_nulls or (d is not None and d["null_is_error"]))
+                lo, hi, bits = (d["keep_lo"], d["keep_hi"], d["flag_bits"]) if d is not None else (0, -1, None)
+                if null or lo <= hi or bits is not None:
+                    call.append((t, null, lo, hi, bits))
+            if call:
+                res = part(table.detect_cells, [x[0] for x in call], [x[1] for x in call], [x[2] for x in call], [x[3] for x in call],
+                           [x[4] for x in call])
+                if dev:
+                    # the call's own count per column: it is the first part, so the set holds nothing else yet and a count-only emit gives it
+                    found = np.zeros(table.c, np.int64)
+                    if descs:
+                        found[set_cols] = table.cellset_emit(fetch=False)
                 else:
-                    parts.append(table.detect_row_bits(con["cols"], con["bits"], cell_cols=attrs))
-            except Exception as e:  # noqa: BLE001
-                if getattr(e, "code", None) == -2:     # RGBM_ERR_PARAM: more pairs than max_pairs, a key span beyond 2^63
-                    raise NotResidentEligible("denial constraint: %s" % e)
-                raise
-            continue
-        eq, iq = con
-        attrs = []
-        for a in list(eq) + [iq]:
-            if a in tg and a not in attrs:
-                attrs.append(a)
-        if attrs:
-            parts.append(table.detect_constraint(list(eq), int(iq), cell_cols=attrs))
-    return _merge_cells(table.n, parts)
+                    found = np.bincount(res[1], minlength=table.c) if len(res[1]) else np.zeros(table.c, np.int64)
+                for d in descs.values():
+                    d["cells"] = int(found[int(d["col"])])
+        elif detect_nulls and tg:
+            part(table.detect_nulls, tg)
+        for con in constraints:
+            if isinstance(con, dict):
+                attrs = [int(a) for a in con["refs"] if a in tg]
+                if not attrs:
+                    continue
+                try:
+                    if con["kind"] == "dc":
+                        part(table.detect_dc, con["preds"], cell_cols=attrs, max_pairs=int(con.get("max_pairs", 0)))
+                    elif con["kind"] == "dc_scan":         # an order constraint by sort and scan (`route_order_constraints`)
+                        part(table.detect_dc_scan, con["preds"], cell_cols=attrs)
+                    else:
+                        part(table.detect_row_bits, con["cols"], con["bits"], cell_cols=attrs)
+                except Exception as e:  # noqa: BLE001
+                    if getattr(e, "code", None) == -2:     # RGBM_ERR_PARAM: more pairs than max_pairs, a key span beyond 2^63
+                        raise NotResidentEligible("denial constraint: %s" % e)
+                    raise
+                continue
+            eq, iq = con
+            attrs = []
+            for a in list(eq) + [iq]:
+                if a in tg and a not in attrs:
+                    attrs.append(a)
+            if attrs:
+                part(table.detect_constraint, list(eq), int(iq), cell_cols=attrs)
+        if dev:
+            rows, cols, codes, _ = table.cellset_emit()
+    finally:
+        if dev:
+            table.cellset_close()
+    if dev and given is None:
+        return rows, cols, codes
+    if dev:
+        parts = [(rows, cols), given]
+    rows, cols = _merge_cells(table.n, parts)
+    return (rows, cols, table.read_cells(rows, cols)) if on_device else (rows, cols)
 
 
 # searched parameter (sklearn alias, train.py:148-156) -> LightGBM core name of rgbm_params
@@ -1138,6 +1177,91 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         return frame
     regex_cells = {k: np.concatenate([d[k] for d in regex_done]) for k in regex_done[0]}
     return frame, _details(enc, df, row_id, res, rules, regex_cells if regex_rules else None)
+
+
+def _detect_only_frame(df, row_id, enc, rows, cols, codes):
+    """[row_id, "attribute", "current_value"] of the cells, `current_value` = CAST(value AS STRING) decoded once per dictionary entry: the
+    codes of a column that occur among its cells are formatted (`repair.errors._to_sql_string`; the float64 dictionary of an integral
+    column prints integral) and gathered; NULL stays None."""
+    import pandas as pd
+    from repair.encode import is_integral_column
+    from repair.errors import _to_sql_string
+    cur = np.empty(len(rows), object)
+    cur[:] = None
+    for j in np.unique(cols):
+        sel = np.flatnonzero((cols == j) & (codes >= 0))
+        if not len(sel):
+            continue
+        used, inverse = np.unique(codes[sel], return_inverse=True)
+        strs = np.empty(len(used), object)
+        strs[:] = [_to_sql_string(v) for v in enc.dicts[j][used]]
+        if is_integral_column(df[enc.columns[j]]):
+            strs[:] = [str(int(float(v))) for v in strs]
+        cur[sel] = strs[inverse]
+    return pd.DataFrame({row_id: pd.Series(df[row_id].to_numpy()[rows], dtype=df[row_id].dtype),
+                         "attribute": pd.Series(np.asarray(enc.columns, object)[cols], dtype=object),
+                         "current_value": pd.Series(cur, dtype=object)})
+
+
+def detect_frame(engine, df, row_id, targets=None, constraints=(), detect_nulls=True, value_detectors=None, domain_analysis=None,
+                 order_scan=False, continuous_columns=(), want_details=False):
+    """`RepairModel.run(detect_errors_only=True)` on the resident table: the frame [row_id, "attribute", "current_value"] of the error cells
+    of ALL target attributes (ErrorModel.detect returns every cell, repairable or not), detected, merged and read on the device.
+
+    The frame is encoded and uploaded once; `constraints`, `value_detectors` and `domain_analysis` are `repair_frame`'s, lowered against
+    the dictionaries (`_column_space`; `order_scan`: `route_order_constraints`); `detect_error_cells(on_device=True)` leaves the union of
+    the detectors' cells and the codes they hold in one emit of the table's cell set.  With `domain_analysis` the cell-domain analysis
+    runs on those cells for the noisy discretizable targets (continuous, or 1 < |domain| <= discrete_thres; `continuous_columns` where
+    the dict names none) and the weak-labelled cells are dropped on the host, as `repair_table`'s phase 1 does.
+
+    Row order: attribute in frame column order, then row position.  (The value-space frame has the detectors' concatenation order; a
+    caller that compares the two sorts both.)  No cell: the empty frame with the same columns and dtypes.  `want_details`: (frame,
+    details) with `constraint_routes`, `value_detectors`, `pairwise_attr_stats` / `noisy_cells` / `weak_cells` as `repair_frame` gives
+    them, and `times` (seconds: encode, upload, detect, domain, shape)."""
+    cols = [c for c in df.columns if c != row_id]
+    targets = list(targets) if targets is not None else list(cols)
+    unknown = [t for t in targets if t not in cols]
+    if unknown:
+        raise ValueError("Target attributes not found in the input: %s" % ",".join(unknown))
+    times = {}
+    t0 = time.perf_counter()
+    enc = FrameEncoding.of_frame(df, cols)
+    times["encode"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    table = _upload(engine, enc)
+    times["upload"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    if domain_analysis is not None and domain_analysis.get("continuous_columns") is None:
+        domain_analysis = dict(domain_analysis, continuous_columns=list(continuous_columns))
+    kw = _column_space(engine, enc, df, targets, constraints, detect_nulls, True, False, domain_analysis=domain_analysis,
+                       value_detectors=value_detectors)
+    cons = route_order_constraints(kw["constraints"], table) if order_scan else kw["constraints"]
+    vdets = kw["value_detectors"](table) if callable(kw["value_detectors"]) else None
+    target_cols = sorted(enc.pos[t] for t in targets)
+    rows, ccols, codes = detect_error_cells(table, target_cols, cons, detect_nulls, None, value_detectors=vdets, on_device=True)
+    times["detect"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    res = dict(constraint_routes=constraint_routes(cons), value_detectors=_detector_report(vdets))
+    spec = kw["domain_analysis"]
+    if spec is not None and len(rows):
+        stats, cont = spec["domain_stats"], spec.get("continuous") or {}
+        discretized = [j for j in range(len(cols)) if j in cont or 1 < stats[j] <= int(spec["discrete_thres"])]
+        noisy = set(int(c) for c in np.unique(ccols))
+        repairable = [j for j in discretized if j in noisy]
+        if repairable and len(discretized) > 1:
+            da = analyse_cell_domains(table, repairable, rows, ccols, spec)
+            res["domain"] = dict(pairwise=da["pairwise"], noisy_cells=int(len(rows)), weak_cells=int(da["weak"].sum()))
+            _logger.info("[Error Detection Phase] %d noisy cells fixed and %d error cells remaining..." % (res["domain"]["weak_cells"],
+                                                                                                       len(rows) - res["domain"]["weak_cells"]))
+            rows, ccols, codes = rows[~da["weak"]], ccols[~da["weak"]], codes[~da["weak"]]
+    times["domain"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    frame = _detect_only_frame(df, row_id, enc, rows, ccols, codes)
+    times["shape"] = time.perf_counter() - t0
+    if not want_details:
+        return frame
+    res["times"] = times
+    return frame, _details(enc, df, row_id, res, None, None)
 
 
 def constraint_to_columns(preds, columns):
