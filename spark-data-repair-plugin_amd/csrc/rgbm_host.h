@@ -39,6 +39,10 @@ inline int fail(int code, const std::string& msg) { last_error() = msg; return c
 void* pool_alloc(size_t bytes, size_t* block_bytes, int* device);     // defined in rgbm_runtime.hip; throws std::runtime_error
 void pool_free(void* p, size_t block_bytes, int device);
 void pool_trim(size_t keep_bytes);
+// The two debugging switches, each read once per process; the first use of either says so on stderr ("[rgbm guard] on, self-check ok",
+// "[rgbm poison] on": a run that was meant to have them can tell that it had).  Defined in rgbm_runtime.hip.
+bool guard_on();                                 // RGBM_GUARD=1: guard zones around every buffer, checked on free
+bool poison_on();                                // RGBM_POISON=1: every DevBuf starts as 0xA5 bytes
 
 template <typename T>
 struct DevBuf {
@@ -52,7 +56,7 @@ struct DevBuf {
         if (count) p = static_cast<T*>(pool_alloc(count * sizeof(T), &block_bytes, &device));
         // RGBM_POISON=1 (tests): every buffer starts out as 0xA5 bytes instead of whatever the pool block held -- a kernel that reads a
         // location nobody wrote then fails the bit-exact comparison with the oracle every time, not once in a few processes
-        static const bool poison = getenv("RGBM_POISON") != nullptr;
+        static const bool poison = poison_on();
         if (poison && count) { HIPCHK(hipMemset(p, 0xA5, count * sizeof(T))); HIPCHK(hipStreamSynchronize(nullptr)); }   // (our streams do not wait for the null stream)
     }
     void release() { if (p) { pool_free(p, block_bytes, device); p = nullptr; } n = 0; block_bytes = 0; }

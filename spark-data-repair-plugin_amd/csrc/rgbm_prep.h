@@ -67,6 +67,7 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
 // radix) or below -1 counts as NULL, so distinct keys never collide.  Neither rgbm_table_create nor rgbm_table_write_cells refuses such
 // codes, and on them the unclamped digit gives other (colliding) keys: rgbm_table_detect_constraint, which has always used it, keeps it
 // (CLAMP = false), so that its result stays what it was on every table; the two forms are the same wherever codes lie in [-1, n_codes).
+// Unclamped keys are not bounded by the span of the dictionaries: a hash table for them is sized by the rows alone (table_capacity(n)).
 template <bool CLAMP>
 __device__ __forceinline__ unsigned long long key_digit(int32_t v, unsigned long long radix) {
     if (!CLAMP) return (unsigned long long)(v + 1);
@@ -142,11 +143,17 @@ enum Scr {
     SCR_FREE_10 = 10, SCR_FREE_11 = 11      // nobody's yet
 };
 
-// scratch buffer `slot` of the table, at least `count` elements of T (grown, never shrunk)
+// scratch buffer `slot` of the table, at least `count` elements of T (grown with a quarter of headroom, never shrunk).  Under RGBM_GUARD the
+// buffer is exactly the bytes asked for, made anew whenever the request differs: the guard zone then begins where the entry's own use must end,
+// not a quarter or many times beyond it.  With RGBM_POISON as well it is made anew on EVERY fetch, so that a call of the same size as the
+// one before it starts on 0xA5 bytes and not on what that call left (a row mask of n bytes, say); under the guard alone such a repeat keeps
+// the earlier content.  Both rest on the rule above: no entry point fetches a slot twice in one call (the earlier pointer would dangle), and
+// the previous call's use ended with its synchronise.
 template <typename T>
 T* scr(const rgbm_table& t, Scr slot, size_t count) {
     const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    if (t.scratch[slot].n < bytes) t.scratch[slot].alloc(bytes + bytes / 4);
+    if (guard_on()) { if (t.scratch[slot].n != bytes || poison_on()) t.scratch[slot].alloc(bytes); }
+    else if (t.scratch[slot].n < bytes) t.scratch[slot].alloc(bytes + bytes / 4);
     return reinterpret_cast<T*>(t.scratch[slot].p);
 }
 template <typename T>

@@ -461,11 +461,15 @@ RGBM_EXPORT int rgbm_table_detect_constraint(rgbm_table* t, const int32_t* eq_co
         check_cols(*t, eq_cols, n_eq, "rgbm_table_detect_constraint");
         check_cols(*t, cell_cols, n_cell_cols, "rgbm_table_detect_constraint");
         if (iq_col < 0 || iq_col >= t->c) throw std::invalid_argument("rgbm_table_detect_constraint: IQ column out of range");
-        unsigned __int128 span = 1;
-        const KeySpec ks = key_spec(*t, eq_cols, n_eq, "rgbm_table_detect_constraint", &span);
+        unsigned __int128 span_unused = 1;
+        const KeySpec ks = key_spec(*t, eq_cols, n_eq, "rgbm_table_detect_constraint", &span_unused);
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
         const long long n = t->n;
-        const unsigned long long cap = table_capacity(n, span);
+        // Sized by the rows alone, not by the span of the dictionaries (key_spec is called for its refusal of 2^63 combinations only): the
+        // unclamped digit gives codes at or above a dictionary keys beyond the span, so the span does not bound the distinct keys here, and
+        // ht_claim needs an empty slot to end.  n rows hold at most n keys, so half the slots stay empty (that also ends the probes of the
+        // one key that equals HT_EMPTY, a code of -2 in a single EQ column).
+        const unsigned long long cap = table_capacity(n);
         unsigned long long* keys = scr<unsigned long long>(*t, SCR_TABLE_A, (size_t)cap);
         unsigned* state = scr<unsigned>(*t, SCR_TABLE_B, (size_t)cap);
         uint8_t* mask = scr<uint8_t>(*t, SCR_ROW_MASK, (size_t)n);

@@ -54,10 +54,16 @@ DevPool& pool() { static DevPool* p = new DevPool(); return *p; }
 
 // RGBM_GUARD=1 (debugging): every buffer sits between two 2 MB guard zones filled with 0xC3, and so is the slack between the bytes asked
 // for and the end of the pool block; pool_free checks that nobody wrote there and says so on stderr.  A kernel that READS out of
-// bounds sees the same 0xC3 bytes in every process instead of a neighbour's live data.
+// bounds sees the same 0xC3 bytes in every process instead of a neighbour's live data.  The first allocation says "[rgbm guard] on" on
+// stderr, after checking the check itself (guard_self_check); RGBM_POISON=1 (DevBuf::alloc, rgbm_host.h) says "[rgbm poison] on".
+bool rgh::guard_on() { static const bool g = getenv("RGBM_GUARD") != nullptr; return g; }
+bool rgh::poison_on() {
+    static const bool p = [] { const bool on = getenv("RGBM_POISON") != nullptr; if (on) fprintf(stderr, "[rgbm poison] on\n"); return on; }();
+    return p;
+}
 namespace {
+using rgh::guard_on;
 constexpr size_t GUARD = 2u << 20;
-bool guard_on() { static const bool g = getenv("RGBM_GUARD") != nullptr; return g; }
 std::mutex g_guard_mu; std::map<void*, size_t> g_guard_bytes;
 __global__ void k_guard_check(const unsigned char* p, size_t n, unsigned long long* bad /* [0] count, [1] first offset */) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -77,13 +83,61 @@ void rgh::trace_sum(const void* src, size_t bytes, unsigned long long* d_out, hi
     hipLaunchKernelGGL(k_trace_sum, dim3(2048), dim3(256), 0, s, (const unsigned long long*)src, bytes / 8, d_out);
 }
 
-void* rgh::pool_alloc(size_t bytes, size_t* block_bytes, int* device) {
-    if (!guard_on()) return pool_alloc_raw(bytes, block_bytes, device);
+namespace {
+// a buffer of `bytes` bytes between its two zones, the slack of the pool block included in the second
+void* guarded_alloc(size_t bytes, size_t* block_bytes, int* device) {
     unsigned char* raw = static_cast<unsigned char*>(pool_alloc_raw(bytes + 2 * GUARD, block_bytes, device));
     if (hipMemset(raw, 0xC3, GUARD) != hipSuccess || hipMemset(raw + GUARD + bytes, 0xC3, *block_bytes - GUARD - bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
         throw std::runtime_error("RGBM_GUARD: hipMemset failed");
-    { std::lock_guard<std::mutex> lk(g_guard_mu); g_guard_bytes[raw + GUARD] = bytes; }
     return raw + GUARD;
+}
+
+// The zone check: how many bytes of the two zones around the buffer of `bytes` bytes at raw + GUARD no longer hold 0xC3, and the first of them
+// (an offset into its zone).  Blocking, on the null stream.
+struct ZoneHit { const char* what; bool front; unsigned long long count, first; };
+void guard_check_zones(const unsigned char* raw, size_t bytes, size_t block_bytes, ZoneHit (&hits)[2]) {
+    static thread_local unsigned long long* d_bad = nullptr;
+    if (!d_bad && hipMalloc(&d_bad, 16) != hipSuccess) { d_bad = nullptr; throw std::runtime_error("RGBM_GUARD: hipMalloc failed"); }
+    const struct { const unsigned char* q; size_t n; const char* what; } zones[2] = {{raw, GUARD, "front guard"},
+                                                                                      {raw + GUARD + bytes, block_bytes - GUARD - bytes, "slack + back guard"}};
+    for (int z = 0; z < 2; ++z) {
+        unsigned long long h[2] = {0ull, ~0ull};
+        bool ok = hipMemcpy(d_bad, h, 16, hipMemcpyHostToDevice) == hipSuccess;
+        hipLaunchKernelGGL(k_guard_check, dim3(1024), dim3(256), 0, nullptr, zones[z].q, zones[z].n, d_bad);
+        ok = ok && hipGetLastError() == hipSuccess && hipMemcpy(h, d_bad, 16, hipMemcpyDeviceToHost) == hipSuccess;
+        if (!ok) throw std::runtime_error("RGBM_GUARD: the zone check did not run");
+        hits[z] = ZoneHit{zones[z].what, z == 0, h[0], h[1]};
+    }
+}
+
+// First use in guard mode: the check must see a byte that IS overwritten, or a clean run says nothing.  One byte just past the end of a small
+// buffer is cleared from the host (inside the buffer's own back zone, so inside its own allocation); the check has to count that byte alone.
+void guard_self_check() {
+    const size_t bytes = 192;
+    size_t block = 0; int dev = 0;
+    unsigned char* p = static_cast<unsigned char*>(guarded_alloc(bytes, &block, &dev));
+    ZoneHit hits[2];
+    const bool wrote = hipMemset(p + bytes, 0, 1) == hipSuccess;
+    try { guard_check_zones(p - GUARD, bytes, block, hits); }
+    catch (...) { pool_free_raw(p - GUARD, block, dev); throw; }
+    pool_free_raw(p - GUARD, block, dev);
+    if (!wrote || hits[0].count != 0 || hits[1].count != 1 || hits[1].first != 0) {
+        char b[256];
+        snprintf(b, sizeof(b), "RGBM_GUARD: self-check failed (one byte cleared past a %zu-byte buffer; the check counts %llu in front, %llu behind, first at %lld)",
+                 bytes, hits[0].count, hits[1].count, (long long)hits[1].first);
+        throw std::runtime_error(b);
+    }
+    fprintf(stderr, "[rgbm guard] on, self-check ok\n");
+}
+}  // namespace
+
+void* rgh::pool_alloc(size_t bytes, size_t* block_bytes, int* device) {
+    if (!guard_on()) return pool_alloc_raw(bytes, block_bytes, device);
+    static std::once_flag self_check;                   // (a check that throws runs again with the next allocation)
+    std::call_once(self_check, guard_self_check);
+    void* p = guarded_alloc(bytes, block_bytes, device);
+    { std::lock_guard<std::mutex> lk(g_guard_mu); g_guard_bytes[p] = bytes; }
+    return p;
 }
 
 void rgh::pool_free(void* p, size_t block_bytes, int device) {
@@ -92,18 +146,12 @@ void rgh::pool_free(void* p, size_t block_bytes, int device) {
     size_t bytes = 0;
     { std::lock_guard<std::mutex> lk(g_guard_mu); auto it = g_guard_bytes.find(p); if (it != g_guard_bytes.end()) { bytes = it->second; g_guard_bytes.erase(it); } }
     unsigned char* raw = static_cast<unsigned char*>(p) - GUARD;
-    static thread_local unsigned long long* d_bad = nullptr;
-    if (!d_bad) (void)hipMalloc(&d_bad, 16);
-    const size_t tail = block_bytes - GUARD - bytes;
-    const struct { const unsigned char* q; size_t n; const char* what; } zones[2] = {{raw, GUARD, "front guard"}, {raw + GUARD + bytes, tail, "slack + back guard"}};
-    for (const auto& z : zones) {
-        unsigned long long h[2] = {0ull, ~0ull};
-        (void)hipMemcpy(d_bad, h, 16, hipMemcpyHostToDevice);
-        hipLaunchKernelGGL(k_guard_check, dim3(1024), dim3(256), 0, nullptr, z.q, z.n, d_bad);
-        (void)hipMemcpy(h, d_bad, 16, hipMemcpyDeviceToHost);
-        if (h[0]) fprintf(stderr, "[rgbm guard] buffer of %zu bytes (block %zu): %llu byte(s) of the %s were overwritten, first at offset %lld from the buffer's %s\n",
-                          bytes, block_bytes, h[0], z.what, z.q == raw ? (long long)h[1] - (long long)GUARD : (long long)h[1], z.q == raw ? "start" : "end");
-    }
+    ZoneHit hits[2] = {};
+    try { guard_check_zones(raw, bytes, block_bytes, hits); }
+    catch (const std::exception& e) { fprintf(stderr, "[rgbm guard] buffer of %zu bytes (block %zu): not checked (%s)\n", bytes, block_bytes, e.what()); }
+    for (const ZoneHit& h : hits)
+        if (h.count) fprintf(stderr, "[rgbm guard] buffer of %zu bytes (block %zu): %llu byte(s) of the %s were overwritten, first at offset %lld from the buffer's %s\n",
+                             bytes, block_bytes, h.count, h.what, h.front ? (long long)h.first - (long long)GUARD : (long long)h.first, h.front ? "start" : "end");
     pool_free_raw(raw, block_bytes, device);
 }
 

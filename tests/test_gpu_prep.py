@@ -72,6 +72,32 @@ def test_constraint_detector_reference_golden_rows():
     assert rows.tolist() == [0, 1, 2, 3, 4] * 2 and cols.tolist() == [0] * 5 + [1] * 5
 
 
+@pytest.mark.parametrize("n", [1, 255, 257, 4097, 12289])
+def test_constraint_detector_with_codes_outside_the_dictionary(n):
+    """rgbm_table_create takes codes at or above a column's dictionary, and the detector gives them keys of their own (the unclamped
+    digit, csrc/rgbm_prep.h): this holds their RESULT to the oracle.  Fewer distinct keys than the span of the declared dictionaries here,
+    so a hash table sized by the span holds them as well as one sized by the rows.  This is therefore NOT the regression test of the
+    probe that never ends on a full table (more such keys than a span-sized table has slots): that case hangs the device where the fix
+    is missing, so no test provokes it; the sizing by rows is argued in rgbm_table_detect_constraint.  Only the first (most significant)
+    EQ column leaves its dictionary, so no two keys collide and the oracle's exact keys apply."""
+    from oracle import prep as P
+    from repair import _native as N
+    rng = np.random.default_rng(n)
+    x0 = rng.choice(np.array([-1, 0, 1, 2, 12, 15], np.int32), n)             # declared 10 codes: 12 and 15 lie outside
+    x1 = rng.integers(-1, 3, n).astype(np.int32)
+    y = rng.choice(np.array([-1, 0, 1, 9, 40], np.int32), n)                  # declared 4 codes: the IQ side leaves its dictionary too
+    y[x0 == 12] = 40                                                          # a group outside the dictionary that holds one value only
+    X = np.stack([x0, x1, y])
+    tab = N.Table(X, [10, 3, 4])
+    for eq in ([0], [0, 1], []):
+        want = P.constraint_rows(X, eq, 2)
+        got = tab.detect_constraint(eq, 2)
+        assert np.array_equal(got, want), "n=%d eq=%r" % (n, eq)
+    rows, cols = tab.detect_constraint([0], 2, cell_cols=[2, 0])
+    er, ec = P.constraint_cells(X, [0], 2, [2, 0])
+    assert np.array_equal(rows, er) and np.array_equal(cols, ec)
+
+
 def test_constraint_detector_rejects_bad_arguments():
     from repair import _native as N
     tab, dirty, cards = _table(100, 3, seed=1)
