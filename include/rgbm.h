@@ -385,6 +385,25 @@ int rgbm_table_count_codes(const rgbm_table* t, int32_t col, int64_t* counts_out
  * 0, 1..254, edges_out == NULL with n_bins > 0; a refused call leaves the table as it was. */
 int rgbm_table_column_stats(const rgbm_table* t, const int32_t* cols, int32_t n_cols, const int32_t* const* len_lut,
                             int32_t n_bins, int64_t* stats_out, int32_t* edges_out);
+/* The measures of the functional dependencies X -> Y of one left-hand side X (lhs_cols, 0 .. 11 distinct columns; none: all rows are one
+ * group) against n_rhs >= 1 right-hand sides (rhs_cols, distinct, none of them in X) in one call (RepairMisc.discoverFunctionalDeps; the
+ * statement is repair.fd_codes.fd_measures).  A code outside [0, n_codes) is NULL, as for rgbm_table_detect_dc, and NULL is a value of its
+ * own on both sides.  groups_out [1] = the distinct X-keys; per right-hand side r: kept_out[r] = the sum over the X-groups of the largest
+ * number of the group's rows that share one Y value (rows - kept = the fewest rows to remove for X -> Y to hold, the g3 measure);
+ * violating_out[r] = the rows in X-groups of two or more Y values; xy_groups_out[r] = the distinct (X, Y) keys.  All integers: the result
+ * does not depend on the order of arrival.  A right-hand side whose dense joint table span(X) * (n_codes[Y] + 1) (span = the product of
+ * n_codes + 1 over X) fits a workgroup's LDS counters is counted there (route 0), every other one through two hash tables (route 1).
+ * No code is written; the table's cell list and cell set stay as they were.
+ * RGBM_ERR_ARG: a NULL argument (lhs_cols may be NULL with n_lhs == 0), n_lhs outside 0 .. 11, n_rhs < 1, a column outside the table, a
+ * column twice in either list, a right-hand side that is also in X.  RGBM_ERR_PARAM: span(X) of 2^63 or more, a table of 2^31 rows or
+ * more.  After either refusal the output arrays and the report below are as they were. */
+int rgbm_table_fd_measures(rgbm_table* t, const int32_t* lhs_cols, int32_t n_lhs /* 0..11 */, const int32_t* rhs_cols, int32_t n_rhs /* >= 1 */,
+                           int64_t* groups_out /* [1] */, int64_t* kept_out, int64_t* violating_out, int64_t* xy_groups_out /* each [n_rhs] */);
+/* The routes the last successful rgbm_table_fd_measures call on the table took (read-only, no device work; for tests that must know their
+ * route).  out [n_rhs + 2]: per right-hand side of that call 0 (LDS counters) or 1 (hash tables), then the two limits: the counters of a
+ * dense joint table on route 0, the columns of a left-hand side.  n_rhs must be that call's (0 before any call), else RGBM_ERR_ARG.
+ * t == NULL with n_rhs == 0 gives the two limits alone and needs no device. */
+int rgbm_table_fd_measures_report(const rgbm_table* t, int32_t* out /* [n_rhs + 2] */, int32_t n_rhs);
 /* Encoding on the device (replaces the pandas encoders of python/repair/model.py:701-729): per column, Arrow-style
  * dictionary indices (idx < 0 = NULL) are mapped through remap[col][idx] (the rank of the dictionary value in
  * sorted order, or -1) into the code table. */

@@ -202,6 +202,8 @@ struct rgbm_table {
     // the plan of that call, as its planner made it (rgbm_table_pair_counts_report): per pair {group (-1 = the HBM kernel), slot of x, slot of y};
     // {groups, cells of the largest group, grid x, rows per workgroup}
     mutable std::vector<int32_t> pc_plan; mutable long long pc_plan_head[4] = {0, 0, 0, 0};
+    // the route of every right-hand side of the last successful rgbm_table_fd_measures call (0 = LDS counters, 1 = hash tables), under prep_mu
+    mutable std::vector<int32_t> fd_routes;
     // the cluster of every row after the last rgbm_table_kmeans_assign call (int32 [n]); it leaves the device through rgbm_table_kmeans_read
     mutable rgh::DevBuf<int32_t> km_assign; mutable bool km_valid = false;
     mutable rgbm_distinct_view view;

@@ -140,7 +140,8 @@ enum Scr {
     SCR_IN_ROWS = 7,      // the caller's row positions
     SCR_IN_COLS = 8,      // int32 per cell or code: the caller's columns, a LUT, top codes
     SCR_VALS = 9,         // values per cell or code, in or out: codes, counts, labels, probabilities, the fd map
-    SCR_FREE_10 = 10, SCR_FREE_11 = 11      // nobody's yet
+    SCR_COUNTS = 10,      // dense 32-bit counters that workgroups flush into: the joint tables of the fd measures
+    SCR_FREE_11 = 11      // nobody's yet
 };
 
 // scratch buffer `slot` of the table, at least `count` elements of T (grown with a quarter of headroom, never shrunk).  Under RGBM_GUARD the

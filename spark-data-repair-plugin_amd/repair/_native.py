@@ -96,7 +96,7 @@ def lib():
             getattr(l, name).restype = C.c_int
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect",
                      "rgbm_table_pair_counts_report", "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit",
-                     "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close"):
+                     "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close", "rgbm_table_fd_measures", "rgbm_table_fd_measures_report"):
             if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass / no count report / no cell set)
                 getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
@@ -126,6 +126,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
     "rgbm_table_pair_counts_report", "rgbm_regex_structure", "rgbm_table_detect_dc_scan",
     "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit", "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close",
+    "rgbm_table_fd_measures", "rgbm_table_fd_measures_report",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -497,6 +498,14 @@ def pair_counts_limits():
     head = np.zeros(6, np.int64)
     _check(lib().rgbm_table_pair_counts_report(None, _p(head, C.c_int64), None, C.c_int32(0)), "rgbm_table_pair_counts_report")
     return dict(lds_cells=int(head[4]), max_cols=int(head[5]))
+
+
+def fd_measures_limits():
+    """The two limits of ``Table.fd_measures`` (rgbm_table_fd_measures_report without a table; needs no device): dict(lds_cells = 32-bit
+    counters of a dense joint table on the LDS route, max_lhs = columns of a left-hand side)."""
+    out = np.zeros(2, np.int32)
+    _check(lib().rgbm_table_fd_measures_report(None, _p(out, C.c_int32), C.c_int32(0)), "rgbm_table_fd_measures_report")
+    return dict(lds_cells=int(out[0]), max_lhs=int(out[1]))
 
 
 def _chain_args(models, feat_cols, class_codes):
@@ -1002,6 +1011,27 @@ class Table:
         out = {f: stats[:, i].copy() for i, f in enumerate(FIELDS)}
         out["edges"] = edges
         return out
+
+    def fd_measures(self, lhs, rhs_cols):
+        """The measures of X -> Y for one left-hand side ``lhs`` (0 .. 11 columns) against the right-hand sides ``rhs_cols`` in one call
+        (include/rgbm.h rgbm_table_fd_measures), exactly the integers of ``repair.fd_codes.fd_measures``: dict(groups = int64, kept,
+        violating, xy_groups = int64 [len(rhs_cols)])."""
+        lc = _i32(np.asarray(lhs, np.int32).reshape(-1))
+        rc = _i32(np.asarray(rhs_cols, np.int32).reshape(-1))
+        g, kept, viol, xy = (np.zeros(1, np.int64),) + tuple(np.zeros(max(len(rc), 1), np.int64) for _ in range(3))
+        _check(lib().rgbm_table_fd_measures(self.h, _p(lc, C.c_int32), C.c_int32(len(lc)), _p(rc, C.c_int32), C.c_int32(len(rc)),
+                                            _p(g, C.c_int64), _p(kept, C.c_int64), _p(viol, C.c_int64), _p(xy, C.c_int64)),
+               "rgbm_table_fd_measures")
+        self._fd_last = len(rc)                           # the right-hand sides of the call whose routes the table now holds
+        return dict(groups=np.int64(g[0]), kept=kept[:len(rc)], violating=viol[:len(rc)], xy_groups=xy[:len(rc)])
+
+    def fd_measures_report(self):
+        """The routes the last successful ``fd_measures`` call on this table took (include/rgbm.h rgbm_table_fd_measures_report):
+        dict(routes = one per right-hand side, 0 = LDS counters, 1 = hash tables; lds_cells, max_lhs = the two limits)."""
+        n_rhs = getattr(self, "_fd_last", 0)
+        out = np.zeros(n_rhs + 2, np.int32)
+        _check(lib().rgbm_table_fd_measures_report(self.h, _p(out, C.c_int32), C.c_int32(n_rhs)), "rgbm_table_fd_measures_report")
+        return dict(routes=[int(r) for r in out[:n_rhs]], lds_cells=int(out[n_rhs]), max_lhs=int(out[n_rhs + 1]))
 
     def fd_map(self, x, y):
         """The rule model of the functional dependency x -> y (include/rgbm.h rgbm_table_fd_map): int32 [n_codes[x]], the single y code

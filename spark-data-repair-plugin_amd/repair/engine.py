@@ -123,6 +123,10 @@ class HipEngine:
         """`repair.table_stats.column_stats` on a resident table (rgbm_table_column_stats), the same integers: the per-code counts stay on the device."""
         return table.column_stats(cols, len_luts=len_luts, n_bins=n_bins)
 
+    def fd_measures(self, table, lhs, rhs_cols):
+        """`repair.fd_codes.fd_measures` on a resident table (rgbm_table_fd_measures), the same integers."""
+        return table.fd_measures(lhs, rhs_cols)
+
     def repair_chain_gather(self, table, models, targets, feats, row_begin, n_rows):
         """C2 on device buffers: the chain over this rank's rows, labels / probabilities all-gathered over the rank's communicator before
         they leave the device (include/rgbm.h rgbm_table_repair_chain_gather) -> (labels, probs of ALL ranks' rows in rank order, first row of this rank)."""

@@ -6,7 +6,10 @@ features, on the resident code table when a device is present: repair/qgram_kmea
 `toErrorMap`, `describe` (the column statistics of Spark's ANALYZE, from per-code row counts: repair/table_stats.py) and
 `generateDepGraph` (the Graphviz text of DepGraph.computeDepGraph from dense pair counts: repair/depgraph.py); the last two run on the
 resident code table when a device is present and on their numpy statements otherwise, with the same result.
+`discoverFunctionalDeps` has no counterpart in the reference: it finds the minimal (approximate) functional dependencies of a table and
+returns them as constraint text for `ConstraintErrorDetector`, on the same two paths (repair/fd_discovery.py).
 """
+import logging
 from typing import Any, Dict, List
 
 import numpy as np
@@ -16,6 +19,7 @@ from repair import session
 from repair.utils import argtype_check
 
 DataFrame = pd.DataFrame
+_logger = logging.getLogger(__name__)
 
 
 class RepairMisc():
@@ -165,6 +169,81 @@ class RepairMisc():
             raise ValueError("Option 'num_bins' must be an integer, but '%s' found" % self.opts["num_bins"]) from None
         from repair import table_stats
         return table_stats.describe_frame(self._input(), n_bins=n_bins, engine=self._resident_engine())
+
+    def discoverFunctionalDeps(self) -> DataFrame:
+        """The minimal (approximate) functional dependencies X -> Y of an input table, found level by level from integer measures of the
+        code table (repair/fd_discovery.py; on the resident table when a device is present, on the numpy statement repair/fd_codes.py
+        otherwise, with the same result: DESIGN.md 5o) -> [lhs, rhs, groups, removed_rows, violating_rows, error, constraint], ordered
+        by the size of X, the columns' positions, then Y.  `constraint` is text that `ConstraintErrorDetector` takes unchanged, and
+        `violating_rows` the rows it then flags.  Options: `row_id` (that column takes no part), `targets` (a comma list: the right-hand
+        sides only), `max_lhs_size` ("2", 1 .. 4), `max_error` ("0.0": the share of the rows that may be removed for a dependency to hold,
+        read exactly from its decimal text), `max_lhs_group_ratio` ("1.0": supersets of a left-hand side with more groups than this share
+        of the rows are not looked at).  The reference cites constraint discovery and has no counterpart."""
+        self._check_required_options(["table_name"])
+        from fractions import Fraction
+        from repair import fd_codes, fd_discovery
+        from repair.errors import parse_constraint
+        from repair.frame_encoding import FrameEncoding
+        if not self.opts.get("max_lhs_size", "2").isdigit() or not 1 <= int(self.opts.get("max_lhs_size", "2")) <= fd_discovery.MAX_LHS_SIZE:
+            raise ValueError("Option 'max_lhs_size' must be an integer in [1, %d], but '%s' found"
+                             % (fd_discovery.MAX_LHS_SIZE, self.opts["max_lhs_size"]))
+        for opt, default, hi in (("max_error", "0.0", 1), ("max_lhs_group_ratio", "1.0", None)):
+            try:
+                v = Fraction(self.opts.get(opt, default).strip())
+                ok = v >= 0 and (hi is None or v < hi)
+            except (ValueError, ZeroDivisionError):
+                ok = False
+            if not ok:
+                raise ValueError("Option '%s' must be a decimal in [0.0, %s, but '%s' found" % (opt, "1.0)" if hi else "inf)", self.opts[opt]))
+        df = self._input()
+        rid = self.opts.get("row_id", "")
+        if rid:
+            self._check_attrs(df, [rid])
+        cols = [c for c in df.columns if c != rid]
+        targets = [a.strip() for a in self.opts.get("targets", "").split(",") if a.strip()]
+        self._check_attrs(df, targets)
+        if rid and rid in targets:
+            raise ValueError("Option 'targets' must not hold the row id '%s'" % rid)
+        names = ["lhs", "rhs", "groups", "removed_rows", "violating_rows", "error", "constraint"]
+        n = len(df)
+        records: List[Dict[str, Any]] = []
+        if n > 0 and cols:
+            enc = FrameEncoding.of_frame(df, cols)
+            engine = self._resident_engine()
+            if engine is not None:
+                table = engine.upload_dictionaries(enc.indices, enc.remaps)
+                measure = lambda lhs, rhs: engine.fd_measures(table, lhs, rhs)  # noqa: E731
+            else:
+                codes = np.stack([np.where(i >= 0, r[np.maximum(i, 0)] if len(r) else -1, -1).astype(np.int32)
+                                  for i, r in zip(enc.indices, enc.remaps)])
+                n_codes = [max(len(d), 1) for d in enc.dicts]
+                measure = lambda lhs, rhs: fd_codes.fd_measures(codes, n_codes, lhs, rhs)  # noqa: E731
+            log: List[str] = []
+            records = fd_discovery.discover(measure, n, cols, targets or cols, max_lhs_size=int(self.opts.get("max_lhs_size", "2")),
+                                            max_error=self.opts.get("max_error", "0.0"),
+                                            max_lhs_group_ratio=self.opts.get("max_lhs_group_ratio", "1.0"), log=log)
+            for line in log:
+                _logger.info("discoverFunctionalDeps: %s" % line)
+        rows = []
+        for r in records:
+            text = "t1&t2&%s&IQ(t1.%s,t2.%s)" % ("&".join("EQ(t1.%s,t2.%s)" % (a, a) for a in r["lhs"]), r["rhs"], r["rhs"])
+            want = [("EQ", a, a, None) for a in r["lhs"]] + [("IQ", r["rhs"], r["rhs"], None)]
+            try:
+                got = [(p.op, p.left, p.right, p.constant) for p in parse_constraint(text)]
+            except ValueError:
+                got = []
+            if got != want:
+                _logger.warning("discoverFunctionalDeps: %s -> %s is left out, its constraint text does not parse back: %s"
+                                % (",".join(r["lhs"]), r["rhs"], text))
+                continue
+            rows.append((",".join(r["lhs"]), r["rhs"], r["groups"], r["removed_rows"], r["violating_rows"], r["removed_rows"] / n, text))
+        out = pd.DataFrame(rows, columns=names)
+        for c in ("groups", "removed_rows", "violating_rows"):
+            out[c] = out[c].astype(np.int64)
+        out["error"] = out["error"].astype(np.float64)
+        for c in ("lhs", "rhs", "constraint"):
+            out[c] = out[c].astype(object)
+        return out
 
     def toHistogram(self) -> DataFrame:
         """The value counts of the listed attributes (RepairMiscApi.convertToHistogram, :276-301): one row [attribute, histogram] per
