@@ -338,6 +338,27 @@ int rgbm_table_cellset_add(rgbm_table* t);
 int rgbm_table_cellset_emit(rgbm_table* t, int64_t* n_cells_out, int64_t* counts_out /* [n_cols] or NULL */);
 int rgbm_table_cells_fetch_codes(const rgbm_table* t, int32_t* codes_out /* [n_cells] */);
 int rgbm_table_cellset_close(rgbm_table* t);
+/* The repair run on the open set: the error cells stay in it from detection through the null-out.  Every entry is
+ * RGBM_ERR_PARAM without an open set, and after every refusal the set, the cell list and the codes of the last emit are as they were.
+ * add_cells: ORs host-given cells into the set, in any order and with duplicates (setErrorCells; the cells of a second pass).  A cell
+ *        outside the table or of a column not in the set is skipped (join semantics, as in add); n_cells == 0 adds nothing.  The
+ *        table's cell list stays as it was.  RGBM_ERR_ARG: n_cells < 0, a NULL array with n_cells > 0.
+ * drop_weak: for every cell of the set's column target_col, exactly the `weak` flag that rgbm_table_cell_domains gives for that row -- on the
+ *        tables of the last rgbm_table_pair_counts call and the codes as they lie now; the other arguments are that entry's -- and the
+ *        cell's bit cleared where it is set.  The examined cells (ascending rows, as they were BEFORE pruning) become the table's cell list,
+ *        as after a detect call; n_cells_out is their number, n_weak_out the bits cleared.  The refusals of rgbm_table_cell_domains (a
+ *        pair index is looked at whatever the number of cells), and RGBM_ERR_PARAM for a target that is not a column of the set.
+ * null:  writes NULL into every cell of the set, straight from the matrix; no other code changes.  n_cells_out = the cells.  A table
+ *        write like rgbm_table_null_cells (the distinct-row view is dropped).  The set, the cell list and the codes of the last emit stay:
+ *        those codes are then what the cells held AT THAT EMIT, no longer what they hold.
+ * rows:  the ascending rows that hold at least one cell of the set become the table's cell list, as a row list without columns -- the
+ *        result shape of rgbm_table_rows_of_cells, fetched with rgbm_table_cells_fetch(rows, NULL). */
+int rgbm_table_cellset_add_cells(rgbm_table* t, const int64_t* rows, const int32_t* cols, int64_t n_cells);
+int rgbm_table_cellset_drop_weak(rgbm_table* t, int32_t target_col, const int32_t* pair_idx, int32_t k, const int64_t* min_cnt /* [k] */,
+                                 const uint8_t* single_ok /* [n_bins[target]] */, double beta, int64_t row_count, int64_t* n_cells_out,
+                                 int64_t* n_weak_out);
+int rgbm_table_cellset_null(rgbm_table* t, int64_t* n_cells_out);
+int rgbm_table_cellset_rows(rgbm_table* t, int64_t* n_rows_out);
 /* convertErrorCellsToNull (src/main/scala/.../python/RepairApi.scala:171-211): NULL the listed cells whose
  * column is one of target_cols; cells outside the table are ignored (join semantics). */
 int rgbm_table_null_cells(rgbm_table* t, const int64_t* rows, const int32_t* cols, int64_t n_cells,

@@ -9,8 +9,12 @@
 //                together (detector results are sorted by column and row, so a wave mostly holds one or two words)
 //   k_cs_count   bcount of every (block, column) entry: popcount over its 64 words, one wave per entry
 //   k_cs_gather  codes[col * n + row] of every emitted cell, as it lies
+//   k_cs_drop_weak  one lane per emitted cell of ONE column: the weak flag of rgbm_domain.h's cell_domain; a set flag clears the cell's bit (atomicAnd:
+//                several weak cells share a word)
+//   k_cs_null    one wave per (block, column) entry: NULL into codes at every set bit, the zero words skipped
+//   k_cs_or_cols the columns of the set ORed word by word: the ballots of the rows that hold a cell
 // The matrix, the column lists and the codes of the last emit are DevBufs of the table, not Scr slots: they outlive the detect calls in between.
-#include "rgbm_prep.h"
+#include "rgbm_domain.h"
 
 namespace {
 
@@ -71,9 +75,69 @@ __global__ __launch_bounds__(256) void k_cs_gather(const int32_t* __restrict__ c
     out[i] = codes[(long long)cols[i] * n + rows[i]];
 }
 
+// cell i = (rows [i], target) is one of the set's column `target` (its words at `bits`): weak -> its bit leaves the set; *n_weak counts them
+__global__ __launch_bounds__(256) void k_cs_drop_weak(const int32_t* __restrict__ codes, long long n, int target, int d_a,
+                                                      const long long* __restrict__ rows, long long m, const unsigned long long* __restrict__ joint,
+                                                      const DomAttr* __restrict__ attrs, int k, const int32_t* __restrict__ colinfo,
+                                                      const long long* __restrict__ lut_off, const int32_t* __restrict__ luts,
+                                                      const uint8_t* __restrict__ single_ok, double beta, double row_count,
+                                                      unsigned long long* __restrict__ bits, unsigned long long* __restrict__ n_weak) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool weak = false;
+    if (i < m) {
+        const long long r = rows[i];                      // inside the table: an emitted row
+        weak = cell_domain(codes, n, target, d_a, r, joint, attrs, k, colinfo, lut_off, luts, single_ok, beta, row_count, nullptr).weak;
+        if (weak) atomicAnd(&bits[r >> 6], ~(1ull << (r & 63)));
+    }
+    const unsigned long long w = __ballot(weak);
+    if (lane_id() == 0 && w) atomicAdd(n_weak, (unsigned long long)__popcll(w));
+}
+
+// entry e = p * nblk + b of the matrix (one wave each, 4 per workgroup): codes[cols[p]][row] = NULL for every set bit; *n_cells counts them
+__global__ __launch_bounds__(PB) void k_cs_null(const unsigned long long* __restrict__ bits, long long m, long long nblk, const int32_t* __restrict__ cols,
+                                                int32_t* __restrict__ codes, long long n, unsigned long long* __restrict__ n_cells) {
+    const long long e = (long long)blockIdx.x * (PB / 64) + (threadIdx.x >> 6);
+    if (e >= m) return;                                   // (whole waves leave: e is uniform over a wave)
+    const int lane = lane_id();
+    const unsigned long long word = bits[e * PBAL + lane];
+    unsigned long long nz = __ballot(word != 0ull);
+    if (!nz) return;
+    const long long col = cols[e / nblk], row0 = (e % nblk) * PROWS;
+    unsigned cnt = (unsigned)__popcll(word);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) cnt += (unsigned)__shfl_xor((int)cnt, d);
+    if (lane == 0) atomicAdd(n_cells, (unsigned long long)cnt);
+    while (nz) {
+        const int q = __ffsll((long long)nz) - 1;
+        const unsigned long long wq = __shfl(word, q);
+        const long long r = row0 + (long long)q * 64 + lane;
+        if (((wq >> lane) & 1ull) && r < n) codes[col * n + r] = -1;
+        nz &= nz - 1ull;
+    }
+}
+
+// out [W] = the OR of the set's n_cols columns, word by word
+__global__ __launch_bounds__(256) void k_cs_or_cols(const unsigned long long* __restrict__ bits, long long W, int n_cols, unsigned long long* __restrict__ out) {
+    const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= W) return;
+    unsigned long long v = 0ull;
+    for (int p = 0; p < n_cols; ++p) v |= bits[(long long)p * W + w];
+    out[w] = v;
+}
+
 bool cs_combine() {                   // RGBM_CELLSET_COMBINE=0: every lane its own atomic (tools/detect_only_bench.py times both forms); read per call
     const char* e = getenv("RGBM_CELLSET_COMBINE");
     return !(e && e[0] == '0');
+}
+
+// k_cs_or over m cells (device arrays) into the open set, in the form cs_combine() chooses; left in flight on s
+void launch_cs_or(rgbm_table& t, const long long* d_rows, const int32_t* d_cols, long long m, hipStream_t s) {
+    const long long W = (long long)PBAL * ((t.n + PROWS - 1) / PROWS);
+    if (cs_combine())
+        hipLaunchKernelGGL(k_cs_or<CS_ROUNDS>, dim3(nblocks(m, 256)), dim3(256), 0, s, d_rows, d_cols, m, t.cs_d_pos.p, (long long)t.n, (int)t.c, W, t.cs_bits.p);
+    else
+        hipLaunchKernelGGL(k_cs_or<0>, dim3(nblocks(m, 256)), dim3(256), 0, s, d_rows, d_cols, m, t.cs_d_pos.p, (long long)t.n, (int)t.c, W, t.cs_bits.p);
+    HIPCHK(hipGetLastError());
 }
 
 }  // namespace
@@ -93,6 +157,7 @@ RGBM_EXPORT int rgbm_table_cellset_open(rgbm_table* t, const int32_t* cols, int3
         bits.zero(s); d_cols.upload(cols, (size_t)n_cols, s); d_pos.upload(pos.data(), pos.size(), s);
         HIPCHK(hipStreamSynchronize(s));
         t->cs_bits.swap(bits); t->cs_d_cols.swap(d_cols); t->cs_d_pos.swap(d_pos);
+        t->cs_cols.assign(cols, cols + n_cols);
         t->cs_n_cols = n_cols; t->cs_open = true; t->cs_emitted = false;
         return RGBM_OK;
     });
@@ -106,14 +171,7 @@ RGBM_EXPORT int rgbm_table_cellset_add(rgbm_table* t) {
         if (!t->cs_open) throw std::invalid_argument("rgbm_table_cellset_add: no open cell set");
         if (t->n_cells > 0 && !t->cell_cols.p) throw std::invalid_argument("rgbm_table_cellset_add: the last result is a row list (no columns)");
         if (t->n_cells == 0) return RGBM_OK;
-        const long long m = t->n_cells, W = (long long)PBAL * ((t->n + PROWS - 1) / PROWS);
-        if (cs_combine())
-            hipLaunchKernelGGL(k_cs_or<CS_ROUNDS>, dim3(nblocks(m, 256)), dim3(256), 0, s, t->cell_rows.p, t->cell_cols.p, m, t->cs_d_pos.p, (long long)t->n,
-                               (int)t->c, W, t->cs_bits.p);
-        else
-            hipLaunchKernelGGL(k_cs_or<0>, dim3(nblocks(m, 256)), dim3(256), 0, s, t->cell_rows.p, t->cell_cols.p, m, t->cs_d_pos.p, (long long)t->n,
-                               (int)t->c, W, t->cs_bits.p);
-        HIPCHK(hipGetLastError());
+        launch_cs_or(*t, t->cell_rows.p, t->cell_cols.p, t->n_cells, s);
         HIPCHK(hipStreamSynchronize(s));
         return RGBM_OK;
     });
@@ -161,13 +219,108 @@ RGBM_EXPORT int rgbm_table_cells_fetch_codes(const rgbm_table* t, int32_t* codes
     });
 }
 
+// scratch slots held together: IN_ROWS IN_COLS
+RGBM_EXPORT int rgbm_table_cellset_add_cells(rgbm_table* t, const int64_t* rows, const int32_t* cols, int64_t n_cells) {
+    if (!t || n_cells < 0 || (n_cells > 0 && (!rows || !cols))) return fail(RGBM_ERR_ARG, "rgbm_table_cellset_add_cells: bad argument");
+    return guarded([&]() {
+        use_device(t->device);
+        std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
+        if (!t->cs_open) throw std::invalid_argument("rgbm_table_cellset_add_cells: no open cell set");
+        if (n_cells == 0) return RGBM_OK;
+        static_assert(sizeof(long long) == sizeof(int64_t), "row positions are 64-bit");
+        const long long* d_rows = scr_upload<long long>(*t, SCR_IN_ROWS, reinterpret_cast<const long long*>(rows), (size_t)n_cells, s);
+        const int32_t* d_cols = scr_upload<int32_t>(*t, SCR_IN_COLS, cols, (size_t)n_cells, s);
+        launch_cs_or(*t, d_rows, d_cols, (long long)n_cells, s);
+        HIPCHK(hipStreamSynchronize(s));      // the caller's arrays are read by the async copies
+        return RGBM_OK;
+    });
+}
+
+// scratch slots held together: TABLE_A (attributes) COLS (single_ok) VALS (the weak counter) | BCOUNT BOFF (the compaction's; its ballots are the column's words)
+RGBM_EXPORT int rgbm_table_cellset_drop_weak(rgbm_table* t, int32_t target_col, const int32_t* pair_idx, int32_t k, const int64_t* min_cnt,
+                                             const uint8_t* single_ok, double beta, int64_t row_count, int64_t* n_cells_out, int64_t* n_weak_out) {
+    if (!t || target_col < 0 || target_col >= t->c || k < 0 || (k > 0 && (!pair_idx || !min_cnt)) || !single_ok || row_count <= 0 || !n_cells_out ||
+        !n_weak_out)
+        return fail(RGBM_ERR_ARG, "rgbm_table_cellset_drop_weak: bad argument");
+    return guarded([&]() {
+        use_device(t->device);
+        std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
+        if (!t->cs_open) throw std::invalid_argument("rgbm_table_cellset_drop_weak: no open cell set");
+        const std::vector<DomAttr> attrs = dom_attrs(*t, target_col, pair_idx, k, min_cnt, "rgbm_table_cellset_drop_weak");
+        const int p = (int)(std::find(t->cs_cols.begin(), t->cs_cols.end(), target_col) - t->cs_cols.begin());
+        if (p >= t->cs_n_cols) throw std::invalid_argument("rgbm_table_cellset_drop_weak: the target is not a column of the cell set");
+        // everything that refuses is behind us: from here on the cell list is replaced
+        const int d_a = t->pc_nbins[target_col];
+        const long long nblk = (t->n + PROWS - 1) / PROWS, W = (long long)PBAL * nblk;
+        unsigned long long* col_bits = t->cs_bits.p + (long long)p * W;          // a one-column Ballots as it lies
+        const Ballots b{col_bits, scr<unsigned>(*t, SCR_BCOUNT, (size_t)nblk), scr<long long>(*t, SCR_BOFF, (size_t)nblk + 1), nblk, 1};
+        hipLaunchKernelGGL(k_cs_count, dim3(nblocks(nblk, PB / 64)), dim3(PB), 0, s, b.ballots, nblk, b.bcount);
+        HIPCHK(hipGetLastError());
+        const long long total = emit_to_table(*t, b, t->cs_d_cols.p + p, s);
+        unsigned long long weak = 0;
+        if (total > 0) {
+            const DomAttr* d_attrs = scr_upload<DomAttr>(*t, SCR_TABLE_A, attrs.data(), attrs.size(), s);
+            const uint8_t* d_ok = scr_upload<uint8_t>(*t, SCR_COLS, single_ok, (size_t)d_a, s);
+            unsigned long long* d_weak = scr<unsigned long long>(*t, SCR_VALS, 1);
+            HIPCHK(hipMemsetAsync(d_weak, 0, 8, s));
+            hipLaunchKernelGGL(k_cs_drop_weak, dim3(nblocks(total, 256)), dim3(256), 0, s, t->codes.p, (long long)t->n, (int)target_col, d_a, t->cell_rows.p,
+                               total, t->pc_counts.p, d_attrs, (int)k, t->pc_bins.p, t->pc_lut_off.p, t->pc_luts.p, d_ok, beta, (double)row_count,
+                               col_bits, d_weak);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&weak, d_weak, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        *n_cells_out = total; *n_weak_out = (int64_t)weak;
+        return RGBM_OK;
+    });
+}
+
+// scratch slots held together: VALS (the cell counter)
+RGBM_EXPORT int rgbm_table_cellset_null(rgbm_table* t, int64_t* n_cells_out) {
+    if (!t || !n_cells_out) return fail(RGBM_ERR_ARG, "rgbm_table_cellset_null: bad argument");
+    return guarded([&]() {
+        use_device(t->device);
+        rgh::ViewWrite view_wr(t);
+        std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
+        if (!t->cs_open) throw std::invalid_argument("rgbm_table_cellset_null: no open cell set");
+        const long long nblk = (t->n + PROWS - 1) / PROWS, m = nblk * t->cs_n_cols;
+        unsigned long long* d_cnt = scr<unsigned long long>(*t, SCR_VALS, 1);
+        unsigned long long cnt = 0;
+        HIPCHK(hipMemsetAsync(d_cnt, 0, 8, s));
+        if (m > 0) hipLaunchKernelGGL(k_cs_null, dim3(nblocks(m, PB / 64)), dim3(PB), 0, s, t->cs_bits.p, m, nblk, t->cs_d_cols.p, t->codes.p, (long long)t->n, d_cnt);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        *n_cells_out = (int64_t)cnt;
+        return RGBM_OK;
+    });
+}
+
+// scratch slots held together: | BALLOTS BCOUNT BOFF
+RGBM_EXPORT int rgbm_table_cellset_rows(rgbm_table* t, int64_t* n_rows_out) {
+    if (!t || !n_rows_out) return fail(RGBM_ERR_ARG, "rgbm_table_cellset_rows: bad argument");
+    return guarded([&]() {
+        use_device(t->device);
+        std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
+        if (!t->cs_open) throw std::invalid_argument("rgbm_table_cellset_rows: no open cell set");
+        const Ballots b = table_ballots(*t, 1);
+        const long long W = (long long)PBAL * b.nblk;
+        hipLaunchKernelGGL(k_cs_or_cols, dim3(nblocks(W, 256)), dim3(256), 0, s, t->cs_bits.p, W, (int)t->cs_n_cols, b.ballots);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_cs_count, dim3(nblocks(b.nblk, PB / 64)), dim3(PB), 0, s, b.ballots, b.nblk, b.bcount);
+        HIPCHK(hipGetLastError());
+        *n_rows_out = emit_to_table(*t, b, nullptr, s);
+        return RGBM_OK;
+    });
+}
+
 RGBM_EXPORT int rgbm_table_cellset_close(rgbm_table* t) {
     if (!t) return fail(RGBM_ERR_ARG, "rgbm_table_cellset_close: bad argument");
     return guarded([&]() {
         use_device(t->device);
         std::lock_guard<std::mutex> prep_lk(t->prep_mu);
         t->cs_bits.release(); t->cs_d_cols.release(); t->cs_d_pos.release();
-        t->cs_n_cols = 0; t->cs_open = false;
+        t->cs_cols.clear(); t->cs_n_cols = 0; t->cs_open = false;
         return RGBM_OK;
     });
 }

@@ -11,7 +11,7 @@
 //                  straight into HBM.  Algorithmic bytes: 4 B per (row, distinct column of a group).
 //   cell_domains   one error cell per lane: the fixed-order score sums and the divisions of repair/domain.py, nothing else.
 // =============================================================================================
-#include "rgbm_prep.h"
+#include "rgbm_domain.h"
 
 namespace {
 
@@ -23,22 +23,9 @@ constexpr int PC_TILE_BYTES = PC_MAXC * PC_B * 2;           // uint16 bins [PC_M
 constexpr int PC_LDS_CELLS = (160 * 1024 - 2048 - PC_TILE_BYTES) / 4;      // 32-bit counters of one group
 constexpr long long PC_ROWS_PER_WG_MAX = 1ll << 30;
 constexpr long long PC_MAX_CELLS_PAIR = 1ll << 24, PC_MAX_CELLS = 1ll << 25;   // dense cells of one pair / of a call
-constexpr int DOM_MAXK = 8;                                 // correlated attributes of one cell-domain call
 
 struct PcPair { int32_t sx, sy, dy1; uint32_t lds_off, cells; long long out_off; };
 struct PcGroup { int32_t col_begin, ncols, pair_begin, npairs; uint32_t cells; };
-struct DomAttr { long long off, sn, sv, min_cnt; int32_t col, d_c; };
-
-// bin of (row r, column col): the code through the column's LUT (if any); NULL / out of range -> slot d = nbins
-__device__ __forceinline__ int pc_bin(const int32_t* __restrict__ codes, long long n, int col, long long r, const int32_t* __restrict__ colinfo,
-                                      const long long* __restrict__ lut_off, const int32_t* __restrict__ luts) {
-    int v = codes[(long long)col * n + r];
-    const int nc = colinfo[2 * col], d = colinfo[2 * col + 1];
-    if (v < 0 || v >= nc) return d;
-    const long long lo = lut_off[col];
-    if (lo >= 0) v = luts[lo + v];
-    return (v < 0 || v >= d) ? d : v;
-}
 
 __global__ __launch_bounds__(PC_B) void k_pair_counts(const int32_t* __restrict__ codes, long long n, const PcGroup* __restrict__ groups,
                                                       const int32_t* __restrict__ gcols, const PcPair* __restrict__ pairs,
@@ -94,51 +81,11 @@ __global__ __launch_bounds__(256) void k_cell_domains(const int32_t* __restrict_
                                                       double* __restrict__ probs) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const long long r = rows[i];
-    const bool inside = r >= 0 && r < n;
-    const unsigned long long* base[DOM_MAXK]; long long sn[DOM_MAXK], mc[DOM_MAXK];
-    // the fold  IF(ISNOTNULL(domain), CONCAT(domain, d), d):  an attribute whose element list is NULL (value NULL / no group above the
-    // threshold) wipes what came before it, so only the attributes after the last such one contribute
-    int j0 = k;
-    if (inside) {
-        j0 = 0;
-#pragma unroll
-        for (int j = 0; j < DOM_MAXK; ++j) {
-            if (j >= k) break;
-            const DomAttr a = attrs[j];
-            const int v = pc_bin(codes, n, a.col, r, colinfo, lut_off, luts);
-            base[j] = joint + a.off + (long long)(v < a.d_c ? v : 0) * a.sv; sn[j] = a.sn; mc[j] = a.min_cnt;
-            bool has = false;
-            if (v < a.d_c) for (int c = 0; c < d_a; ++c) if ((long long)base[j][(long long)c * a.sn] > a.min_cnt) { has = true; break; }
-            if (!has) j0 = j + 1;
-        }
-    }
-    auto score = [&](int c) -> double {
-        double s = 0.0;
-        if (!single_ok[c]) return s;
-#pragma unroll
-        for (int j = 0; j < DOM_MAXK; ++j) {
-            if (j >= k) break;
-            if (j < j0) continue;
-            const long long cnt = (long long)base[j][(long long)c * sn[j]];
-            if (cnt > mc[j]) { const double b = fmax((double)cnt - 1.0, 0.1); s = s + b / row_count; }
-        }
-        return s;
-    };
-    double den = 0.0;
-    if (j0 < k) for (int c = 0; c < d_a; ++c) den = den + score(c);          // ascending code, sequential
-    double best = 0.0; int bt = -1;
-    for (int c = 0; c < d_a; ++c) {
-        const double p = (j0 < k && den > 0.0) ? score(c) / den : 0.0;
-        if (probs) probs[i * d_a + c] = p;
-        if (p > best) { best = p; bt = c; }                                   // first maximum: ties by ascending code
-    }
-    const bool valid = bt >= 0 && best > beta;
-    int cur = inside ? codes[(long long)target * n + r] : -1;
-    if (cur >= d_a) cur = -1;
-    weak[i] = (uint8_t)(valid && cur >= 0 && cur == bt);
-    top[i] = valid ? bt : -1;
-    top_prob[i] = valid ? best : 0.0;
+    const DomCell d = cell_domain(codes, n, target, d_a, rows[i], joint, attrs, k, colinfo, lut_off, luts, single_ok, beta, row_count,
+                                  probs ? probs + i * d_a : nullptr);
+    weak[i] = (uint8_t)d.weak;
+    top[i] = d.top;
+    top_prob[i] = d.top_prob;
 }
 
 }  // namespace
@@ -269,17 +216,7 @@ RGBM_EXPORT int rgbm_table_cell_domains(rgbm_table* t, int32_t target_col, const
         if (t->pc_has_lut[target_col]) throw std::invalid_argument("rgbm_table_cell_domains: the target must be a discrete attribute (no LUT)");
         if (n_cells == 0) return RGBM_OK;
         const int d_a = t->pc_nbins[target_col];
-        std::vector<DomAttr> attrs((size_t)std::max(k, 1));
-        for (int j = 0; j < k; ++j) {
-            const int p = pair_idx[j];
-            if (p < 0 || p >= (int)t->pc_x.size()) throw std::invalid_argument("rgbm_table_cell_domains: pair index out of range");
-            DomAttr a;
-            a.off = t->pc_off[p]; a.min_cnt = std::max<long long>(min_cnt[j], 0);
-            if (t->pc_x[p] == target_col) { a.col = t->pc_y[p]; a.d_c = t->pc_dy[p]; a.sn = (long long)t->pc_dy[p] + 1; a.sv = 1; }
-            else if (t->pc_y[p] == target_col) { a.col = t->pc_x[p]; a.d_c = t->pc_dx[p]; a.sn = 1; a.sv = (long long)t->pc_dy[p] + 1; }
-            else throw std::invalid_argument("rgbm_table_cell_domains: a pair does not hold the target column");
-            attrs[j] = a;
-        }
+        const std::vector<DomAttr> attrs = dom_attrs(*t, target_col, pair_idx, k, min_cnt, "rgbm_table_cell_domains");
         std::lock_guard<std::mutex> prep_lk(t->prep_mu); hipStream_t s = table_stream(*t);
         const DomAttr* d_attrs = scr_upload<DomAttr>(*t, SCR_TABLE_A, attrs.data(), attrs.size(), s);
         const uint8_t* d_ok = scr_upload<uint8_t>(*t, SCR_COLS, single_ok, (size_t)d_a, s);

@@ -187,6 +187,7 @@ struct rgbm_table {
     // the cell list while cell_version is still that emit's
     rgh::DevBuf<unsigned long long> cs_bits; rgh::DevBuf<int32_t> cs_d_cols, cs_d_pos, cs_codes;
     int32_t cs_n_cols = 0; bool cs_open = false, cs_emitted = false; uint64_t cs_emit_version = 0;
+    std::vector<int32_t> cs_cols;                  // the set's columns on the host (rgbm_table_cellset_drop_weak looks its target up), under prep_mu
     // stream + scratch of the relational steps (rgbm_prep.h: table_stream, enum Scr), kept with the table: a hipMalloc / hipFree / stream
     // creation per call costs more than the kernels (one call at a time per table, as the header says)
     // Python threads share one table (the folds of a hyper-parameter search gather from the training table, ctypes drops the
@@ -215,7 +216,7 @@ namespace rgh {
 // holds one of these for the length of the call: the view is dropped and the version bumped when the call begins and again when it ends,
 // so a fit that starts in between (which the caller must not do anyway) never leaves a view of half-written codes behind.  Declared BEFORE
 // the call takes prep_mu: view.mu is never taken under prep_mu.  The entry points:
-//   rgbm_table_repair_chain, rgbm_table_repair_chain_gather, rgbm_table_null_cells, rgbm_table_write_cells, rgbm_table_rule_fill,
+//   rgbm_table_repair_chain, rgbm_table_repair_chain_gather, rgbm_table_null_cells, rgbm_table_cellset_null, rgbm_table_write_cells, rgbm_table_rule_fill,
 //   rgbm_table_set_column_kind, rgbm_table_set_column_values, rgbm_table_set_row_multiplicity.
 // (rgbm_table_repair_pmf and rgbm_table_repair_pmf_weighted return candidates and write no cell: they are not in the list.)
 struct ViewWrite {

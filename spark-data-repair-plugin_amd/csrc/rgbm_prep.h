@@ -1,5 +1,6 @@
 // rgbm_prep.h -- what the sources of the relational steps on the HBM-resident code table share (internal, never installed): rgbm_prep.hip
-// defines the host functions declared here, every rgbm_<step>.hip beside it includes this header and nothing of another step.
+// defines the host functions declared here, every rgbm_<step>.hip beside it includes this header and nothing of another step (one exception:
+// rgbm_domain.h, the cell-domain arithmetic as a __device__ function, which rgbm_domain.hip and rgbm_cellset.hip both compile into a kernel).
 // Every source uses the ONE copy of each mechanism that this header holds -- compaction: flags_to_ballots, scan_emit (into the
 // table's cell list: emit_to_table, compact<MODE>), rows_to_cells;  keys: key_digit / row_key, key_spec, table_capacity, ht_claim, wave_add;
 // bitsets: append_bitset, bitset_stage / bitset_test;  scratch: enum Scr, with its rule; every entry point names its slots above its definition.

@@ -96,7 +96,8 @@ def lib():
             getattr(l, name).restype = C.c_int
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect",
                      "rgbm_table_pair_counts_report", "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit",
-                     "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close", "rgbm_table_fd_measures", "rgbm_table_fd_measures_report"):
+                     "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close", "rgbm_table_fd_measures", "rgbm_table_fd_measures_report",
+                     "rgbm_table_cellset_add_cells", "rgbm_table_cellset_drop_weak", "rgbm_table_cellset_null", "rgbm_table_cellset_rows"):
             if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass / no count report / no cell set)
                 getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
@@ -127,6 +128,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_pair_counts_report", "rgbm_regex_structure", "rgbm_table_detect_dc_scan",
     "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit", "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close",
     "rgbm_table_fd_measures", "rgbm_table_fd_measures_report",
+    "rgbm_table_cellset_add_cells", "rgbm_table_cellset_drop_weak", "rgbm_table_cellset_null", "rgbm_table_cellset_rows",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -868,6 +870,42 @@ class Table:
     def cellset_close(self):
         _check(lib().rgbm_table_cellset_close(self.h), "rgbm_table_cellset_close")
         self._cellset_cols = 0
+
+    # ---- the repair run on the open set: given cells in, weak labels out, null-out and dirty rows straight from the matrix
+    def cellset_add_cells(self, rows, cols):
+        """ORs host-given cells (any order, duplicates allowed) into the open set; cells outside the table or the set's columns are skipped."""
+        r, c2 = np.ascontiguousarray(rows, np.int64).reshape(-1), _i32(np.asarray(cols, np.int32).reshape(-1))
+        if len(r) != len(c2):
+            raise ValueError("rows and cols must have the same length")
+        _check(lib().rgbm_table_cellset_add_cells(self.h, _p(r, C.c_int64), _p(c2, C.c_int32), C.c_int64(len(r))), "rgbm_table_cellset_add_cells")
+
+    def cellset_drop_weak(self, target_col, pair_idx, min_cnt, single_ok, beta, row_count):
+        """Clears the weak-labelled cells of the set's column ``target_col``: the `weak` flag of ``cell_domains`` on the same rows, evaluated
+        on the device.  The examined cells stay behind as the table's cell list.  Returns (cells examined, cells cleared)."""
+        pi, mc = _i32(np.asarray(pair_idx, np.int32).reshape(-1)), np.ascontiguousarray(min_cnt, np.int64).reshape(-1)
+        ok = np.ascontiguousarray(single_ok, np.uint8).reshape(-1)
+        if len(pi) != len(mc):
+            raise ValueError("one min_cnt per pair")
+        last = getattr(self, "_pc_last", None)            # (without one the library refuses the call before it reads single_ok)
+        if last is not None and 0 <= int(target_col) < self.c and len(ok) != int(last[1][int(target_col)]):
+            raise ValueError("single_ok must hold one entry per bin of the target (%d), not %d" % (int(last[1][int(target_col)]), len(ok)))
+        cells, weak = C.c_int64(0), C.c_int64(0)
+        _check(lib().rgbm_table_cellset_drop_weak(self.h, C.c_int32(target_col), _p(pi, C.c_int32), C.c_int32(len(pi)), _p(mc, C.c_int64),
+                                                  _p(ok, C.c_uint8), C.c_double(beta), C.c_int64(row_count), C.byref(cells), C.byref(weak)),
+               "rgbm_table_cellset_drop_weak")
+        return int(cells.value), int(weak.value)
+
+    def cellset_null(self):
+        """NULL into every cell of the open set, in place in HBM (`null_cells` without a cell list); returns the number of cells."""
+        n = C.c_int64(0)
+        _check(lib().rgbm_table_cellset_null(self.h, C.byref(n)), "rgbm_table_cellset_null")
+        return int(n.value)
+
+    def cellset_rows(self, fetch=True):
+        """Ascending positions of the rows that hold a cell of the open set (`rows_of_cells` without an upload); ``fetch=False``: their number."""
+        n = C.c_int64(0)
+        _check(lib().rgbm_table_cellset_rows(self.h, C.byref(n)), "rgbm_table_cellset_rows")
+        return self._fetch_cells(int(n.value), False, fetch)
 
     def null_cells(self, rows, cols, target_cols):
         """convertErrorCellsToNull (RepairApi.scala:171-211), in place in HBM."""

@@ -315,18 +315,27 @@ class HostBackend:
 
 
 def analyse(backend: Any, n_rows: int, view: View, targets: Sequence[int], domain_stats: Sequence[int], cell_rows: Any, cell_cols: Any,
-            options: Dict[str, Any], want_weak: bool = True) -> Dict[str, Any]:
+            options: Dict[str, Any], want_weak: bool = True, cell_counts: Optional[Dict[int, int]] = None) -> Dict[str, Any]:
     """computeAttrStats + computeDomainInErrorCells + the weak-label rule on any backend with `pair_counts` / `cell_domains`.
 
     targets: the repairable (noisy, discretised) columns, in order.  Returns dict(pairwise={target: [(attr column, H(target|attr))]},
-    weak [cells] bool, top [cells] int32, top_prob [cells])."""
+    weak [cells] bool, top [cells] int32, top_prob [cells]).
+
+    cell_counts: {column: its error cells} -- the cells stay WITH THE BACKEND (the cell set of a resident table) and `cell_rows` /
+    `cell_cols` are None: per target with cells, `backend.drop_weak(target, corr, table, min_cnt, single_ok, beta, n_rows)` -> (cells
+    examined, cells pruned) applies the weak-label rule where the cells lie.  The result then holds `weak_counts` {target: cells pruned}
+    (a target that is not examined has none) and no `weak` / `top` / `top_prob`."""
     g = lambda k: options.get(k, OPTION_DEFAULTS[k])  # noqa: E731
+    if cell_counts is not None:
+        cell_rows, cell_cols = np.zeros(0, np.int64), np.zeros(0, np.int32)
     cell_rows, cell_cols = np.asarray(cell_rows, np.int64), np.asarray(cell_cols, np.int32)
     weak = np.zeros(len(cell_rows), bool)
     top = np.full(len(cell_rows), -1, np.int32)
     top_prob = np.zeros(len(cell_rows), np.float64)
     targets = [int(t) for t in targets if int(t) in view.n_bins]
     out: Dict[str, Any] = dict(pairwise={t: [] for t in targets}, weak=weak, top=top, top_prob=top_prob)
+    if cell_counts is not None:
+        out = dict(pairwise=out["pairwise"], weak_counts={})
     if not targets or len(view.cols) <= 1:
         return out
     pairs = all_pairs(targets, view.cols)
@@ -349,10 +358,15 @@ def analyse(backend: Any, n_rows: int, view: View, targets: Sequence[int], domai
     for t in targets:
         corr = [y for y, _ in stats[t][:k]]
         sel = np.flatnonzero(cell_cols == t)
-        if t in view.continuous or not corr or len(sel) == 0:
+        if t in view.continuous or not corr or (len(sel) == 0 if cell_counts is None else int(cell_counts.get(t, 0)) == 0):
             continue
         min_cnt = [max(tau_of(alpha, n_rows, domain_stats[c], domain_stats[t]), fmin, 0) for c in corr]
         ok = singles[t][:view.n_bins[t]] > fmin
+        if cell_counts is not None:
+            examined, pruned = backend.drop_weak(t, corr, table, min_cnt, ok, beta, n_rows)
+            assert int(examined) == int(cell_counts[t]), "the cell set holds %d cells of column %d, not %d" % (examined, t, cell_counts[t])
+            out["weak_counts"][t] = int(pruned)
+            continue
         w, tp, pr, _ = backend.cell_domains(t, cell_rows[sel], corr, table, min_cnt, ok, beta, n_rows)
         weak[sel], top[sel], top_prob[sel] = np.asarray(w, bool), tp, pr
     return out

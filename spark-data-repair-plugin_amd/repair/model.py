@@ -124,6 +124,12 @@ class RepairModel():
     # detectors admitted by the options above run on the device, their cells are merged there (the table's cell set) and leave
     # it once, with the codes they hold.  None of the model conditions of the resident repair run applies.  Off by default.
     _opt_detect_only_resident = _option("error.detect_only.resident", False, bool, None, None)
+    # new in this engine: a resident REPAIR run keeps its error cells in the table's cell set from detection through the null-out
+    # (`pipeline._cells_on_set`): every detector's cells are merged on the device, the weak-labelled ones are pruned there, the
+    # given cells go up once and the remaining ones come down once; the null-out and the dirty rows are read off the set.  The same cells,
+    # frame and details; `_last_resident_info["cells_route"]` says 'set', or 'host' where the engine's table lacks the entries or the job
+    # runs on several ranks.  Off by default.
+    _opt_cells_resident = _option("error.cells.resident", False, bool, None, None)
     # new in this engine: on the HBM-resident pipeline, train every attribute's model on the DISTINCT rows of the table with their
     # multiplicities (found on the device, `Table.distinct_rows`): the same models, bytes included, at the cost of the distinct rows.  It
     # only matters for an attribute that `model.max_training_row_num` does not sample (a sampled attribute trains on its sample); the
@@ -139,7 +145,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident, _opt_rule_regex_resident, _opt_rebalance_resident,
-        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_constraints_order_scan, _opt_detect_only_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_constraints_order_scan, _opt_detect_only_resident, _opt_cells_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -1144,7 +1150,8 @@ class RepairModel():
                                    continuous_columns=[c for c in continous_columns if c in target_columns],
                                    train_rows=self._training_row_sampler(), want_details=True,
                                    search_opts=dict(self.opts) if plan.get("search") else None, rules=rules,
-                                   distinct_training_rows=None if prob else plan.get("distinct"), rebalance=plan.get("rebalance"), **cells)
+                                   distinct_training_rows=None if prob else plan.get("distinct"), rebalance=plan.get("rebalance"),
+                                   cells_resident=bool(self._get_option_value(*self._opt_cells_resident)), **cells)
         info["times"]["pipeline_wall"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         self._last_resident_info = info

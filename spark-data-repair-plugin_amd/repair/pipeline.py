@@ -31,7 +31,8 @@ def _merge_cells(n, parts):
     return key % n, (key // n).astype(np.int32)
 
 
-def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_cells=None, value_detectors=None, on_device=False):
+def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_cells=None, value_detectors=None, on_device=False,
+                       keep_open=False):
     """Error cells of the target attributes: (rows, cols), ordered by (column, row), every cell once.
 
     on_device   : returns (rows, cols, codes), `codes` being what the cells hold now.  On a table with `cellset_open` the detectors'
@@ -39,6 +40,9 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
                   ``fetch=False`` and followed by `Table.cellset_add`, and ONE `Table.cellset_emit` brings the union and its codes to the host
                   (csrc/rgbm_cellset.hip).  Given `error_cells` are host arrays: they join last, by the host merge, and the codes
                   are then read with `Table.read_cells`.  A table without the methods detects as with on_device=False and reads the codes.
+    keep_open   : (with on_device, on a table that has `cellset_add_cells`, for at least one target) nothing is emitted: the given
+                  `error_cells` join the set through `Table.cellset_add_cells`, the set STAYS OPEN for the caller -- who emits, prunes,
+                  NULLs and closes it (`_cells_on_set`) -- and None is returned.  The set is closed here only when a detector raises.
 
     constraints : [(eq_cols, iq_col)] -- denial constraints  EQ(X1)..EQ(Xm) & IQ(Y)  (ErrorDetectorApi.scala:189-244); a
                   violating row contributes the constraint's attributes that are targets (`attrs`, line 211).  Next to them the
@@ -72,8 +76,11 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
         return parts[-1]
 
     set_cols = sorted(set(tg))                         # the set emits by position in this list: column order, as `_merge_cells` orders
+    if keep_open and not dev:
+        raise ValueError("keep_open needs a table with a cell set and at least one target")
     if dev:
         table.cellset_open(set_cols)
+    opened = dev
     try:
         if value_detectors:
             descs = {int(d["col"]): d for d in value_detectors if int(d["col"]) in tg}
@@ -122,10 +129,15 @@ def detect_error_cells(table, targets, constraints=(), detect_nulls=True, error_
                     attrs.append(a)
             if attrs:
                 part(table.detect_constraint, list(eq), int(iq), cell_cols=attrs)
+        if keep_open:
+            if given is not None and len(given[0]):
+                table.cellset_add_cells(*given)
+            opened = False                                 # the caller's from here on
+            return None
         if dev:
             rows, cols, codes, _ = table.cellset_emit()
     finally:
-        if dev:
+        if opened:
             table.cellset_close()
     if dev and given is None:
         return rows, cols, codes
@@ -438,16 +450,24 @@ class TableBackend:
         pidx = [ptable.index[frozenset((int(c), int(target)))] for c in corr]
         return self.table.cell_domains(target, rows, pidx, min_cnt, single_ok, beta, row_count, want_probs=want_probs)
 
+    def drop_weak(self, target, corr, ptable, min_cnt, single_ok, beta, row_count):
+        """(cells examined, cells cleared) of the target's column of the table's open cell set (`Table.cellset_drop_weak`)."""
+        if len(corr) > self.MAX_CORR:
+            raise NotResidentEligible("cell-domain analysis: %d correlated attributes (the device entry takes %d)" % (len(corr), self.MAX_CORR))
+        pidx = [ptable.index[frozenset((int(c), int(target)))] for c in corr]
+        return self.table.cellset_drop_weak(target, pidx, min_cnt, single_ok, beta, row_count)
 
-def analyse_cell_domains(table, targets, rows, cols, spec):
+
+def analyse_cell_domains(table, targets, rows, cols, spec, cell_counts=None):
     """The second half of ErrorModel.detect (errors.py:553-578) on the resident table, BEFORE any cell is NULLed: pair counts on the
     device, entropies and attribute selection on the host from the integer counts, cell domains on the device.
     spec: dict(options={error.*: value}, discrete_thres, domain_stats [C], continuous={column: ascending distinct values},
-    keep_weak=False).  Returns repair.domain.analyse's dict."""
+    keep_weak=False).  Returns repair.domain.analyse's dict.  `cell_counts` {column: cells}: the cells lie in the table's open cell set
+    (rows and cols are None) and the weak-labelled ones are cleared there; the dict then holds `weak_counts` (repair.domain.analyse)."""
     from repair import domain
     view = domain.discretised_view(table.n_codes, spec["domain_stats"], spec.get("continuous") or {}, int(spec["discrete_thres"]))
     return domain.analyse(TableBackend(table, view), int(table.n), view, targets, spec["domain_stats"], rows, cols, spec.get("options") or {},
-                          want_weak=not spec.get("keep_weak", False))
+                          want_weak=not spec.get("keep_weak", False), cell_counts=cell_counts)
 
 
 def nearest_value_merges(engine, table, targets, rows, cols, current, spec):
@@ -598,6 +618,71 @@ def _detect_and_prune(table, targets, constraints, detect_nulls, error_cells, on
             raise DeadClasses("%d detected cells lie in attributes with a regex-structure repair" % int(in_regex.sum()), rows, cols,
                               domain_info=domain_info, value_detectors=_detector_report(value_detectors))
     return rows, cols, kept, domain_info, value_detectors, seconds
+
+
+SET_ROUTE_METHODS = ("cellset_open", "cellset_add", "cellset_emit", "cellset_close", "cellset_add_cells", "cellset_drop_weak", "cellset_null",
+                     "cellset_rows")
+
+
+def set_route_refusal(table, targets):
+    """Why phases 1 and 2 cannot run on the table's cell set (`_cells_on_set`), or None."""
+    missing = [m for m in SET_ROUTE_METHODS if not hasattr(table, m)]
+    if missing:
+        return "the engine's table has no %s" % ", ".join(missing)
+    if not targets:
+        return "no target attribute"
+    from repair import dist
+    if dist.world()[1] > 1:
+        return "a job on %d ranks merges its cells on the host" % dist.world()[1]
+    return None
+
+
+def _cells_on_set(engine, table, targets, constraints, detect_nulls, error_cells, only_noisy_targets, domain_analysis, value_detectors, regex_cols,
+                  nearest):
+    """Phases 1 and 2 of `repair_table` on the table's CELL SET: what `_detect_and_prune` and `_null_and_merge` give, cell for
+    cell, without the error cells travelling in between.  Every detector's cells join the set on the device and the given `error_cells` go
+    up once (`detect_error_cells(keep_open=True)`); a count-only emit names the noisy columns; the cell-domain analysis clears the
+    weak-labelled cells in the set (`Table.cellset_drop_weak`, one call per target); ONE fetching emit brings the remaining cells down with
+    the codes they hold; `Table.cellset_null` NULLs them from the matrix and `Table.cellset_rows` gives the dirty rows.  With
+    nearest-value merges the merged cells are written back and the dirty rows of the others come from `Table.rows_of_cells`.
+    Returns (the pruned cells as detected: rows, cols; the targets to repair; domain summary or None; the detectors' descriptors; seconds
+    of phase 1; then `_null_and_merge`'s tuple)."""
+    t0 = time.perf_counter()
+    if callable(value_detectors):
+        value_detectors = value_detectors(table)
+    set_cols = sorted(set(targets))
+    detect_error_cells(table, targets, constraints, detect_nulls, error_cells, value_detectors=value_detectors, on_device=True, keep_open=True)
+    try:
+        counts = np.asarray(table.cellset_emit(fetch=False), np.int64)
+        noisy = set(c for c, k in zip(set_cols, counts) if k > 0)
+        noisy_cells = int(counts.sum())
+        kept = [t for t in targets if t in noisy] if only_noisy_targets else targets
+        domain_info = None
+        if domain_analysis is not None and noisy_cells:
+            da = analyse_cell_domains(table, [t for t in kept if t in noisy], None, None, domain_analysis,
+                                      cell_counts={c: int(k) for c, k in zip(set_cols, counts)})
+            domain_info = dict(pairwise=da["pairwise"], noisy_cells=noisy_cells, weak_cells=int(sum(da["weak_counts"].values())))
+            _logger.info("[Error Detection Phase] %d noisy cells fixed and %d error cells remaining..." % (domain_info["weak_cells"],
+                                                                                                       noisy_cells - domain_info["weak_cells"]))
+        rows, cols, current, _ = table.cellset_emit()
+        seconds = time.perf_counter() - t0
+        if regex_cols and error_cells is None and len(rows):
+            in_regex = np.isin(cols, list(regex_cols))
+            if in_regex.any():                             # as in `_detect_and_prune`: nothing is NULLed, the caller comes back with the cells
+                raise DeadClasses("%d detected cells lie in attributes with a regex-structure repair" % int(in_regex.sum()), rows, cols,
+                                  domain_info=domain_info, value_detectors=_detector_report(value_detectors))
+        table.cellset_null()
+        if nearest is None or not len(rows):
+            tail = (rows, cols, current, None, table.cellset_rows())
+        else:
+            near = nearest_value_merges(engine, table, kept, rows, cols, current, nearest)
+            done = near >= 0
+            merged = dict(rows=rows[done], cols=cols[done], current=current[done], repaired=near[done])
+            table.write_cells(merged["rows"], merged["cols"], merged["repaired"])
+            tail = (rows[~done], cols[~done], current[~done], merged, table.rows_of_cells(rows[~done]))
+    finally:
+        table.cellset_close()
+    return (rows, cols, kept, domain_info, value_detectors, seconds) + tail
 
 
 def _null_and_merge(engine, table, targets, rows, cols, nearest):
@@ -781,12 +866,16 @@ def _shape(engine, table, dirty_tab, pmf_tab, res, chain, rows, cols, current, d
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None, rebalance=None, regex_cols=None):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None, regex_cols=None, cells_resident=False):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).  The phases, and where each
     parameter is described: `_detect_and_prune` (constraints, detect_nulls and error_cells as `detect_error_cells` takes them,
     only_noisy_targets, domain_analysis, value_detectors, regex_cols), `_null_and_merge` (rules['nearest']: `nearest_value_merges`),
     `_target_plan` (rules['fd'], only_noisy_targets), `_training_tables` (train_rows, rebalance, check_unseen, distinct_training_rows),
     `_train_and_repair` (search_opts), `_shape` (want_pmf, top_k, threshold, pmf_costs).
+
+    cells_resident : phases 1 and 2 on the table's cell set (`_cells_on_set`): the same cells, codes and dirty rows, the error cells going up
+                 at most once (the given ones) and coming down once.  A table without the set's methods, or a job on several ranks, takes
+                 the host route and the log says why.  The result then holds `cells_route`: 'set' or 'host'.
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
                  double in the reference, RepairBase.scala:41-44): repaired by an L2 regressor on the values behind their codes
@@ -799,12 +888,27 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     ordered by (column, row).
     """
     continuous = dict(continuous or {})
-    det_rows, det_cols, run_targets, domain_info, detectors, t_detect = _detect_and_prune(
-        table, [int(t) for t in targets], constraints, detect_nulls, error_cells, only_noisy_targets, domain_analysis, value_detectors, regex_cols)
-    t_null = time.perf_counter()
-    rows, cols, current, merged, dirty_rows = _null_and_merge(engine, table, run_targets, det_rows, det_cols,
-                                                              rules.get("nearest") if rules is not None else None)
+    tg = [int(t) for t in targets]
+    nearest = rules.get("nearest") if rules is not None else None
+    route = None
+    if cells_resident:
+        why = set_route_refusal(table, tg)
+        route = "host" if why else "set"
+        if why:
+            _logger.info("[Error Detection Phase] the cell set's route is not taken (%s): the cells are merged on the host" % why)
+    if route == "set":
+        t_null = time.perf_counter()
+        det_rows, det_cols, run_targets, domain_info, detectors, t_detect, rows, cols, current, merged, dirty_rows = _cells_on_set(
+            engine, table, tg, constraints, detect_nulls, error_cells, only_noisy_targets, domain_analysis, value_detectors, regex_cols, nearest)
+        t_null += t_detect                                 # `prepare` starts where detection ends, as on the host route
+    else:
+        det_rows, det_cols, run_targets, domain_info, detectors, t_detect = _detect_and_prune(
+            table, tg, constraints, detect_nulls, error_cells, only_noisy_targets, domain_analysis, value_detectors, regex_cols)
+        t_null = time.perf_counter()
+        rows, cols, current, merged, dirty_rows = _null_and_merge(engine, table, run_targets, det_rows, det_cols, nearest)
     out = dict(rows=rows, cols=cols, current=current, dirty_rows=dirty_rows, models={}, stats=[])
+    if route is not None:
+        out["cells_route"] = route
     if rules is not None:
         out.update(rule_steps=[], merged=merged)
     if domain_info is not None:
@@ -1043,6 +1147,8 @@ def _details(enc, df, row_id, res, rules, regex_done):
         d = res["domain"]
         details.update(pairwise_attr_stats={cols[t]: [(cols[y], h) for y, h in lst] for t, lst in d["pairwise"].items()},
                        noisy_cells=d["noisy_cells"], weak_cells=d["weak_cells"])
+    if res.get("cells_route") is not None:
+        details["cells_route"] = res["cells_route"]
     if res.get("value_detectors"):
         details["value_detectors"] = [dict(attribute=cols[d["col"]], kinds=d["kinds"], codes_flagged=d["codes_flagged"], cells=d["cells"])
                                       for d in res["value_detectors"]]
@@ -1076,7 +1182,7 @@ def _details(enc, df, row_id, res, rules, regex_done):
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None, rebalance=None, order_scan=False):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None, order_scan=False, cells_resident=False):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
@@ -1123,6 +1229,9 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     distinct_training_rows: None or dict(max_ratio=float), as `repair_table` takes it; the details then hold `distinct_rows` with attribute
     names: dict(rows, distinct, used_for=[attributes], skipped={attribute: reason}).
 
+    cells_resident: as `repair_table` takes it, in both passes; the details then hold `cells_route` ('set' or 'host'; the second pass's when
+    there is one: its cells are the given ones).
+
     rebalance: None or dict(k=5, random_state=42), as `repair_table` takes it.  A column whose dictionary is not in the order of its sorted
     values (mixed types) raises NotResidentEligible; the details hold `rebalanced` {attribute: dict(median, rows, synthetic, classes)}."""
     cols = [c for c in df.columns if c != row_id]
@@ -1142,6 +1251,8 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                    keep_weak=error_cells is not None)
     through = dict(base_params=dict(base_params or {}), want_pmf=want_pmf, top_k=top_k, threshold=threshold, search_opts=search_opts,
                    only_noisy_targets=only_noisy_targets, distinct_training_rows=distinct_training_rows)
+    if cells_resident:                                     # (`repair_table` sees the keyword only when it is set)
+        through["cells_resident"] = True
     cells = None
     regex_done = [dict(rows=np.zeros(0, np.int64), cols=np.zeros(0, np.int32), current=np.zeros(0, object), repaired=np.zeros(0, object))]
     if error_cells is not None:
