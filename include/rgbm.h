@@ -425,6 +425,24 @@ int rgbm_table_fd_measures(rgbm_table* t, const int32_t* lhs_cols, int32_t n_lhs
  * dense joint table on route 0, the columns of a left-hand side.  n_rhs must be that call's (0 before any call), else RGBM_ERR_ARG.
  * t == NULL with n_rhs == 0 gives the two limits alone and needs no device. */
 int rgbm_table_fd_measures_report(const rgbm_table* t, int32_t* out /* [n_rhs + 2] */, int32_t n_rhs);
+/* A resident table in ANOTHER CODE SPACE (a kept fit applied to a later table, whose dictionaries are its own: repair/fitted.py; the statement
+ * is repair.recode_codes.recode; the reference left it a TODO, python/repair/model.py:1094).  `out` is a new resident table of the
+ * same rows and columns with the dictionary sizes n_codes_out.  A cell whose code lies outside [0, n_codes[j]) is NULL (-1) in `out`; under
+ * luts[j] == NULL (identity) every other code stays, and n_codes_out[j] must equal n_codes[j]; otherwise the cell holds luts[j][code] --
+ * n_codes[j] entries, each in [-1, n_codes_out[j]).  unmapped_out[j] = cells of column j that were not NULL in `t` and are NULL in `out`: exact
+ * integers, whatever the order of arrival.  One streaming pass: a LUT of at most the limit below is staged in LDS per workgroup, a larger one
+ * is gathered from global memory.
+ * `t` is not written; its cell list, cell set and distinct-row view stay as they were.  `out` inherits NO column kinds, column values or
+ * multiplicities: the code space changed, the caller sets them.
+ * RGBM_ERR_ARG: a NULL argument (unmapped_out may be NULL), n_codes_out[j] < 1, an identity column whose sizes differ, a LUT entry outside its
+ * range (the message names the column and the entry; LUTs are dictionary-sized and validated on the host).  RGBM_ERR_PARAM: a table of 2^31
+ * rows or more.  After a refusal *out, unmapped_out and the report below are as they were. */
+int rgbm_table_recode(const rgbm_table* t, const int32_t* const* luts /* [c]; luts[j] == NULL: identity */,
+                      const int32_t* n_codes_out /* [c] */, rgbm_table** out, int64_t* unmapped_out /* [c] or NULL */);
+/* The route of each column of the last successful rgbm_table_recode call on the table (read-only, no device work; for tests that must know
+ * their route): out [c + 1] = per column 0 (identity copy), 1 (LDS LUT) or 2 (global LUT) -- -1 before any call --, then the largest LUT that
+ * is staged in LDS.  c must be the table's columns, else RGBM_ERR_ARG.  t == NULL with c == 0 gives the limit alone and needs no device. */
+int rgbm_table_recode_report(const rgbm_table* t, int32_t* out /* [c + 1] */, int32_t c);
 /* Encoding on the device (replaces the pandas encoders of python/repair/model.py:701-729): per column, Arrow-style
  * dictionary indices (idx < 0 = NULL) are mapped through remap[col][idx] (the rank of the dictionary value in
  * sorted order, or -1) into the code table. */

@@ -205,6 +205,8 @@ struct rgbm_table {
     mutable std::vector<int32_t> pc_plan; mutable long long pc_plan_head[4] = {0, 0, 0, 0};
     // the route of every right-hand side of the last successful rgbm_table_fd_measures call (0 = LDS counters, 1 = hash tables), under prep_mu
     mutable std::vector<int32_t> fd_routes;
+    // the route of every column of the last successful rgbm_table_recode call (0 = identity, 1 = LDS LUT, 2 = global LUT), under prep_mu
+    mutable std::vector<int32_t> recode_routes;
     // the cluster of every row after the last rgbm_table_kmeans_assign call (int32 [n]); it leaves the device through rgbm_table_kmeans_read
     mutable rgh::DevBuf<int32_t> km_assign; mutable bool km_valid = false;
     mutable rgbm_distinct_view view;

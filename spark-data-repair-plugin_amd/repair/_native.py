@@ -97,7 +97,8 @@ def lib():
         for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect",
                      "rgbm_table_pair_counts_report", "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit",
                      "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close", "rgbm_table_fd_measures", "rgbm_table_fd_measures_report",
-                     "rgbm_table_cellset_add_cells", "rgbm_table_cellset_drop_weak", "rgbm_table_cellset_null", "rgbm_table_cellset_rows"):
+                     "rgbm_table_cellset_add_cells", "rgbm_table_cellset_drop_weak", "rgbm_table_cellset_null", "rgbm_table_cellset_rows",
+                     "rgbm_table_recode", "rgbm_table_recode_report"):
             if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass / no count report / no cell set)
                 getattr(l, name).restype = C.c_int
         l.rgbm_local_group_free.restype = None
@@ -129,6 +130,7 @@ EXPORTED_SYMBOLS = [
     "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit", "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close",
     "rgbm_table_fd_measures", "rgbm_table_fd_measures_report",
     "rgbm_table_cellset_add_cells", "rgbm_table_cellset_drop_weak", "rgbm_table_cellset_null", "rgbm_table_cellset_rows",
+    "rgbm_table_recode", "rgbm_table_recode_report",
 ]
 # exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
 EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
@@ -508,6 +510,14 @@ def fd_measures_limits():
     out = np.zeros(2, np.int32)
     _check(lib().rgbm_table_fd_measures_report(None, _p(out, C.c_int32), C.c_int32(0)), "rgbm_table_fd_measures_report")
     return dict(lds_cells=int(out[0]), max_lhs=int(out[1]))
+
+
+def recode_limits():
+    """The limit of ``Table.recode`` (rgbm_table_recode_report without a table; needs no device): dict(lds_codes = the largest LUT that a
+    workgroup stages in LDS)."""
+    out = np.zeros(1, np.int32)
+    _check(lib().rgbm_table_recode_report(None, _p(out, C.c_int32), C.c_int32(0)), "rgbm_table_recode_report")
+    return dict(lds_codes=int(out[0]))
 
 
 def _chain_args(models, feat_cols, class_codes):
@@ -1070,6 +1080,36 @@ class Table:
         out = np.zeros(n_rhs + 2, np.int32)
         _check(lib().rgbm_table_fd_measures_report(self.h, _p(out, C.c_int32), C.c_int32(n_rhs)), "rgbm_table_fd_measures_report")
         return dict(routes=[int(r) for r in out[:n_rhs]], lds_cells=int(out[n_rhs]), max_lhs=int(out[n_rhs + 1]))
+
+    def recode(self, luts, n_codes_out, want_unmapped=True):
+        """This table in ANOTHER CODE SPACE (include/rgbm.h rgbm_table_recode), exactly the integers of ``repair.recode_codes.recode``:
+        ``luts[j]`` is None (the codes of column j stay; ``n_codes_out[j]`` must be its dictionary size) or int32 [n_codes[j]] with
+        entries in [-1, n_codes_out[j]).  Returns (a new resident Table of the same rows with the dictionary sizes ``n_codes_out`` and NO
+        column kinds, values or multiplicities; int64 [c]: the cells per column that held a value and are NULL now, or None)."""
+        luts = list(luts)
+        if len(luts) != self.c:
+            raise ValueError("one LUT (or None) per column expected")
+        maps = [None if m is None else np.ascontiguousarray(m, np.int32) for m in luts]
+        for j, m in enumerate(maps):
+            if m is not None and len(m) != int(self.n_codes[j]):
+                raise ValueError("the LUT of column %d has %d entries, its dictionary %d" % (j, len(m), int(self.n_codes[j])))
+        # (an empty array has no address of its own: a LUT column never passes NULL, which would mean identity)
+        keep = [None if m is None else (m if len(m) else np.zeros(1, np.int32)) for m in maps]
+        ptrs = (C.POINTER(C.c_int32) * max(self.c, 1))(*[_p(m, C.c_int32) for m in keep])
+        nco = _i32(np.asarray(n_codes_out, np.int32).reshape(-1))
+        if len(nco) != self.c:
+            raise ValueError("one output dictionary size per column expected")
+        un = np.zeros(max(self.c, 1), np.int64) if want_unmapped else None
+        h = C.c_void_p()
+        _check(lib().rgbm_table_recode(self.h, ptrs, _p(nco, C.c_int32), C.byref(h), _p(un, C.c_int64)), "rgbm_table_recode")
+        return Table._adopt(h, self.device_id), (un[:self.c] if want_unmapped else None)
+
+    def recode_report(self):
+        """The route each column took in the last successful ``recode`` call on this table (include/rgbm.h rgbm_table_recode_report):
+        dict(routes = one per column, 0 = identity copy, 1 = LDS LUT, 2 = global LUT, -1 before any call; lds_codes = the limit)."""
+        out = np.zeros(self.c + 1, np.int32)
+        _check(lib().rgbm_table_recode_report(self.h, _p(out, C.c_int32), C.c_int32(self.c)), "rgbm_table_recode_report")
+        return dict(routes=[int(r) for r in out[:self.c]], lds_codes=int(out[self.c]))
 
     def fd_map(self, x, y):
         """The rule model of the functional dependency x -> y (include/rgbm.h rgbm_table_fd_map): int32 [n_codes[x]], the single y code

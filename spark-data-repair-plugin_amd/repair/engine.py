@@ -127,6 +127,11 @@ class HipEngine:
         """`repair.fd_codes.fd_measures` on a resident table (rgbm_table_fd_measures), the same integers."""
         return table.fd_measures(lhs, rhs_cols)
 
+    def recode(self, table, luts, n_codes_out):
+        """`repair.recode_codes.recode` on a resident table (rgbm_table_recode), the same integers: (the table in the other code space,
+        without kinds or values; unmapped cells per column)."""
+        return table.recode(luts, n_codes_out)
+
     def repair_chain_gather(self, table, models, targets, feats, row_begin, n_rows):
         """C2 on device buffers: the chain over this rank's rows, labels / probabilities all-gathered over the rank's communicator before
         they leave the device (include/rgbm.h rgbm_table_repair_chain_gather) -> (labels, probs of ALL ranks' rows in rank order, first row of this rank)."""

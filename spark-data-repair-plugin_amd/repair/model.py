@@ -138,6 +138,9 @@ class RepairModel():
     # ... unless the table holds more than this share of distinct rows (a policy default, not a measured break-even: DESIGN 5g)
     _opt_train_distinct_rows_max_ratio = _option("model.train.distinct_rows.max_ratio", 0.5, float, lambda v: 0.0 < v <= 1.0,
                                                  "`{}` should be in (0.0, 1.0]")
+    # new in this engine: a resident repair run KEEPS its fit (`fittedModels()`: repair.fitted.FittedRepairModels -- the final dictionaries, the
+    # chain, the model blobs), so that `setFittedModels` repairs later tables without training.  Off by default: nothing is kept.
+    _opt_fitted_keep = _option("model.fitted.keep", False, bool, None, None)
     # new in this engine: which HIP device trains/predicts (read by repair.train.fixed_params)
     _opt_gpu_device_id = _train_opt_gpu_device_id
 
@@ -145,7 +148,7 @@ class RepairModel():
         _opt_max_training_row_num, _opt_max_training_column_num, _opt_small_domain_threshold, _opt_repair_by_regex_disabled,
         _opt_repair_by_nearest_values_disabled, _opt_merge_threshold, _opt_repair_by_functional_deps_disabled,
         _opt_max_domain_size, _opt_cost_weight, _opt_prob_threshold, _opt_prob_top_k, _opt_pmf_resident, _opt_rule_resident, _opt_rule_regex_resident, _opt_rebalance_resident,
-        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_constraints_order_scan, _opt_detect_only_resident, _opt_cells_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_gpu_device_id)] +
+        _opt_value_detectors_resident, _opt_lof_resident, _opt_constraints_resident, _opt_constraints_order_scan, _opt_detect_only_resident, _opt_cells_resident, _opt_train_distinct_rows, _opt_train_distinct_rows_max_ratio, _opt_fitted_keep, _opt_gpu_device_id)] +
         list(ErrorModel.option_keys) + list(train_option_keys))
 
     def __init__(self) -> None:
@@ -163,6 +166,9 @@ class RepairModel():
         self.repair_validation_enabled: bool = False
         self.cf: Optional[UpdateCostFunction] = None
         self.opts: Dict[str, str] = {}
+        self._fitted: Any = None                      # `setFittedModels`: the fit that `run()` applies instead of training
+        self._kept_fit: Any = None                    # `fittedModels()`: what the last run kept, or why it kept nothing
+        self._kept_fit_why: str = "no run has kept a fit: set the option `model.fitted.keep` and run"
 
     # ------------------------------------------------------------------ fluent setters
     @argtype_check  # type: ignore
@@ -218,6 +224,22 @@ class RepairModel():
     def setErrorDetectors(self, detectors: List[ErrorDetector]) -> "RepairModel":
         self.error_detectors = detectors
         return self
+
+    def setFittedModels(self, fitted_or_path: Any) -> "RepairModel":
+        """`run()` and `run(repair_data=True)` train nothing: the error cells, detected as ever, are repaired by the chain of a kept fit
+        (`fittedModels()` of an earlier run, or the path of its `save`).  None clears it."""
+        from repair.fitted import FittedRepairModels
+        if fitted_or_path is not None and not isinstance(fitted_or_path, FittedRepairModels):
+            fitted_or_path = FittedRepairModels.load(str(fitted_or_path))
+        self._fitted = fitted_or_path
+        return self
+
+    def fittedModels(self) -> Any:
+        """The fit the last `run()` kept under `model.fitted.keep` (repair.fitted.FittedRepairModels).  ValueError, with the reason, when
+        there is none: the option was off, the run used rule steps, was a multi-rank job or took the value-space path."""
+        if self._kept_fit is None:
+            raise ValueError("No fitted models: %s" % self._kept_fit_why)
+        return self._kept_fit
 
     @argtype_check  # type: ignore
     def setDiscreteThreshold(self, thres: int) -> "RepairModel":
@@ -1144,6 +1166,11 @@ class RepairModel():
                          threshold=float(self._get_option_value(*self._opt_prob_threshold)),
                          pmf_costs=lambda attr, classes, rows: self._cost_spec(plan["engine"], attr, classes, current(attr, rows),
                                                                                maximal_likelihood_repair))
+        keep = bool(self._get_option_value(*self._opt_fitted_keep)) and self._fitted is None
+        if self._fitted is not None:
+            cells.update(fitted=self._fitted)
+        elif keep:                                         # (`repair_frame` sees either keyword only when it is used)
+            cells.update(keep_fit=True)
         t0 = time.perf_counter()
         # (the probability modes train on the whole table: `model.train.distinct_rows` is not wired to them)
         frame, info = repair_frame(plan["engine"], input_df, rid, targets=target_columns, base_params=plan["params"],
@@ -1156,6 +1183,14 @@ class RepairModel():
         t0 = time.perf_counter()
         self._last_resident_info = info
         self._last_detection_on_device = detect
+        if self._fitted is not None and error_cells_df is not None:
+            # the cells of an attribute without a kept model were counted and left as they are: they are not part of the result
+            error_cells_df = error_cells_df[error_cells_df["attribute"].isin(self._fitted.chain)].reset_index(drop=True)
+        if keep:
+            from repair.fitted import FittedRepairModels
+            pieces = info.get("fit")
+            self._kept_fit = FittedRepairModels.from_pieces(pieces) if pieces is not None else None
+            self._kept_fit_why = info.get("fit_refusal", "")
         try:
             by_rule = [f for f in (info.get("regex_cells"), info.get("merged_cells")) if f is not None and len(f)]
             return self._resident_result(input_df, frame, pd.concat(by_rule, ignore_index=True) if by_rule else None, error_cells_df,
@@ -1285,6 +1320,54 @@ class RepairModel():
             _logger.info("%s not taken: %s" % (what, e))
             return None
 
+    def _fitted_plan(self) -> Dict[str, Any]:
+        """The plan of a run that applies a kept fit: the checks that do not depend on the table (ValueError with the reason), the engine,
+        and the one info line about the settings such a run does not read."""
+        from repair import dist
+        fitted = self._fitted
+        if self.repair_by_rules:
+            raise ValueError("Cannot apply fitted models with `setRepairByRules(True)`: a rule is a map of the fitted table, not a kept model")
+        if dist.world()[1] > 1:
+            raise ValueError("Cannot apply fitted models in a job on %d ranks" % dist.world()[1])
+        if self.targets and set(self.targets) != set(fitted.chain):
+            raise ValueError("Cannot apply fitted models: the targets of the run are the fitted targets %s, but `setTargets` gave %s"
+                             % (to_list_str(fitted.chain), to_list_str(self.targets)))
+        engine = self._resident_engine()
+        if engine is None:
+            raise ValueError("Cannot apply fitted models: no engine for the HBM-resident table (no HIP device, or REPAIR_RESIDENT=0)")
+        ignored = sorted(k for k in self.opts if k.startswith(("model.lgb.", "model.hp.", "model.cv.")) or k in (
+            self._opt_max_training_row_num.key, self._opt_train_distinct_rows.key, self._opt_train_distinct_rows_max_ratio.key))
+        if self.training_data_rebalancing_enabled:
+            ignored.append("setTrainingDataRebalancingEnabled")
+        if ignored:
+            _logger.info("[Repairing Phase] fitted models are applied, nothing is trained: %s not read" % to_list_str(ignored))
+        return dict(engine=engine, params={}, search=False, rules=None, distinct=None, rebalance=None)
+
+    def _run_fitted(self, input_df: DataFrame, continous_columns: List[str], flags: Any) -> DataFrame:
+        """`_run` with `setFittedModels`: detection on whichever route the detectors take today -- the device detection plan, or the pandas
+        detectors followed by given cells -- then ONE resident attempt that applies the fit (`pipeline.repair_frame(fitted=..)`); there is
+        no value-space continuation: what would send a training run there is a ValueError here."""
+        from repair.pipeline import NotResidentEligible
+        fitted, repair_data = self._fitted, flags[3]
+        plan = self._fitted_plan()
+        missing = [c for c in fitted.columns if c not in input_df.columns]
+        if missing:
+            raise ValueError("Cannot apply fitted models: the fitted column `%s` is not in the input" % missing[0])
+        try:
+            dplan = self._device_detection_plan(input_df, continous_columns, False, False) if self.error_detectors else None
+            if dplan is not None:
+                dplan = dict(dplan, engine=plan["engine"], params={}, search=False, rules=None, distinct=None, rebalance=None)
+                return self._resident_run(dplan, input_df, dplan["candidates"], continous_columns, None, *flags)
+            _logger.info("[Error Detection Phase] Detecting errors in a table... ")
+            error_cells_df, target_columns, _, _ = self._detect_errors(input_df, continous_columns)
+            if len(error_cells_df) == 0:
+                _logger.info("Any error cell not found, so the input data is already clean")
+                return input_df if repair_data else error_cells_df.assign(repaired=pd.Series([], dtype=object))
+            error_cells_df = error_cells_df[error_cells_df["attribute"].isin(target_columns)].reset_index(drop=True)
+            return self._resident_run(plan, input_df, target_columns, continous_columns, error_cells_df, *flags)
+        except NotResidentEligible as e:
+            raise ValueError("Cannot apply fitted models: %s" % e)
+
     @elapsed_time  # type: ignore
     def _run(self, input_df: DataFrame, continous_columns: List[str], detect_errors_only: bool,
              compute_repair_candidate_prob: bool, compute_repair_prob: bool, compute_repair_score: bool,
@@ -1292,6 +1375,11 @@ class RepairModel():
         rid = self._row_id
         flags = (compute_repair_candidate_prob, compute_repair_prob, compute_repair_score, repair_data, maximal_likelihood_repair)
         self._last_detection_on_device = False
+        if self._fitted is not None and not detect_errors_only:
+            return self._run_fitted(input_df, continous_columns, flags)
+        if bool(self._get_option_value(*self._opt_fitted_keep)):
+            self._kept_fit = None
+            self._kept_fit_why = "the run took the value-space path: only a run on the HBM-resident table keeps its fit"
         # 0. Everything on the HBM-resident table, detection included, when the detectors and the run allow it
         dplan = None if detect_errors_only else self._device_detection_plan(input_df, continous_columns, compute_repair_candidate_prob,
                                                                             maximal_likelihood_repair)
@@ -1383,6 +1471,9 @@ class RepairModel():
         if self._repair_by_nearest_values_enabled and (maximal_likelihood_repair or compute_repair_candidate_prob or compute_repair_prob or compute_repair_score):
             raise ValueError("Cannot repair data by nearest values when enabling `maximal_likelihood_repair`, "
                              "`compute_repair_candidate_prob`, `compute_repair_prob`, or `compute_repair_score`")
+        if self._fitted is not None and (compute_repair_candidate_prob or compute_repair_prob or compute_repair_score or maximal_likelihood_repair):
+            raise ValueError("Cannot apply fitted models in the probability modes (`compute_repair_candidate_prob`, `compute_repair_prob`, "
+                             "`compute_repair_score`, `maximal_likelihood_repair`): they are answered by a run that trains")
         if compute_repair_prob or compute_repair_score:
             compute_repair_candidate_prob = True
         if compute_repair_score:

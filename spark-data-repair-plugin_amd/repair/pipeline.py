@@ -836,6 +836,40 @@ def _train_and_repair(engine, table, dirty_tab, chain, label_counts, base_params
     return res
 
 
+def _apply_fitted(engine, dirty_tab, fitted):
+    """The phase that stands for `_target_plan`, `_training_tables` and `_train_and_repair` when a kept fit is applied (`repair_table(fitted=..)`,
+    DESIGN 5q): nothing is trained.  The dirty rows are translated into the code space of the fit on the device (`engine.recode`:
+    rgbm_table_recode), the table gets the fitted column kinds and values, every blob is loaded (`engine.load_model`) and `chained_repair` runs the
+    fitted chain on it.  Labels are FITTED codes.  Returns (the model-space table, a result shaped like `run_job`'s, dict(unmapped {column:
+    cells that held a value the fitted dictionaries cannot express}, recode_seconds)).
+
+    fitted : dict(chain=[target columns in prediction order], feats={target: feature columns in the fit's order}, blobs={target: bytes},
+             y_values={continuous target: the fitted values}, integral={targets}, luts=[per column int32 LUT or None], n_codes_out=[per column],
+             categorical=[columns], values={numeric column: the fitted values})."""
+    from repair.engine import chained_repair
+    t0 = time.perf_counter()
+    model_tab, unmapped = engine.recode(dirty_tab, fitted["luts"], fitted["n_codes_out"])
+    for j in fitted.get("categorical", ()):
+        model_tab.set_column_kind(int(j), True)
+    for j, v in (fitted.get("values") or {}).items():
+        if len(v):
+            model_tab.set_column_values(int(j), v)
+    t_recode = time.perf_counter() - t0
+    chain = [int(t) for t in fitted["chain"]]
+    t0 = time.perf_counter()
+    models = [engine.load_model(fitted["blobs"][t]) for t in chain]
+    t_load = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    y_values = {int(t): np.asarray(v, np.float64) for t, v in (fitted.get("y_values") or {}).items()}
+    labels, probs, values = chained_repair(engine, model_tab, models, chain, [list(fitted["feats"][t]) for t in chain], 0, model_tab.n, y_values,
+                                           set(int(t) for t in fitted.get("integral", ())))
+    res = dict(labels=labels, probs=probs, values=values if y_values else None, models={}, stats=[],
+               times=dict(train=0.0, exchange=t_load, infer=time.perf_counter() - t0, gather=0.0, recode=t_recode))
+    info = dict(unmapped={j: int(k) for j, k in enumerate(np.asarray(unmapped, np.int64)) if fitted["luts"][j] is not None},
+                recode_seconds=t_recode)
+    return model_tab, res, info
+
+
 def _shape(engine, table, dirty_tab, pmf_tab, res, chain, rows, cols, current, dirty_rows, rule_steps, want_rule_steps, continuous, y_values,
            integral, want_pmf, top_k, threshold, pmf_costs):
     """Phase 6: flatten + join with the error cells (RepairMiscApi.scala:41-49, model.py:1398-1401).  Returns the per-cell entries of the
@@ -866,7 +900,8 @@ def _shape(engine, table, dirty_tab, pmf_tab, res, chain, rows, cols, current, d
 def repair_table(engine, table, targets, base_params, constraints=(), detect_nulls=True, error_cells=None,
                  want_pmf=False, top_k=32, threshold=0.0, want_stats=False, continuous=None, train_rows=None,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None, rebalance=None, regex_cols=None, cells_resident=False):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None, regex_cols=None, cells_resident=False, keep_fit=False,
+                 fitted=None):
     """Detect, NULL out, split, train, repair, shape.  ``table`` is modified in place (error cells become NULL).  The phases, and where each
     parameter is described: `_detect_and_prune` (constraints, detect_nulls and error_cells as `detect_error_cells` takes them,
     only_noisy_targets, domain_analysis, value_detectors, regex_cols), `_null_and_merge` (rules['nearest']: `nearest_value_merges`),
@@ -876,6 +911,11 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     cells_resident : phases 1 and 2 on the table's cell set (`_cells_on_set`): the same cells, codes and dirty rows, the error cells going up
                  at most once (the given ones) and coming down once.  A table without the set's methods, or a job on several ranks, takes
                  the host route and the log says why.  The result then holds `cells_route`: 'set' or 'host'.
+
+    keep_fit   : the result also holds `fit`: dict(chain, y_values, integral) -- with `models`, what an apply run needs of this one.
+    fitted     : apply a kept fit (`_apply_fitted` describes the dict) instead of training: phases 1 and 2 are unchanged but look at the fitted
+                 targets only; the error cells of the other targets are counted (`fitted`: dict(unmapped, unfitted_cells, recode_seconds) of
+                 the result), not NULLed and not repaired.  The chain is the fitted one, whatever targets hold error cells.
 
     continuous : {column: (ascending distinct values, is_integral)} -- CONTINUOUS target attributes (byte/short/int/long/float/
                  double in the reference, RepairBase.scala:41-44): repaired by an L2 regressor on the values behind their codes
@@ -890,6 +930,19 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     continuous = dict(continuous or {})
     tg = [int(t) for t in targets]
     nearest = rules.get("nearest") if rules is not None else None
+    unfitted = {}
+    if fitted is not None:
+        if rules is not None or want_pmf:
+            raise ValueError("a kept fit is applied without rule steps and without the probability modes")
+        in_fit = set(int(t) for t in fitted["chain"])
+        others = [t for t in tg if t not in in_fit]
+        tg = [t for t in tg if t in in_fit]
+        if callable(value_detectors):
+            value_detectors = value_detectors(table)
+        if others:                                         # counted before anything is NULLed; they stay as they are
+            _, ocols = detect_error_cells(table, others, constraints, detect_nulls, error_cells, value_detectors=value_detectors)
+            unfitted = {int(c): int(k) for c, k in zip(*np.unique(ocols, return_counts=True))}
+        only_noisy_targets = False                         # (no class of a kept model is counted on this table)
     route = None
     if cells_resident:
         why = set_route_refusal(table, tg)
@@ -915,11 +968,23 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
         out["domain"] = domain_info
     if detectors:
         out["value_detectors"] = _detector_report(detectors)
+    if fitted is not None:
+        out["fitted"] = dict(unmapped={}, unfitted_cells=unfitted, recode_seconds=0.0)
     if len(rows) == 0:
         out.update(repaired=np.zeros(0, np.int32), repaired_value=np.zeros(0, np.float64), prob=np.zeros(0, np.float64),
                    times=dict(detect=t_detect, prepare=time.perf_counter() - t_null))
         return out
     dirty_tab = table.gather_rows(dirty_rows)
+    if fitted is not None:
+        t_prep = time.perf_counter() - t_null
+        model_tab, res, finfo = _apply_fitted(engine, dirty_tab, fitted)
+        out["fitted"].update(finfo)
+        chain = [int(t) for t in fitted["chain"]]
+        t_shape = time.perf_counter()
+        out.update(_shape(engine, table, model_tab, None, res, chain, rows, cols, current, dirty_rows, {}, False, continuous,
+                          fitted.get("y_values") or {}, fitted.get("integral", ()), False, top_k, threshold, None))
+        out["times"] = dict(res["times"], detect=t_detect, prepare=t_prep, shape=time.perf_counter() - t_shape)
+        return out
     pmf_tab = table.gather_rows(dirty_rows) if want_pmf else None      # stays un-repaired: pmf mode does not chain
     label_counts, rule_steps, chain = _target_plan(table, run_targets, continuous, rules, only_noisy_targets,
                                                    dict(rows=det_rows, cols=det_cols, domain_info=domain_info, value_detectors=out.get("value_detectors")))
@@ -939,6 +1004,8 @@ def repair_table(engine, table, targets, base_params, constraints=(), detect_nul
     out.update(_shape(engine, table, dirty_tab, pmf_tab, res, chain, rows, cols, current, dirty_rows, rule_steps, rules is not None,
                       continuous, y_values, integral, want_pmf, top_k, threshold, pmf_costs))
     out["times"] = dict(res["times"], detect=t_detect, prepare=t_prep, shape=time.perf_counter() - t_shape)
+    if keep_fit:
+        out["fit"] = dict(chain=list(chain), y_values=y_values, integral=sorted(integral), rule_targets=sorted(rule_steps))
     return out
 
 
@@ -1082,7 +1149,25 @@ def constraint_routes(constraints):
     return [con["kind"] if isinstance(con, dict) else "fd" for con in constraints]
 
 
-def _upload_and_run(engine, enc, df, targets, cells, regex_rules, by_name, through, analyse=True, order_scan=False):
+def _fitted_column_space(fitted, enc):
+    """A kept fit (`repair.fitted.FittedRepairModels`) against the encoding of a later frame, as `repair_table(fitted=..)` takes it: the
+    LUTs of `repair.fitted.fitted_luts`, and the chain, features, dictionaries, kinds and values by the FRAME's column positions."""
+    from repair.fitted import fitted_luts
+    luts = fitted_luts(fitted, enc)
+    pos = enc.pos
+    fdict = {c: fitted.dicts[j] for j, c in enumerate(fitted.columns)}
+    n_codes_out = [max(len(enc.dicts[j]), 1) if luts[j] is None else max(len(fdict[c]), 1) for j, c in enumerate(enc.columns)]
+    tg = fitted.targets
+    return dict(chain=[pos[t] for t in fitted.chain], feats={pos[t]: [pos[f] for f in tg[t]["features"]] for t in fitted.chain},
+                blobs={pos[t]: tg[t]["blob"] for t in fitted.chain},
+                y_values={pos[t]: np.asarray(tg[t]["y_values"], np.float64) for t in fitted.chain if tg[t]["continuous"]},
+                integral={pos[t] for t in fitted.chain if tg[t]["continuous"] and tg[t]["integral"]},
+                luts=luts, n_codes_out=n_codes_out,
+                categorical=[pos[c] for j, c in enumerate(fitted.columns) if fitted.categorical[j]],
+                values={pos[c]: np.asarray(fitted.dicts[j], np.float64) for j, c in enumerate(fitted.columns) if not fitted.categorical[j]})
+
+
+def _upload_and_run(engine, enc, df, targets, cells, regex_rules, by_name, through, analyse=True, order_scan=False, fitted=None):
     """One pass: upload the encoding, `repair_table` on it.  `cells`: the known error cells or None; `by_name` / `through`: the keywords of
     `_column_space` / those `repair_table` takes as they are; `order_scan`: `route_order_constraints` on the lowered constraints.
     Returns (the continuous targets {column: (values, is_integral)}, result); the result (or the DeadClasses raised) holds
@@ -1093,6 +1178,8 @@ def _upload_and_run(engine, enc, df, targets, cells, regex_rules, by_name, throu
         kw["constraints"] = route_order_constraints(kw["constraints"], table)
     routes = constraint_routes(kw["constraints"])
     regex_cols = [enc.pos[r["attr"]] for r in regex_rules if r["attr"] in enc.pos] if cells is None else None
+    if fitted is not None:                                 # (the keyword reaches `repair_table` only when a fit is applied)
+        through = dict(through, fitted=_fitted_column_space(fitted, enc))
     try:
         res = repair_table(engine, table, [enc.pos[t] for t in targets], error_cells=cells, regex_cols=regex_cols, **through, **kw)
     except DeadClasses as e:
@@ -1102,11 +1189,12 @@ def _upload_and_run(engine, enc, df, targets, cells, regex_rules, by_name, throu
     return kw["continuous"], res
 
 
-def _result_frame(enc, df, row_id, res, cont, want_pmf, with_costs):
-    """(row_id, attribute, current_value, repaired[, prob][, pmf, current_prob[, top1_cost, pmf_value]]) of the repaired cells."""
+def _result_frame(enc, df, row_id, res, cont, want_pmf, with_costs, label_dicts=None):
+    """(row_id, attribute, current_value, repaired[, prob][, pmf, current_prob[, top1_cost, pmf_value]]) of the repaired cells.
+    `label_dicts`: the dictionaries behind the labels where they are not the encoding's (an applied fit: the FITTED ones, by column)."""
     import pandas as pd
     rows, ccols = res["rows"], res["cols"]
-    repaired = enc.decode(res["repaired"], ccols)
+    repaired = (enc if label_dicts is None else FrameEncoding(enc.columns, enc.indices, enc.remaps, label_dicts)).decode(res["repaired"], ccols)
     for j, (_, is_int) in cont.items():                       # continuous attributes: the regressor's value, not a dictionary entry
         sel = ccols == j
         v = res["repaired_value"][sel]
@@ -1179,10 +1267,33 @@ def _details(enc, df, row_id, res, rules, regex_done):
     return details
 
 
+def _fit_pieces(enc, res, cont):
+    """What `repair_frame(keep_fit=True)` adds to its details: `fit` (the pieces of `repair.fitted.FittedRepairModels.from_pieces`, from the
+    encoding of the FINAL pass and that pass's result) or `fit_refusal` (why there is none)."""
+    from repair import dist
+    fit = res.get("fit")
+    if fit is None:
+        return dict(fit_refusal="the run trained nothing (it found no error cell)")
+    if fit["rule_targets"]:
+        return dict(fit_refusal="the run used rule steps (%s): a rule is a map of the fitted table, not a model"
+                    % ", ".join("`%s`" % enc.columns[t] for t in fit["rule_targets"]))
+    if dist.world()[1] > 1:
+        return dict(fit_refusal="the run was a job on %d ranks" % dist.world()[1])
+    cols = enc.columns
+    targets = {}
+    for t in fit["chain"]:
+        targets[cols[t]] = dict(blob=bytes(res["models"][t]), features=[cols[c] for c in range(len(cols)) if c != t], continuous=t in cont,
+                                integral=bool(t in cont and cont[t][1]),
+                                y_values=np.asarray(fit["y_values"][t], np.float64) if t in fit["y_values"] else None)
+    return dict(fit=dict(columns=list(cols), dicts=[np.array(d, copy=True) for d in enc.dicts], categorical=[d.dtype == object for d in enc.dicts],
+                         chain=[cols[t] for t in fit["chain"]], targets=targets))
+
+
 def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=None, want_pmf=False, top_k=32, threshold=0.0,
                  error_cells=None, detect_nulls=True, continuous_columns=(), train_rows=None, want_details=False,
                  check_unseen=False, search_opts=None, only_noisy_targets=False, pmf_costs=None, domain_analysis=None, rules=None,
-                 value_detectors=None, distinct_training_rows=None, rebalance=None, order_scan=False, cells_resident=False):
+                 value_detectors=None, distinct_training_rows=None, rebalance=None, order_scan=False, cells_resident=False, keep_fit=False,
+                 fitted=None):
     """DataFrame in, the reference's result frame out: (row_id, attribute, current_value, repaired, prob[, pmf]) -- the
     shape of `RepairModel.run()` / `run(compute_repair_candidate_prob=True)` (python/repair/model.py:1398-1419).
 
@@ -1232,6 +1343,17 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     cells_resident: as `repair_table` takes it, in both passes; the details then hold `cells_route` ('set' or 'host'; the second pass's when
     there is one: its cells are the given ones).
 
+    keep_fit: the details hold `fit`, the pieces of `repair.fitted.FittedRepairModels.from_pieces` -- the column names, the dictionaries the
+    FINAL pass uploaded (after the pruning of known cells and after a DeadClasses second pass), the kinds as `_upload` decides them, the chain
+    and per chain target its blob, features, continuous / integral flags and y_values -- or `fit_refusal`, the reason there is none (rule
+    steps, a multi-rank job, nothing trained).
+    fitted: a `repair.fitted.FittedRepairModels`: nothing is trained.  Detection, the NULL-out, the cell-set route, the dirty rows
+    and the frame's shape are as ever; between them `_apply_fitted` translates the dirty rows into the fit's code space on the device and
+    runs the kept chain.  `repaired` is decoded with the FITTED dictionaries.  Error cells of a target without a kept model stay as they are
+    and are counted: the details hold `fitted`: dict(unmapped {attribute: cells}, unfitted_cells {attribute: cells}, recode_seconds), and
+    one warning names them.  Rules, the probability modes, a hyper-parameter search and the training options do not apply (ValueError for
+    the first two; `base_params`, `train_rows`, `rebalance`, `distinct_training_rows` are not read).
+
     rebalance: None or dict(k=5, random_state=42), as `repair_table` takes it.  A column whose dictionary is not in the order of its sorted
     values (mixed types) raises NotResidentEligible; the details hold `rebalanced` {attribute: dict(median, rows, synthetic, classes)}."""
     cols = [c for c in df.columns if c != row_id]
@@ -1239,12 +1361,20 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
     unknown = [t for t in targets if t not in cols]
     if unknown:
         raise ValueError("Target attributes not found in the input: %s" % ",".join(unknown))
+    if fitted is not None:
+        if rules is not None or want_pmf:
+            raise ValueError("a kept fit is applied without rule steps and without the probability modes")
+        missing = [c for c in fitted.columns if c not in cols]
+        if missing:
+            raise ValueError("the fitted column `%s` is not in the frame" % missing[0])
+        train_rows = rebalance = distinct_training_rows = search_opts = None
+        check_unseen = keep_fit = False
     enc = FrameEncoding.of_frame(df, cols)
     if rebalance is not None:
         from repair.rebalance_codes import check_dictionary_order
         for j, c in enumerate(cols):
             check_dictionary_order(enc.dicts[j], "`%s`" % c)
-    target_cols = sorted(enc.pos[t] for t in targets)
+    target_cols = sorted(enc.pos[t] for t in targets if fitted is None or t in fitted.targets)     # (applying a fit: the cells of the others stay)
     regex_rules = list((rules or {}).get("regex") or [])
     by_name = dict(continuous_columns=continuous_columns, train_rows=train_rows, check_unseen=check_unseen, pmf_costs=pmf_costs,
                    domain_analysis=domain_analysis, rules=rules, value_detectors=value_detectors, rebalance=rebalance,
@@ -1253,12 +1383,14 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                    only_noisy_targets=only_noisy_targets, distinct_training_rows=distinct_training_rows)
     if cells_resident:                                     # (`repair_table` sees the keyword only when it is set)
         through["cells_resident"] = True
+    if keep_fit:
+        through["keep_fit"] = True
     cells = None
     regex_done = [dict(rows=np.zeros(0, np.int64), cols=np.zeros(0, np.int32), current=np.zeros(0, object), repaired=np.zeros(0, object))]
     if error_cells is not None:
         done, cells = _known_cells(engine, enc, target_cols, *_cell_positions(enc, df, row_id, error_cells), regex_rules)
         regex_done.append(done)
-    if error_cells is not None and not detect_nulls and not constraints and rules is None:
+    if error_cells is not None and not detect_nulls and not constraints and rules is None and fitted is None:
         # every error cell is known and NULLed: the class counts the models will see are final.  Say so BEFORE anything is uploaded
         # (a constraint / regex / user-given cell may hold the only occurrence of a class; an all-NULL numeric column has no value)
         for t in targets:
@@ -1267,7 +1399,7 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
                 raise NotResidentEligible("target `%s` is left with %d distinct value(s) once the error cells are removed" % (t, live))
     try:
         cont, res = _upload_and_run(engine, enc, df, targets, cells, regex_rules, dict(by_name, constraints=constraints, detect_nulls=detect_nulls),
-                                    through, order_scan=order_scan)
+                                    through, order_scan=order_scan, fitted=fitted)
     except DeadClasses as e:
         # Detection ran on the device; some values of a target were held by error cells only (a typo occurs once).  The cells are
         # known now: NULL them on the host side of the encoding, drop the dead values, upload the (cached) encoding again and go on
@@ -1283,11 +1415,28 @@ def repair_frame(engine, df, row_id, targets=None, constraints=(), base_params=N
         if e.value_detectors:
             res["value_detectors"] = e.value_detectors
         res["constraint_routes"] = e.constraint_routes
-    frame = _result_frame(enc, df, row_id, res, cont, want_pmf, pmf_costs is not None)
+    label_dicts = None
+    if fitted is not None:
+        fdict = {c: fitted.dicts[j] for j, c in enumerate(fitted.columns)}
+        label_dicts = [fdict.get(c, enc.dicts[j]) for j, c in enumerate(enc.columns)]
+        cont = {enc.pos[t]: (np.asarray(fitted.targets[t]["y_values"], np.float64), bool(fitted.targets[t]["integral"]))
+                for t in fitted.chain if fitted.targets[t]["continuous"]}
+        left = {enc.columns[j]: k for j, k in sorted(res["fitted"]["unfitted_cells"].items())}
+        if left:
+            _logger.warning("[Repairing Phase] error cells in attributes without a kept model are left as they are: %s"
+                            % ", ".join("`%s`: %d" % (a, k) for a, k in left.items()))
+    frame = _result_frame(enc, df, row_id, res, cont, want_pmf, pmf_costs is not None, label_dicts=label_dicts)
     if not want_details:
         return frame
     regex_cells = {k: np.concatenate([d[k] for d in regex_done]) for k in regex_done[0]}
-    return frame, _details(enc, df, row_id, res, rules, regex_cells if regex_rules else None)
+    details = _details(enc, df, row_id, res, rules, regex_cells if regex_rules else None)
+    if fitted is not None:
+        f = res["fitted"]
+        details["fitted"] = dict(unmapped={enc.columns[j]: k for j, k in sorted(f["unmapped"].items())}, unfitted_cells=left,
+                                 recode_seconds=f["recode_seconds"])
+    if keep_fit:
+        details.update(_fit_pieces(enc, res, cont))
+    return frame, details
 
 
 def _detect_only_frame(df, row_id, enc, rows, cols, codes):
