@@ -3,6 +3,9 @@
 There is deliberately no fallback: if the shared library is missing or no HIP device is usable
 the calls raise ``RepairGbmError`` (the caller in train.py turns a failed build into
 ``PoorModel(None)`` exactly like the reference does, python/repair/train.py:227-229).
+
+The C signature of every entry point is written down once, in ``SIGNATURES`` below; ``lib()`` hands it to ctypes, which converts and
+checks the arguments of every call.  A new entry point is declared in include/rgbm.h and in that table, nowhere else.
 """
 import ctypes as C
 import os
@@ -39,6 +42,24 @@ class RgbmTrainStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RgbmFitSpec(C.Structure):
+    _fields_ = [("table", C.c_void_p), ("target_col", C.c_int32), ("n_features", C.c_int32), ("feat_cols", C.POINTER(C.c_int32)),
+                ("y_value", C.POINTER(C.c_double)), ("class_weight", C.POINTER(C.c_double)), ("params", C.POINTER(RgbmParams)),
+                ("valid_table", C.c_void_p), ("valid_label_out", C.POINTER(C.c_int32)), ("valid_value_out", C.POINTER(C.c_double))]
+
+
+class DcPred(C.Structure):
+    """``rgbm_dc_pred`` of include/rgbm.h."""
+    _fields_ = [("op", C.c_int32), ("left_col", C.c_int32), ("right_col", C.c_int32), ("reserved", C.c_int32),
+                ("left_rank", C.POINTER(C.c_int32)), ("right_rank", C.POINTER(C.c_int32))]
+
+
+class RxSeg(C.Structure):
+    """``rgbm_rx_seg`` of include/rgbm.h."""
+    _fields_ = [("kind", C.c_int32), ("min", C.c_int32), ("max", C.c_int32), ("cls", C.c_uint32 * 4), ("const_off", C.c_int32),
+                ("const_len", C.c_int32)]
+
+
 PARAM_DEFAULTS = dict(objective=1, num_class=2, n_estimators=300, num_leaves=31, max_depth=7, max_bin=255,
                       min_data_in_leaf=20, min_data_in_bin=3, bagging_freq=0, seed=42, device_id=0, reserved=0,
                       learning_rate=0.01, lambda_l1=0.0, lambda_l2=0.0, min_gain_to_split=0.0,
@@ -67,11 +88,115 @@ def make_params(**kw):
     return RgbmParams(**d)
 
 
+# ---- the C signatures of include/rgbm.h (tests/test_abi_signatures.py holds this table to the header, type by type).
+# H: an opaque handle (rgbm_table*, rgbm_model*, a group) or any void*;  HP: where a handle is returned, or an array of handles.
+INT, I32, I64, F64, SIZE, H = C.c_int, C.c_int32, C.c_int64, C.c_double, C.c_size_t, C.c_void_p
+I32P, I64P, F64P, U8P, U64P, SIZEP, HP = (C.POINTER(t) for t in (I32, I64, F64, C.c_uint8, C.c_uint64, SIZE, H))
+I32PP, U64PP = C.POINTER(I32P), C.POINTER(U64P)                         # const int32_t* const*, const uint64_t* const*
+PARAMS, STATS, FITS, PREDS, SEGS = (C.POINTER(t) for t in (RgbmParams, RgbmTrainStats, RgbmFitSpec, DcPred, RxSeg))
+
+SIGNATURES = {        # name: (restype, argtypes), in the order of the header
+    "rgbm_device_count": (INT, ()),
+    "rgbm_release_cache": (INT, ()),
+    "rgbm_last_error": (C.c_char_p, ()),
+    "rgbm_version": (INT, ()),
+    "rgbm_train": (INT, (I32P, I64, I32, I32P, I32P, I32, F64P, F64P, F64P, PARAMS, HP, STATS)),
+    "rgbm_predict": (INT, (H, I32P, I64, I32, I32, F64P)),
+    "rgbm_repair_chain": (INT, (HP, I32, I32P, I32P, I32P, I32P, I32P, I32P, I64, I32, I32, I32P, F64P)),
+    "rgbm_table_create": (INT, (I32P, I64, I32, I32P, I32, HP)),
+    "rgbm_table_set_column_kind": (INT, (H, I32, I32)),
+    "rgbm_table_set_column_values": (INT, (H, I32, F64P, I32)),
+    "rgbm_host_alloc": (INT, (SIZE, HP)),
+    "rgbm_host_free": (None, (H,)),
+    "rgbm_table_free": (None, (H,)),
+    "rgbm_table_train": (INT, (H, I32, I32P, I32, F64P, F64P, PARAMS, HP, STATS)),
+    "rgbm_table_set_row_multiplicity": (INT, (H, U8P)),
+    "rgbm_table_read_row_multiplicity": (INT, (H, U8P)),
+    "rgbm_table_distinct_rows": (INT, (H, HP, I64P, I64P)),
+    "rgbm_table_distinct_view_info": (INT, (H, I32P, I64P, I64P)),
+    "rgbm_distinct_view_eligible": (INT, (I64, I32, PARAMS, I32, I64)),
+    "rgbm_table_train_batch": (INT, (FITS, I32, HP, I32P)),
+    "rgbm_table_train_batch_report": (INT, (I32P, I32)),
+    "rgbm_table_repair_chain": (INT, (H, HP, I32, I32P, I32P, I32P, I64, I64, I32P, F64P)),
+    "rgbm_table_read_column": (INT, (H, I32, I32P)),
+    "rgbm_table_detect_nulls": (INT, (H, I32P, I32, I64P)),
+    "rgbm_table_detect_cells": (INT, (H, I32P, I32, U8P, I32P, I32P, U64PP, I64P)),
+    "rgbm_table_detect_constraint": (INT, (H, I32P, I32, I32, I32P, I32, I64P, I64P)),
+    "rgbm_table_detect_dc": (INT, (H, PREDS, I32, I32P, I32, I64, I64P, I64P)),
+    "rgbm_table_detect_dc_scan": (INT, (H, PREDS, I32, I32P, I32, I64P, I64P)),
+    "rgbm_table_detect_row_bits": (INT, (H, I32P, I32, U64PP, I32P, I32, I64P, I64P)),
+    "rgbm_table_rows_of_cells": (INT, (H, I64P, I64, I64P)),
+    "rgbm_table_cells_fetch": (INT, (H, I64P, I32P)),
+    "rgbm_table_cellset_open": (INT, (H, I32P, I32)),
+    "rgbm_table_cellset_add": (INT, (H,)),
+    "rgbm_table_cellset_emit": (INT, (H, I64P, I64P)),
+    "rgbm_table_cells_fetch_codes": (INT, (H, I32P)),
+    "rgbm_table_cellset_close": (INT, (H,)),
+    "rgbm_table_cellset_add_cells": (INT, (H, I64P, I32P, I64)),
+    "rgbm_table_cellset_drop_weak": (INT, (H, I32, I32P, I32, I64P, U8P, F64, I64, I64P, I64P)),
+    "rgbm_table_cellset_null": (INT, (H, I64P)),
+    "rgbm_table_cellset_rows": (INT, (H, I64P)),
+    "rgbm_table_null_cells": (INT, (H, I64P, I32P, I64, I32P, I32)),
+    "rgbm_table_read_cells": (INT, (H, I64P, I32P, I64, I32P)),
+    "rgbm_table_write_cells": (INT, (H, I64P, I32P, I32P, I64)),
+    "rgbm_table_gather_rows": (INT, (H, I64P, I64, HP)),
+    "rgbm_table_concat": (INT, (HP, I32, HP)),
+    "rgbm_table_smoten": (INT, (H, I32, I32P, I32, I64P, I64, I32, I32P, I32, I64P, I64P, I64P, HP)),
+    "rgbm_table_count_codes": (INT, (H, I32, I64P, I64P)),
+    "rgbm_table_column_stats": (INT, (H, I32P, I32, I32PP, I32, I64P, I32P)),
+    "rgbm_table_fd_measures": (INT, (H, I32P, I32, I32P, I32, I64P, I64P, I64P, I64P)),
+    "rgbm_table_fd_measures_report": (INT, (H, I32P, I32)),
+    "rgbm_table_recode": (INT, (H, I32PP, I32P, HP, I64P)),
+    "rgbm_table_recode_report": (INT, (H, I32P, I32)),
+    "rgbm_table_create_dict": (INT, (I32P, I64, I32, I32PP, I32P, I32, HP)),
+    "rgbm_table_repair_pmf": (INT, (H, H, I32, I32P, I32, I32, F64, I32P, I64, I64P, I64P, I32P, F64P, F64P)),
+    "rgbm_table_repair_pmf_weighted": (INT, (H, H, I32, I32P, I32, I32, F64, I32P, I32P, F64P, I64, F64, I32, I64, I64P, I64P, I32P, F64P,
+                                             F64P, F64P)),
+    "rgbm_edit_distance": (INT, (I32, I32P, I64P, I64, I32P, I64P, I64, I32P)),
+    "rgbm_table_pair_counts": (INT, (H, I32P, I32, I32PP, I32P, I64P)),
+    "rgbm_table_pair_counts_report": (INT, (H, I64P, I32P, I32)),
+    "rgbm_table_cell_domains": (INT, (H, I32, I64P, I64, I32P, I32, I64P, U8P, F64, I64, U8P, I32P, F64P, F64P)),
+    "rgbm_table_fd_map": (INT, (H, I32, I32, I32P)),
+    "rgbm_table_rule_fill": (INT, (H, I32, I32, I32P, I32, I64, I64, I32P)),
+    "rgbm_nearest_values": (INT, (I32, I32P, I64P, I64, I32P, I64P, I64, F64P, F64, I32P)),
+    "rgbm_regex_structure": (INT, (I32, SEGS, I32, I32, I32P, I32, I32P, I64P, I64, U8P, I64P, I32P, I64P)),
+    "rgbm_lof_1d": (INT, (I32, F64P, I64P, I32, I32, F64, F64P, U64P, I64P)),
+    "rgbm_table_kmeans_assign": (INT, (H, I32P, I32, I64P, I32, F64P, I64, F64P, I32, I64P, I64P, I64P)),
+    "rgbm_table_kmeans_bisect": (INT, (H, I32P, I32, I64P, I64, I32P, I32, I32, I32P, F64P, F64P, I32, I64P, I64P, I64P)),
+    "rgbm_table_kmeans_read": (INT, (H, I32P)),
+    "rgbm_table_shape": (INT, (H, I64P, I32P, I32P)),
+    "rgbm_comm_unique_id": (INT, (H,)),
+    "rgbm_comm_init": (INT, (H, I32, I32, I32)),
+    "rgbm_comm_finalize": (INT, ()),
+    "rgbm_comm_info": (INT, (I32P,)),
+    "rgbm_comm_count": (INT, (I32P,)),
+    "rgbm_comm_all_gather_sizes": (INT, (I64P, I32, I64P)),
+    "rgbm_comm_all_gather_bytes": (INT, (H, I64, I64, H)),
+    "rgbm_table_repair_chain_gather": (INT, (H, HP, I32, I32P, I32P, I32P, I64, I64, I64, I32P, F64P)),
+    "rgbm_comm_gather_stats": (INT, (I64P,)),
+    "rgbm_local_group_create": (INT, (I32, I32, HP)),
+    "rgbm_local_group_free": (None, (H,)),
+    "rgbm_comm_init_local": (INT, (H, I32)),
+    "rgbm_fusion_create": (INT, (I32, HP)),
+    "rgbm_fusion_join": (INT, (H, I32)),
+    "rgbm_fusion_leave": (INT, (I32,)),
+    "rgbm_fusion_info": (INT, (H, I64P)),
+    "rgbm_fusion_free": (INT, (H,)),
+    "rgbm_model_save": (INT, (H, H, SIZEP)),
+    "rgbm_model_load": (INT, (H, SIZE, HP)),
+    "rgbm_model_free": (None, (H,)),
+    "rgbm_model_info": (INT, (H, I32P)),
+    "rgbm_model_predict_form": (INT, (H, I32P)),
+    "rgbm_level_pass_plan": (INT, (I32P, I32, I64, I32, I32, I32, F64P, I32, I32P)),
+    "rgbm_model_importance": (INT, (H, I32, F64P)),
+}
+EXPORTED_SYMBOLS = list(SIGNATURES)
+
 _lib = None
 
 
 def lib():
-    """Load librepairgbm.so (fails loudly when it has not been built)."""
+    """Load librepairgbm.so (fails loudly when it has not been built) and give every entry point its signature."""
     global _lib
     if _lib is None:
         path = os.path.abspath(os.environ.get("RGBM_LIB_PATH") or LIB_PATH)   # RGBM_LIB_PATH: A/B runs of differently built libraries
@@ -79,61 +204,60 @@ def lib():
             raise RepairGbmError("librepairgbm.so is not built (%s); run `python __graft_entry__.py` or `make -C "
                                  "spark-data-repair-plugin_amd/csrc`" % path)
         l = C.CDLL(path)
-        l.rgbm_last_error.restype = C.c_char_p
-        for name in ("rgbm_device_count", "rgbm_version", "rgbm_release_cache", "rgbm_train", "rgbm_predict", "rgbm_repair_chain",
-                     "rgbm_table_create", "rgbm_table_train", "rgbm_table_train_batch", "rgbm_table_train_batch_report", "rgbm_table_repair_chain",
-                     "rgbm_table_read_column", "rgbm_model_save", "rgbm_model_load", "rgbm_model_info", "rgbm_model_importance", "rgbm_model_predict_form",
-                     "rgbm_comm_unique_id", "rgbm_comm_init", "rgbm_comm_finalize", "rgbm_comm_info", "rgbm_comm_count",
-                     "rgbm_local_group_create", "rgbm_comm_init_local",
-                     "rgbm_table_detect_nulls", "rgbm_table_detect_constraint", "rgbm_table_rows_of_cells", "rgbm_table_cells_fetch",
-                     "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict",
-                     "rgbm_table_shape", "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_repair_pmf_weighted",
-                     "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains", "rgbm_table_fd_map", "rgbm_table_rule_fill",
-                     "rgbm_nearest_values", "rgbm_table_detect_cells", "rgbm_table_distinct_rows",
-                     "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_dc_scan", "rgbm_table_detect_row_bits",
-                     "rgbm_table_kmeans_assign", "rgbm_table_kmeans_read", "rgbm_lof_1d", "rgbm_table_column_stats",
-                     "rgbm_table_smoten", "rgbm_table_concat", "rgbm_regex_structure"):
-            getattr(l, name).restype = C.c_int
-        for name in ("rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible", "rgbm_level_pass_plan", "rgbm_table_kmeans_bisect",
-                     "rgbm_table_pair_counts_report", "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit",
-                     "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close", "rgbm_table_fd_measures", "rgbm_table_fd_measures_report",
-                     "rgbm_table_cellset_add_cells", "rgbm_table_cellset_drop_weak", "rgbm_table_cellset_null", "rgbm_table_cellset_rows",
-                     "rgbm_table_recode", "rgbm_table_recode_report"):
-            if hasattr(l, name):                  # (an older build under RGBM_LIB_PATH has no distinct-row view / no plan entry / no bisect pass / no count report / no cell set)
-                getattr(l, name).restype = C.c_int
-        l.rgbm_local_group_free.restype = None
-        l.rgbm_table_free.restype = None
-        l.rgbm_model_free.restype = None
-        l.rgbm_host_free.restype = None
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(l, name, None)           # (an older build under RGBM_LIB_PATH lacks the newer entries: `_call` names the one that is asked for)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = l
     return _lib
 
 
-EXPORTED_SYMBOLS = [
-    "rgbm_device_count", "rgbm_last_error", "rgbm_version", "rgbm_release_cache", "rgbm_train", "rgbm_predict", "rgbm_repair_chain",
-    "rgbm_table_create", "rgbm_table_free", "rgbm_table_train", "rgbm_table_train_batch", "rgbm_table_repair_chain", "rgbm_table_read_column",
-    "rgbm_model_save", "rgbm_model_load", "rgbm_model_free", "rgbm_model_info", "rgbm_model_importance",
-    "rgbm_comm_unique_id", "rgbm_comm_init", "rgbm_comm_finalize", "rgbm_comm_info", "rgbm_comm_count",
-    "rgbm_local_group_create", "rgbm_local_group_free", "rgbm_comm_init_local",
-    "rgbm_comm_all_gather_sizes", "rgbm_comm_all_gather_bytes", "rgbm_table_repair_chain_gather", "rgbm_comm_gather_stats",
-    "rgbm_fusion_create", "rgbm_fusion_join", "rgbm_fusion_leave", "rgbm_fusion_info", "rgbm_fusion_free",
-    "rgbm_table_detect_nulls", "rgbm_table_detect_constraint", "rgbm_table_rows_of_cells", "rgbm_table_cells_fetch",
-    "rgbm_table_null_cells", "rgbm_table_gather_rows", "rgbm_table_count_codes", "rgbm_table_create_dict", "rgbm_table_shape",
-    "rgbm_table_repair_pmf", "rgbm_table_read_cells", "rgbm_table_write_cells", "rgbm_host_alloc", "rgbm_host_free",
-    "rgbm_table_set_column_values", "rgbm_table_set_column_kind", "rgbm_table_set_row_multiplicity",
-    "rgbm_table_repair_pmf_weighted", "rgbm_edit_distance", "rgbm_table_pair_counts", "rgbm_table_cell_domains",
-    "rgbm_table_fd_map", "rgbm_table_rule_fill", "rgbm_nearest_values", "rgbm_table_detect_cells",
-    "rgbm_table_distinct_rows", "rgbm_table_read_row_multiplicity", "rgbm_table_detect_dc", "rgbm_table_detect_row_bits", "rgbm_model_predict_form",
-    "rgbm_table_kmeans_assign", "rgbm_table_kmeans_bisect", "rgbm_table_kmeans_read", "rgbm_table_distinct_view_info", "rgbm_distinct_view_eligible",
-    "rgbm_table_column_stats", "rgbm_level_pass_plan", "rgbm_table_train_batch_report", "rgbm_table_smoten", "rgbm_table_concat",
-    "rgbm_table_pair_counts_report", "rgbm_regex_structure", "rgbm_table_detect_dc_scan",
-    "rgbm_table_cellset_open", "rgbm_table_cellset_add", "rgbm_table_cellset_emit", "rgbm_table_cells_fetch_codes", "rgbm_table_cellset_close",
-    "rgbm_table_fd_measures", "rgbm_table_fd_measures_report",
-    "rgbm_table_cellset_add_cells", "rgbm_table_cellset_drop_weak", "rgbm_table_cellset_null", "rgbm_table_cellset_rows",
-    "rgbm_table_recode", "rgbm_table_recode_report",
-]
-# exported as well; kept apart because the list above is held to a scan of include/rgbm.h for names of letters and underscores only
-EXPORTED_SYMBOLS_WITH_DIGITS = ["rgbm_lof_1d"]
+def _check(rc, what):
+    if rc != 0:
+        err = RepairGbmError("%s failed (%d): %s" % (what, rc, lib().rgbm_last_error().decode("utf-8", "replace")))
+        err.code = rc                      # the RGBM_ERR_* value of include/rgbm.h
+        raise err
+
+
+def _call(name, *args):
+    """Call the entry point ``name`` of ``SIGNATURES`` and raise as `_check` does when it returns an error code.  A numpy array among
+    ``args`` goes through `_p` with the element type the table declares for its place; everything else is ctypes' to convert."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RepairGbmError("%s is not exported by %s" % (name, lib()._name))
+    args = list(args)
+    for i, a in enumerate(args):
+        if isinstance(a, np.ndarray):
+            args[i] = _p(a, fn.argtypes[i]._type_)
+    _check(fn(*args), name)
+
+
+_DTYPE = {t: np.dtype(t) for t in (C.c_int32, C.c_int64, C.c_double, C.c_uint8, C.c_uint64)}      # (np.dtype(ctype) costs microseconds per call)
+
+
+def _p(a, t):
+    """The array ``a`` as a ``POINTER(t)`` argument (None: NULL).  TypeError for an array of another dtype or one that is not C-contiguous:
+    the library would read other numbers than the caller's.  A zero-length array has no address of its own; where NULL means
+    something else to the library (a LUT column: identity) the caller passes one element in its place."""
+    if a is None:
+        return None
+    if a.dtype != (_DTYPE.get(t) or np.dtype(t)) or not a.flags.c_contiguous:
+        raise TypeError("a C-contiguous %s array expected, not %s%s" % (np.dtype(t), a.dtype, "" if a.flags.c_contiguous else " (not contiguous)"))
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, np.int32)
+
+
+def _f64(a):
+    return None if a is None else np.ascontiguousarray(a, np.float64)
+
+
+def _flat(a, dtype):
+    """``a`` as a C-contiguous 1-d array of ``dtype`` (a copy only where one is needed)."""
+    return np.ascontiguousarray(a, dtype).reshape(-1)
+
 
 COMM_ID_BYTES = 128
 
@@ -141,23 +265,23 @@ COMM_ID_BYTES = 128
 def comm_unique_id():
     """128 opaque bytes (an ncclUniqueId) created on one rank; every rank passes them to ``comm_init``."""
     buf = (C.c_ubyte * COMM_ID_BYTES)()
-    _check(lib().rgbm_comm_unique_id(buf), "rgbm_comm_unique_id")
+    _call("rgbm_comm_unique_id", buf)
     return bytes(buf)
 
 
 def comm_init(uid, rank, nranks, device_id=0):
     """RCCL communicator of the calling thread for row-sharded training (include/rgbm.h)."""
     buf = (C.c_ubyte * COMM_ID_BYTES).from_buffer_copy(bytes(uid))
-    _check(lib().rgbm_comm_init(buf, C.c_int32(rank), C.c_int32(nranks), C.c_int32(device_id)), "rgbm_comm_init")
+    _call("rgbm_comm_init", buf, rank, nranks, device_id)
 
 
 def comm_finalize():
-    _check(lib().rgbm_comm_finalize(), "rgbm_comm_finalize")
+    _call("rgbm_comm_finalize")
 
 
 def comm_info():
     a = np.zeros(3, np.int32)
-    _check(lib().rgbm_comm_info(_p(a, C.c_int32)), "rgbm_comm_info")
+    _call("rgbm_comm_info", a)
     return dict(kind=int(a[0]), rank=int(a[1]), nranks=int(a[2]))
 
 
@@ -217,15 +341,15 @@ def needed_built_rows(blob, max_depth):
 def comm_count():
     """Ranks the calling thread's communicator really spans (ncclCommCount); 1 without a communicator."""
     n = C.c_int32(0)
-    _check(lib().rgbm_comm_count(C.byref(n)), "rgbm_comm_count")
+    _call("rgbm_comm_count", C.byref(n))
     return int(n.value)
 
 
 def comm_all_gather_sizes(values):
     """Every rank of the calling thread's communicator contributes the int64 vector `values`; returns [nranks][len(values)]."""
-    v = np.ascontiguousarray(values, np.int64).reshape(-1)
+    v = _flat(values, np.int64)
     out = np.zeros((max(1, comm_info()["nranks"]), v.size), np.int64)
-    _check(lib().rgbm_comm_all_gather_sizes(_p(v, C.c_int64), C.c_int32(v.size), _p(out, C.c_int64)), "rgbm_comm_all_gather_sizes")
+    _call("rgbm_comm_all_gather_sizes", v, v.size, out)
     return out
 
 
@@ -236,14 +360,13 @@ def comm_all_gather_bytes(payload):
     sizes = comm_all_gather_sizes([mine.size])[:, 0]
     block = int(max(int(sizes.max()), 1))
     recv = np.zeros((len(sizes), block), np.uint8)
-    _check(lib().rgbm_comm_all_gather_bytes(_p(mine, C.c_uint8) if mine.size else None, C.c_int64(mine.size), C.c_int64(block), _p(recv, C.c_uint8)),
-           "rgbm_comm_all_gather_bytes")
+    _call("rgbm_comm_all_gather_bytes", _p(mine, C.c_uint8) if mine.size else None, mine.size, block, _p(recv, C.c_uint8))
     return [recv[r, :int(sizes[r])].copy() for r in range(len(sizes))]
 
 
 def comm_gather_stats():
     a = np.zeros(3, np.int64)
-    _check(lib().rgbm_comm_gather_stats(_p(a, C.c_int64)), "rgbm_comm_gather_stats")
+    _call("rgbm_comm_gather_stats", a)
     return dict(bytes=int(a[0]), seconds=float(a[1]) * 1e-9, collectives=int(a[2]))
 
 
@@ -254,7 +377,7 @@ class FusionGroup:
 
     def __init__(self, n_members):
         self.h = C.c_void_p()
-        _check(lib().rgbm_fusion_create(C.c_int32(n_members), C.byref(self.h)), "rgbm_fusion_create")
+        _call("rgbm_fusion_create", n_members, C.byref(self.h))
         self.n_members = n_members
 
     class _Member:
@@ -262,11 +385,11 @@ class FusionGroup:
             self.group, self.j = group, j
 
         def __enter__(self):
-            _check(lib().rgbm_fusion_join(self.group.h, C.c_int32(self.j)), "rgbm_fusion_join")
+            _call("rgbm_fusion_join", self.group.h, self.j)
             return self
 
         def __exit__(self, et, ev, tb):
-            lib().rgbm_fusion_leave(C.c_int32(0 if et is None else 1))
+            lib().rgbm_fusion_leave(0 if et is None else 1)
             return False
 
     def member(self, j):
@@ -274,13 +397,13 @@ class FusionGroup:
 
     def info(self):
         a = np.zeros(4, np.int64)
-        _check(lib().rgbm_fusion_info(self.h, _p(a, C.c_int64)), "rgbm_fusion_info")
+        _call("rgbm_fusion_info", self.h, a)
         return dict(collectives=int(a[0]), parts=int(a[1]), members_in=int(a[2]), broken=bool(a[3]))
 
     def close(self):
         """Hands the communicator back to the calling thread (call it on the thread that created the group, after every member left)."""
         if self.h:
-            _check(lib().rgbm_fusion_free(self.h), "rgbm_fusion_free")
+            _call("rgbm_fusion_free", self.h)
             self.h = C.c_void_p()
 
 
@@ -289,24 +412,17 @@ class LocalGroup:
 
     def __init__(self, nranks, device_id=0):
         self.h = C.c_void_p()
-        _check(lib().rgbm_local_group_create(C.c_int32(nranks), C.c_int32(device_id), C.byref(self.h)), "rgbm_local_group_create")
+        _call("rgbm_local_group_create", nranks, device_id, C.byref(self.h))
         self.nranks = nranks
 
     def join(self, rank):
         """Call from the thread that plays ``rank``; pair with ``comm_finalize()`` in the same thread."""
-        _check(lib().rgbm_comm_init_local(self.h, C.c_int32(rank)), "rgbm_comm_init_local")
+        _call("rgbm_comm_init_local", self.h, rank)
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         if h and _lib is not None:
             _lib.rgbm_local_group_free(h)
-
-
-def _check(rc, what):
-    if rc != 0:
-        err = RepairGbmError("%s failed (%d): %s" % (what, rc, lib().rgbm_last_error().decode("utf-8", "replace")))
-        err.code = rc                      # the RGBM_ERR_* value of include/rgbm.h
-        raise err
 
 
 def device_count():
@@ -315,19 +431,7 @@ def device_count():
 
 def release_cache():
     """Return the device blocks parked in the library's caching pool to the driver (include/rgbm.h)."""
-    _check(lib().rgbm_release_cache(), "rgbm_release_cache")
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, np.int32)
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, np.float64)
+    _call("rgbm_release_cache")
 
 
 class Model:
@@ -343,33 +447,33 @@ class Model:
 
     def info(self):
         a = np.zeros(5, np.int32)
-        _check(lib().rgbm_model_info(self.h, _p(a, C.c_int32)), "rgbm_model_info")
+        _call("rgbm_model_info", self.h, a)
         return dict(objective=int(a[0]), num_class=int(a[1]), K=int(a[2]), n_iter=int(a[3]), F=int(a[4]))
 
     def save(self):
         n = C.c_size_t(0)
-        _check(lib().rgbm_model_save(self.h, None, C.byref(n)), "rgbm_model_save")
+        _call("rgbm_model_save", self.h, None, C.byref(n))
         buf = bytearray(max(n.value, 1))
-        _check(lib().rgbm_model_save(self.h, (C.c_char * len(buf)).from_buffer(buf), C.byref(n)), "rgbm_model_save")
+        _call("rgbm_model_save", self.h, (C.c_char * len(buf)).from_buffer(buf), C.byref(n))
         return bytes(buf[:n.value]) if n.value != len(buf) else bytes(buf)
 
     @staticmethod
     def load(b):
         h = C.c_void_p()
         arr = np.frombuffer(b, np.uint8)
-        _check(lib().rgbm_model_load(arr.ctypes.data_as(C.c_void_p), C.c_size_t(len(b)), C.byref(h)), "rgbm_model_load")
+        _call("rgbm_model_load", arr.ctypes.data_as(C.c_void_p), len(b), C.byref(h))
         return Model(h)
 
     def importance(self, kind="gain"):
         out = np.zeros(self.info()["F"], np.float64)
-        _check(lib().rgbm_model_importance(self.h, C.c_int32(0 if kind == "split" else 1), _p(out, C.c_double)), "rgbm_model_importance")
+        _call("rgbm_model_importance", self.h, 0 if kind == "split" else 1, out)
         return out
 
     def predict_form(self):
         """The kernel the predictor runs for this model (rgbm_model_predict_form; needs no device): form "fixed" | "dynamic" | "walk",
         MW mask words per table entry, TW padded mask words per tree (fixed form), tb trees per LDS stage, lds bytes per workgroup."""
         a = np.zeros(5, np.int32)
-        _check(lib().rgbm_model_predict_form(self.h, _p(a, C.c_int32)), "rgbm_model_predict_form")
+        _call("rgbm_model_predict_form", self.h, a)
         return dict(form=("fixed", "dynamic", "walk")[int(a[0])], MW=int(a[1]), TW=int(a[2]), tb=int(a[3]), lds=int(a[4]))
 
     def predict(self, X, device_id=0):
@@ -379,7 +483,7 @@ class Model:
         inf = self.info()
         ncol = 1 if inf["objective"] == 2 else inf["num_class"]
         out = np.zeros((n, ncol), np.float64)
-        _check(lib().rgbm_predict(self.h, _p(X, C.c_int32), C.c_int64(n), C.c_int32(F), C.c_int32(device_id), _p(out, C.c_double)), "rgbm_predict")
+        _call("rgbm_predict", self.h, X, n, F, device_id, out)
         return out
 
 
@@ -392,17 +496,9 @@ def train(X, n_codes, y_code, n_y_codes, y_value=None, class_weight=None, sample
     p = make_params(**params)
     h = C.c_void_p()
     st = RgbmTrainStats()
-    _check(lib().rgbm_train(_p(X, C.c_int32), C.c_int64(N), C.c_int32(F), _p(n_codes, C.c_int32), _p(y_code, C.c_int32),
-                            C.c_int32(n_y_codes), _p(yv, C.c_double), _p(cw, C.c_double), _p(sw, C.c_double),
-                            C.byref(p), C.byref(h), C.byref(st) if want_stats else None), "rgbm_train")
+    _call("rgbm_train", X, N, F, n_codes, y_code, n_y_codes, yv, cw, sw, C.byref(p), C.byref(h), C.byref(st) if want_stats else None)
     m = Model(h)
     return (m, st.as_dict()) if want_stats else m
-
-
-class RgbmFitSpec(C.Structure):
-    _fields_ = [("table", C.c_void_p), ("target_col", C.c_int32), ("n_features", C.c_int32), ("feat_cols", C.POINTER(C.c_int32)),
-                ("y_value", C.POINTER(C.c_double)), ("class_weight", C.POINTER(C.c_double)), ("params", C.POINTER(RgbmParams)),
-                ("valid_table", C.c_void_p), ("valid_label_out", C.POINTER(C.c_int32)), ("valid_value_out", C.POINTER(C.c_double))]
 
 
 def level_pass_plan(nbins, rows, K, max_depth=7, with_mult=False):
@@ -412,8 +508,7 @@ def level_pass_plan(nbins, rows, K, max_depth=7, with_mult=False):
     nb = _i32(nbins)
     out = np.zeros(6 + 12 * 4096, np.float64)      # (<= 6 levels x 16 chunks x 32 windows of built slots)
     n = C.c_int32(0)
-    _check(lib().rgbm_level_pass_plan(_p(nb, C.c_int32), C.c_int32(len(nb)), C.c_int64(rows), C.c_int32(K), C.c_int32(max_depth), C.c_int32(1 if with_mult else 0),
-                                      _p(out, C.c_double), C.c_int32(len(out)), C.byref(n)), "rgbm_level_pass_plan")
+    _call("rgbm_level_pass_plan", nb, len(nb), rows, K, max_depth, 1 if with_mult else 0, out, len(out), C.byref(n))
     keys = ("level", "ch", "slot0", "nslots", "route", "T", "G", "gx", "acc2", "rot")
     launches = []
     for i in range(int(out[2])):
@@ -425,7 +520,7 @@ def level_pass_plan(nbins, rows, K, max_depth=7, with_mult=False):
 def distinct_view_eligible(rows, f, table_has_mult=False, min_rows=0, **params):
     """Whether a Table.train of this shape MAY use the table's distinct-row view (rgbm_distinct_view_eligible; no device needed)."""
     p = make_params(**params)
-    r = lib().rgbm_distinct_view_eligible(C.c_int64(rows), C.c_int32(f), C.byref(p), C.c_int32(1 if table_has_mult else 0), C.c_int64(min_rows))
+    r = lib().rgbm_distinct_view_eligible(rows, f, C.byref(p), 1 if table_has_mult else 0, min_rows)
     if r < 0:
         _check(r, "rgbm_distinct_view_eligible")
     return bool(r)
@@ -469,7 +564,7 @@ def train_batch(fits):
         specs[i].params = C.pointer(p)
     handles = (C.c_void_p * n)()
     status = np.zeros(n, np.int32)
-    _check(lib().rgbm_table_train_batch(specs, C.c_int32(n), handles, _p(status, C.c_int32)), "rgbm_table_train_batch")
+    _call("rgbm_table_train_batch", specs, n, handles, status)
     out = []
     # rgbm_last_error() is ONE thread-local string: it describes the LAST failing fit of the batch; the others report their status code only
     failing = [i for i in range(n) if status[i] != 0]
@@ -492,7 +587,7 @@ def train_batch_report(n):
     dict(route, scan_waves, nchunk, lds_bytes) -- route 0 failed before a route was chosen, 1 fused kernels, 2 single-fit trainer (not
     eligible), 3 single-fit trainer (one eligible fit in the batch), 4 single-fit trainer (LDS); scan_waves 0 = one wave per feature."""
     a = np.zeros((max(int(n), 1), 4), np.int32)
-    _check(lib().rgbm_table_train_batch_report(_p(a, C.c_int32), C.c_int32(n)), "rgbm_table_train_batch_report")
+    _call("rgbm_table_train_batch_report", a, n)
     return [dict(route=int(r[0]), scan_waves=int(r[1]), nchunk=int(r[2]), lds_bytes=int(r[3])) for r in a[:int(n)]]
 
 
@@ -500,7 +595,7 @@ def pair_counts_limits():
     """The two limits that close a group of ``Table.pair_counts`` (rgbm_table_pair_counts_report without a table; needs no device):
     dict(lds_cells = 32-bit counters of a group, max_cols = distinct columns of a group)."""
     head = np.zeros(6, np.int64)
-    _check(lib().rgbm_table_pair_counts_report(None, _p(head, C.c_int64), None, C.c_int32(0)), "rgbm_table_pair_counts_report")
+    _call("rgbm_table_pair_counts_report", None, head, None, 0)
     return dict(lds_cells=int(head[4]), max_cols=int(head[5]))
 
 
@@ -508,7 +603,7 @@ def fd_measures_limits():
     """The two limits of ``Table.fd_measures`` (rgbm_table_fd_measures_report without a table; needs no device): dict(lds_cells = 32-bit
     counters of a dense joint table on the LDS route, max_lhs = columns of a left-hand side)."""
     out = np.zeros(2, np.int32)
-    _check(lib().rgbm_table_fd_measures_report(None, _p(out, C.c_int32), C.c_int32(0)), "rgbm_table_fd_measures_report")
+    _call("rgbm_table_fd_measures_report", None, out, 0)
     return dict(lds_cells=int(out[0]), max_lhs=int(out[1]))
 
 
@@ -516,7 +611,7 @@ def recode_limits():
     """The limit of ``Table.recode`` (rgbm_table_recode_report without a table; needs no device): dict(lds_codes = the largest LUT that a
     workgroup stages in LDS)."""
     out = np.zeros(1, np.int32)
-    _check(lib().rgbm_table_recode_report(None, _p(out, C.c_int32), C.c_int32(0)), "rgbm_table_recode_report")
+    _call("rgbm_table_recode_report", None, out, 0)
     return dict(lds_codes=int(out[0]))
 
 
@@ -545,9 +640,7 @@ def repair_chain(models, target_col, feat_cols, class_codes, table, device_id=0)
     tc = _i32(target_col)
     lab = np.zeros((T, n), np.int32)
     prob = np.zeros((T, n), np.float64)
-    _check(lib().rgbm_repair_chain(arr, C.c_int32(T), _p(tc, C.c_int32), _p(fc, C.c_int32), _p(fo, C.c_int32), _p(cc, C.c_int32),
-                                   _p(co, C.c_int32), _p(table, C.c_int32), C.c_int64(n), C.c_int32(Cc), C.c_int32(device_id),
-                                   _p(lab, C.c_int32), _p(prob, C.c_double)), "rgbm_repair_chain")
+    _call("rgbm_repair_chain", arr, T, tc, fc, fo, cc, co, table, n, Cc, device_id, lab, prob)
     return lab, prob
 
 
@@ -556,7 +649,7 @@ class _PinnedBlock:
 
     def __init__(self, nbytes):
         p = C.c_void_p()
-        _check(lib().rgbm_host_alloc(C.c_size_t(nbytes), C.byref(p)), "rgbm_host_alloc")
+        _call("rgbm_host_alloc", nbytes, C.byref(p))
         self.p, self.nbytes = p, nbytes
         self.__array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (p.value, False), "version": 3}
 
@@ -589,9 +682,7 @@ def edit_distance(a, b, device_id=0):
     a_cp, a_off = pack_code_points(a)
     b_cp, b_off = pack_code_points(b)
     out = np.zeros((len(a_off) - 1, len(b_off) - 1), np.int32)
-    _check(lib().rgbm_edit_distance(C.c_int32(device_id), _p(a_cp, C.c_int32), _p(a_off, C.c_int64), C.c_int64(len(a_off) - 1),
-                                    _p(b_cp, C.c_int32), _p(b_off, C.c_int64), C.c_int64(len(b_off) - 1), _p(out, C.c_int32)),
-           "rgbm_edit_distance")
+    _call("rgbm_edit_distance", device_id, a_cp, a_off, len(a_off) - 1, b_cp, b_off, len(b_off) - 1, out)
     return out
 
 
@@ -604,15 +695,12 @@ def nearest_values(a=None, b=None, cost=None, threshold=0.0, device_id=0):
         if m.ndim != 2:
             raise ValueError("cost must be a [n_a][n_b] matrix")
         out = np.full(m.shape[0], -1, np.int32)
-        _check(lib().rgbm_nearest_values(C.c_int32(device_id), None, None, C.c_int64(m.shape[0]), None, None, C.c_int64(m.shape[1]),
-                                         _p(m, C.c_double), C.c_double(threshold), _p(out, C.c_int32)), "rgbm_nearest_values")
+        _call("rgbm_nearest_values", device_id, None, None, m.shape[0], None, None, m.shape[1], m, threshold, out)
         return out
     a_cp, a_off = pack_code_points(a)
     b_cp, b_off = pack_code_points(b)
     out = np.full(len(a_off) - 1, -1, np.int32)
-    _check(lib().rgbm_nearest_values(C.c_int32(device_id), _p(a_cp, C.c_int32), _p(a_off, C.c_int64), C.c_int64(len(a_off) - 1),
-                                     _p(b_cp, C.c_int32), _p(b_off, C.c_int64), C.c_int64(len(b_off) - 1), None, C.c_double(threshold),
-                                     _p(out, C.c_int32)), "rgbm_nearest_values")
+    _call("rgbm_nearest_values", device_id, a_cp, a_off, len(a_off) - 1, b_cp, b_off, len(b_off) - 1, None, threshold, out)
     return out
 
 
@@ -621,22 +709,14 @@ def lof_1d(values, counts, k=20, threshold=1.5, want_scores=True, device_id=0):
     repair.lof_codes.lof_codes): ``values`` float64 [d] ascending, ``counts`` rows per entry -> (scores float64 [d] or None,
     flag words uint64 [ceil(d / 64)], n_ties, n_near)."""
     v = _f64(values).reshape(-1)
-    m = np.ascontiguousarray(counts, np.int64).reshape(-1)
+    m = _flat(counts, np.int64)
     if len(v) != len(m):
         raise ValueError("values and counts must have one length")
     score = np.zeros(len(v), np.float64) if want_scores else None
     bits = np.zeros((len(v) + 63) // 64, np.uint64)
     info = np.zeros(2, np.int64)
-    _check(lib().rgbm_lof_1d(C.c_int32(device_id), _p(v, C.c_double), _p(m, C.c_int64), C.c_int32(len(v)), C.c_int32(int(k)),
-                             C.c_double(threshold), _p(score, C.c_double) if want_scores else None, _p(bits, C.c_uint64),
-                             _p(info, C.c_int64)), "rgbm_lof_1d")
+    _call("rgbm_lof_1d", device_id, v, m, len(v), int(k), threshold, score, bits, info)
     return score, bits, int(info[0]), int(info[1])
-
-
-class RxSeg(C.Structure):
-    """``rgbm_rx_seg`` of include/rgbm.h."""
-    _fields_ = [("kind", C.c_int32), ("min", C.c_int32), ("max", C.c_int32), ("cls", C.c_uint32 * 4), ("const_off", C.c_int32),
-                ("const_len", C.c_int32)]
 
 
 RX_WORD_MAX_CP = 63           # the longest string one lane matches
@@ -649,17 +729,13 @@ def regex_structure_raw(segs, anchors, const_cp, cp, off, device_id=0):
     arr = (RxSeg * max(len(segs), 1))()
     for i, (kind, mn, mx, cls, c_off, c_len) in enumerate(segs):
         arr[i] = RxSeg(int(kind), int(mn), int(mx), (C.c_uint32 * 4)(*[int(w) for w in cls]), int(c_off), int(c_len))
-    const_cp = np.ascontiguousarray(const_cp, np.int32).reshape(-1)
-    cp = np.ascontiguousarray(cp, np.int32).reshape(-1)
-    off = np.ascontiguousarray(off, np.int64).reshape(-1)
+    const_cp, cp, off = _flat(const_cp, np.int32), _flat(cp, np.int32), _flat(off, np.int64)
     n = len(off) - 1
     state = np.zeros(max(n, 0), np.uint8)
     out_off = np.zeros(max(n, 0) + 1, np.int64)
     out = np.zeros(max(int(off[-1]) + n * len(const_cp), 1) if n > 0 else 1, np.int32)
     info = np.zeros(4, np.int64)
-    _check(lib().rgbm_regex_structure(C.c_int32(device_id), arr, C.c_int32(len(segs)), C.c_int32(int(anchors)), _p(const_cp, C.c_int32),
-                                      C.c_int32(len(const_cp)), _p(cp, C.c_int32), _p(off, C.c_int64), C.c_int64(n), _p(state, C.c_uint8),
-                                      _p(out_off, C.c_int64), _p(out, C.c_int32), _p(info, C.c_int64)), "rgbm_regex_structure")
+    _call("rgbm_regex_structure", device_id, arr, len(segs), int(anchors), const_cp, len(const_cp), cp, off, n, state, out_off, out, info)
     return state, out_off, out[:int(out_off[-1])], info
 
 
@@ -678,12 +754,6 @@ def regex_structure(program, strings, device_id=0, want_info=False):
     return (res, info) if want_info else res
 
 
-class DcPred(C.Structure):
-    """``rgbm_dc_pred`` of include/rgbm.h."""
-    _fields_ = [("op", C.c_int32), ("left_col", C.c_int32), ("right_col", C.c_int32), ("reserved", C.c_int32),
-                ("left_rank", C.POINTER(C.c_int32)), ("right_rank", C.POINTER(C.c_int32))]
-
-
 class Table:
     """An int32 code table resident in HBM (``rgbm_table``)."""
 
@@ -693,8 +763,7 @@ class Table:
         self.n_codes = _i32(n_codes)
         self.device_id = device_id
         h = C.c_void_p()
-        _check(lib().rgbm_table_create(_p(codes, C.c_int32), C.c_int64(self.n), C.c_int32(self.c), _p(self.n_codes, C.c_int32),
-                                       C.c_int32(device_id), C.byref(h)), "rgbm_table_create")
+        _call("rgbm_table_create", codes, self.n, self.c, self.n_codes, device_id, C.byref(h))
         self.h = h
 
     @classmethod
@@ -703,10 +772,10 @@ class Table:
         t = cls.__new__(cls)
         t.h, t.device_id = handle, device_id
         n, c = C.c_int64(0), C.c_int32(0)
-        _check(lib().rgbm_table_shape(handle, C.byref(n), C.byref(c), None), "rgbm_table_shape")
+        _call("rgbm_table_shape", handle, C.byref(n), C.byref(c), None)
         t.n, t.c = int(n.value), int(c.value)
         t.n_codes = np.zeros(t.c, np.int32)
-        _check(lib().rgbm_table_shape(handle, None, None, _p(t.n_codes, C.c_int32)), "rgbm_table_shape")
+        _call("rgbm_table_shape", handle, None, None, t.n_codes)
         return t
 
     @classmethod
@@ -721,8 +790,7 @@ class Table:
         ptrs = (C.POINTER(C.c_int32) * c)(*[_p(m if len(m) else np.zeros(1, np.int32), C.c_int32) for m in maps])
         sizes = np.asarray([len(m) for m in maps], np.int32)
         h = C.c_void_p()
-        _check(lib().rgbm_table_create_dict(_p(idx, C.c_int32), C.c_int64(n), C.c_int32(c), ptrs, _p(sizes, C.c_int32), C.c_int32(device_id),
-                                            C.byref(h)), "rgbm_table_create_dict")
+        _call("rgbm_table_create_dict", idx, n, c, ptrs, sizes, device_id, C.byref(h))
         return cls._adopt(h, device_id)
 
     # ---- relational steps around the models (csrc/rgbm_prep.hip and the rgbm_<step>.hip sources beside it)
@@ -732,14 +800,14 @@ class Table:
         rows = np.zeros(n, np.int64)
         cols = np.zeros(n, np.int32) if want_cols else None
         if n:
-            _check(lib().rgbm_table_cells_fetch(self.h, _p(rows, C.c_int64), _p(cols, C.c_int32)), "rgbm_table_cells_fetch")
+            _call("rgbm_table_cells_fetch", self.h, rows, cols)
         return (rows, cols) if want_cols else rows
 
     def detect_nulls(self, cols, fetch=True):
         """NULL cells of ``cols`` as (rows, cols), ordered by position in ``cols`` then row (ErrorDetectorApi.scala:128-157)."""
-        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
+        cc = _flat(cols, np.int32)
         n = C.c_int64(0)
-        _check(lib().rgbm_table_detect_nulls(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), C.byref(n)), "rgbm_table_detect_nulls")
+        _call("rgbm_table_detect_nulls", self.h, cc, len(cc), C.byref(n))
         return self._fetch_cells(int(n.value), True, fetch)
 
     def detect_cells(self, cols, null_is_error, keep_lo, keep_hi, flag_bits=None, fetch=True):
@@ -747,10 +815,10 @@ class Table:
         regex / value-domain / outlier detectors) as (rows, cols), ordered by position in ``cols`` then row.  Per column j: NULL cells
         when ``null_is_error[j]``; codes outside [keep_lo[j], keep_hi[j]] unless keep_lo[j] > keep_hi[j]; codes whose bit is set in
         ``flag_bits[j]`` (uint64 [ceil(n_codes / 64)], or None)."""
-        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
+        cc = _flat(cols, np.int32)
         k = len(cc)
         ne = np.ascontiguousarray(np.asarray(null_is_error).reshape(-1) != 0, np.uint8)
-        lo, hi = _i32(np.asarray(keep_lo, np.int32).reshape(-1)), _i32(np.asarray(keep_hi, np.int32).reshape(-1))
+        lo, hi = _flat(keep_lo, np.int32), _flat(keep_hi, np.int32)
         fb = list(flag_bits) if flag_bits is not None else [None] * k
         if not (len(ne) == len(lo) == len(hi) == len(fb) == k):
             raise ValueError("detect_cells: one predicate per column")
@@ -758,25 +826,22 @@ class Table:
         for j in range(k):
             if fb[j] is None:
                 continue
-            w = np.ascontiguousarray(fb[j], np.uint64).reshape(-1)
+            w = _flat(fb[j], np.uint64)
             if 0 <= cc[j] < self.c and len(w) != (int(self.n_codes[cc[j]]) + 63) // 64:
                 raise ValueError("detect_cells: the bitset of column %d holds %d words, its %d codes need %d"
                                  % (cc[j], len(w), int(self.n_codes[cc[j]]), (int(self.n_codes[cc[j]]) + 63) // 64))
             keep.append(w)
-            ptrs[j] = w.ctypes.data_as(C.POINTER(C.c_uint64))
+            ptrs[j] = _p(w, C.c_uint64)
         n = C.c_int64(0)
-        _check(lib().rgbm_table_detect_cells(self.h, _p(cc, C.c_int32), C.c_int32(k), _p(ne, C.c_uint8), _p(lo, C.c_int32), _p(hi, C.c_int32),
-                                             ptrs, C.byref(n)), "rgbm_table_detect_cells")
+        _call("rgbm_table_detect_cells", self.h, cc, k, ne, lo, hi, ptrs, C.byref(n))
         return self._fetch_cells(int(n.value), True, fetch)
 
     def detect_constraint(self, eq_cols, iq_col, cell_cols=(), fetch=True):
         """Rows violating  EQ(eq_cols...) & IQ(iq_col)  (ErrorDetectorApi.scala:189-244).  Returns the ascending violating rows
         when ``cell_cols`` is empty, else the cells (rows, cols) = violating rows x cell_cols, column-major."""
-        eq = _i32(np.asarray(eq_cols, np.int32).reshape(-1))
-        cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
+        eq, cc = _flat(eq_cols, np.int32), _flat(cell_cols, np.int32)
         nr, nc = C.c_int64(0), C.c_int64(0)
-        _check(lib().rgbm_table_detect_constraint(self.h, _p(eq, C.c_int32), C.c_int32(len(eq)), C.c_int32(iq_col),
-                                                  _p(cc, C.c_int32), C.c_int32(len(cc)), C.byref(nr), C.byref(nc)), "rgbm_table_detect_constraint")
+        _call("rgbm_table_detect_constraint", self.h, eq, len(eq), iq_col, cc, len(cc), C.byref(nr), C.byref(nc))
         return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
     def _dc_preds(self, preds, who):
@@ -789,11 +854,11 @@ class Table:
             for name, col, r in (("left_rank", lc, lr), ("right_rank", rc, rr)):
                 if r is None:
                     continue
-                r = _i32(np.asarray(r, np.int32).reshape(-1))
+                r = _flat(r, np.int32)
                 if 0 <= int(col) < self.c and len(r) != int(self.n_codes[int(col)]):
                     raise ValueError("%s: the rank array of column %d holds %d entries, its dictionary %d" % (who, col, len(r), int(self.n_codes[int(col)])))
                 keep.append(r)
-                setattr(arr[k], name, r.ctypes.data_as(C.POINTER(C.c_int32)))
+                setattr(arr[k], name, _p(r, C.c_int32))
         return arr, keep
 
     def detect_dc(self, preds, cell_cols=(), max_pairs=0, fetch=True):
@@ -802,10 +867,9 @@ class Table:
         [n_codes[col]] arrays (an entry < 0 = the value has no number) or None.  ``max_pairs`` <= 0: the library default; a table
         whose EQ groups hold more pairs raises RepairGbmError with code -2.  Returns as ``detect_constraint`` does."""
         arr, keep = self._dc_preds(preds, "detect_dc")
-        cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
+        cc = _flat(cell_cols, np.int32)
         nr, nc = C.c_int64(0), C.c_int64(0)
-        _check(lib().rgbm_table_detect_dc(self.h, arr, C.c_int32(len(preds)), _p(cc, C.c_int32), C.c_int32(len(cc)), C.c_int64(int(max_pairs)),
-                                          C.byref(nr), C.byref(nc)), "rgbm_table_detect_dc")
+        _call("rgbm_table_detect_dc", self.h, arr, len(preds), cc, len(cc), int(max_pairs), C.byref(nr), C.byref(nc))
         return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
     def detect_dc_scan(self, preds, cell_cols=(), fetch=True):
@@ -813,51 +877,49 @@ class Table:
         predicates plus one or two LT / GT and no IQ (`repair.dc_codes.scan_eligible`; anything else raises RepairGbmError with code -2).
         No pair is evaluated, so there is no ``max_pairs``: the result is that of `detect_dc` without a limit."""
         arr, keep = self._dc_preds(preds, "detect_dc_scan")
-        cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
+        cc = _flat(cell_cols, np.int32)
         nr, nc = C.c_int64(0), C.c_int64(0)
-        _check(lib().rgbm_table_detect_dc_scan(self.h, arr, C.c_int32(len(preds)), _p(cc, C.c_int32), C.c_int32(len(cc)),
-                                               C.byref(nr), C.byref(nc)), "rgbm_table_detect_dc_scan")
+        _call("rgbm_table_detect_dc_scan", self.h, arr, len(preds), cc, len(cc), C.byref(nr), C.byref(nc))
         return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
     def detect_row_bits(self, cols, bits, cell_cols=(), fetch=True):
         """Rows whose code has its bit set in EVERY listed column (rgbm_table_detect_row_bits: single-tuple constraints).  ``bits[k]``:
         uint64 [ceil((n_codes[cols[k]] + 1) / 64)], bit v = the predicates on the column hold for code v, the last bit for NULL."""
-        cols_ = _i32(np.asarray(cols, np.int32).reshape(-1))
+        cols_ = _flat(cols, np.int32)
         k = len(cols_)
         if len(bits) != k:
             raise ValueError("detect_row_bits: one bitset per column")
         keep, ptrs = [], (C.POINTER(C.c_uint64) * max(k, 1))()
         for j in range(k):
-            w = np.ascontiguousarray(bits[j], np.uint64).reshape(-1)
+            w = _flat(bits[j], np.uint64)
             if 0 <= cols_[j] < self.c and len(w) != (int(self.n_codes[cols_[j]]) + 1 + 63) // 64:
                 raise ValueError("detect_row_bits: the bitset of column %d holds %d words, its %d codes and NULL need %d"
                                  % (cols_[j], len(w), int(self.n_codes[cols_[j]]), (int(self.n_codes[cols_[j]]) + 64) // 64))
             keep.append(w)
-            ptrs[j] = w.ctypes.data_as(C.POINTER(C.c_uint64))
-        cc = _i32(np.asarray(cell_cols, np.int32).reshape(-1))
+            ptrs[j] = _p(w, C.c_uint64)
+        cc = _flat(cell_cols, np.int32)
         nr, nc = C.c_int64(0), C.c_int64(0)
-        _check(lib().rgbm_table_detect_row_bits(self.h, _p(cols_, C.c_int32), C.c_int32(k), ptrs, _p(cc, C.c_int32), C.c_int32(len(cc)),
-                                                C.byref(nr), C.byref(nc)), "rgbm_table_detect_row_bits")
+        _call("rgbm_table_detect_row_bits", self.h, cols_, k, ptrs, cc, len(cc), C.byref(nr), C.byref(nc))
         return self._fetch_cells(int(nc.value), len(cc) > 0, fetch)
 
     def rows_of_cells(self, rows):
         """Ascending positions of the rows that hold at least one of the given cells (the dirty rows, model.py:549-553)."""
         r = np.ascontiguousarray(rows, np.int64)
         n = C.c_int64(0)
-        _check(lib().rgbm_table_rows_of_cells(self.h, _p(r, C.c_int64), C.c_int64(len(r)), C.byref(n)), "rgbm_table_rows_of_cells")
+        _call("rgbm_table_rows_of_cells", self.h, r, len(r), C.byref(n))
         return self._fetch_cells(int(n.value), False)
 
     # ---- the cell set (csrc/rgbm_cellset.hip): the union of detector results, kept on the device.  Every `detect_*` method takes
     # ``fetch=False``: the result then stays in the table's cell list for `cellset_add` and the method returns its cell count.
     def cellset_open(self, cols):
         """A zeroed cell set over the distinct columns ``cols`` (rgbm_table_cellset_open); a second open replaces it."""
-        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
-        _check(lib().rgbm_table_cellset_open(self.h, _p(cc, C.c_int32), C.c_int32(len(cc))), "rgbm_table_cellset_open")
+        cc = _flat(cols, np.int32)
+        _call("rgbm_table_cellset_open", self.h, cc, len(cc))
         self._cellset_cols = len(cc)
 
     def cellset_add(self):
         """ORs the cell list the last ``detect_*`` call left into the set; cells of columns outside the set are skipped."""
-        _check(lib().rgbm_table_cellset_add(self.h), "rgbm_table_cellset_add")
+        _call("rgbm_table_cellset_add", self.h)
 
     def cellset_emit(self, fetch=True):
         """The set as (rows, cols, codes, counts): ordered by position in the set's columns, then ascending row; ``codes`` are the codes the
@@ -865,7 +927,7 @@ class Table:
         table's cell list and ``counts`` alone is returned."""
         k = getattr(self, "_cellset_cols", 0)
         n, counts = C.c_int64(0), np.zeros(max(k, 1), np.int64)
-        _check(lib().rgbm_table_cellset_emit(self.h, C.byref(n), _p(counts, C.c_int64)), "rgbm_table_cellset_emit")
+        _call("rgbm_table_cellset_emit", self.h, C.byref(n), counts)
         if not fetch:
             return counts[:k]
         rows, cols = self._fetch_cells(int(n.value), True)
@@ -874,80 +936,76 @@ class Table:
     def cells_fetch_codes(self, n):
         """The codes of the last `cellset_emit` (rgbm_table_cells_fetch_codes; refused once another result replaced its cell list)."""
         codes = np.zeros(n, np.int32)
-        _check(lib().rgbm_table_cells_fetch_codes(self.h, _p(codes, C.c_int32)), "rgbm_table_cells_fetch_codes")
+        _call("rgbm_table_cells_fetch_codes", self.h, codes)
         return codes
 
     def cellset_close(self):
-        _check(lib().rgbm_table_cellset_close(self.h), "rgbm_table_cellset_close")
+        _call("rgbm_table_cellset_close", self.h)
         self._cellset_cols = 0
 
     # ---- the repair run on the open set (DESIGN 5p): given cells in, weak labels out, null-out and dirty rows straight from the matrix
     def cellset_add_cells(self, rows, cols):
         """ORs host-given cells (any order, duplicates allowed) into the open set; cells outside the table or the set's columns are skipped."""
-        r, c2 = np.ascontiguousarray(rows, np.int64).reshape(-1), _i32(np.asarray(cols, np.int32).reshape(-1))
+        r, c2 = _flat(rows, np.int64), _flat(cols, np.int32)
         if len(r) != len(c2):
             raise ValueError("rows and cols must have the same length")
-        _check(lib().rgbm_table_cellset_add_cells(self.h, _p(r, C.c_int64), _p(c2, C.c_int32), C.c_int64(len(r))), "rgbm_table_cellset_add_cells")
+        _call("rgbm_table_cellset_add_cells", self.h, r, c2, len(r))
 
     def cellset_drop_weak(self, target_col, pair_idx, min_cnt, single_ok, beta, row_count):
         """Clears the weak-labelled cells of the set's column ``target_col``: the `weak` flag of ``cell_domains`` on the same rows, evaluated
         on the device.  The examined cells stay behind as the table's cell list.  Returns (cells examined, cells cleared)."""
-        pi, mc = _i32(np.asarray(pair_idx, np.int32).reshape(-1)), np.ascontiguousarray(min_cnt, np.int64).reshape(-1)
-        ok = np.ascontiguousarray(single_ok, np.uint8).reshape(-1)
+        pi, mc, ok = _flat(pair_idx, np.int32), _flat(min_cnt, np.int64), _flat(single_ok, np.uint8)
         if len(pi) != len(mc):
             raise ValueError("one min_cnt per pair")
         last = getattr(self, "_pc_last", None)            # (without one the library refuses the call before it reads single_ok)
         if last is not None and 0 <= int(target_col) < self.c and len(ok) != int(last[1][int(target_col)]):
             raise ValueError("single_ok must hold one entry per bin of the target (%d), not %d" % (int(last[1][int(target_col)]), len(ok)))
         cells, weak = C.c_int64(0), C.c_int64(0)
-        _check(lib().rgbm_table_cellset_drop_weak(self.h, C.c_int32(target_col), _p(pi, C.c_int32), C.c_int32(len(pi)), _p(mc, C.c_int64),
-                                                  _p(ok, C.c_uint8), C.c_double(beta), C.c_int64(row_count), C.byref(cells), C.byref(weak)),
-               "rgbm_table_cellset_drop_weak")
+        _call("rgbm_table_cellset_drop_weak", self.h, target_col, pi, len(pi), mc, ok, beta, row_count, C.byref(cells), C.byref(weak))
         return int(cells.value), int(weak.value)
 
     def cellset_null(self):
         """NULL into every cell of the open set, in place in HBM (`null_cells` without a cell list); returns the number of cells."""
         n = C.c_int64(0)
-        _check(lib().rgbm_table_cellset_null(self.h, C.byref(n)), "rgbm_table_cellset_null")
+        _call("rgbm_table_cellset_null", self.h, C.byref(n))
         return int(n.value)
 
     def cellset_rows(self, fetch=True):
         """Ascending positions of the rows that hold a cell of the open set (`rows_of_cells` without an upload); ``fetch=False``: their number."""
         n = C.c_int64(0)
-        _check(lib().rgbm_table_cellset_rows(self.h, C.byref(n)), "rgbm_table_cellset_rows")
+        _call("rgbm_table_cellset_rows", self.h, C.byref(n))
         return self._fetch_cells(int(n.value), False, fetch)
 
     def null_cells(self, rows, cols, target_cols):
         """convertErrorCellsToNull (RepairApi.scala:171-211), in place in HBM."""
-        r, c2, tc = np.ascontiguousarray(rows, np.int64), _i32(cols), _i32(np.asarray(target_cols, np.int32).reshape(-1))
+        r, c2, tc = np.ascontiguousarray(rows, np.int64), _i32(cols), _flat(target_cols, np.int32)
         if len(r) != len(c2):
             raise ValueError("rows and cols must have the same length")
-        _check(lib().rgbm_table_null_cells(self.h, _p(r, C.c_int64), _p(c2, C.c_int32), C.c_int64(len(r)), _p(tc, C.c_int32), C.c_int32(len(tc))),
-               "rgbm_table_null_cells")
+        _call("rgbm_table_null_cells", self.h, r, c2, len(r), tc, len(tc))
 
     def read_cells(self, rows, cols):
         r, c2 = np.ascontiguousarray(rows, np.int64), _i32(cols)
         out = np.zeros(len(r), np.int32)
-        _check(lib().rgbm_table_read_cells(self.h, _p(r, C.c_int64), _p(c2, C.c_int32), C.c_int64(len(r)), _p(out, C.c_int32)), "rgbm_table_read_cells")
+        _call("rgbm_table_read_cells", self.h, r, c2, len(r), out)
         return out
 
     def set_column_kind(self, col, categorical=True):
         """CATEGORICAL column: codes that no training row of a model holds are missing for that model (per-model dictionaries)."""
-        _check(lib().rgbm_table_set_column_kind(self.h, C.c_int32(col), C.c_int32(1 if categorical else 0)), "rgbm_table_set_column_kind")
+        _call("rgbm_table_set_column_kind", self.h, col, 1 if categorical else 0)
 
     def set_column_values(self, col, values):
         """NUMERIC column: the ascending distinct values behind its codes (bin bounds at value midpoints)."""
         v = np.ascontiguousarray(values, np.float64)
-        _check(lib().rgbm_table_set_column_values(self.h, C.c_int32(col), _p(v, C.c_double), C.c_int32(len(v))), "rgbm_table_set_column_values")
+        _call("rgbm_table_set_column_values", self.h, col, v, len(v))
 
     def write_cells(self, rows, cols, codes):
         r, c2, v = np.ascontiguousarray(rows, np.int64), _i32(cols), _i32(codes)
-        _check(lib().rgbm_table_write_cells(self.h, _p(r, C.c_int64), _p(c2, C.c_int32), _p(v, C.c_int32), C.c_int64(len(r))), "rgbm_table_write_cells")
+        _call("rgbm_table_write_cells", self.h, r, c2, v, len(r))
 
     def gather_rows(self, rows):
         r = np.ascontiguousarray(rows, np.int64)
         h = C.c_void_p()
-        _check(lib().rgbm_table_gather_rows(self.h, _p(r, C.c_int64), C.c_int64(len(r)), C.byref(h)), "rgbm_table_gather_rows")
+        _call("rgbm_table_gather_rows", self.h, r, len(r), C.byref(h))
         return Table._adopt(h, self.device_id)
 
     @staticmethod
@@ -956,7 +1014,7 @@ class Table:
         parts = list(parts)
         hs = (C.c_void_p * len(parts))(*[p.h for p in parts])
         h = C.c_void_p()
-        _check(lib().rgbm_table_concat(hs, C.c_int32(len(parts)), C.byref(h)), "rgbm_table_concat")
+        _call("rgbm_table_concat", hs, len(parts), C.byref(h))
         return Table._adopt(h, parts[0].device_id)
 
     def smoten(self, target_col, feat_cols, fit_rows, classes, pick_off, picks, k=5, want_nn=False):
@@ -974,9 +1032,8 @@ class Table:
             m = [int((y == c).sum()) for c in cl]
             nn = np.full((max(sum(m), 1), int(k)), -1, np.int64)
         h = C.c_void_p()
-        _check(lib().rgbm_table_smoten(self.h, C.c_int32(target_col), _p(fc, C.c_int32), C.c_int32(len(fc)), _p(fr, C.c_int64), C.c_int64(len(fr)),
-                                       C.c_int32(k), _p(cl, C.c_int32), C.c_int32(len(cl)), _p(po, C.c_int64), _p(pk if len(pk) else np.zeros(1, np.int64), C.c_int64),
-                                       _p(nn, C.c_int64), C.byref(h)), "rgbm_table_smoten")
+        _call("rgbm_table_smoten", self.h, target_col, fc, len(fc), fr, len(fr), k, cl, len(cl), po, pk if len(pk) else np.zeros(1, np.int64), nn,
+              C.byref(h))
         tab = Table._adopt(h, self.device_id)
         if not want_nn:
             return tab
@@ -996,9 +1053,7 @@ class Table:
             raise ValueError("cur_codes must hold one code per NULL cell of the target (%d)" % n_null)
         cp = np.zeros(n_null, np.float64) if (want_cur_prob or cur is not None) else None
         n = C.c_int64(0)
-        _check(lib().rgbm_table_repair_pmf(self.h, model.h, C.c_int32(target_col), _p(fc, C.c_int32), C.c_int32(len(fc)), C.c_int32(top_k),
-                                           C.c_double(threshold), _p(cur, C.c_int32), C.c_int64(n_null), C.byref(n), _p(rows, C.c_int64),
-                                           _p(cls, C.c_int32), _p(pr, C.c_double), _p(cp, C.c_double)), "rgbm_table_repair_pmf")
+        _call("rgbm_table_repair_pmf", self.h, model.h, target_col, fc, len(fc), top_k, threshold, cur, n_null, C.byref(n), rows, cls, pr, cp)
         assert int(n.value) == n_null
         return (rows, cls, pr, cp) if cp is not None else (rows, cls, pr)
 
@@ -1023,11 +1078,8 @@ class Table:
         cp = np.zeros(n_null, np.float64)
         tc = np.full(n_null, np.nan, np.float64)
         n = C.c_int64(0)
-        _check(lib().rgbm_table_repair_pmf_weighted(self.h, model.h, C.c_int32(target_col), _p(fc, C.c_int32), C.c_int32(len(fc)), C.c_int32(top_k),
-                                                    C.c_double(threshold), _p(cur, C.c_int32), _p(crow, C.c_int32), _p(cst, C.c_double),
-                                                    C.c_int64(n_cost_rows), C.c_double(weight), C.c_int32(1 if renormalise else 0), C.c_int64(n_null),
-                                                    C.byref(n), _p(rows, C.c_int64), _p(cls, C.c_int32), _p(pr, C.c_double), _p(cp, C.c_double),
-                                                    _p(tc, C.c_double)), "rgbm_table_repair_pmf_weighted")
+        _call("rgbm_table_repair_pmf_weighted", self.h, model.h, target_col, fc, len(fc), top_k, threshold, cur, crow, cst, n_cost_rows, weight,
+              1 if renormalise else 0, n_null, C.byref(n), rows, cls, pr, cp, tc)
         assert int(n.value) == n_null
         return rows, cls, pr, cp, tc
 
@@ -1035,7 +1087,7 @@ class Table:
         """(rows per code [n_codes[col]], NULL rows) of one column."""
         out = np.zeros(int(self.n_codes[col]), np.int64)
         nn = C.c_int64(0)
-        _check(lib().rgbm_table_count_codes(self.h, C.c_int32(col), _p(out, C.c_int64), C.byref(nn)), "rgbm_table_count_codes")
+        _call("rgbm_table_count_codes", self.h, col, out, C.byref(nn))
         return out, int(nn.value)
 
     def column_stats(self, cols, len_luts=None, n_bins=0):
@@ -1044,8 +1096,8 @@ class Table:
         ``len_sum``, ``len_max`` and ``edges`` (int32 [len(cols)][n_bins + 1], None when n_bins == 0).  ``len_luts``: per listed column an
         int32 [n_codes] array (the length of every dictionary entry) or None; a column may be listed more than once."""
         from repair.table_stats import FIELDS
-        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
-        luts = [None] * len(cc) if len_luts is None else [None if l is None else _i32(np.asarray(l, np.int32).reshape(-1)) for l in len_luts]
+        cc = _flat(cols, np.int32)
+        luts = [None] * len(cc) if len_luts is None else [None if l is None else _flat(l, np.int32) for l in len_luts]
         if len(luts) != len(cc):
             raise ValueError("one length LUT (or None) per listed column expected")
         for c, l in zip(cc, luts):
@@ -1054,8 +1106,7 @@ class Table:
         ptrs = (C.POINTER(C.c_int32) * max(len(cc), 1))(*[_p(l, C.c_int32) for l in luts])
         stats = np.zeros((len(cc), len(FIELDS)), np.int64)
         edges = np.full((len(cc), n_bins + 1), -1, np.int32) if n_bins > 0 else None
-        _check(lib().rgbm_table_column_stats(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), ptrs if any(l is not None for l in luts) else None,
-                                             C.c_int32(n_bins), _p(stats, C.c_int64), _p(edges, C.c_int32)), "rgbm_table_column_stats")
+        _call("rgbm_table_column_stats", self.h, cc, len(cc), ptrs if any(l is not None for l in luts) else None, n_bins, stats, edges)
         out = {f: stats[:, i].copy() for i, f in enumerate(FIELDS)}
         out["edges"] = edges
         return out
@@ -1064,12 +1115,9 @@ class Table:
         """The measures of X -> Y for one left-hand side ``lhs`` (0 .. 11 columns) against the right-hand sides ``rhs_cols`` in one call
         (include/rgbm.h rgbm_table_fd_measures), exactly the integers of ``repair.fd_codes.fd_measures``: dict(groups = int64, kept,
         violating, xy_groups = int64 [len(rhs_cols)])."""
-        lc = _i32(np.asarray(lhs, np.int32).reshape(-1))
-        rc = _i32(np.asarray(rhs_cols, np.int32).reshape(-1))
+        lc, rc = _flat(lhs, np.int32), _flat(rhs_cols, np.int32)
         g, kept, viol, xy = (np.zeros(1, np.int64),) + tuple(np.zeros(max(len(rc), 1), np.int64) for _ in range(3))
-        _check(lib().rgbm_table_fd_measures(self.h, _p(lc, C.c_int32), C.c_int32(len(lc)), _p(rc, C.c_int32), C.c_int32(len(rc)),
-                                            _p(g, C.c_int64), _p(kept, C.c_int64), _p(viol, C.c_int64), _p(xy, C.c_int64)),
-               "rgbm_table_fd_measures")
+        _call("rgbm_table_fd_measures", self.h, lc, len(lc), rc, len(rc), g, kept, viol, xy)
         self._fd_last = len(rc)                           # the right-hand sides of the call whose routes the table now holds
         return dict(groups=np.int64(g[0]), kept=kept[:len(rc)], violating=viol[:len(rc)], xy_groups=xy[:len(rc)])
 
@@ -1078,7 +1126,7 @@ class Table:
         dict(routes = one per right-hand side, 0 = LDS counters, 1 = hash tables; lds_cells, max_lhs = the two limits)."""
         n_rhs = getattr(self, "_fd_last", 0)
         out = np.zeros(n_rhs + 2, np.int32)
-        _check(lib().rgbm_table_fd_measures_report(self.h, _p(out, C.c_int32), C.c_int32(n_rhs)), "rgbm_table_fd_measures_report")
+        _call("rgbm_table_fd_measures_report", self.h, out, n_rhs)
         return dict(routes=[int(r) for r in out[:n_rhs]], lds_cells=int(out[n_rhs]), max_lhs=int(out[n_rhs + 1]))
 
     def recode(self, luts, n_codes_out, want_unmapped=True):
@@ -1096,36 +1144,35 @@ class Table:
         # (an empty array has no address of its own: a LUT column never passes NULL, which would mean identity)
         keep = [None if m is None else (m if len(m) else np.zeros(1, np.int32)) for m in maps]
         ptrs = (C.POINTER(C.c_int32) * max(self.c, 1))(*[_p(m, C.c_int32) for m in keep])
-        nco = _i32(np.asarray(n_codes_out, np.int32).reshape(-1))
+        nco = _flat(n_codes_out, np.int32)
         if len(nco) != self.c:
             raise ValueError("one output dictionary size per column expected")
         un = np.zeros(max(self.c, 1), np.int64) if want_unmapped else None
         h = C.c_void_p()
-        _check(lib().rgbm_table_recode(self.h, ptrs, _p(nco, C.c_int32), C.byref(h), _p(un, C.c_int64)), "rgbm_table_recode")
+        _call("rgbm_table_recode", self.h, ptrs, nco, C.byref(h), un)
         return Table._adopt(h, self.device_id), (un[:self.c] if want_unmapped else None)
 
     def recode_report(self):
         """The route each column took in the last successful ``recode`` call on this table (include/rgbm.h rgbm_table_recode_report):
         dict(routes = one per column, 0 = identity copy, 1 = LDS LUT, 2 = global LUT, -1 before any call; lds_codes = the limit)."""
         out = np.zeros(self.c + 1, np.int32)
-        _check(lib().rgbm_table_recode_report(self.h, _p(out, C.c_int32), C.c_int32(self.c)), "rgbm_table_recode_report")
+        _call("rgbm_table_recode_report", self.h, out, self.c)
         return dict(routes=[int(r) for r in out[:self.c]], lds_codes=int(out[self.c]))
 
     def fd_map(self, x, y):
         """The rule model of the functional dependency x -> y (include/rgbm.h rgbm_table_fd_map): int32 [n_codes[x]], the single y code
         each x code occurs with over the rows where both are non-NULL, -1 for none or several."""
         out = np.full(int(self.n_codes[x]), -1, np.int32)
-        _check(lib().rgbm_table_fd_map(self.h, C.c_int32(x), C.c_int32(y), _p(out, C.c_int32)), "rgbm_table_fd_map")
+        _call("rgbm_table_fd_map", self.h, x, y, out)
         return out
 
     def rule_fill(self, y, x, lut, row_begin=0, n_rows=None, want_labels=True):
         """One rule step of the chained repair (include/rgbm.h rgbm_table_rule_fill): pred = lut[x code] (x = -1: the constant lut[0]);
         NULL cells of column y in the row range receive pred >= 0.  Returns pred per row (int32 [n_rows]) or None."""
         n_rows = self.n - row_begin if n_rows is None else n_rows
-        l = _i32(np.asarray(lut, np.int32).reshape(-1))
+        l = _flat(lut, np.int32)
         out = np.full(n_rows, -1, np.int32) if want_labels else None
-        _check(lib().rgbm_table_rule_fill(self.h, C.c_int32(y), C.c_int32(x), _p(l, C.c_int32), C.c_int32(len(l)), C.c_int64(row_begin),
-                                          C.c_int64(n_rows), _p(out, C.c_int32)), "rgbm_table_rule_fill")
+        _call("rgbm_table_rule_fill", self.h, y, x, l, len(l), row_begin, n_rows, out)
         return out
 
     def pair_counts(self, pairs, luts=None, n_bins=None):
@@ -1144,8 +1191,7 @@ class Table:
                                                  for c in range(self.c)])
         shapes = [(int(nb[x]) + 1, int(nb[y]) + 1) for x, y in pc]
         out = np.zeros(int(sum(a * b for a, b in shapes)), np.int64)
-        _check(lib().rgbm_table_pair_counts(self.h, _p(pc, C.c_int32), C.c_int32(len(pc)), ptrs if keep else None, _p(nb, C.c_int32),
-                                            _p(out, C.c_int64)), "rgbm_table_pair_counts")
+        _call("rgbm_table_pair_counts", self.h, pc, len(pc), ptrs if keep else None, nb, out)
         self._pc_last = (len(pc), nb)                     # what the table now holds: the pairs and the bins per column of this call
         res, at = [], 0
         for a, b in shapes:
@@ -1158,8 +1204,7 @@ class Table:
         the two limits that close a group)."""
         n_pairs = getattr(self, "_pc_last", (0, None))[0]
         head, rows = np.zeros(6, np.int64), np.zeros((max(n_pairs, 1), 3), np.int32)
-        _check(lib().rgbm_table_pair_counts_report(self.h, _p(head, C.c_int64), _p(rows, C.c_int32), C.c_int32(n_pairs)),
-               "rgbm_table_pair_counts_report")
+        _call("rgbm_table_pair_counts_report", self.h, head, rows, n_pairs)
         return dict(pairs=[dict(group=int(r[0]), slot_x=int(r[1]), slot_y=int(r[2])) for r in rows[:n_pairs]], groups=int(head[0]),
                     max_group_cells=int(head[1]), grid_x=int(head[2]), rows_per_wg=int(head[3]), lds_cells=int(head[4]), max_cols=int(head[5]))
 
@@ -1167,8 +1212,7 @@ class Table:
         """Domains / weak labels of the error cells (``rows``) of one discrete target on the tables of the last ``pair_counts`` call
         (include/rgbm.h rgbm_table_cell_domains).  Returns (weak [m] uint8, top [m] int32, top_prob [m] float64, probs [m][d] or None)."""
         r = np.ascontiguousarray(rows, np.int64)
-        pi, mc = _i32(np.asarray(pair_idx, np.int32).reshape(-1)), np.ascontiguousarray(min_cnt, np.int64).reshape(-1)
-        ok = np.ascontiguousarray(single_ok, np.uint8).reshape(-1)
+        pi, mc, ok = _flat(pair_idx, np.int32), _flat(min_cnt, np.int64), _flat(single_ok, np.uint8)
         if len(pi) != len(mc):
             raise ValueError("one min_cnt per pair")
         last = getattr(self, "_pc_last", None)            # (without one the library refuses the call before it reads single_ok)
@@ -1177,25 +1221,20 @@ class Table:
         m = len(r)
         weak, top, tp = np.zeros(m, np.uint8), np.full(m, -1, np.int32), np.zeros(m, np.float64)
         probs = np.zeros((m, len(ok)), np.float64) if want_probs else None
-        _check(lib().rgbm_table_cell_domains(self.h, C.c_int32(target_col), _p(r, C.c_int64), C.c_int64(m), _p(pi, C.c_int32), C.c_int32(len(pi)),
-                                             _p(mc, C.c_int64), _p(ok, C.c_uint8), C.c_double(beta), C.c_int64(row_count), _p(weak, C.c_uint8),
-                                             _p(top, C.c_int32), _p(tp, C.c_double), _p(probs, C.c_double)), "rgbm_table_cell_domains")
+        _call("rgbm_table_cell_domains", self.h, target_col, r, m, pi, len(pi), mc, ok, beta, row_count, weak, top, tp, probs)
         return weak, top, tp, probs
 
     def kmeans_assign(self, cols, code_off, p, h, first):
         """One Lloyd assignment step of the q-gram k-means in code space (include/rgbm.h rgbm_table_kmeans_assign; the statement is
         repair.qgram_kmeans.assign_step).  ``p`` float64 [d_tot][k], ``h`` float64 [k], ``code_off[j]`` = start of column cols[j]'s dictionary
         among the d_tot entries.  Returns (counts int64 [k][d_tot], sizes int64 [k], n_changed); the labels stay on the device (``kmeans_read``)."""
-        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
-        off = np.ascontiguousarray(code_off, np.int64).reshape(-1)
-        pp, hh = np.ascontiguousarray(p, np.float64), np.ascontiguousarray(h, np.float64).reshape(-1)
+        cc, off = _flat(cols, np.int32), _flat(code_off, np.int64)
+        pp, hh = np.ascontiguousarray(p, np.float64), _flat(h, np.float64)
         if pp.ndim != 2 or pp.shape[1] != len(hh) or len(off) != len(cc):
             raise ValueError("kmeans_assign: p must be [d_tot][k], h [k], one offset per column")
         d_tot, k = pp.shape
         counts, sizes, nch = np.zeros((k, d_tot), np.int64), np.zeros(k, np.int64), C.c_int64(0)
-        _check(lib().rgbm_table_kmeans_assign(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), _p(off, C.c_int64), C.c_int32(k), _p(pp, C.c_double),
-                                              C.c_int64(d_tot), _p(hh, C.c_double), C.c_int32(1 if first else 0), _p(counts, C.c_int64),
-                                              _p(sizes, C.c_int64), C.byref(nch)), "rgbm_table_kmeans_assign")
+        _call("rgbm_table_kmeans_assign", self.h, cc, len(cc), off, k, pp, d_tot, hh, 1 if first else 0, counts, sizes, C.byref(nch))
         return counts, sizes, int(nch.value)
 
     def kmeans_bisect(self, cols, code_off, slot_of, child, p, h, first):
@@ -1203,24 +1242,21 @@ class Table:
         repair.qgram_bisect.bisect_step).  ``slot_of`` int32 [n_nodes] (-1 = the node is not being split), ``child`` int32 [2m], ``p`` float64
         [d_tot][2m], ``h`` float64 [2m].  Returns (counts int64 [2m][d_tot], sizes int64 [2m], n_changed); the labels (node ids) stay on the
         device (``kmeans_read``)."""
-        cc = _i32(np.asarray(cols, np.int32).reshape(-1))
-        off = np.ascontiguousarray(code_off, np.int64).reshape(-1)
-        so, ch = _i32(np.asarray(slot_of, np.int32).reshape(-1)), _i32(np.asarray(child, np.int32).reshape(-1))
-        pp, hh = np.ascontiguousarray(p, np.float64), np.ascontiguousarray(h, np.float64).reshape(-1)
+        cc, off = _flat(cols, np.int32), _flat(code_off, np.int64)
+        so, ch = _flat(slot_of, np.int32), _flat(child, np.int32)
+        pp, hh = np.ascontiguousarray(p, np.float64), _flat(h, np.float64)
         if pp.ndim != 2 or pp.shape[1] != len(hh) or len(hh) != len(ch) or len(ch) % 2 or len(off) != len(cc):
             raise ValueError("kmeans_bisect: p must be [d_tot][2m], h and child [2m], one offset per column")
         d_tot, k = pp.shape
         counts, sizes, nch = np.zeros((k, d_tot), np.int64), np.zeros(k, np.int64), C.c_int64(0)
-        _check(lib().rgbm_table_kmeans_bisect(self.h, _p(cc, C.c_int32), C.c_int32(len(cc)), _p(off, C.c_int64), C.c_int64(d_tot), _p(so, C.c_int32),
-                                              C.c_int32(len(so)), C.c_int32(k // 2), _p(ch, C.c_int32), _p(pp, C.c_double), _p(hh, C.c_double),
-                                              C.c_int32(1 if first else 0), _p(counts, C.c_int64), _p(sizes, C.c_int64), C.byref(nch)),
-               "rgbm_table_kmeans_bisect")
+        _call("rgbm_table_kmeans_bisect", self.h, cc, len(cc), off, d_tot, so, len(so), k // 2, ch, pp, hh, 1 if first else 0, counts, sizes,
+              C.byref(nch))
         return counts, sizes, int(nch.value)
 
     def kmeans_read(self):
         """The labels the last ``kmeans_assign`` left on the device, int32 [n]."""
         out = np.zeros(self.n, np.int32)
-        _check(lib().rgbm_table_kmeans_read(self.h, _p(out, C.c_int32)), "rgbm_table_kmeans_read")
+        _call("rgbm_table_kmeans_read", self.h, out)
         return out
 
     def close(self):
@@ -1237,8 +1273,7 @@ class Table:
         p = make_params(**params)
         h = C.c_void_p()
         st = RgbmTrainStats()
-        _check(lib().rgbm_table_train(self.h, C.c_int32(target_col), _p(fc, C.c_int32), C.c_int32(len(fc)), _p(yv, C.c_double),
-                                      _p(cw, C.c_double), C.byref(p), C.byref(h), C.byref(st) if want_stats else None), "rgbm_table_train")
+        _call("rgbm_table_train", self.h, target_col, fc, len(fc), yv, cw, C.byref(p), C.byref(h), C.byref(st) if want_stats else None)
         m = Model(h)
         return (m, st.as_dict()) if want_stats else m
 
@@ -1249,9 +1284,7 @@ class Table:
         tc = _i32(target_col)
         lab = np.zeros((T, n_rows), np.int32)
         prob = np.zeros((T, n_rows), np.float64) if want_prob else None
-        _check(lib().rgbm_table_repair_chain(self.h, arr, C.c_int32(T), _p(tc, C.c_int32), _p(fc, C.c_int32), _p(fo, C.c_int32),
-                                             C.c_int64(row_begin), C.c_int64(n_rows), _p(lab, C.c_int32), _p(prob, C.c_double)),
-               "rgbm_table_repair_chain")
+        _call("rgbm_table_repair_chain", self.h, arr, T, tc, fc, fo, row_begin, n_rows, lab, prob)
         return lab, prob
 
     def set_row_multiplicity(self, mult):
@@ -1260,12 +1293,12 @@ class Table:
         m = None if mult is None else np.ascontiguousarray(mult, np.uint8)
         if m is not None and m.shape != (self.n,):
             raise ValueError("one multiplicity per row")
-        _check(lib().rgbm_table_set_row_multiplicity(self.h, _p(m, C.c_uint8)), "rgbm_table_set_row_multiplicity")
+        _call("rgbm_table_set_row_multiplicity", self.h, m)
 
     def row_multiplicity(self):
         """The multiplicities the table carries, uint8 [n] (1 everywhere when it carries none)."""
         out = np.zeros(self.n, np.uint8)
-        _check(lib().rgbm_table_read_row_multiplicity(self.h, _p(out, C.c_uint8)), "rgbm_table_read_row_multiplicity")
+        _call("rgbm_table_read_row_multiplicity", self.h, out)
         return out
 
     def distinct_rows(self, want_inverse=False):
@@ -1274,7 +1307,7 @@ class Table:
         the models of this table, byte for byte.  `want_inverse`: also int64 [n], the position of every row's group in the new table."""
         h, m = C.c_void_p(), C.c_int64(0)
         inv = np.zeros(self.n, np.int64) if want_inverse else None
-        _check(lib().rgbm_table_distinct_rows(self.h, C.byref(h), C.byref(m), _p(inv, C.c_int64)), "rgbm_table_distinct_rows")
+        _call("rgbm_table_distinct_rows", self.h, C.byref(h), C.byref(m), inv)
         d = Table._adopt(h, self.device_id)
         return (d, inv) if want_inverse else d
 
@@ -1282,7 +1315,7 @@ class Table:
         """The distinct-row view train() keeps for this table (rgbm_table_distinct_view_info): its state ("none", "built", "not worth it",
         "cannot"), its rows, and the distinct passes run for this table object."""
         st, rows, builds = C.c_int32(0), C.c_int64(0), C.c_int64(0)
-        _check(lib().rgbm_table_distinct_view_info(self.h, C.byref(st), C.byref(rows), C.byref(builds)), "rgbm_table_distinct_view_info")
+        _call("rgbm_table_distinct_view_info", self.h, C.byref(st), C.byref(rows), C.byref(builds))
         return {"state": VIEW_STATES[st.value], "rows": int(rows.value), "builds": int(builds.value)}
 
     def repair_chain_gather(self, models, target_col, feat_cols, row_begin=0, n_rows=None):
@@ -1297,9 +1330,7 @@ class Table:
         tc = _i32(target_col)
         lab = np.zeros((nr, T, mx), np.int32)
         prob = np.zeros((nr, T, mx), np.float64)
-        _check(lib().rgbm_table_repair_chain_gather(self.h, arr, C.c_int32(T), _p(tc, C.c_int32), _p(fc, C.c_int32), _p(fo, C.c_int32),
-                                                    C.c_int64(row_begin), C.c_int64(n_rows), C.c_int64(mx), _p(lab, C.c_int32), _p(prob, C.c_double)),
-               "rgbm_table_repair_chain_gather")
+        _call("rgbm_table_repair_chain_gather", self.h, arr, T, tc, fc, fo, row_begin, n_rows, mx, lab, prob)
         labels = np.concatenate([lab[r, :, :int(counts[r])] for r in range(nr)], axis=1)
         probs = np.concatenate([prob[r, :, :int(counts[r])] for r in range(nr)], axis=1)
         me = comm_info()["rank"]
@@ -1307,5 +1338,5 @@ class Table:
 
     def read_column(self, col):
         out = np.zeros(self.n, np.int32)
-        _check(lib().rgbm_table_read_column(self.h, C.c_int32(col), _p(out, C.c_int32)), "rgbm_table_read_column")
+        _call("rgbm_table_read_column", self.h, col, out)
         return out

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _declared():
     src = open(os.path.join(ROOT, "include", "rgbm.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(rgbm_[a-z_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(rgbm_[a-z0-9_]+)\s*\(", src)))
 
 
 def test_header_symbols_are_exported():

@@ -145,7 +145,7 @@ def test_refusals_leave_the_set_the_cell_list_and_the_last_emits_codes():
         return lib.rgbm_table_cellset_drop_weak(tab.h, C.c_int32(target), p.ctypes.data_as(i32) if pidx is not None else None, C.c_int32(k),
                                                 m.ctypes.data_as(i64) if min_cnt is not None else None,
                                                 single_ok.ctypes.data_as(u8) if single_ok is not None else None, C.c_double(0.5), C.c_int64(row_count),
-                                                C.byref(out, 0) if counts else None, C.byref(out, 8) if counts else None)
+                                                C.cast(C.byref(out, 0), i64) if counts else None, C.cast(C.byref(out, 8), i64) if counts else None)
 
     # ---- no open set: RGBM_ERR_PARAM from all four, and the detector's cell list stays
     want = tab.detect_nulls([2, 5])
@@ -194,7 +194,7 @@ def test_refusals_leave_the_set_the_cell_list_and_the_last_emits_codes():
     tab.pair_counts([(0, 1)], luts={1: lut}, n_bins={0: X.K, 1: 3})
     _refused(N, -2, tab.cellset_drop_weak, 1, [0], [0], np.ones(3, np.uint8), 0.5, n)
     intact()
-    for rc in (lib.rgbm_table_cellset_null(tab.h, None), lib.rgbm_table_cellset_rows(tab.h, None), lib.rgbm_table_cellset_null(None, C.byref(out, 0))):
+    for rc in (lib.rgbm_table_cellset_null(tab.h, None), lib.rgbm_table_cellset_rows(tab.h, None), lib.rgbm_table_cellset_null(None, C.cast(C.byref(out, 0), i64))):
         assert rc == -1
         intact()
     assert np.array_equal(np.stack([tab.read_column(j) for j in range(X.C)]), codes)           # nothing wrote a code

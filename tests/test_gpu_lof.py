@@ -127,7 +127,7 @@ def test_argument_errors_come_back_as_errors():
 def test_the_symbol_is_exported_and_declared():
     import os
     from repair import _native as N
-    assert hasattr(N.lib(), "rgbm_lof_1d") and "rgbm_lof_1d" in N.EXPORTED_SYMBOLS_WITH_DIGITS
+    assert hasattr(N.lib(), "rgbm_lof_1d") and "rgbm_lof_1d" in N.EXPORTED_SYMBOLS
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     assert "int rgbm_lof_1d(" in open(os.path.join(root, "include", "rgbm.h")).read()
 
